@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """TCSC sparse-ternary GEMM benchmark (BASELINE.json metric) on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 4]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 4] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...
 
 A "step" is one pass of the hot path over one batch: one launch of the gfx950
@@ -21,12 +21,23 @@ shard across 8 x MI355X"):
 There is no collective on the data path; the only collectives are the
 timing barrier and the max-over-ranks of the elapsed time.
 
-Prints ONE JSON line on rank 0 (contract in the task statement), with
-`roofline` for the gather kernel (algorithmic bytes per launch / average
-launch time measured with HIP events on the launch stream) and
+A plain run does only what the headline figure needs: set-up, the untimed
+launches that let the GPU clocks settle, W warm-up steps, the K timed steps,
+and ONE JSON line on rank 0 (`value`, `ms_per_step`, the step-level
+`roofline` figures).  --dump-outputs DIR then writes what the last timed
+step computed (DIR/Y.npy, float32: a fixed seeded sample of Y's rows, all
+columns; one Y_rank<r>.npy per rank at N>1); inputs are seeded, so two
+builds can be compared output for output.
+
+--full adds everything else to the line, each measured in runs of its own:
+`validation` (one step against the dense product, bit-identical repeats) in
+place of the settling launches, the per-kernel split of `roofline` (average
+launch time measured with HIP events on the launch stream), `dense_baseline`,
+`bcsr`, `host_api`, `reference_order`, `graph`, `other_configs`,
 `cpu_baseline` (the reference's own sparse/tcsc.c, compiled in place into
 oracle/_ref, timed on this host's cores on a bounded sample of the same
-workload; its OpenMP form on every usable core beside it).
+workload; its OpenMP form on every usable core beside it) and, at N>1,
+`alt_shard`.  The --no-* options switch single parts of --full off.
 """
 from __future__ import annotations
 
@@ -45,6 +56,10 @@ HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md chip table (spec)
 # LDS gather roof: ds_read_b64/b128 move 256 B/clk/CU = 64 fp32 per clk per CU
 LDS_GATHER_PEAK = 64 * 256 * 2.4e9  # gathered fp32 values / s
 VALU_ADD_PEAK = 128 * 256 * 2.4e9  # fp32 adds / s (4 SIMD32 per CU)
+# a plain run's untimed launches before the warm-up: as many as --full's
+# validation phase makes (1 + 24), so the clocks have settled alike
+SETTLE_LAUNCHES = 25
+DUMP_BYTES = 48 << 20  # --dump-outputs: budget over all ranks' files
 
 
 def parse():
@@ -53,6 +68,12 @@ def parse():
     p.add_argument("--steps", type=int, default=20)
     p.add_argument("--warmup", type=int, default=5)
     p.add_argument("--config", type=int, default=4)
+    p.add_argument("--full", action="store_true",
+                   help="also validate, split the step per kernel and time the baselines, the other configs, the host "
+                        "API, the graph replay and (N>1) the other shard axis; without it only the headline is timed")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write the last step's output (a seeded row sample of Y, float32) "
+                        "as DIR/Y.npy (DIR/Y_rank<r>.npy at N>1)")
     p.add_argument("--scaling", choices=("weak", "strong"), default="strong",
                    help="strong (default): cfg's matrix split over the N ranks (--shard); weak: every rank a full copy")
     p.add_argument("--variant", default=None, help="override the config's variant")
@@ -72,7 +93,9 @@ def parse():
                    help="nccl (= RCCL, one GPU per rank); gloo lets ranks share a GPU (rehearsal only)")
     p.add_argument("--no-other-configs", action="store_true",
                    help="skip the other BASELINE configs' timings (N=1 only)")
-    p.add_argument("--no-validate", action="store_true", help="skip the pre-timing check against the dense product")
+    p.add_argument("--no-validate", action="store_true",
+                   help="skip the pre-timing phase: --full's check against the dense product, a plain run's "
+                        "settling launches")
     p.add_argument("--no-graph", action="store_true",
                    help="skip the HIP-graph line (the same steps captured once and replayed; N=1 only)")
     p.add_argument("--no-host-api", action="store_true",
@@ -164,13 +187,18 @@ def main():
     def step():
         plan.sgemm(X, B, Y, cfg.M, ncols, variant, 0.2, sh)
 
-    # ---- validation (not timed): as the reference harness validates before it
-    # measures (main.cpp:299-368), every rank checks one step's full output
+    # ---- validation (--full, not timed): as the reference harness validates before
+    # it measures (main.cpp:299-368), every rank checks one step's full output.
+    # A plain run makes the same number of launches unchecked: the timed steps
+    # start from the same settled clocks either way (DESIGN.md §7 "clock ramp")
     validation = None
-    if not args.no_validate:
+    if args.full and not args.no_validate:
         validation = validate_against_dense(tcsc_amd, cfg, ncols, variant, X, Wd, B, Y, step, sh)
-        validation["determinism"] = check_determinism(step, Y, 24)
-    if world > 1 or (args.no_dense_baseline and args.no_bcsr):
+        validation["determinism"] = check_determinism(step, Y, SETTLE_LAUNCHES - 1)
+    elif not args.no_validate:
+        for _ in range(SETTLE_LAUNCHES):
+            step()
+    if not args.full or world > 1 or (args.no_dense_baseline and args.no_bcsr):
         Wd = None
     torch.cuda.synchronize(dev)
 
@@ -193,9 +221,10 @@ def main():
     torch.cuda.synchronize(dev)
     elapsed = time.perf_counter() - t0
     step_events_s = ev0.elapsed_time(ev1) / 1e3 / max(args.steps, 1)
+    dumped = dump_outputs(args.dump_outputs, Y, rank, world) if args.dump_outputs else None
 
-    # Per-kernel split on the same stream (not part of `value`): the X^T
-    # staging (k_transpose) and the gather (k_stream) back to back, each
+    # Per-kernel split on the same stream (--full; not part of `value`): the
+    # X^T staging (k_transpose) and the gather (k_stream) back to back, each
     # averaged over `steps` launches with HIP events, so roofline.kernel_ms is
     # the average duration of the kernel the rocprofv3 summary lists.
     def timed(fn, n):
@@ -213,11 +242,13 @@ def main():
     # split and not combined in the launch), timed with HIP events on the
     # launch stream: the whole step, then the X^T staging and the gather apart
     path, slices = plan.launch_info(cfg.M)
-    step_kernels_s = timed(step, nsplit)
-    transpose_s = timed(lambda: plan.prepare_x(X, cfg.M, sh), nsplit)
-    plan.prepare_x(X, cfg.M, sh)
-    gather_s = timed(lambda: plan.sgemm_prepared(B, Y, cfg.M, ncols, variant, 0.2, sh), nsplit)
-    kernel_s = gather_s
+    step_kernels_s = transpose_s = gather_s = kernel_s = None
+    if args.full:
+        step_kernels_s = timed(step, nsplit)
+        transpose_s = timed(lambda: plan.prepare_x(X, cfg.M, sh), nsplit)
+        plan.prepare_x(X, cfg.M, sh)
+        gather_s = timed(lambda: plan.sgemm_prepared(B, Y, cfg.M, ncols, variant, 0.2, sh), nsplit)
+        kernel_s = gather_s
     combine = plan.combine_mode(cfg.M) if slices > 1 else None
     # the two halves per path: prepare_x / sgemm_prepared run k_transpose / k_stream
     # on the gather path, k_split3 / k_gemm3 + k_fixup on the MFMA path
@@ -229,7 +260,7 @@ def main():
         stage_names = ("k_transpose", "gather")
 
     alt = None
-    if distributed and args.scaling == "strong" and not args.no_alt_shard and args.shard_of <= 1:
+    if args.full and distributed and args.scaling == "strong" and not args.no_alt_shard and args.shard_of <= 1:
         # the other collective-free split of the same config, timed with the same
         # protocol (SURVEY.md §8e "Alternative"): row blocks when the line is column
         # blocks.  Every rank takes part; rank 0 reports it beside the main line.
@@ -249,7 +280,6 @@ def main():
 
     if rank == 0:
         algo_bytes = workloads.algorithmic_bytes(cfg.M, cfg.K, ncols, nnz)
-        achieved = algo_bytes / kernel_s / 1e9
         adds_per_launch = workloads.add_ops(cfg.M, nnz, ncols)
         traffic = None
         try:
@@ -289,29 +319,37 @@ def main():
             },
             "roofline": {
                 "bound": "hbm",
-                "achieved": achieved,
                 "peak": HBM_PEAK_GBS,
                 "unit": "GB/s",
-                "frac": achieved / HBM_PEAK_GBS,
                 "traffic": traffic,
                 "kernel": kernel_name,
                 "path": path,
                 "k_slices": slices,
                 "combine_in_launch": combine,
                 "algorithmic_bytes_per_launch": algo_bytes,
-                "kernel_ms": kernel_s * 1e3,
                 "step_ms_events": step_events_s * 1e3,
                 # the same algorithmic bytes over the whole step (k_transpose
                 # included): the HBM fraction that matches `value`
                 "step_achieved": algo_bytes / (elapsed_max / args.steps) / 1e9,
                 "step_frac": algo_bytes / (elapsed_max / args.steps) / 1e9 / HBM_PEAK_GBS,
+            },
+        }
+        if args.full:
+            # the gather kernel's own figures, from the per-kernel split above
+            achieved = algo_bytes / kernel_s / 1e9
+            out["roofline"].update({
+                "achieved": achieved,
+                "frac": achieved / HBM_PEAK_GBS,
+                "kernel_ms": kernel_s * 1e3,
                 "step_parts_ms": {stage_names[0]: transpose_s * 1e3, stage_names[1]: gather_s * 1e3,
                                   "step_kernels": step_kernels_s * 1e3,
                                   "note": "HIP events on the launch stream, each averaged over the same launches"},
                 "lds_gather_frac": (cfg.M * nnz / kernel_s) / LDS_GATHER_PEAK,
                 "valu_add_frac": (adds_per_launch / kernel_s) / VALU_ADD_PEAK,
-            },
-        }
+            })
+        if dumped is not None:
+            out["outputs"] = dumped
+        solo = args.full and world == 1  # the lines below are --full's, most of them at N=1 only
         if validation is not None:
             out["validation"] = validation
         if alt is not None:
@@ -336,13 +374,13 @@ def main():
             del Yd
         if Wd is not None and not args.no_bcsr:
             out["bcsr"] = bcsr_line(cfg, Wd, X, B, Y, nnz, kernel_s, timed, sh, nsplit)
-        if world == 1 and not args.no_host_api:
+        if solo and not args.no_host_api:
             # end to end through the drop-in symbol, H2D of X/B and D2H of Y
             # included (pageable numpy buffers, as main.cpp passes them); Y still holds the
             # device API's output of the same X, so the two are compared bit for bit
             out["host_api"] = host_api_line(tcsc_amd, cfg, ncols, variant, X, B, Y, csp, csn, rip[:npos],
                                             rin[:nneg], adds_per_launch)
-        if world == 1 and not args.no_reference_order:
+        if solo and not args.no_reference_order:
             # include/tcsc_gpu.h TCSC_ORDER_REFERENCE: each variant in the reference's own
             # summation order (float outputs bit-identical to sparse/tcsc.c); K is walked once
             # per sign, so the gather is slower than the merged (fast) order the value uses
@@ -360,13 +398,13 @@ def main():
                 ref[v] = {"ms": t * 1e3, "g_add_ops_per_s": adds_per_launch / t / 1e9, "vs_fast_order": t / kernel_s}
             rplan.destroy()
             out["reference_order"] = ref
-        if world == 1 and not args.no_graph:
+        if solo and not args.no_graph:
             # the same K steps captured in one HIP graph and replayed (not `value`): what the
             # launch gaps between k_transpose and k_stream cost on the eager stream
             out["graph"] = graph_line(plan, X, B, Y, cfg.M, ncols, variant, args.steps, stream, elapsed_max)
-        if world == 1 and not args.no_other_configs and not args.override:
+        if solo and not args.no_other_configs and not args.override:
             out["other_configs"] = other_configs(args, tcsc_amd, workloads, dev, sh, timed, cfg.idx)
-        if world == 1 and not args.no_cpu_baseline:
+        if solo and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args, cfg, variant, X, B, csp, csn, rip[:npos], rin[:nneg])
         print(json.dumps(out), flush=True)
     if distributed:
@@ -430,6 +468,26 @@ def alt_shard_line(args, tcsc_amd, workloads, cfg, variant, rank, world, dev, sh
             "ms_per_step": float(t_max.item()) / args.steps * 1e3, "rows_per_gpu": c.M, "columns_per_gpu": ncols,
             "note": "same protocol as the line; X rows split (W replicated)" if shard == "rows" else
                     "same protocol as the line; W columns split (X replicated)"}
+
+
+def dump_outputs(dirname, Y, rank, world):
+    """--dump-outputs: this rank's Y after the last timed step, as float32
+    DIR/Y.npy (DIR/Y_rank<r>.npy at N>1).  All columns of a fixed row sample
+    (numpy default_rng(0), sorted, the same for every run of one shape) sized
+    so that all ranks' files stay within DUMP_BYTES; every row where Y is
+    smaller.  Returns what the result line says about the file."""
+    import numpy as np
+    import torch
+
+    os.makedirs(dirname, exist_ok=True)
+    M, n = Y.shape
+    rows = max(1, min(M, DUMP_BYTES // world // (4 * n)))
+    idx = np.sort(np.random.default_rng(0).choice(M, rows, replace=False))
+    sample = Y[torch.from_numpy(idx).to(Y.device)].cpu().numpy()
+    name = "Y.npy" if world == 1 else f"Y_rank{rank}.npy"
+    np.save(os.path.join(dirname, name), sample)
+    return {"dir": dirname, "file": name, "dtype": "float32", "shape": list(sample.shape),
+            "rows": "all" if rows == M else f"{rows} of {M} rows (numpy default_rng(0).choice, sorted), all columns"}
 
 
 def host_api_line(tcsc_amd, cfg, ncols, variant, X, B, Y, csp, csn, rip, rin, adds, calls=6):

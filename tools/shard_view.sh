@@ -3,7 +3,7 @@
 # block, bench.py --shard-of 8): the column split (the north star's layout)
 # and the row split beside it.
 cd "${GRAFT_REPO_ROOT:-.}"; mkdir -p gpurun_out
-F="--steps 20 --warmup 5 --no-cpu-baseline --no-dense-baseline --no-bcsr --no-host-api --no-graph --no-other-configs --no-reference-order"
+F="--full --steps 20 --warmup 5 --no-cpu-baseline --no-dense-baseline --no-bcsr --no-host-api --no-graph --no-other-configs --no-reference-order"
 for s in ${SHARDS:-8}; do
   for ax in cols rows; do
     timeout -k 10 300 python bench.py --shard-of $s --shard $ax $F > gpurun_out/shard${s}_$ax.json 2> gpurun_out/shard${s}_$ax.err || exit 1
