@@ -149,13 +149,31 @@ int tcsc_gpu_launch_combine(const tcsc_gpu_plan *plan, int M, int *in_launch);
 /* Allocate the plan's workspace for launches of up to `max_M` rows: X^T
  * (K x max_M rounded up to 256 floats; the kernel streams X^T rows into LDS)
  * plus, where the gather's cost model or the MFMA GEMM's grid splits K over
- * workgroups, the fp32 partial slabs combined in a fixed order.  Optional: tcsc_gpu_sgemm grows the
- * workspace itself on the first call with a larger M (that call then
- * allocates and synchronises the device); reserving up front keeps every
- * sgemm call allocation-free.  Not thread-safe against concurrent launches
- * of the same plan. */
+ * workgroups, the fp32 partial slabs combined in a fixed order.  Both split K
+ * more at smaller M, so the slabs can peak below max_M: the workspace is sized
+ * for the largest need of every M <= max_M on every path the plan has (with
+ * the $TCSC_SLICES / $TCSC_MFMA_WGS / $TCSC_SMALL_M in force at this call).
+ * Optional: tcsc_gpu_sgemm grows the workspace itself on the first call that
+ * needs more (that call then allocates and synchronises the device, and a
+ * graph captured before it holds the freed workspace); reserving up front
+ * keeps every sgemm call of every M <= max_M allocation-free.  Not
+ * thread-safe against concurrent launches of the same plan. */
 int tcsc_gpu_plan_reserve(tcsc_gpu_plan *plan, int max_M);
 void tcsc_gpu_plan_destroy(tcsc_gpu_plan *plan);
+
+/* Workspace arithmetic of a plan, on the host (no launch, no allocation):
+ * *need = the workspace bytes a tcsc_gpu_sgemm of M rows wants on `path`,
+ * *reserved = the bytes the plan holds now.  `path` is TCSC_PATH_AUTO (the
+ * path tcsc_gpu_launch_info names for this M) or one of TCSC_PATH_GATHER,
+ * TCSC_PATH_MFMA, TCSC_PATH_SMALL: what that path would need at this M
+ * whatever the cost model prefers, 0 where the plan cannot run it (no MFMA
+ * image, M below mfma_min_M, M > 4 or an X too long for the small-M path).
+ * The gather's need is its X^T plus the split-K slabs of the split the cost
+ * model (or $TCSC_SLICES) picks with room to spare.  After
+ * tcsc_gpu_plan_reserve(max_M), need <= reserved for every M <= max_M and
+ * every path.  Either output pointer may be NULL. */
+#define TCSC_PATH_AUTO (-1)
+int tcsc_gpu_plan_workspace(const tcsc_gpu_plan *plan, int M, int path, size_t *need, size_t *reserved);
 
 /* Y[m, j] = act(B[j] + sum_{k in P(j)} X[m,k] - sum_{k in Q(j)} X[m,k])
  * for m < M and the plan's columns j < cols.

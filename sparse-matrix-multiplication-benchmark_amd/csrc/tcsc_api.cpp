@@ -489,13 +489,72 @@ int combine_giveup_knob() {
     return s && std::atoi(s) != 0 ? 1 : 0;
 }
 
-// Workspace of one call = [X^T: xt_bytes(M, K)] [split-K slabs, if any].
-size_t wanted_workspace(const tcsc_gpu_plan* p, int M) {
-    if (use_mfma(p, M)) return mfma_ws_bytes(M, p->rows, p->cols);
-    if (use_small(p, M)) return align256((size_t)M * p->rows * sizeof(float));  // staged X (prepare_x)
-    const int s = tcsc::choose_slices(M, p->cols, p->rows, p->n_pos + p->n_neg, p->n_groups, (size_t)-1,
-                                      slices_override());
+// Workspace of one call on each path, whatever the cost model prefers at this
+// M; 0 where the plan cannot run the path (tcsc_gpu_plan_workspace).
+// Gather = [X^T: xt_bytes(M, K)] [split-K slabs, if any].
+size_t gather_ws_bytes(const tcsc_gpu_plan* p, int M) {
+    // the reference orders walk K in order: never split
+    const int s = p->order == TCSC_ORDER_REFERENCE
+                      ? 1
+                      : tcsc::choose_slices(M, p->cols, p->rows, p->n_pos + p->n_neg, p->n_groups, (size_t)-1,
+                                            slices_override());
     return tcsc::xt_bytes(M, p->rows) + tcsc::workspace_bytes(M, p->cols, s);
+}
+
+size_t path_ws_bytes(const tcsc_gpu_plan* p, int M, int path) {
+    if (M <= 0 || p->cols == 0) return 0;
+    switch (path) {
+        case TCSC_PATH_GATHER:
+            return gather_ws_bytes(p, M);
+        case TCSC_PATH_MFMA:
+            return p->wt && M >= p->mfma_min_M && p->rows > 0 ? mfma_ws_bytes(M, p->rows, p->cols) : 0;
+        case TCSC_PATH_SMALL:  // staged X (prepare_x)
+            return p->crq && p->rows > 0 && M <= small_max_m() && tcsc::small_m_fits(M, p->rows)
+                       ? align256((size_t)M * p->rows * sizeof(float))
+                       : 0;
+    }
+    return 0;
+}
+
+int launch_path(const tcsc_gpu_plan* p, int M) {
+    return use_mfma(p, M) ? TCSC_PATH_MFMA : use_small(p, M) ? TCSC_PATH_SMALL : TCSC_PATH_GATHER;
+}
+
+// Workspace of the call tcsc_gpu_sgemm makes at this M.
+size_t wanted_workspace(const tcsc_gpu_plan* p, int M) { return path_ws_bytes(p, M, launch_path(p, M)); }
+
+// tcsc_gpu_plan_reserve(max_M): the largest need of any M <= max_M on any path
+// the plan has.  Neither need grows with M: both cost models split K more at
+// smaller M (fewer row tiles to fill the CUs), so slices x M x N peaks inside
+// the range -- K = 512, N = 4096 at 2 % wants 14x more at M = 339 than at 512.
+// So every M is evaluated (16 cost-model steps each) up to the row count from
+// which the answer is known:
+//  * gather: choose_slices takes s > 1 only where t(s) < 0.97 t(1); t(s) is at
+//    least base nch / 256 chunk times (base = row tiles x column blocks) and
+//    t(1) is ceil(base / 256) nch of them, so from base = 8278 on nothing is
+//    split (kNoSplitBase adds a margin for the rounding of the doubles) and
+//    the need is xt_bytes(M), which grows with M; a forced split
+//    ($TCSC_SLICES) is the same for every M and its need grows with M too;
+//  * MFMA: the slice count changes only where a tile count does, at multiples
+//    of 64 rows, and between those the need grows with M: the top row of every
+//    64-row step is evaluated (one division each);
+// and max_M itself.
+constexpr long long kNoSplitBase = 40 * 256;
+size_t reserve_bytes(const tcsc_gpu_plan* p, int max_M) {
+    if (max_M <= 0 || p->cols == 0) return 0;
+    const long long cb = std::max(1, (p->n_groups + tcsc::kWaves - 1) / tcsc::kWaves);
+    const int every = (int)std::min<long long>(max_M, (kNoSplitBase + cb - 1) / cb * tcsc::kTM);
+    size_t want = 0;
+    auto all_paths = [&](int M) {
+        for (int path : {TCSC_PATH_GATHER, TCSC_PATH_MFMA, TCSC_PATH_SMALL})
+            want = std::max(want, path_ws_bytes(p, M, path));
+    };
+    for (int M = 1; M <= every; ++M) all_paths(M);
+    if (p->wt)
+        for (long long M = ((long long)every / 64 + 1) * 64; M < max_M; M += 64)
+            want = std::max(want, path_ws_bytes(p, (int)M, TCSC_PATH_MFMA));
+    all_paths(max_M);
+    return want;
 }
 
 // The plan build assumes what tcsc_from_dense produces (tcsc.c:48-60): in
@@ -635,8 +694,20 @@ int sgemm_mfma(const tcsc_gpu_plan* p, const float* dX, const float* dB, float* 
     return TCSC_OK;
 }
 
+// How one sgemm_ws call is routed.  In: path < 0 lets the call choose by its
+// own M (launch_path), TCSC_PATH_GATHER pins the gather -- a caller that cuts
+// one job into several launches (run_bands, the 2^22-row pieces below) decides
+// once for the whole job, because the cost model is not monotone in M and a
+// piece on another path would sum in another order, in a workspace sized for
+// the job's path; slices > 0 forces the gather's K split.  Out: the path and
+// K split that ran.
+struct Route {
+    int path = -1;
+    int slices = 0;
+};
+
 int sgemm_ws(const tcsc_gpu_plan* p, const float* dX, const float* dB, float* dY, int M, int ldy, int variant,
-             float a, void* stream, float* ws, size_t ws_bytes, int stage = 0, int force_slices = 0) {
+             float a, void* stream, float* ws, size_t ws_bytes, int stage = 0, Route* route = nullptr) {
     if (!p || M < 0 || (stage != 1 && (ldy < p->cols || !valid_variant(variant)))) {
         set_error("tcsc_gpu_sgemm: bad arguments (M=%d ldy=%d variant=%d)", M, ldy, variant);
         return TCSC_E_ARG;
@@ -646,8 +717,16 @@ int sgemm_ws(const tcsc_gpu_plan* p, const float* dX, const float* dB, float* dY
         set_error("tcsc_gpu_sgemm: NULL device pointer");
         return TCSC_E_ARG;
     }
-    if (use_mfma(p, M)) return sgemm_mfma(p, dX, dB, dY, M, ldy, variant, a, stream, ws, ws_bytes, stage);
-    if (use_small(p, M)) {
+    Route own;
+    if (!route) route = &own;
+    const int force_slices = route->slices;
+    if (route->path != TCSC_PATH_GATHER) route->path = launch_path(p, M);
+    route->slices = 1;
+    if (route->path == TCSC_PATH_MFMA) {
+        route->slices = tcsc::mfma_slices(M, p->cols, p->rows);
+        return sgemm_mfma(p, dX, dB, dY, M, ldy, variant, a, stream, ws, ws_bytes, stage);
+    }
+    if (route->path == TCSC_PATH_SMALL) {
         // stage 1 stages X as is (the kernel reads X rows directly), stage 2 reads the staged copy
         hipStream_t st = static_cast<hipStream_t>(stream);
         const size_t xb = (size_t)M * p->rows * sizeof(float);
@@ -681,9 +760,11 @@ int sgemm_ws(const tcsc_gpu_plan* p, const float* dX, const float* dB, float* dY
         }
         for (int r0 = 0; r0 < M; r0 += kMaxLaunchRows) {
             const int r = std::min(kMaxLaunchRows, M - r0);
+            Route piece{TCSC_PATH_GATHER, force_slices > 0 ? force_slices : 1};  // a short tail stays on the gather too
             const int rc = sgemm_ws(p, dX + (size_t)r0 * p->rows, dB, dY + (size_t)r0 * ldy, r, ldy, variant, a,
-                                    stream, ws, ws_bytes, 0, force_slices > 0 ? force_slices : 1);
+                                    stream, ws, ws_bytes, 0, &piece);
             if (rc != TCSC_OK) return rc;
+            route->slices = piece.slices;
         }
         return TCSC_OK;
     }
@@ -725,6 +806,8 @@ int sgemm_ws(const tcsc_gpu_plan* p, const float* dX, const float* dB, float* dY
     g.ws_bytes = g.ws ? ws_bytes - xtb : 0;
     g.force_slices = force_slices > 0 ? force_slices : slices_override();
     g.stage = stage;
+    if (g.order == 0)  // what tcsc::launch_gemm picks with this workspace; the reference orders walk K in order
+        route->slices = tcsc::choose_slices(M, g.ncols, g.K, g.nnz, g.n_groups, g.ws ? g.ws_bytes : 0, g.force_slices);
     // the plan's own workspace (device API) with its combine words: the
     // in-launch split-K combine (tcsc::launch_gemm decides if it applies)
     if (ws == p->ws && p->csync) {
@@ -923,19 +1006,7 @@ int tcsc_gpu_plan_reserve(tcsc_gpu_plan* p, int max_M) {
         set_error("tcsc_gpu_plan_reserve: bad arguments");
         return TCSC_E_ARG;
     }
-    // both paths' needs at max_M: a later launch with fewer rows may take the other one
-    size_t want = wanted_workspace(p, max_M);
-    if (p->wt) {
-        const int s = tcsc::choose_slices(max_M, p->cols, p->rows, p->n_pos + p->n_neg, p->n_groups, (size_t)-1,
-                                          slices_override());
-        want = std::max(want, tcsc::xt_bytes(max_M, p->rows) + tcsc::workspace_bytes(max_M, p->cols, s));
-        // the MFMA path at any M <= max_M: its split-K slabs (slices x M x N)
-        // peak at the top row of some count of 128-row tiles; from 512 row
-        // tiles on every grid holds at least 512 tiles and never splits
-        want = std::max(want, mfma_ws_bytes(max_M, p->rows, p->cols));
-        for (long long m = 128; m - 127 <= max_M && m <= 512LL * 128; m += 128)
-            want = std::max(want, mfma_ws_bytes((int)std::min<long long>(m, max_M), p->rows, p->cols));
-    }
+    const size_t want = reserve_bytes(p, max_M);
     if (!p->csync && p->rows > 0 && p->order == TCSC_ORDER_FAST) {
         DeviceGuard dg(p->device);
         HIP_TRY(hipMalloc(&p->csync, tcsc::kCombineBytes));
@@ -957,6 +1028,16 @@ int tcsc_gpu_plan_reserve(tcsc_gpu_plan* p, int max_M) {
     return TCSC_OK;
 }
 
+int tcsc_gpu_plan_workspace(const tcsc_gpu_plan* p, int M, int path, size_t* need, size_t* reserved) {
+    if (!p || M < 0 || (path != TCSC_PATH_AUTO && path != TCSC_PATH_GATHER && path != TCSC_PATH_MFMA &&
+                        path != TCSC_PATH_SMALL)) {
+        set_error("tcsc_gpu_plan_workspace: bad arguments (M=%d path=%d)", M, path);
+        return TCSC_E_ARG;
+    }
+    if (need) *need = path_ws_bytes(p, M, path == TCSC_PATH_AUTO ? launch_path(p, M) : path);
+    if (reserved) *reserved = p->ws_bytes;
+    return TCSC_OK;
+}
 
 int tcsc_gpu_launch_info(const tcsc_gpu_plan* p, int M, int* path, int* slices) {
     if (!p || M < 0 || !path || !slices) {
@@ -1176,6 +1257,9 @@ struct Shard {
     int device = 0;
     int c0 = 0, c1 = 0;
     tcsc_gpu_plan* plan = nullptr;
+    // the path and K split of the last launch on this shard, for $TCSC_HOST_PATHS
+    // (written by the one thread that runs the shard's device)
+    mutable int ran_path = -1, ran_slices = 1;
 };
 
 // How the host API spreads a call over the GPUs ($TCSC_SHARD_AXIS, read when
@@ -1590,10 +1674,12 @@ struct Job {
 // through torch's HIP runtime, 11.2 -> 9.2 ms in the native driver, where 16
 // bands of 16 MB lose the H2D/D2H overlap again; 2048x8192: 3.0 -> 2.3 ms);
 // below ~48 MB the single-shot pageable copies win (cfg 2: 0.82 ms against
-// 0.86-1.0 banded).  Only on the gather path
-// with the split-K factor of the whole job forced on every band: each
-// element is then summed in the same order as by one launch, so the bits
-// do not change.  TCSC_HOST_BANDS=1 turns the pipeline off, =n asks for n.
+// 0.86-1.0 banded).  Only where the whole job takes the gather path, and
+// then every band runs the gather with the split-K factor of the whole job
+// (run_bands pins both: a band of M / n rows asked on its own may prefer the
+// MFMA path, the cost model is not monotone in M): each element is summed in
+// the same order as by one launch, so the bits do not change.
+// TCSC_HOST_BANDS=1 turns the pipeline off, =n asks for n.
 int host_bands(const tcsc_gpu_plan* p, int M, int K) {
     if (use_mfma(p, M) || use_small(p, M) || K <= 0) return 1;
     const double xbytes = (double)M * K * sizeof(float), MiB = 1024.0 * 1024;
@@ -1733,9 +1819,14 @@ int run_bands(int dev, DevState& ds, const Shard& sh, int m0, int M, int nb, con
         if (he == hipSuccess) he = hipEventRecord(ds.ev_in[b], ds.s_in);
         if (he == hipSuccess) he = hipStreamWaitEvent(st, ds.ev_in[b], 0);
         if (he != hipSuccess) return finish(hip_fail(he, "band H2D"));
+        // the whole job's path (host_bands: the gather) and K split: a band of bm rows
+        // chooses neither for itself, and ds.ws is sized for exactly this
+        Route route{TCSC_PATH_GATHER, s};
         if ((rc = sgemm_ws(p, xb, ds.b, ds.y + (size_t)r0 * nc, r1 - r0, nc, variant, a, st, ds.ws, ds.ws_cap, 0,
-                           s)) != TCSC_OK)
+                           &route)) != TCSC_OK)
             return finish(rc);
+        sh.ran_path = route.path;
+        sh.ran_slices = route.slices;
         he = hipEventRecord(ds.ev_k[b], st);
         if (he == hipSuccess) he = hipStreamWaitEvent(ds.s_out, ds.ev_k[b], 0);
         if (he != hipSuccess) return finish(hip_fail(he, "band kernels"));
@@ -1802,9 +1893,11 @@ int run_device(int dev, const std::vector<Job>& jobs, const float* X, const floa
         const size_t wsb = wanted_workspace(sh->plan, M);
         if (wsb && (rc = ensure(&ds.ws, &ds.ws_cap, wsb)) != TCSC_OK) return rc;
         HIP_TRY(hipMemcpyAsync(ds.b, B + sh->c0, (size_t)nc * sizeof(float), hipMemcpyHostToDevice, st));
-        if ((rc = sgemm_ws(sh->plan, ds.x, ds.b, ds.y, M, nc, variant, a, st, ds.ws, ds.ws_cap, 0, exact ? 1 : 0)) !=
-            TCSC_OK)
+        Route route{-1, exact ? 1 : 0};
+        if ((rc = sgemm_ws(sh->plan, ds.x, ds.b, ds.y, M, nc, variant, a, st, ds.ws, ds.ws_cap, 0, &route)) != TCSC_OK)
             return rc;
+        sh->ran_path = route.path;
+        sh->ran_slices = route.slices;
         HIP_TRY(hipMemcpy2DAsync(Y + (size_t)j.m0 * N + sh->c0, (size_t)N * sizeof(float), ds.y,
                                  (size_t)nc * sizeof(float), (size_t)nc * sizeof(float), M, hipMemcpyDeviceToHost,
                                  st));
@@ -1815,8 +1908,9 @@ int run_device(int dev, const std::vector<Job>& jobs, const float* X, const floa
 }
 
 // $TCSC_HOST_PATHS: one stderr line per matrix and variant (its first call),
-// naming the path and K-split each block took, so a failed validation in a
-// harness run (tests/test_reference_main_gpu.py) says which code computed it.
+// naming the path and K-split each block took (recorded by run_device /
+// run_bands when they launched, not recomputed here), so a failed validation
+// in a harness run (tests/test_reference_main_gpu.py) says which code computed it.
 void trace_paths(CacheEntry& e, int variant, int M, int N, int K) {
     static const bool on = std::getenv("TCSC_HOST_PATHS") != nullptr;
     if (!on || variant < 0 || variant >= 32 || (e.traced & (1u << variant))) return;
@@ -1825,15 +1919,13 @@ void trace_paths(CacheEntry& e, int variant, int M, int N, int K) {
                                    "sparse_gemm"};
     std::string paths;
     for (const Shard& sh : e.shards) {
-        const tcsc_gpu_plan* p = sh.plan;
-        const int rows = e.axis == kAxisRows ? (M + e.blocks - 1) / e.blocks : M;
-        const char* path = use_mfma(p, rows) ? "mfma" : use_small(p, rows) ? "small" : "gather";
-        int s = 1;
-        if (!e.exact && !use_mfma(p, rows) && !use_small(p, rows))
-            s = tcsc::choose_slices(rows, p->cols, p->rows, p->n_pos + p->n_neg, p->n_groups, (size_t)-1,
-                                    slices_override());
+        // what run_device / run_bands ran on this shard (its last block, when it served several)
+        const char* path = sh.ran_path == TCSC_PATH_MFMA    ? "mfma"
+                           : sh.ran_path == TCSC_PATH_SMALL ? "small"
+                           : sh.ran_path == TCSC_PATH_GATHER ? "gather"
+                                                             : "none";
         char buf[96];
-        std::snprintf(buf, sizeof buf, "%s%s/s%d", paths.empty() ? "" : ",", path, s);
+        std::snprintf(buf, sizeof buf, "%s%s/s%d", paths.empty() ? "" : ",", path, sh.ran_slices);
         paths += buf;
     }
     std::fprintf(stderr, "[tcsc_amd] path: %s M=%d N=%d K=%d blocks=%d axis=%s exact=%d -> %s\n",

@@ -45,6 +45,7 @@ EXPORTED_SYMBOLS = (
     "tcsc_gpu_sgemm_prepared", "tcsc_gpu_from_dense", "tcsc_gpu_dense_sgemm", "tcsc_gpu_last_error",
     "tcsc_gpu_cache_clear", "tcsc_gpu_num_shards", "tcsc_gpu_set_num_shards", "tcsc_gpu_set_order",
     "tcsc_gpu_get_order", "tcsc_gpu_launch_info", "tcsc_gpu_launch_combine", "tcsc_gpu_build_flags",
+    "tcsc_gpu_plan_workspace",
     # include/sparse/bcsr.h
     "bcsr_from_dense", "bcsr_sgemm_basic", "bcsr_sgemm_prelu_basic", "bcsr_sgemm_avx", "bcsr_sgemm_prelu_avx",
     "bcsr_sgemm_avx2", "bcsr_free",
@@ -138,6 +139,7 @@ def lib():
     L.tcsc_gpu_launch_info.argtypes = [vp, i, C.POINTER(i), C.POINTER(i)]
     L.tcsc_gpu_launch_combine.argtypes = [vp, i, C.POINTER(i)]
     L.tcsc_gpu_plan_reserve.argtypes = [vp, i]
+    L.tcsc_gpu_plan_workspace.argtypes = [vp, i, i, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
     L.tcsc_gpu_plan_destroy.argtypes = [vp]
     L.tcsc_gpu_plan_destroy.restype = None
     L.tcsc_gpu_sgemm.argtypes = [vp, vp, vp, vp, i, i, i, f, vp]
@@ -480,6 +482,18 @@ class Plan:
     def reserve(self, max_M: int) -> None:
         """Allocate the workspace (X^T + split-K slabs) for launches of up to max_M rows."""
         _check(lib().tcsc_gpu_plan_reserve(self.handle, int(max_M)), "tcsc_gpu_plan_reserve")
+
+    PATH_ID = {None: -1, "gather": 0, "mfma": 2, "small": 3}
+
+    def workspace(self, M: int, path: str | None = None) -> tuple[int, int]:
+        """(bytes a launch of M rows wants, bytes reserved now): host arithmetic, no
+        launch.  path None: the path launch_info(M) names; 'gather', 'mfma' or
+        'small': that path's need at M whatever the cost model prefers, 0 where the
+        plan cannot run it (tcsc_gpu_plan_workspace)."""
+        need, reserved = C.c_size_t(), C.c_size_t()
+        _check(lib().tcsc_gpu_plan_workspace(self.handle, int(M), self.PATH_ID[path], C.byref(need),
+                                             C.byref(reserved)), "tcsc_gpu_plan_workspace")
+        return need.value, reserved.value
 
     def sgemm(self, X, B, Y, M: int, ldy: int, variant: str = "prelu_basic", a: float = 0.2,
               stream: int = 0) -> None:

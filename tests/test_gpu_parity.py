@@ -257,6 +257,129 @@ def test_host_bands_bit_identical(gpu, torch_cuda, oracle, M, K, N, bands, host_
     W.free()
 
 
+# (density, K, N, M, bands): shapes where the cost model is expected to send the
+# whole job to the gather and a band of M / bands rows, asked on its own, to
+# the MFMA path
+CROSSOVER_CANDIDATES = [(0.06, 1024, 4096, 2048, 8), (0.06, 2048, 4096, 2048, 8), (0.06, 1024, 8192, 1024, 4)]
+CROSSOVER_ENV = {"TCSC_HOST_FAST": "1", "TCSC_ON_ERROR": "continue"}
+
+
+def crossover_case(oracle, monkeypatch):
+    """The first candidate whose plan says path(M) == gather and path(M / bands)
+    == mfma (Plan.launch_info), with its W; fails when none does."""
+    for k in ("TCSC_PATH", "TCSC_SLICES", "TCSC_SMALL_M", "TCSC_MFMA_WGS", "TCSC_NUM_GPUS", "TCSC_SHARD_AXIS"):
+        monkeypatch.delenv(k, raising=False)
+    seen = []
+    for idx, (d, K, N, M, bands) in enumerate(CROSSOVER_CANDIDATES):
+        Wd = oracle.ternary((K, N), d, 7700 + idx)
+        W = tcsc_amd.TcscMatrix.from_dense(Wd)
+        plan = tcsc_amd.Plan(W)
+        plan.reserve(M)
+        whole, band = plan.launch_info(M), plan.launch_info(M // bands)
+        if whole[0] == "gather" and band[0] == "mfma":
+            return idx, Wd, W, plan, whole
+        seen.append(((d, K, N, M, bands), whole, band))
+        plan.destroy()
+        W.free()
+    pytest.fail(f"no candidate has a gather job with MFMA bands: {seen}")
+
+
+def test_host_bands_at_the_path_crossover(gpu, torch_cuda, oracle, monkeypatch):
+    """A host call whose whole job the cost model sends to the gather while a
+    band of it, asked on its own, would take the MFMA path (the model is not
+    monotone in M).  Every band must stay on the job's path with the job's K
+    split: the banded result has the bits of the unbanded host call and of one
+    device launch, no error is reported, and it is within the fp32 bound."""
+    torch = torch_cuda
+    idx, Wd, W, plan, whole = crossover_case(oracle, monkeypatch)
+    d, K, N, M, bands = CROSSOVER_CANDIDATES[idx]
+    for k, v in CROSSOVER_ENV.items():
+        monkeypatch.setenv(k, v)
+    tcsc_amd.cache_clear()
+    X, B = oracle.uniform((M, K), 7710 + idx), oracle.uniform((N,), 7720 + idx)
+    dev = torch.device("cuda:0")
+    stream = torch.cuda.current_stream().cuda_stream
+    dX, dB = torch.from_numpy(X).to(dev), torch.from_numpy(B).to(dev)
+    Yd = torch.empty((M, N), device=dev)
+    plan.sgemm(dX, dB, Yd, M, N, "prelu_basic", 0.2, stream)
+    torch.cuda.synchronize()
+    Yd = Yd.cpu().numpy()
+    def host_call(nbands):
+        """(Y, last_error()) of one host call made on a fresh thread: the message
+        is per thread and nothing clears it, so a new thread starts with none."""
+        import threading
+
+        monkeypatch.setenv("TCSC_HOST_BANDS", str(nbands))
+        out = {}
+
+        def work():
+            out["Y"] = tcsc_amd.sgemm("prelu_basic", X, W, B, 0.2, Y=np.full((M, N), np.nan, np.float32))
+            out["err"] = tcsc_amd.last_error()
+
+        t = threading.Thread(target=work)
+        t.start()
+        t.join()
+        return out["Y"], out["err"]
+
+    tcsc_amd.set_num_shards(1)  # one block: the job is the whole call
+    try:
+        Yb, err_b = host_call(bands)
+        Y1, err_1 = host_call(1)
+    finally:
+        tcsc_amd.set_num_shards(0)
+    assert err_b == "" and err_1 == "", (err_b, err_1)
+    np.testing.assert_array_equal(Yb.view(np.uint32), Y1.view(np.uint32), err_msg="banded vs unbanded host call")
+    np.testing.assert_array_equal(Yb.view(np.uint32), Yd.view(np.uint32), err_msg="banded vs one device launch")
+    Y64, S64 = oracle.f64_rows(X, oracle.tcsc_from_dense(Wd, rowmajor=True), B)
+    ok, ratio = pyoracle.check_close(Yb, Y64, S64, 0.2)
+    assert ok, f"worst err/bound = {ratio:.3g}"
+    plan.destroy()
+    W.free()
+
+
+HOST_PATHS_CHILD = r"""
+import re, sys
+sys.path[:0] = [{pkg!r}, {oracle_dir!r}]
+import numpy as np, pyoracle, tcsc_amd
+d, K, N, M, seed = {d!r}, {K}, {N}, {M}, {seed}
+o = pyoracle.load_oracle()
+W = tcsc_amd.TcscMatrix.from_dense(o.ternary((K, N), d, seed))
+tcsc_amd.set_num_shards(1)
+Y = tcsc_amd.sgemm("prelu_basic", o.uniform((M, K), seed + 10), W, o.uniform((N,), seed + 20), 0.2)
+assert np.isfinite(Y).all()
+plan = tcsc_amd.Plan(W)
+plan.reserve(M)
+print("LAUNCH_INFO %s %d" % plan.launch_info(M))
+"""
+
+
+def test_host_paths_trace_names_what_ran(gpu, oracle, monkeypatch):
+    """$TCSC_HOST_PATHS (read once per process: a fresh child) at the crossover
+    shape: the line names the path and K split the bands ran, which are those
+    of one launch of the whole job (Plan.launch_info), not a band's own."""
+    import subprocess
+    import sys
+
+    from conftest import ORACLE_DIR_FOR_WORKERS, PKG_DIR_FOR_WORKERS
+
+    idx, Wd, W, plan, whole = crossover_case(oracle, monkeypatch)
+    plan.destroy()
+    W.free()
+    d, K, N, M, bands = CROSSOVER_CANDIDATES[idx]
+    env = dict(os.environ, TCSC_HOST_PATHS="1", TCSC_HOST_BANDS=str(bands), **CROSSOVER_ENV)
+    code = HOST_PATHS_CHILD.format(pkg=PKG_DIR_FOR_WORKERS, oracle_dir=ORACLE_DIR_FOR_WORKERS, d=d, K=K, N=N, M=M,
+                                   seed=7700 + idx)
+    r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert "[tcsc_amd] error" not in r.stderr, r.stderr[-2000:]
+    info = [l.split()[1:] for l in r.stdout.splitlines() if l.startswith("LAUNCH_INFO")]
+    assert info == [[whole[0], str(whole[1])]], (info, whole)
+    lines = [l for l in r.stderr.splitlines() if l.startswith("[tcsc_amd] path: prelu_basic")]
+    assert len(lines) == 1, r.stderr[-2000:]
+    assert f"M={M} N={N} K={K} " in lines[0] and "exact=0" in lines[0], lines[0]
+    assert lines[0].endswith(f"-> {whole[0]}/s{whole[1]}"), (lines[0], whole)
+
+
 def test_device_plan_from_device_arrays_and_gpu_builder(gpu, torch_cuda, oracle):
     torch = torch_cuda
     dev = torch.device("cuda:0")
