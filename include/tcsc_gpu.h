@@ -247,6 +247,86 @@ int tcsc_gpu_dense_sgemm(const float *dX, const float *dW, const float *dB,
                          float *dY, int M, int N, int K, int ldy, int variant,
                          float a, void *stream);
 
+/* ---- Backward pass ------------------------------------------
+ * For Y = act(X.W + b) with upstream gradient G = dL/dY:
+ *   dZ = G masked by the PReLU derivative, db = column sums of dZ
+ *        (tcsc_gpu_prelu_backward)
+ *   dX = dZ . W^T                          (tcsc_gpu_sgemm_t on a transposed plan)
+ * W^T of a TCSC matrix is again a TCSC matrix, so dX runs on an ordinary plan
+ * built from the transposed index arrays: every kernel family, the cost model,
+ * reserve and split K serve it unchanged.  There is no host-pointer version. */
+
+/* Device-side transposition of the index structure: from the TCSC arrays of
+ * W (rows x cols, on the current device, absolute offsets) to those of
+ * W[:, col_begin:col_end)^T, a matrix of col_end - col_begin rows and `rows`
+ * columns: d_t_csp / d_t_csn get rows + 1 offsets starting at 0, d_t_rip /
+ * d_t_rin the range's n_pos = csp[col_end] - csp[col_begin] and n_neg column
+ * indices j - col_begin, ascending inside every output column -- bit for bit
+ * what tcsc_from_dense (tcsc.c:6-66) gives for the dense transposed slice.
+ * Deterministic: integer counters only, and every output column is sorted, so
+ * no order of execution shows in the output.  The order inside an input
+ * column does not matter (unsorted input columns are accepted); a col_start
+ * that is no range or a row outside [0, rows) is TCSC_E_ARG.  An empty range,
+ * rows == 0 or no entries still write the offsets (all zero).  The row index
+ * pointers may be NULL where the range has no entry of that sign.  Allocates
+ * scratch and synchronises `stream`, as tcsc_gpu_from_dense does. */
+int tcsc_gpu_transpose_index(int rows, int cols,
+                             const int *d_col_start_pos, const int *d_col_start_neg,
+                             const int *d_row_index_pos, const int *d_row_index_neg,
+                             int col_begin, int col_end,
+                             int *d_t_col_start_pos, int *d_t_col_start_neg,
+                             int *d_t_row_index_pos, int *d_t_row_index_neg,
+                             void *stream);
+
+/* The plan of W[:, col_begin:col_end)^T: uploads the column range as
+ * tcsc_gpu_plan_create does, transposes it on the device and builds an
+ * ordinary plan from the result: info.rows = col_end - col_begin, info.cols =
+ * W->rows, info.col_begin = 0.  Everything that takes a plan works on it
+ * unchanged; it honours tcsc_gpu_set_order, $TCSC_ORDER and $TCSC_PATH at
+ * creation as any plan does.  It also owns a zero bias of info.cols floats
+ * (counted in device_bytes) for tcsc_gpu_sgemm_t.  A second plan costs what
+ * the first does: about 8 bytes per nonzero plus the per-chunk headers, plus
+ * the CSC copy and, for denser W, the bf16 image. */
+int tcsc_gpu_plan_create_transposed(const tcsc_t *W, int col_begin, int col_end,
+                                    int device, void *stream, tcsc_gpu_plan **out);
+
+/* Same, from raw TCSC arrays of W that already live on `device` (the layout
+ * tcsc_gpu_plan_create_device takes).  Nothing crosses PCIe. */
+int tcsc_gpu_plan_create_transposed_device(int rows, int cols,
+                                           const int *d_col_start_pos,
+                                           const int *d_col_start_neg,
+                                           const int *d_row_index_pos,
+                                           const int *d_row_index_neg,
+                                           int col_begin, int col_end, int device,
+                                           void *stream, tcsc_gpu_plan **out);
+
+/* dX[m, k] = sum_j G[m, j] * W[k, col_begin + j] for m < M, k < K:
+ *   dG  : M x (col_end - col_begin) row-major, contiguous (the plan's rows)
+ *   dDX : M rows with pitch ldx >= K floats; columns beyond K are not touched
+ * tcsc_gpu_sgemm on the transposed plan with TCSC_VARIANT_SPARSE_GEMM and the
+ * plan's zero bias, with every guarantee of tcsc_gpu_sgemm (asynchronous,
+ * allocation-free once reserved, safe to capture).  Column shards of W give
+ * partial dX's that the caller adds.  TCSC_E_ARG on a plan that no
+ * _transposed constructor made. */
+int tcsc_gpu_sgemm_t(const tcsc_gpu_plan *tplan, const float *dG, float *dDX,
+                     int M, int ldx, void *stream);
+
+/* The elementwise half of the layer's backward, for m < M, j < N:
+ *   dDZ[m, j] = dY[m, j] < 0.0f ? a * dG[m, j] : dG[m, j]
+ *   dDB[j]    = sum_m dDZ[m, j]   (fp32, of the rounded dDZ values)
+ * dY is the forward's OUTPUT and the predicate is the forward's own
+ * (tcsc.c:162), so the mask is exact: NaN, -0.0 and +0.0 in dY pass dG
+ * through.  dY NULL: identity activation (dDZ = dG).  dDZ may alias dG, or be
+ * NULL when only dDB is wanted; dDB may be NULL.  dG, dY and dDZ have their
+ * own row pitches (ldg, ldy, lddz >= N floats; 16-byte accesses when every
+ * pointer is 16-B aligned and every pitch a multiple of 4, scalar otherwise).
+ * dDB is summed in a fixed order (each of 32 row-lanes its rows m = r, r + 32,
+ * ... in ascending m, then the lanes pairwise), so it is bitwise reproducible;
+ * no float atomics, no scratch, no allocation, no synchronisation: safe to
+ * capture.  M == 0 writes dDB = 0.  Asynchronous on `stream`. */
+int tcsc_gpu_prelu_backward(const float *dG, int ldg, const float *dY, int ldy, float a,
+                            float *dDZ, int lddz, float *dDB, int M, int N, void *stream);
+
 /* Message for the last failing call on this thread ("" if none). */
 const char *tcsc_gpu_last_error(void);
 

@@ -80,6 +80,10 @@ struct tcsc_gpu_plan {
     unsigned* csync = nullptr;
     mutable bool csync_dirty = false;
     int num_cus = 0;
+    // transposed plans (tcsc_gpu_plan_create_transposed*): `cols` zeros, the
+    // bias tcsc_gpu_sgemm_t hands to the launch; null on every other plan
+    float* tbias = nullptr;
+    size_t tbias_bytes = 0;
 };
 
 namespace {
@@ -973,8 +977,8 @@ int tcsc_gpu_plan_get_info(const tcsc_gpu_plan* p, tcsc_gpu_plan_info* info) {
     info->n_neg = p->n_neg;
     info->chunk_k = tcsc::kTK;
     info->n_chunks = p->n_chunks;
-    info->device_bytes = p->bytes + p->ws_bytes + p->mfma_bytes + p->csc_bytes + (p->chain_pos ? p->chain_pos->bytes : 0) +
-                         (p->chain_neg ? p->chain_neg->bytes : 0);
+    info->device_bytes = p->bytes + p->ws_bytes + p->mfma_bytes + p->csc_bytes + p->tbias_bytes +
+                         (p->chain_pos ? p->chain_pos->bytes : 0) + (p->chain_neg ? p->chain_neg->bytes : 0);
     info->order = p->order;
     info->mfma_min_M = p->wt ? p->mfma_min_M : 0;
     return TCSC_OK;
@@ -994,6 +998,7 @@ void tcsc_gpu_plan_destroy(tcsc_gpu_plan* p) {
     if (p->sptr) (void)hipFree(p->sptr);
     if (p->ws) (void)hipFree(p->ws);
     if (p->csync) (void)hipFree(p->csync);
+    if (p->tbias) (void)hipFree(p->tbias);
     free_mfma(p);
     free_csc(p);
     tcsc_gpu_plan_destroy(p->chain_pos);
@@ -1241,6 +1246,250 @@ int tcsc_gpu_dense_sgemm(const float* dX, const float* dW, const float* dB, floa
         }
     }
     HIP_TRY(tcsc::launch_bias_act(dY, M, N, ldy, dB, is_prelu(variant), a, st));
+    return TCSC_OK;
+}
+
+// ---- backward pass -------------------------------------------
+
+// The arguments every transpose entry point shares, checked before any HIP call.
+static int transpose_args_ok(const char* who, int rows, int cols, const int* d_csp, const int* d_csn, int col_begin,
+                             int col_end) {
+    if (rows < 0 || cols < 0 || col_begin < 0 || col_end > cols || col_begin > col_end ||
+        (col_end > col_begin && (!d_csp || !d_csn))) {
+        set_error("%s: bad arguments (rows=%d cols=%d range [%d, %d)%s)", who, rows, cols, col_begin, col_end,
+                  (!d_csp || !d_csn) ? ", NULL col_start" : "");
+        return TCSC_E_ARG;
+    }
+    return TCSC_OK;
+}
+
+// ends = {csp[col_begin], csp[col_end], csn[col_begin], csn[col_end]} (zeros for an empty range)
+static int read_range_ends(const int* d_csp, const int* d_csn, int col_begin, int col_end, int ends[4],
+                           hipStream_t st) {
+    ends[0] = ends[1] = ends[2] = ends[3] = 0;
+    if (col_end <= col_begin) return TCSC_OK;
+    HIP_TRY(hipMemcpyAsync(&ends[0], d_csp + col_begin, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&ends[1], d_csp + col_end, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&ends[2], d_csn + col_begin, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&ends[3], d_csn + col_end, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return TCSC_OK;
+}
+
+// The transpose proper, `ends` already read.  Validates the input range
+// (check_index_device: bit 0 is an error, bit 1 -- a column out of order -- is
+// not: the output does not depend on the order inside an input column), then
+// per sign: histogram, scan, scatter, per-column sort.  Synchronises st.
+static int transpose_index_impl(const char* who, int rows, const int* d_csp, const int* d_csn, const int* d_rip,
+                                const int* d_rin, int col_begin, int col_end, const int ends[4], int* d_t_csp,
+                                int* d_t_csn, int* d_t_rip, int* d_t_rin, hipStream_t st) {
+    const int nc = col_end - col_begin;
+    const int np = ends[1] - ends[0], nn = ends[3] - ends[2];
+    if (nc > 0 && (np < 0 || nn < 0 || ends[0] < 0 || ends[2] < 0)) {
+        set_error("%s: col_start decreases over the column range", who);
+        return TCSC_E_ARG;
+    }
+    if ((np > 0 && (!d_rip || !d_t_rip)) || (nn > 0 && (!d_rin || !d_t_rin))) {
+        set_error("%s: NULL row index array (n_pos=%d n_neg=%d in the range)", who, np, nn);
+        return TCSC_E_ARG;
+    }
+    if (nc == 0 || rows == 0 || np + (long long)nn == 0) {
+        // nothing to move: the offsets are still written, all zero
+        if (nc > 0 && rows == 0 && np + (long long)nn > 0) {
+            set_error("%s: entries in a matrix of 0 rows", who);
+            return TCSC_E_ARG;
+        }
+        HIP_TRY(hipMemsetAsync(d_t_csp, 0, (size_t)(rows + 1) * sizeof(int), st));
+        HIP_TRY(hipMemsetAsync(d_t_csn, 0, (size_t)(rows + 1) * sizeof(int), st));
+        HIP_TRY(hipStreamSynchronize(st));
+        return TCSC_OK;
+    }
+    DevBuf flag, cnt, cursor, unsorted, tmp;
+    HIP_TRY(flag.alloc(sizeof(int)));
+    HIP_TRY(hipMemsetAsync(flag.p, 0, sizeof(int), st));
+    HIP_TRY(tcsc::check_index_device(d_csp, d_rip, col_begin, nc, rows, ends[1], flag.as<int>(), st));
+    HIP_TRY(tcsc::check_index_device(d_csn, d_rin, col_begin, nc, rows, ends[3], flag.as<int>(), st));
+    int hflag = 0;
+    HIP_TRY(hipMemcpyAsync(&hflag, flag.p, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (hflag & 1) {
+        set_error("%s: a col_start range or a row index outside [0, %d)", who, rows);
+        return TCSC_E_ARG;
+    }
+    const int nmax = std::max(np, nn);
+    size_t tb_scan = 0, tb_sort = 0;
+    HIP_TRY(tcsc::plan_scan_tmp_bytes((long long)rows + 1, &tb_scan));
+    HIP_TRY(tcsc::sort_columns_tmp_bytes(nmax, rows, &tb_sort));
+    const size_t tb = std::max(tb_scan, tb_sort);
+    HIP_TRY(cnt.alloc((size_t)(rows + 1) * sizeof(int)));
+    HIP_TRY(cursor.alloc((size_t)(rows + 1) * sizeof(int)));
+    HIP_TRY(unsorted.alloc((size_t)nmax * sizeof(int)));
+    HIP_TRY(tmp.alloc(tb));
+    HIP_TRY(tcsc::transpose_sign(d_csp, d_rip, col_begin, nc, rows, ends[0], np, cnt.as<int>(), cursor.as<int>(),
+                                 unsorted.as<int>(), tmp.p, tb, d_t_csp, d_t_rip, st));
+    HIP_TRY(tcsc::transpose_sign(d_csn, d_rin, col_begin, nc, rows, ends[2], nn, cnt.as<int>(), cursor.as<int>(),
+                                 unsorted.as<int>(), tmp.p, tb, d_t_csn, d_t_rin, st));
+    HIP_TRY(hipStreamSynchronize(st));  // the scratch is freed on return
+    return TCSC_OK;
+}
+
+int tcsc_gpu_transpose_index(int rows, int cols, const int* d_csp, const int* d_csn, const int* d_rip,
+                             const int* d_rin, int col_begin, int col_end, int* d_t_csp, int* d_t_csn, int* d_t_rip,
+                             int* d_t_rin, void* stream) {
+    const int rc = transpose_args_ok("tcsc_gpu_transpose_index", rows, cols, d_csp, d_csn, col_begin, col_end);
+    if (rc != TCSC_OK) return rc;
+    if (!d_t_csp || !d_t_csn) {
+        set_error("tcsc_gpu_transpose_index: NULL output col_start array");
+        return TCSC_E_ARG;
+    }
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    int ends[4];
+    const int re = read_range_ends(d_csp, d_csn, col_begin, col_end, ends, st);
+    if (re != TCSC_OK) return re;
+    return transpose_index_impl("tcsc_gpu_transpose_index", rows, d_csp, d_csn, d_rip, d_rin, col_begin, col_end, ends,
+                                d_t_csp, d_t_csn, d_t_rip, d_t_rin, st);
+}
+
+// The plan of W[:, col_begin:col_end)^T from device arrays of W (the current
+// device is `device`): transposed index arrays in scratch, an ordinary plan
+// built from them, and the plan's zero bias.
+static int plan_create_transposed_impl(const char* who, int rows, const int* d_csp, const int* d_csn,
+                                       const int* d_rip, const int* d_rin, int col_begin, int col_end, int device,
+                                       hipStream_t st, tcsc_gpu_plan** out) {
+    int ends[4];
+    int rc = read_range_ends(d_csp, d_csn, col_begin, col_end, ends, st);
+    if (rc != TCSC_OK) return rc;
+    const int nc = col_end - col_begin;
+    const int np = std::max(ends[1] - ends[0], 0), nn = std::max(ends[3] - ends[2], 0);
+    DevBuf tcsp, tcsn, trip, trin;
+    HIP_TRY(tcsp.alloc((size_t)(rows + 1) * sizeof(int)));
+    HIP_TRY(tcsn.alloc((size_t)(rows + 1) * sizeof(int)));
+    HIP_TRY(trip.alloc((size_t)np * sizeof(int)));
+    HIP_TRY(trin.alloc((size_t)nn * sizeof(int)));
+    rc = transpose_index_impl(who, rows, d_csp, d_csn, d_rip, d_rin, col_begin, col_end, ends, tcsp.as<int>(),
+                              tcsn.as<int>(), trip.as<int>(), trin.as<int>(), st);
+    if (rc != TCSC_OK) return rc;
+    // W^T of the range: nc rows, `rows` columns, every column in order
+    rc = build_plan_ordered(nc, 0, rows, np, nn, tcsp.as<int>(), tcsn.as<int>(), trip.as<int>(), trin.as<int>(),
+                            device, st, current_order(), out);
+    if (rc != TCSC_OK) return rc;
+    std::unique_ptr<tcsc_gpu_plan, PlanDeleter> plan(*out);
+    *out = nullptr;
+    const size_t bb = std::max<size_t>((size_t)rows * sizeof(float), 4);
+    HIP_TRY(hipMalloc(&plan->tbias, bb));
+    plan->tbias_bytes = bb;
+    HIP_TRY(hipMemsetAsync(plan->tbias, 0, bb, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    *out = plan.release();
+    return TCSC_OK;
+}
+
+int tcsc_gpu_plan_create_transposed_device(int rows, int cols, const int* d_csp, const int* d_csn, const int* d_rip,
+                                           const int* d_rin, int col_begin, int col_end, int device, void* stream,
+                                           tcsc_gpu_plan** out) {
+    const char* who = "tcsc_gpu_plan_create_transposed_device";
+    const int rc = transpose_args_ok(who, rows, cols, d_csp, d_csn, col_begin, col_end);
+    if (rc != TCSC_OK) return rc;
+    if (!out) {
+        set_error("%s: NULL out", who);
+        return TCSC_E_ARG;
+    }
+    *out = nullptr;
+    DeviceGuard dg(device);
+    if (!dg.ok()) {
+        set_error("%s: cannot select device %d", who, device);
+        return TCSC_E_NODEV;
+    }
+    return plan_create_transposed_impl(who, rows, d_csp, d_csn, d_rip, d_rin, col_begin, col_end, device,
+                                       static_cast<hipStream_t>(stream), out);
+}
+
+int tcsc_gpu_plan_create_transposed(const tcsc_t* W, int col_begin, int col_end, int device, void* stream,
+                                    tcsc_gpu_plan** out) {
+    const char* who = "tcsc_gpu_plan_create_transposed";
+    if (!W || !out || col_begin < 0 || col_end > W->cols || col_begin > col_end || W->rows < 0) {
+        set_error("%s: bad arguments", who);
+        return TCSC_E_ARG;
+    }
+    *out = nullptr;
+    const int nc = col_end - col_begin;
+    // the host check of tcsc_gpu_plan_create; the sorted copies are not needed
+    // (the transpose does not depend on the order inside an input column)
+    std::vector<int> unused;
+    int rc = check_index_host(W->col_start_pos, W->row_index_pos, col_begin, col_end, W->rows, W->n_elem_pos, "pos",
+                              unused);
+    if (rc == TCSC_OK)
+        rc = check_index_host(W->col_start_neg, W->row_index_neg, col_begin, col_end, W->rows, W->n_elem_neg, "neg",
+                              unused);
+    if (rc != TCSC_OK) return rc;
+    unused = std::vector<int>();
+    DeviceGuard dg(device);
+    if (!dg.ok()) {
+        set_error("%s: cannot select device %d", who, device);
+        return TCSC_E_NODEV;
+    }
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int p0 = W->col_start_pos[col_begin], p1 = W->col_start_pos[col_end];
+    const int q0 = W->col_start_neg[col_begin], q1 = W->col_start_neg[col_end];
+    // column slice, rebased to 0 (as tcsc_gpu_plan_create uploads it)
+    std::vector<int> csp(nc + 1), csn(nc + 1);
+    for (int j = 0; j <= nc; ++j) {
+        csp[j] = W->col_start_pos[col_begin + j] - p0;
+        csn[j] = W->col_start_neg[col_begin + j] - q0;
+    }
+    DevBuf dcsp, dcsn, drip, drin;
+    HIP_TRY(dcsp.alloc((nc + 1) * sizeof(int)));
+    HIP_TRY(dcsn.alloc((nc + 1) * sizeof(int)));
+    HIP_TRY(drip.alloc((size_t)(p1 - p0) * sizeof(int)));
+    HIP_TRY(drin.alloc((size_t)(q1 - q0) * sizeof(int)));
+    HIP_TRY(hipMemcpyAsync(dcsp.p, csp.data(), (nc + 1) * sizeof(int), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(dcsn.p, csn.data(), (nc + 1) * sizeof(int), hipMemcpyHostToDevice, st));
+    if (p1 > p0)
+        HIP_TRY(hipMemcpyAsync(drip.p, W->row_index_pos + p0, (size_t)(p1 - p0) * sizeof(int), hipMemcpyHostToDevice,
+                               st));
+    if (q1 > q0)
+        HIP_TRY(hipMemcpyAsync(drin.p, W->row_index_neg + q0, (size_t)(q1 - q0) * sizeof(int), hipMemcpyHostToDevice,
+                               st));
+    HIP_TRY(hipStreamSynchronize(st));  // csp / csn are pageable host vectors
+    return plan_create_transposed_impl(who, W->rows, dcsp.as<int>(), dcsn.as<int>(), drip.as<int>(), drin.as<int>(), 0,
+                                       nc, device, st, out);
+}
+
+int tcsc_gpu_sgemm_t(const tcsc_gpu_plan* tplan, const float* dG, float* dDX, int M, int ldx, void* stream) {
+    if (!tplan) {
+        set_error("tcsc_gpu_sgemm_t: NULL plan");
+        return TCSC_E_ARG;
+    }
+    if (!tplan->tbias) {
+        set_error("tcsc_gpu_sgemm_t: not a transposed plan (tcsc_gpu_plan_create_transposed*)");
+        return TCSC_E_ARG;
+    }
+    if (M < 0 || ldx < tplan->cols || ((long long)M * tplan->cols > 0 && (!dDX || (!dG && tplan->rows > 0)))) {
+        set_error("tcsc_gpu_sgemm_t: bad arguments (M=%d ldx=%d < K=%d, or a NULL device pointer)", M, ldx,
+                  tplan->cols);
+        return TCSC_E_ARG;
+    }
+    return tcsc_gpu_sgemm(tplan, dG, tplan->tbias, dDX, M, ldx, TCSC_VARIANT_SPARSE_GEMM, 0.0f, stream);
+}
+
+int tcsc_gpu_prelu_backward(const float* dG, int ldg, const float* dY, int ldy, float a, float* dDZ, int lddz,
+                            float* dDB, int M, int N, void* stream) {
+    if (M < 0 || N < 0 || ldg < N || (dY && ldy < N) || (dDZ && lddz < N)) {
+        set_error("tcsc_gpu_prelu_backward: bad arguments (M=%d N=%d ldg=%d ldy=%d lddz=%d)", M, N, ldg, ldy, lddz);
+        return TCSC_E_ARG;
+    }
+    if (!dG && (long long)M * N > 0) {
+        set_error("tcsc_gpu_prelu_backward: NULL G");
+        return TCSC_E_ARG;
+    }
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (N == 0) return TCSC_OK;
+    if (M == 0) {  // the sum over no rows
+        if (dDB) HIP_TRY(hipMemsetAsync(dDB, 0, (size_t)N * sizeof(float), st));
+        return TCSC_OK;
+    }
+    if (!dDZ && !dDB) return TCSC_OK;
+    HIP_TRY(tcsc::launch_prelu_bwd(dG, ldg, dY, ldy, a, dDZ, lddz, dDB, M, N, st));
     return TCSC_OK;
 }
 

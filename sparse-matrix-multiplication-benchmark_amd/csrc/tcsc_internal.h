@@ -345,6 +345,22 @@ hipError_t mfma_fixup(const uint16_t* x3, int M, int K, int ldk, const int* cq, 
                       const float* B, float* Y, int ldy, bool bias_first, bool prelu, float a, const int* flags,
                       hipStream_t st);
 
+// ---- backward pass (tcsc_backward.hip) ------------------------
+// One sign of the index transpose: the n entries ri[e0, e0 + n) of columns
+// [col_begin, col_begin + ncols) of a matrix with `rows` rows (cs absolute,
+// checked by check_index_device) -> t_cs (rows + 1 offsets from 0) and t_ri
+// (n column indices relative to col_begin, ascending inside every output
+// column).  Scratch: cnt and cursor (rows + 1 ints each), unsorted (n ints),
+// tmp (enough for exclusive_scan_i32 of rows + 1 and sort_columns of n keys in
+// `rows` segments).
+hipError_t transpose_sign(const int* cs, const int* ri, int col_begin, int ncols, int rows, int e0, int n, int* cnt,
+                          int* cursor, int* unsorted, void* tmp, size_t tmp_bytes, int* t_cs, int* t_ri,
+                          hipStream_t st);
+// k_prelu_bwd: DZ[m, j] = Y[m, j] < 0 ? a * G[m, j] : G[m, j] (Y null: G) and
+// DB[j] = sum_m DZ[m, j] in a fixed order; DZ may be G or null, DB may be null
+hipError_t launch_prelu_bwd(const float* G, int ldg, const float* Y, int ldy, float a, float* DZ, int lddz, float* DB,
+                            int M, int N, hipStream_t st);
+
 // Error channel shared by every entry point of the library (tcsc_api.cpp):
 // the message behind tcsc_gpu_last_error(), and the host API's policy
 // (stderr + abort unless TCSC_ON_ERROR=continue).

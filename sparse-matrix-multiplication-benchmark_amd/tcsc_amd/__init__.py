@@ -45,7 +45,8 @@ EXPORTED_SYMBOLS = (
     "tcsc_gpu_sgemm_prepared", "tcsc_gpu_from_dense", "tcsc_gpu_dense_sgemm", "tcsc_gpu_last_error",
     "tcsc_gpu_cache_clear", "tcsc_gpu_num_shards", "tcsc_gpu_set_num_shards", "tcsc_gpu_set_order",
     "tcsc_gpu_get_order", "tcsc_gpu_launch_info", "tcsc_gpu_launch_combine", "tcsc_gpu_build_flags",
-    "tcsc_gpu_plan_workspace",
+    "tcsc_gpu_plan_workspace", "tcsc_gpu_transpose_index", "tcsc_gpu_plan_create_transposed",
+    "tcsc_gpu_plan_create_transposed_device", "tcsc_gpu_sgemm_t", "tcsc_gpu_prelu_backward",
     # include/sparse/bcsr.h
     "bcsr_from_dense", "bcsr_sgemm_basic", "bcsr_sgemm_prelu_basic", "bcsr_sgemm_avx", "bcsr_sgemm_prelu_avx",
     "bcsr_sgemm_avx2", "bcsr_free",
@@ -147,6 +148,11 @@ def lib():
     L.tcsc_gpu_sgemm_prepared.argtypes = [vp, vp, vp, i, i, i, f, vp]
     L.tcsc_gpu_from_dense.argtypes = [vp, i, i, vp, vp, vp, vp, C.POINTER(i), C.POINTER(i), vp]
     L.tcsc_gpu_dense_sgemm.argtypes = [vp, vp, vp, vp, i, i, i, i, i, f, vp]
+    L.tcsc_gpu_transpose_index.argtypes = [i, i, vp, vp, vp, vp, i, i, vp, vp, vp, vp, vp]
+    L.tcsc_gpu_plan_create_transposed.argtypes = [P, i, i, i, vp, C.POINTER(vp)]
+    L.tcsc_gpu_plan_create_transposed_device.argtypes = [i, i, vp, vp, vp, vp, i, i, i, vp, C.POINTER(vp)]
+    L.tcsc_gpu_sgemm_t.argtypes = [vp, vp, vp, i, i, vp]
+    L.tcsc_gpu_prelu_backward.argtypes = [vp, i, vp, i, f, vp, i, vp, i, i, vp]
     L.tcsc_gpu_num_shards.restype = i
     L.tcsc_gpu_set_num_shards.argtypes = [i]
     L.tcsc_gpu_set_num_shards.restype = None
@@ -451,6 +457,35 @@ class Plan:
         self.handle = h
         return self
 
+    @classmethod
+    def transposed(cls, W: TcscMatrix, col_begin: int = 0, col_end: int | None = None, device: int = 0,
+                   stream: int = 0) -> "Plan":
+        """The plan of W[:, col_begin:col_end]^T (tcsc_gpu_plan_create_transposed): an ordinary
+        plan of col_end - col_begin rows and W.rows columns, for :meth:`sgemm_t`."""
+        if not getattr(W, "ptr", None):
+            raise TcscError("W is freed or not a TcscMatrix")
+        self = cls.__new__(cls)
+        col_end = W.cols if col_end is None else col_end
+        h = C.c_void_p()
+        _check(lib().tcsc_gpu_plan_create_transposed(W.ptr, col_begin, col_end, device, C.c_void_p(stream),
+                                                     C.byref(h)), "tcsc_gpu_plan_create_transposed")
+        self.handle = h
+        return self
+
+    @classmethod
+    def transposed_from_device(cls, rows, cols, csp, csn, rip, rin, col_begin=0, col_end=None, device=0,
+                               stream=0) -> "Plan":
+        """Same from W's TCSC arrays on the device (tcsc_gpu_plan_create_transposed_device)."""
+        self = cls.__new__(cls)
+        col_end = cols if col_end is None else col_end
+        h = C.c_void_p()
+        _check(lib().tcsc_gpu_plan_create_transposed_device(rows, cols, C.c_void_p(_ptr(csp)), C.c_void_p(_ptr(csn)),
+                                                            C.c_void_p(_ptr(rip)), C.c_void_p(_ptr(rin)), col_begin,
+                                                            col_end, device, C.c_void_p(stream), C.byref(h)),
+               "tcsc_gpu_plan_create_transposed_device")
+        self.handle = h
+        return self
+
     def info(self) -> dict:
         inf = plan_info_t()
         _check(lib().tcsc_gpu_plan_get_info(self.handle, C.byref(inf)), "tcsc_gpu_plan_get_info")
@@ -501,6 +536,12 @@ class Plan:
                                     int(M), int(ldy), VARIANT_ID[variant], float(a), C.c_void_p(stream)),
                "tcsc_gpu_sgemm")
 
+    def sgemm_t(self, G, DX, M: int, ldx: int, stream: int = 0) -> None:
+        """dX (M x K, pitch ldx) = G (M x plan rows, contiguous) . W[:, range]^T on a transposed
+        plan (tcsc_gpu_sgemm_t); TcscError on a plan that :meth:`transposed` did not make."""
+        _check(lib().tcsc_gpu_sgemm_t(self.handle, C.c_void_p(_ptr(G)), C.c_void_p(_ptr(DX)), int(M), int(ldx),
+                                      C.c_void_p(stream)), "tcsc_gpu_sgemm_t")
+
     def prepare_x(self, X, M: int, stream: int = 0) -> None:
         """First half of sgemm: stage X^T in the plan's workspace (k_transpose)."""
         _check(lib().tcsc_gpu_prepare_x(self.handle, C.c_void_p(_ptr(X)), int(M), C.c_void_p(stream)),
@@ -541,3 +582,26 @@ def gpu_from_dense(d_dense, rows: int, cols: int, d_csp, d_csn, d_rip=None, d_ri
                                      C.c_void_p(_ptr(d_csn)), C.c_void_p(_ptr(d_rip)), C.c_void_p(_ptr(d_rin)),
                                      C.byref(p), C.byref(q), C.c_void_p(stream)), "tcsc_gpu_from_dense")
     return p.value, q.value
+
+
+def gpu_transpose_index(rows: int, cols: int, d_csp, d_csn, d_rip, d_rin, col_begin: int, col_end: int, d_t_csp,
+                        d_t_csn, d_t_rip, d_t_rin, stream: int = 0) -> None:
+    """Device transpose of the index structure (tcsc_gpu_transpose_index): the TCSC arrays of W (rows x cols) ->
+    those of W[:, col_begin:col_end]^T; d_t_csp / d_t_csn hold rows + 1 ints, d_t_rip / d_t_rin the range's
+    n_pos / n_neg ints.  Synchronises the stream."""
+    _check(lib().tcsc_gpu_transpose_index(int(rows), int(cols), C.c_void_p(_ptr(d_csp)), C.c_void_p(_ptr(d_csn)),
+                                          C.c_void_p(_ptr(d_rip)), C.c_void_p(_ptr(d_rin)), int(col_begin),
+                                          int(col_end), C.c_void_p(_ptr(d_t_csp)), C.c_void_p(_ptr(d_t_csn)),
+                                          C.c_void_p(_ptr(d_t_rip)), C.c_void_p(_ptr(d_t_rin)), C.c_void_p(stream)),
+           "tcsc_gpu_transpose_index")
+
+
+def prelu_backward(G, Y, a: float, DZ, DB, M: int, N: int, ldg: int | None = None, ldy: int | None = None,
+                   lddz: int | None = None, stream: int = 0) -> None:
+    """dZ = where(Y < 0, a * G, G) and db = dZ.sum(0) on the device (tcsc_gpu_prelu_backward).  Y None: the
+    identity activation; DZ may be G (in place) or None; DB may be None.  Pitches default to N."""
+    N = int(N)
+    _check(lib().tcsc_gpu_prelu_backward(C.c_void_p(_ptr(G)), N if ldg is None else int(ldg), C.c_void_p(_ptr(Y)),
+                                         N if ldy is None else int(ldy), float(a), C.c_void_p(_ptr(DZ)),
+                                         N if lddz is None else int(lddz), C.c_void_p(_ptr(DB)), int(M), N,
+                                         C.c_void_p(stream)), "tcsc_gpu_prelu_backward")

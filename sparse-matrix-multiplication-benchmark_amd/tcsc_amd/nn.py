@@ -1,0 +1,152 @@
+"""torch autograd layer over the TCSC device API.
+
+``TernaryLinear`` computes ``y = act(x . W + b)`` for a frozen ternary ``W``
+(K x N) held as a :class:`tcsc_amd.Plan`, and its backward: ``dZ`` and ``db`` by
+``tcsc_gpu_prelu_backward``, ``dX = dZ . W^T`` by ``tcsc_gpu_sgemm_t`` on the
+transposed plan.  Every launch goes on torch's current stream.
+
+torch is imported lazily, as ``tcsc_amd.lib()`` does: importing this module
+needs neither torch nor a GPU; the first access to ``TernaryLinear`` does the
+import and defines the classes (a ``torch.nn.Module`` subclass needs torch to
+exist).
+"""
+from __future__ import annotations
+
+import numpy as np
+
+from . import Plan, TcscError, TcscMatrix, prelu_backward
+
+__all__ = ["TernaryLinear"]
+
+_classes = None
+
+
+def _define():
+    import torch
+
+    def _stream(device) -> int:
+        return torch.cuda.current_stream(device).cuda_stream
+
+    class _TernaryLinearFn(torch.autograd.Function):
+        """y = act(x . W + b) on an (M x K) contiguous fp32 x; W and `a` come from the layer."""
+
+        @staticmethod
+        def forward(ctx, x, bias, layer):
+            M, N = x.shape[0], layer.out_features
+            y = torch.empty((M, N), dtype=torch.float32, device=x.device)
+            if layer.a is None:
+                layer.plan.sgemm(x, bias, y, M, N, "basic", 0.0, _stream(x.device))
+            else:
+                layer.plan.sgemm(x, bias, y, M, N, "prelu_basic", layer.a, _stream(x.device))
+                ctx.save_for_backward(y)  # the mask is the forward's own predicate on its output
+            ctx.layer = layer
+            return y
+
+        @staticmethod
+        def backward(ctx, g):
+            layer = ctx.layer
+            need_dx, need_db = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+            if not (need_dx or need_db):
+                return None, None, None
+            if g.dtype != torch.float32 or not g.is_cuda:
+                raise TcscError(f"TernaryLinear backward: expected an fp32 CUDA gradient, got {g.dtype} on {g.device}")
+            g = g.contiguous()
+            M, N, K = g.shape[0], layer.out_features, layer.in_features
+            stream = _stream(g.device)
+            y = ctx.saved_tensors[0] if layer.a is not None else None
+            masked = y is not None and need_dx  # identity activation: dZ is g itself
+            dz = torch.empty_like(g) if masked else g
+            db = torch.empty(N, dtype=torch.float32, device=g.device) if need_db else None
+            if masked or need_db:
+                prelu_backward(g, y, layer.a or 0.0, dz if masked else None, db, M, N, stream=stream)
+            dx = None
+            if need_dx:
+                dx = torch.empty((M, K), dtype=torch.float32, device=g.device)
+                layer._transposed().sgemm_t(dz, dx, M, K, stream)
+            return dx, db, None
+
+    class TernaryLinear(torch.nn.Module):
+        """``y = act(x . W + bias)`` with a frozen ternary ``W`` (K x N).
+
+        W:    a dense K x N tensor or array with entries in {-1, 0, +1}, or a
+              :class:`tcsc_amd.TcscMatrix` (kept by reference; do not free it
+              while the layer lives).  W is not a parameter and has no grad.
+        bias: N fp32 values (tensor or array) for the ``nn.Parameter``; default zeros.
+        a:    the PReLU slope ``act(v) = v < 0 ? a * v : v``, a fixed float as in
+              the reference, or None for the identity activation.
+        device: the GPU ordinal the plans live on.
+
+        ``forward`` takes fp32 CUDA tensors of shape (..., K) on that device and
+        returns (..., N).  The transposed plan for ``dX`` is built on the first
+        backward that needs it, or by :meth:`reserve`.  One module must not be
+        used from several streams at once (the plans own their workspaces).
+        """
+
+        def __init__(self, W, bias=None, a: float | None = None, device: int = 0):
+            super().__init__()
+            if isinstance(W, TcscMatrix):
+                if not W.ptr:
+                    raise TcscError("TernaryLinear: W is a freed TcscMatrix")
+                self._W = W
+            else:
+                Wd = W.detach().cpu().numpy() if torch.is_tensor(W) else np.asarray(W)
+                if Wd.ndim != 2:
+                    raise TcscError(f"TernaryLinear: W must be 2-D (K x N), got shape {Wd.shape}")
+                Wd = np.ascontiguousarray(Wd, dtype=np.float32)
+                if not np.isin(Wd, (-1.0, 0.0, 1.0)).all():
+                    raise TcscError("TernaryLinear: W must hold only -1, 0 and +1")
+                self._W = TcscMatrix.from_dense(Wd)
+            self.in_features, self.out_features = self._W.rows, self._W.cols
+            self.a = None if a is None else float(a)
+            self.device_index = int(device)
+            dev = torch.device("cuda", self.device_index)
+            if bias is None:
+                b = torch.zeros(self.out_features, dtype=torch.float32, device=dev)
+            else:
+                b = torch.as_tensor(bias).detach().to(device=dev, dtype=torch.float32).reshape(-1).clone()
+                if b.numel() != self.out_features:
+                    raise TcscError(f"TernaryLinear: bias has {b.numel()} elements, W has N={self.out_features} columns")
+            self.bias = torch.nn.Parameter(b)
+            self.plan = Plan(self._W, 0, self.out_features, self.device_index, _stream(dev))
+            self.transposed_plan = None  # built by the first backward that needs dX, or by reserve()
+
+        def _transposed(self) -> Plan:
+            if self.transposed_plan is None:
+                dev = torch.device("cuda", self.device_index)
+                self.transposed_plan = Plan.transposed(self._W, 0, self.out_features, self.device_index, _stream(dev))
+            return self.transposed_plan
+
+        def reserve(self, max_rows: int) -> None:
+            """Workspaces of both plans for up to max_rows rows (the flattened leading
+            dimensions), building the transposed plan if it is absent: afterwards a
+            forward + backward step allocates nothing in the library and can be captured."""
+            self.plan.reserve(max_rows)
+            self._transposed().reserve(max_rows)
+
+        def forward(self, x):
+            if not torch.is_tensor(x) or x.dtype != torch.float32 or not x.is_cuda:
+                raise TcscError("TernaryLinear: x must be an fp32 CUDA tensor")
+            if x.device.index != self.device_index or self.bias.device != x.device:
+                raise TcscError(f"TernaryLinear: x on {x.device}, bias on {self.bias.device}, plans on cuda:"
+                                f"{self.device_index}")
+            if x.dim() < 1 or x.shape[-1] != self.in_features:
+                raise TcscError(f"TernaryLinear: x has shape {tuple(x.shape)}, expected (..., {self.in_features})")
+            if self.bias.dtype != torch.float32 or not self.bias.is_contiguous():
+                raise TcscError("TernaryLinear: bias must stay a contiguous fp32 tensor")
+            lead = x.shape[:-1]
+            y = _TernaryLinearFn.apply(x.reshape(-1, self.in_features).contiguous(), self.bias, self)
+            return y.reshape(*lead, self.out_features)
+
+        def extra_repr(self) -> str:
+            return f"in_features={self.in_features}, out_features={self.out_features}, nnz={self._W.nnz}, a={self.a}"
+
+    return {"TernaryLinear": TernaryLinear}
+
+
+def __getattr__(name):
+    global _classes
+    if name in __all__:
+        if _classes is None:
+            _classes = _define()
+        return _classes[name]
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
