@@ -25,7 +25,9 @@
 // captured graph replays correctly); k_fixup rewrites those rows from the
 // plan's merged per-column CSC copy, +1 and -1 rows in ascending k (+1 first
 // on a tie), then the bias, then the PReLU -- the exact arithmetic of
-// k_stream's fast order (= the reference's dense.c gemm_basic order).
+// k_stream's fast order (= the reference's dense.c gemm_basic order).  It
+// rebuilds x from X3, so a tiny x, whose low bits no bf16 can hold, is stored
+// there as its bits (split3).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -48,15 +50,28 @@ inline int grid_of(long long n, int block) {
 __device__ inline uint32_t f2u(float x) { return __float_as_uint(x); }
 __device__ inline float u2f(uint32_t u) { return __uint_as_float(u); }
 
-// x -> (h, m, l) bf16 bit patterns with h + m + l == x exactly (finite x);
-// a non-finite x goes whole into h (a quiet NaN keeps its sign), m = l = 0.
+// x -> (h, m, l) bf16 bit patterns with h + m + l == x exactly (finite x of
+// magnitude >= 2^-100); a non-finite x goes whole into h (a quiet NaN keeps
+// its sign), m = l = 0.  A nonzero |x| < 2^-100 is stored as its bits, h the
+// high and m the low 16 (l = 0): its remainders fall below bf16's range (x -
+// h is an fp32 denormal from 2^-118 down, and nothing under 2^-133 is a bf16
+// at all), so three truncations would lose them.  Its row is flagged, the
+// GEMM's sums for it are discarded, and exact_out() reassembles the bits (it
+// tells the two forms apart by h's exponent: below 2^-100 or not).
 // Returns whether the row needs the exact fixup.
+constexpr uint32_t kTinyExp = 27;  // biased exponent of 2^-100
 __device__ inline bool split3(float x, uint16_t& h, uint16_t& m, uint16_t& l) {
     const uint32_t u = f2u(x);
     if ((u & 0x7f800000u) == 0x7f800000u) {  // inf or NaN
         const bool nan = (u & 0x007fffffu) != 0;
         h = (uint16_t)(nan ? ((u >> 16) | 0x0040u) : (u >> 16));
         m = l = 0;
+        return true;
+    }
+    if (x != 0.0f && ((u >> 23) & 0xffu) < kTinyExp) {  // 0 < |x| < 2^-100
+        h = (uint16_t)(u >> 16);
+        m = (uint16_t)u;
+        l = 0;
         return true;
     }
     const uint32_t hu = u & 0xffff0000u;
@@ -66,7 +81,7 @@ __device__ inline bool split3(float x, uint16_t& h, uint16_t& m, uint16_t& l) {
     h = (uint16_t)(hu >> 16);
     m = (uint16_t)(mu >> 16);
     l = (uint16_t)(f2u(s) >> 16);
-    return x != 0.0f && fabsf(x) < 0x1p-100f;
+    return false;
 }
 
 // X (M x K, pitch K) -> X3 (M x ldk bf16): [h | m | l | 0 ...] per row, one
@@ -205,7 +220,7 @@ __global__ void k_merge_csc(const int* __restrict__ cp, const int* __restrict__ 
 }
 
 // Output (row, j) recomputed exactly as k_stream's fast order (see the file
-// comment): x rebuilt from its three parts, the column's merged rows in
+// comment): x rebuilt from its three parts (or its stored bits), the column's merged rows in
 // ascending k, the bias first or last, then the PReLU.
 template <bool BIAS_FIRST, bool PRELU>
 __device__ inline float exact_out(const uint16_t* __restrict__ X3, int K, int ldk, const int* __restrict__ cq,
@@ -213,8 +228,10 @@ __device__ inline float exact_out(const uint16_t* __restrict__ X3, int K, int ld
                                   float a) {
     const uint16_t* x3 = X3 + (size_t)row * ldk;
     auto xk = [&](int k) {
-        return (u2f((uint32_t)x3[x3_index(k, 0)] << 16) + u2f((uint32_t)x3[x3_index(k, 1)] << 16)) +
-               u2f((uint32_t)x3[x3_index(k, 2)] << 16);
+        // all three loads, then a select: no branch in the column walk
+        const uint32_t hb = x3[x3_index(k, 0)], mb = x3[x3_index(k, 1)], lb = x3[x3_index(k, 2)];
+        const float sum = (u2f(hb << 16) + u2f(mb << 16)) + u2f(lb << 16);
+        return (hb & 0x7f80u) < (kTinyExp << 7) ? u2f(hb << 16 | mb) : sum;  // |x| < 2^-100 (or 0): its bits
     };
     float acc = BIAS_FIRST ? Bias[j] : 0.0f;
     const int g = j / kCscGroup, n = 4 * (cq[g + 1] - cq[g]);
