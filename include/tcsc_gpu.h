@@ -220,6 +220,41 @@ int tcsc_gpu_prepare_x(const tcsc_gpu_plan *plan, const float *dX, int M, void *
 int tcsc_gpu_sgemm_prepared(const tcsc_gpu_plan *plan, const float *dB, float *dY, int M, int ldy,
                             int variant, float a, void *stream);
 
+/* tcsc_gpu_sgemm for bf16 activations: the same Y (fp32) from X given as
+ * bf16, with no fp32 copy of X made by the caller.
+ *   dX_bf16 : M x K row-major, contiguous array of bf16 bit patterns
+ *             (uint16_t, the high half of the fp32 value), 2-byte aligned
+ *   dB, dY, ldy, variant, a, stream : exactly as in tcsc_gpu_sgemm
+ * Every bf16 value is an fp32 value and W is exact in bf16, so the numeric
+ * contract is tcsc_gpu_sgemm's on the widened X: bit-exact on integer-valued
+ * inputs, within 2^-20 (|b| + sum |x|) otherwise; on one path and K split the
+ * bits are those of tcsc_gpu_sgemm(X widened to fp32).
+ *   gather : k_transpose_bf16 widens X into the same fp32 X^T; k_stream, the
+ *            reduce and the in-launch combine are the fp32 call's
+ *   small  : k_small_m stages the widened rows (M <= 4)
+ *   MFMA   : k_pack1 (X -> X1, M x 64-k blocks of bf16, and the row flags
+ *            by k_split3's rule: a non-finite x or a nonzero |x| < 2^-100),
+ *            the one-part k_gemm3 -- one sub-step per 64-k block instead of
+ *            three -- and the one-part k_fixup / k_reduce_fix
+ * Same guarantees: asynchronous on `stream`, allocation-free once the
+ * workspace covers M, capturable in a graph, M > 2^22 rows on the gather as
+ * several launches; the same argument checks, answered with TCSC_E_ARG before
+ * any HIP call.  Works on every plan (forward, transposed, reference order --
+ * gather only, as for fp32 -- and column shards).
+ * Workspace: for every M and path no more than tcsc_gpu_plan_workspace reports
+ * for the fp32 call (the gather's is the same; the MFMA path's holds X1, a
+ * third of X3; the small-M path needs none), so tcsc_gpu_plan_reserve(max_M)
+ * covers bf16 launches as it is.
+ * Routing: the fp32 call's cost model with the GEMM term and the K walk
+ * divided by 3; $TCSC_PATH, $TCSC_SLICES, $TCSC_MFMA_WGS and
+ * $TCSC_SMALL_M act as on the fp32 call.  tcsc_gpu_launch_info_bf16 reports
+ * what a bf16 call of M rows runs (as tcsc_gpu_launch_info does for fp32).
+ * Out of scope: a host-pointer version, bf16 Y, bf16 B, and a
+ * prepare_x / sgemm_prepared pair for bf16. */
+int tcsc_gpu_sgemm_bf16(const tcsc_gpu_plan *plan, const void *dX_bf16, const float *dB,
+                        float *dY, int M, int ldy, int variant, float a, void *stream);
+int tcsc_gpu_launch_info_bf16(const tcsc_gpu_plan *plan, int M, int *path, int *slices);
+
 /* Device-side tcsc_from_dense: dense K x N row-major float matrix on the
  * device -> TCSC arrays on the device, bit-exact with the reference builder
  * (tcsc.c:6-66).  Two calls: first with the four output pointers NULL to

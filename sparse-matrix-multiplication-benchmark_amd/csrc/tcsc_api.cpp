@@ -267,6 +267,12 @@ size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 size_t mfma_flags_off(int M, int K) { return align256((size_t)M * tcsc::mfma_ldk(K) * 2); }
 size_t mfma_slabs_off(int M, int K) { return mfma_flags_off(M, K) + align256((size_t)M * sizeof(int)); }
 size_t mfma_ws_bytes(int M, int K, int N) { return mfma_slabs_off(M, K) + tcsc::mfma_slab_bytes(M, N, K); }
+// the same for a bf16 call: X1 (M x mfma_ldw(K) bf16, a third of X3), the
+// flags, the same slabs -- never more than the fp32 call's, so what
+// tcsc_gpu_plan_workspace reports and tcsc_gpu_plan_reserve allocates covers it
+size_t mfma1_flags_off(int M, int K) { return align256((size_t)M * tcsc::mfma_ldw(K) * 2); }
+size_t mfma1_slabs_off(int M, int K) { return mfma1_flags_off(M, K) + align256((size_t)M * sizeof(int)); }
+size_t mfma1_ws_bytes(int M, int K, int N) { return mfma1_slabs_off(M, K) + tcsc::mfma_slab_bytes(M, N, K); }
 
 // Variants 0-4 are the tcsc_sgemm_* family (sparse/tcsc.h); 5 is
 // SparseGEMM.h's sparseGEMM<float> (bias last, no activation).  Bias first
@@ -297,9 +303,26 @@ bool mfma_cheaper(const tcsc_gpu_plan* p, int M) {
     return mfma_us < gather_us;
 }
 
+// The bf16 call's model: the same gather (only its transpose reads less), the
+// GEMM with one part instead of three -- 2 flops per (m, k, n), and a third of
+// the sub-steps in a workgroup's K walk (~8.1 ns per k).  The fixed cost and
+// the reduce are the fp32 call's.  Derived from the fp32 fit, checked against
+// tools/crossover.py --dtype bf16.
+bool mfma_cheaper_bf16(const tcsc_gpu_plan* p, int M) {
+    const double nnz = (double)(p->n_pos + p->n_neg), Kb = (double)tcsc::mfma_ldw(p->rows);
+    const double Mp = (double)(((long long)M + tcsc::kTM - 1) / tcsc::kTM * tcsc::kTM);
+    const double gather_us = 38.0 + Mp * nnz / 23.0e6;
+    const int s = tcsc::mfma_slices(M, p->cols, p->rows);
+    const double walk_us = Kb * (0.0244 / 3.0) / s * (tcsc::mfma_tiles(M, p->cols) * s > 256 ? 1.5 : 1.0);
+    const double reduce_us = s > 1 ? 3.0 + (s + 1.0) * M * p->cols * 4.0 / 4.0e6 : 0.0;
+    const double mfma_us = 10.0 + std::max(2.0 * M * Kb * p->cols / 1.5e9, walk_us) + reduce_us;
+    return mfma_us < gather_us;
+}
+
 // forced (TCSC_PATH=mfma: mfma_min_M 1): every launch; default: by the cost model
-bool use_mfma(const tcsc_gpu_plan* p, int M) {
-    return p->wt && M >= p->mfma_min_M && p->rows > 0 && (p->mfma_min_M == 1 || mfma_cheaper(p, M));
+bool use_mfma(const tcsc_gpu_plan* p, int M, bool bf16 = false) {
+    return p->wt && M >= p->mfma_min_M && p->rows > 0 &&
+           (p->mfma_min_M == 1 || (bf16 ? mfma_cheaper_bf16(p, M) : mfma_cheaper(p, M)));
 }
 
 rocblas_handle rocblas_for_device(int dev) {
@@ -405,8 +428,8 @@ int small_max_m() {
     return std::max(0, std::min(kSmallMaxM, std::atoi(e)));
 }
 
-bool use_small(const tcsc_gpu_plan* p, int M) {
-    return p->crq && p->rows > 0 && M >= 1 && M <= small_max_m() && !use_mfma(p, M) &&
+bool use_small(const tcsc_gpu_plan* p, int M, bool bf16 = false) {
+    return p->crq && p->rows > 0 && M >= 1 && M <= small_max_m() && !use_mfma(p, M, bf16) &&
            tcsc::small_m_fits(M, p->rows);
 }
 
@@ -520,12 +543,27 @@ size_t path_ws_bytes(const tcsc_gpu_plan* p, int M, int path) {
     return 0;
 }
 
-int launch_path(const tcsc_gpu_plan* p, int M) {
-    return use_mfma(p, M) ? TCSC_PATH_MFMA : use_small(p, M) ? TCSC_PATH_SMALL : TCSC_PATH_GATHER;
+// bf16: the path of a tcsc_gpu_sgemm_bf16 call (its own mfma_cheaper)
+int launch_path(const tcsc_gpu_plan* p, int M, bool bf16 = false) {
+    return use_mfma(p, M, bf16) ? TCSC_PATH_MFMA : use_small(p, M, bf16) ? TCSC_PATH_SMALL : TCSC_PATH_GATHER;
 }
 
 // Workspace of the call tcsc_gpu_sgemm makes at this M.
 size_t wanted_workspace(const tcsc_gpu_plan* p, int M) { return path_ws_bytes(p, M, launch_path(p, M)); }
+
+// Workspace of the call tcsc_gpu_sgemm_bf16 makes at this M: the gather's is
+// the fp32 call's (the same fp32 X^T and slabs), the MFMA path's holds X1
+// for X3, the small-M path reads X in place.
+size_t wanted_workspace_bf16(const tcsc_gpu_plan* p, int M) {
+    if (M <= 0 || p->cols == 0) return 0;
+    switch (launch_path(p, M, true)) {
+        case TCSC_PATH_GATHER:
+            return gather_ws_bytes(p, M);
+        case TCSC_PATH_MFMA:
+            return mfma1_ws_bytes(M, p->rows, p->cols);
+    }
+    return 0;
+}
 
 // tcsc_gpu_plan_reserve(max_M): the largest need of any M <= max_M on any path
 // the plan has.  Neither need grows with M: both cost models split K more at
@@ -698,6 +736,30 @@ int sgemm_mfma(const tcsc_gpu_plan* p, const float* dX, const float* dB, float* 
     return TCSC_OK;
 }
 
+// The same for bf16 X: k_pack1 (X -> X1 + row flags, k_split3's rule), the
+// one-part k_gemm3, the one-part k_fixup.
+int sgemm_mfma_bf16(const tcsc_gpu_plan* p, const uint16_t* dX, const float* dB, float* dY, int M, int ldy,
+                    int variant, float a, void* stream, float* ws, size_t ws_bytes) {
+    const int K = p->rows, N = p->cols, ldw = tcsc::mfma_ldw(K);
+    const size_t need = mfma1_ws_bytes(M, K, N);
+    if (!ws || ws_bytes < need) {
+        set_error("tcsc_gpu_sgemm_bf16: workspace of %zu bytes < %zu needed for M=%d", ws ? ws_bytes : (size_t)0, need,
+                  M);
+        return TCSC_E_ARG;
+    }
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    uint16_t* x1 = reinterpret_cast<uint16_t*>(ws);
+    int* flags = reinterpret_cast<int*>(reinterpret_cast<char*>(ws) + mfma1_flags_off(M, K));
+    float* slabs = reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + mfma1_slabs_off(M, K));
+    HIP_TRY(tcsc::mfma_pack_x(dX, M, K, x1, ldw, flags, st));
+    const bool prelu = is_prelu(variant);
+    HIP_TRY(tcsc::mfma_gemm1(x1, ldw, p->wt, ldw, K, M, N, dB, dY, ldy, prelu, a, slabs,
+                             ws_bytes - mfma1_slabs_off(M, K), flags, p->ccq, p->crq, st));
+    if (tcsc::mfma_slices(M, N, K) <= 1)
+        HIP_TRY(tcsc::mfma_fixup1(x1, M, K, ldw, p->ccq, p->crq, N, dB, dY, ldy, false, prelu, a, flags, st));
+    return TCSC_OK;
+}
+
 // How one sgemm_ws call is routed.  In: path < 0 lets the call choose by its
 // own M (launch_path), TCSC_PATH_GATHER pins the gather -- a caller that cuts
 // one job into several launches (run_bands, the 2^22-row pieces below) decides
@@ -710,24 +772,34 @@ struct Route {
     int slices = 0;
 };
 
-int sgemm_ws(const tcsc_gpu_plan* p, const float* dX, const float* dB, float* dY, int M, int ldy, int variant,
-             float a, void* stream, float* ws, size_t ws_bytes, int stage = 0, Route* route = nullptr) {
+// bf16: dX_ is M x K bf16 bit patterns (tcsc_gpu_sgemm_bf16; stage 0 only), else fp32.
+int sgemm_ws(const tcsc_gpu_plan* p, const void* dX_, const float* dB, float* dY, int M, int ldy, int variant,
+             float a, void* stream, float* ws, size_t ws_bytes, int stage = 0, Route* route = nullptr,
+             bool bf16 = false) {
+    const float* dX = bf16 ? nullptr : static_cast<const float*>(dX_);
+    const uint16_t* dXb = bf16 ? static_cast<const uint16_t*>(dX_) : nullptr;
+    const char* who = bf16 ? "tcsc_gpu_sgemm_bf16" : "tcsc_gpu_sgemm";
+    if (bf16 && stage != 0) {
+        set_error("tcsc_gpu_sgemm_bf16: no staged form");
+        return TCSC_E_ARG;
+    }
     if (!p || M < 0 || (stage != 1 && (ldy < p->cols || !valid_variant(variant)))) {
-        set_error("tcsc_gpu_sgemm: bad arguments (M=%d ldy=%d variant=%d)", M, ldy, variant);
+        set_error("%s: bad arguments (M=%d ldy=%d variant=%d)", who, M, ldy, variant);
         return TCSC_E_ARG;
     }
     if (M == 0 || p->cols == 0) return TCSC_OK;
-    if ((stage != 1 && (!dY || !dB)) || (stage != 2 && !dX && p->rows > 0)) {
-        set_error("tcsc_gpu_sgemm: NULL device pointer");
+    if ((stage != 1 && (!dY || !dB)) || (stage != 2 && !dX_ && p->rows > 0)) {
+        set_error("%s: NULL device pointer", who);
         return TCSC_E_ARG;
     }
     Route own;
     if (!route) route = &own;
     const int force_slices = route->slices;
-    if (route->path != TCSC_PATH_GATHER) route->path = launch_path(p, M);
+    if (route->path != TCSC_PATH_GATHER) route->path = launch_path(p, M, bf16);
     route->slices = 1;
     if (route->path == TCSC_PATH_MFMA) {
         route->slices = tcsc::mfma_slices(M, p->cols, p->rows);
+        if (bf16) return sgemm_mfma_bf16(p, dXb, dB, dY, M, ldy, variant, a, stream, ws, ws_bytes);
         return sgemm_mfma(p, dX, dB, dY, M, ldy, variant, a, stream, ws, ws_bytes, stage);
     }
     if (route->path == TCSC_PATH_SMALL) {
@@ -741,6 +813,11 @@ int sgemm_ws(const tcsc_gpu_plan* p, const float* dX, const float* dB, float* dY
         }
         if (stage == 1) {
             HIP_TRY(hipMemcpyAsync(ws, dX, xb, hipMemcpyDeviceToDevice, st));
+            return TCSC_OK;
+        }
+        if (bf16) {
+            HIP_TRY(tcsc::launch_small_m_bf16(dXb, M, p->rows, p->ccq, p->crq, p->cols, dB, dY, ldy, false,
+                                              is_prelu(variant), a, st));
             return TCSC_OK;
         }
         HIP_TRY(tcsc::launch_small_m(stage == 2 ? ws : dX, M, p->rows, p->ccq, p->crq, p->cols, dB, dY, ldy, false,
@@ -765,8 +842,10 @@ int sgemm_ws(const tcsc_gpu_plan* p, const float* dX, const float* dB, float* dY
         for (int r0 = 0; r0 < M; r0 += kMaxLaunchRows) {
             const int r = std::min(kMaxLaunchRows, M - r0);
             Route piece{TCSC_PATH_GATHER, force_slices > 0 ? force_slices : 1};  // a short tail stays on the gather too
-            const int rc = sgemm_ws(p, dX + (size_t)r0 * p->rows, dB, dY + (size_t)r0 * ldy, r, ldy, variant, a,
-                                    stream, ws, ws_bytes, 0, &piece);
+            const void* xr = bf16 ? static_cast<const void*>(dXb + (size_t)r0 * p->rows)
+                                  : static_cast<const void*>(dX + (size_t)r0 * p->rows);
+            const int rc = sgemm_ws(p, xr, dB, dY + (size_t)r0 * ldy, r, ldy, variant, a, stream, ws, ws_bytes, 0,
+                                    &piece, bf16);
             if (rc != TCSC_OK) return rc;
             route->slices = piece.slices;
         }
@@ -774,11 +853,12 @@ int sgemm_ws(const tcsc_gpu_plan* p, const float* dX, const float* dB, float* dY
     }
     const size_t xtb = tcsc::xt_bytes(M, p->rows);
     if (p->rows > 0 && (!ws || ws_bytes < xtb)) {
-        set_error("tcsc_gpu_sgemm: workspace of %zu bytes < %zu needed for M=%d", ws ? ws_bytes : (size_t)0, xtb, M);
+        set_error("%s: workspace of %zu bytes < %zu needed for M=%d", who, ws ? ws_bytes : (size_t)0, xtb, M);
         return TCSC_E_ARG;
     }
     tcsc::GemmArgs g;
     g.X = dX;
+    g.Xb = dXb;
     g.XT = p->rows > 0 ? ws : nullptr;
     g.M = M;
     g.K = p->rows;
@@ -1044,18 +1124,18 @@ int tcsc_gpu_plan_workspace(const tcsc_gpu_plan* p, int M, int path, size_t* nee
     return TCSC_OK;
 }
 
-int tcsc_gpu_launch_info(const tcsc_gpu_plan* p, int M, int* path, int* slices) {
+static int launch_info_impl(const char* who, const tcsc_gpu_plan* p, int M, int* path, int* slices, bool bf16) {
     if (!p || M < 0 || !path || !slices) {
-        set_error("tcsc_gpu_launch_info: bad arguments");
+        set_error("%s: bad arguments", who);
         return TCSC_E_ARG;
     }
     *slices = 1;
-    if (use_mfma(p, M)) {
+    if (use_mfma(p, M, bf16)) {
         *path = TCSC_PATH_MFMA;
         *slices = tcsc::mfma_slices(M, p->cols, p->rows);
         return TCSC_OK;
     }
-    if (use_small(p, M)) {
+    if (use_small(p, M, bf16)) {
         *path = TCSC_PATH_SMALL;
         return TCSC_OK;
     }
@@ -1067,6 +1147,14 @@ int tcsc_gpu_launch_info(const tcsc_gpu_plan* p, int M, int* path, int* slices) 
                                 : tcsc::choose_slices(rows, p->cols, p->rows, p->n_pos + p->n_neg, p->n_groups,
                                                       p->ws_bytes > xtb ? p->ws_bytes - xtb : 0, slices_override());
     return TCSC_OK;
+}
+
+int tcsc_gpu_launch_info(const tcsc_gpu_plan* p, int M, int* path, int* slices) {
+    return launch_info_impl("tcsc_gpu_launch_info", p, M, path, slices, false);
+}
+
+int tcsc_gpu_launch_info_bf16(const tcsc_gpu_plan* p, int M, int* path, int* slices) {
+    return launch_info_impl("tcsc_gpu_launch_info_bf16", p, M, path, slices, true);
 }
 
 int tcsc_gpu_launch_combine(const tcsc_gpu_plan* p, int M, int* in_launch) {
@@ -1098,6 +1186,19 @@ int tcsc_gpu_sgemm(const tcsc_gpu_plan* p, const float* dX, const float* dB, flo
     }
     if (p) const_cast<tcsc_gpu_plan*>(p)->staged_M = -1;  // this call's X^T replaces any staged one
     return sgemm_ws(p, dX, dB, dY, M, ldy, variant, a, stream, p ? p->ws : nullptr, p ? p->ws_bytes : 0);
+}
+
+int tcsc_gpu_sgemm_bf16(const tcsc_gpu_plan* p, const void* dX_bf16, const float* dB, float* dY, int M, int ldy,
+                        int variant, float a, void* stream) {
+    // tcsc_gpu_plan_reserve's size covers every bf16 launch (never more than
+    // the fp32 call's need on the same path), so after it this call allocates nothing
+    if (p && M > 0 && p->cols > 0 && p->ws_bytes < wanted_workspace_bf16(p, M)) {
+        const int rc = tcsc_gpu_plan_reserve(const_cast<tcsc_gpu_plan*>(p), M);
+        if (rc != TCSC_OK) return rc;
+    }
+    if (p) const_cast<tcsc_gpu_plan*>(p)->staged_M = -1;  // the workspace is overwritten
+    return sgemm_ws(p, dX_bf16, dB, dY, M, ldy, variant, a, stream, p ? p->ws : nullptr, p ? p->ws_bytes : 0, 0,
+                    nullptr, true);
 }
 
 static int ensure_workspace(const tcsc_gpu_plan* p, int M) {

@@ -175,6 +175,7 @@ constexpr size_t kCombineBytes = (size_t)kCombineTiles * kCombineWords * 4;
 
 struct GemmArgs {
     const float* X = nullptr;
+    const uint16_t* Xb = nullptr;  // bf16 X instead of X (tcsc_gpu_sgemm_bf16): the transpose widens it
     float* XT = nullptr;       // K x ldxt workspace: X transposed (ldxt = M rounded up to kTM)
     int M = 0, K = 0;
     const int2* ent = nullptr;
@@ -321,6 +322,10 @@ inline bool small_m_fits(int M, int K) { return M >= 1 && M <= 4 && small_m_lds_
 // the fast order's exact arithmetic (bit-identical to k_stream unsplit).
 hipError_t launch_small_m(const float* X, int M, int K, const int* cq, const int* crq, int ncols, const float* B,
                           float* Y, int ldy, bool bias_first, bool prelu, float a, hipStream_t st);
+// the same from bf16 X (bit patterns): the staged image is the widened fp32 one
+hipError_t launch_small_m_bf16(const uint16_t* X, int M, int K, const int* cq, const int* crq, int ncols,
+                               const float* B, float* Y, int ldy, bool bias_first, bool prelu, float a,
+                               hipStream_t st);
 // X (M x K) -> x3 (M x ldk bf16, [h | m | l | 0..]); flags[m] = 1 for the
 // rows the fixup recomputes, 0 otherwise (every row, every call).
 hipError_t mfma_split_x(const float* X, int M, int K, uint16_t* x3, int ldk, int* flags, hipStream_t st);
@@ -339,6 +344,18 @@ size_t mfma_slab_bytes(int M, int N, int K);
 hipError_t mfma_gemm3(const uint16_t* x3, int ldk, const uint16_t* wt, int ldw, int K, int M, int N, const float* B,
                       float* Y, int ldy, bool prelu, float a, float* slabs, size_t slab_bytes, const int* flags,
                       const int* cq, const int* crq, hipStream_t st);
+
+// The one-part forms for bf16 X (tcsc_gpu_sgemm_bf16): x1 is X1, M x
+// mfma_ldw(K) bf16 -- the row itself in 64-k blocks, zeros past K (the W
+// image's pitch) -- with k_split3's flag rule; the GEMM runs one sub-step per
+// block (a third of mfma_gemm3's), same tiles and K split (mfma_slices).
+hipError_t mfma_pack_x(const uint16_t* X, int M, int K, uint16_t* x1, int ldw, int* flags, hipStream_t st);
+hipError_t mfma_gemm1(const uint16_t* x1, int ldk, const uint16_t* wt, int ldw, int K, int M, int N, const float* B,
+                      float* Y, int ldy, bool prelu, float a, float* slabs, size_t slab_bytes, const int* flags,
+                      const int* cq, const int* crq, hipStream_t st);
+hipError_t mfma_fixup1(const uint16_t* x1, int M, int K, int ldk, const int* cq, const int* crq, int ncols,
+                       const float* B, float* Y, int ldy, bool bias_first, bool prelu, float a, const int* flags,
+                       hipStream_t st);
 
 // Rewrites the flagged rows in k_stream's fast order (no-op when none is).
 hipError_t mfma_fixup(const uint16_t* x3, int M, int K, int ldk, const int* cq, const int* crq, int ncols,

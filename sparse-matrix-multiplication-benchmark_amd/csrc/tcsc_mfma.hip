@@ -143,6 +143,56 @@ __global__ void __launch_bounds__(256) k_split3(const float* __restrict__ X, int
     if (threadIdx.x == 0) flags[row] = fix ? 1 : 0;
 }
 
+// k_split3's flag rule on a bf16 x (its fp32 value is bits << 16): non-finite,
+// or nonzero below 2^-100.  The same rows are flagged as by split3 on the
+// widened x.
+__device__ inline bool flag1(uint32_t b) {
+    const uint32_t e = (b >> 7) & 0xffu;
+    return e == 0xffu || ((b & 0x7fffu) != 0 && e < kTinyExp);
+}
+
+// bf16 X (M x K, pitch K) -> X1 (M x ldw bf16): the row as it is, zeros past
+// K (the W image's pitch: whole 64-k blocks), one workgroup per row; flags[row]
+// as k_split3 writes it (every row, every call).  A flagged x stays its own
+// bits.  VEC (K % 8 == 0, X 16-B aligned): kSplitU 16-B loads (8 bf16 each) in
+// flight per thread, 16-B stores; otherwise scalar.
+__global__ void __launch_bounds__(256) k_pack1(const uint16_t* __restrict__ X, int M, int K, uint16_t* __restrict__ X1,
+                                              int ldw, int* __restrict__ flags) {
+    const int row = blockIdx.x;
+    const uint16_t* src = X + (size_t)row * K;
+    uint16_t* dst = X1 + (size_t)row * ldw;
+    const bool vec = (K & 7) == 0 && (reinterpret_cast<uintptr_t>(X) & 15) == 0;
+    bool fix = false;
+    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+    if (vec) {
+        const int ko = K / 8;
+        for (int q0 = threadIdx.x; q0 < ko; q0 += kSplitU * blockDim.x) {
+            u32x4 w[kSplitU];
+#pragma unroll
+            for (int u = 0; u < kSplitU; ++u) {
+                const int q = q0 + u * blockDim.x;
+                if (q < ko) w[u] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(src + 8 * q));
+            }
+#pragma unroll
+            for (int u = 0; u < kSplitU; ++u) {
+                const int q = q0 + u * blockDim.x;
+                if (q >= ko) break;
+                for (int j = 0; j < 4; ++j) fix |= flag1(w[u][j] & 0xffffu) || flag1(w[u][j] >> 16);
+                *reinterpret_cast<u32x4*>(dst + 8 * q) = w[u];
+            }
+        }
+    } else {
+        for (int k = threadIdx.x; k < K; k += blockDim.x) {
+            const uint16_t b = src[k];
+            fix |= flag1(b);
+            dst[k] = b;
+        }
+    }
+    for (int i = K + threadIdx.x; i < ldw; i += blockDim.x) dst[i] = 0;
+    fix = __syncthreads_or(fix);
+    if (threadIdx.x == 0) flags[row] = fix ? 1 : 0;
+}
+
 // The +1/-1 entries of column j (rebased CSC) added into a dense fp32 image
 // of W^T (ncols x K, k contiguous; atomics: a row may repeat in a column).
 __global__ void k_w_scatter(const int* __restrict__ cs, const int* __restrict__ ri, int col_begin, int ncols,
@@ -221,13 +271,16 @@ __global__ void k_merge_csc(const int* __restrict__ cp, const int* __restrict__ 
 
 // Output (row, j) recomputed exactly as k_stream's fast order (see the file
 // comment): x rebuilt from its three parts (or its stored bits), the column's merged rows in
-// ascending k, the bias first or last, then the PReLU.
-template <bool BIAS_FIRST, bool PRELU>
+// ascending k, the bias first or last, then the PReLU.  PARTS = 1: X3 is the
+// one-part image X1 (pitch ldk = mfma_ldw(K)) and x is its bf16 widened, a
+// flagged tiny x included (it is its own bits).
+template <bool BIAS_FIRST, bool PRELU, int PARTS = 3>
 __device__ inline float exact_out(const uint16_t* __restrict__ X3, int K, int ldk, const int* __restrict__ cq,
                                   const int* __restrict__ rm, const float* __restrict__ Bias, int row, int j,
                                   float a) {
     const uint16_t* x3 = X3 + (size_t)row * ldk;
     auto xk = [&](int k) {
+        if constexpr (PARTS == 1) return u2f((uint32_t)x3[k] << 16);
         // all three loads, then a select: no branch in the column walk
         const uint32_t hb = x3[x3_index(k, 0)], mb = x3[x3_index(k, 1)], lb = x3[x3_index(k, 2)];
         const float sum = (u2f(hb << 16) + u2f(mb << 16)) + u2f(lb << 16);
@@ -250,7 +303,7 @@ __device__ inline float exact_out(const uint16_t* __restrict__ X3, int K, int ld
 // Flagged rows, after the GEMM (which wrote act(sum + bias) for every row):
 // one thread per column.  A block first ORs the row flags; most calls have
 // none and the kernel ends there.
-template <bool BIAS_FIRST, bool PRELU>
+template <bool BIAS_FIRST, bool PRELU, int PARTS = 3>
 __global__ void __launch_bounds__(256) k_fixup(const uint16_t* __restrict__ X3, int M, int K, int ldk,
                                                const int* __restrict__ cq, const int* __restrict__ rm,
                                                int ncols,
@@ -263,7 +316,7 @@ __global__ void __launch_bounds__(256) k_fixup(const uint16_t* __restrict__ X3, 
     if (j >= ncols) return;
     for (int row = 0; row < M; ++row)
         if (flags[row])
-            Y[(size_t)row * ldy + j] = exact_out<BIAS_FIRST, PRELU>(X3, K, ldk, cq, rm, Bias, row, j, a);
+            Y[(size_t)row * ldy + j] = exact_out<BIAS_FIRST, PRELU, PARTS>(X3, K, ldk, cq, rm, Bias, row, j, a);
 }
 
 // ---------------------------------------------------------------------------
@@ -301,7 +354,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 // k_fixup folded in: a flagged row takes exact_out() instead, so a split call
 // needs no fixup launch.  VEC: 4 columns per thread (N % 4 == 0, ldy % 4 ==
 // 0, 16-B aligned slabs, bias and Y), all slices' loads in flight.
-template <bool PRELU, bool VEC>
+template <bool PRELU, bool VEC, int PARTS = 3>
 __global__ void __launch_bounds__(256) k_reduce_fix(const float* __restrict__ ws, int slices, int M, int N,
                                                     const float* __restrict__ Bias, float* __restrict__ Y, int ldy,
                                                     float a, const int* __restrict__ flags,
@@ -316,7 +369,7 @@ __global__ void __launch_bounds__(256) k_reduce_fix(const float* __restrict__ ws
         float v[W];
         if (flags[row]) {
 #pragma unroll
-            for (int u = 0; u < W; ++u) v[u] = exact_out<false, PRELU>(X3, K, ldk, cq, rm, Bias, row, col + u, a);
+            for (int u = 0; u < W; ++u) v[u] = exact_out<false, PRELU, PARTS>(X3, K, ldk, cq, rm, Bias, row, col + u, a);
         } else {
             const size_t slab = (size_t)M * N, e = (size_t)row * N + col;
             float p[16][W];
@@ -371,7 +424,10 @@ __device__ __forceinline__ void gemm3_tile(int tiles_m, int tiles_n, int gm, int
 // The k_gemm3 epilogue (both staging forms): Y = act(acc + bias) for the
 // workgroup's tile, the raw sums parked in the LDS (LDSB bytes, free once the
 // k loop has drained) and stored as whole rows.
-template <int WM, int WN, int FI, int FJ, bool PRELU, bool BIAS, int LDSB>
+// PARTS only names the caller: each k_gemm3 form gets its own instance, so
+// adding the one-part kernels leaves the three-part ones' code as it was (a
+// shared instance changed how the epilogue's addresses were folded).
+template <int WM, int WN, int FI, int FJ, bool PRELU, bool BIAS, int LDSB, int PARTS>
 __device__ __forceinline__ void gemm3_store(const f32x4 (&acc)[FI][FJ], char* lds, int lane, int wr, int wc, int m0,
                                             int n0, int M, int N, const float* __restrict__ bias,
                                             float* __restrict__ Y, int ldy, float a) {
@@ -435,12 +491,18 @@ __device__ __forceinline__ void gemm3_store(const f32x4 (&acc)[FI][FJ], char* ld
 // [y * bps, min(nblk, (y + 1) * bps)) and stores its raw fp32 sums into slab
 // y of Y (M x ldy floats per slab); k_reduce4 adds the slabs in slice order,
 // then the bias and the PReLU.
-template <int WM, int WN, int FI, int FJ, bool PRELU, bool PARTIAL>
+//
+// PARTS = 1 (bf16 X, tcsc_gpu_sgemm_bf16): A = X1 (M x ldk, ldk = mfma_ldw(K):
+// the row itself in 64-k blocks), every sub-step a whole block: A and W are
+// both staged per sub-step into their 2-slot rings and W's fragments are read
+// every sub-step.  Same tiles, swizzle, half-step pipeline and epilogue.
+template <int WM, int WN, int FI, int FJ, bool PRELU, bool PARTIAL, int PARTS = 3>
 __global__ void __launch_bounds__(WM * WN * 64) k_gemm3(const uint16_t* __restrict__ A, const uint16_t* __restrict__ Bt,
                                                       int ldk, int ldw, int M, int N, int nblk,
                                                       const float* __restrict__ bias, float* __restrict__ Y, int ldy,
                                                       float a, int tiles_m, int tiles_n, int gm, int bps) {
     static_assert(!(PARTIAL && PRELU), "a partial slab carries raw sums");
+    static_assert(PARTS == 3 || PARTS == 1, "three bf16 parts of an fp32 x, or a bf16 x");
     constexpr int TM = WM * FI * 16, TN = WN * FJ * 16, NW = WM * WN;
     constexpr int PA = TM / 8, PB = TN / 8;  // 1-KiB pieces of a slot
     constexpr int ASLOT = PA * 1024, BSLOT = PB * 1024, BOFF = 2 * ASLOT;
@@ -465,7 +527,7 @@ __global__ void __launch_bounds__(WM * WN * 64) k_gemm3(const uint16_t* __restri
     const char* abase = reinterpret_cast<const char*>(A + (size_t)m0 * ldk);
     const char* bbase = reinterpret_cast<const char*>(Bt + (size_t)n0 * ldw);
     auto dma_a = [&](int blk, int part, int slot) {  // X3's part `part` of 64-k block `blk`
-        const char* g = abase + 2 * (size_t)(kMfmaBlk * (3 * blk + part));
+        const char* g = abase + 2 * (size_t)(kMfmaBlk * (PARTS * blk + part));
 #pragma unroll
         for (int i = 0; i < PAW; ++i)
             __builtin_amdgcn_global_load_lds(reinterpret_cast<const void*>(g + offa[i]),
@@ -556,37 +618,68 @@ __global__ void __launch_bounds__(WM * WN * 64) k_gemm3(const uint16_t* __restri
     const int b0 = PARTIAL ? (int)blockIdx.y * bps : 0;
     const int b1 = PARTIAL ? min(nblk, b0 + bps) : nblk;
     const int last = b1 - 1;
-    dma_a(b0, 0, 0);
-    dma_b(b0, 0);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    dma_a(b0, 1, 1);
-    frag_b(0, 0, 0);
-    frag_a(0, 0, 0);
-    for (int blk = b0; blk < b1; ++blk) {
-        const int bs = (blk - b0) & 1;
+    if constexpr (PARTS == 3) {
+        dma_a(b0, 0, 0);
+        dma_b(b0, 0);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+        dma_a(b0, 1, 1);
+        frag_b(0, 0, 0);
+        frag_a(0, 0, 0);
+        for (int blk = b0; blk < b1; ++blk) {
+            const int bs = (blk - b0) & 1;
 #pragma unroll
-        for (int part = 0; part < 3; ++part) {
-            const int as = (blk - b0 + part) & 1;  // (3 * (blk - b0) + part) & 1
-            if (part == 0) frag_b(1, bs, 1);
-            frag_a(1, as, 1);
+            for (int part = 0; part < 3; ++part) {
+                const int as = (blk - b0 + part) & 1;  // (3 * (blk - b0) + part) & 1
+                if (part == 0) frag_b(1, bs, 1);
+                frag_a(1, as, 1);
+                mma(0);
+                if (part == 0) pin(with_b{}); else pin(a_only{});
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                __syncthreads();
+                __builtin_amdgcn_sched_barrier(0);
+                // A of sub-step s + 2: (blk, 2) after part 0, else (blk + 1, part - 1)
+                if (part == 0) {
+                    dma_a(blk, 2, as);
+                    dma_b(min(blk + 1, last), bs ^ 1);
+                } else {
+                    const bool tail = blk == last;  // uniform: a scalar select, no branch
+                    dma_a(tail ? last : blk + 1, tail ? 2 : part - 1, as);
+                }
+                if (part == 2) frag_b(0, bs ^ 1, 0);  // the next block's
+                frag_a(0, as ^ 1, 0);
+                mma(1);
+                if (part == 2) pin(with_b{}); else pin(a_only{});
+            }
+        }
+    } else {
+        // One part: sub-step s = blk - b0, A and W slots s & 1.  The same
+        // half steps; both carry W's reads (with_b), and the DMA after the
+        // barrier brings A and W of block s + 2 into the slots s just left.
+        dma_a(b0, 0, 0);
+        dma_b(b0, 0);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+        dma_a(min(b0 + 1, last), 0, 1);
+        dma_b(min(b0 + 1, last), 1);
+        frag_b(0, 0, 0);
+        frag_a(0, 0, 0);
+        for (int blk = b0; blk < b1; ++blk) {
+            const int sl = (blk - b0) & 1;
+            frag_b(1, sl, 1);
+            frag_a(1, sl, 1);
             mma(0);
-            if (part == 0) pin(with_b{}); else pin(a_only{});
+            pin(with_b{});
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __syncthreads();
             __builtin_amdgcn_sched_barrier(0);
-            // A of sub-step s + 2: (blk, 2) after part 0, else (blk + 1, part - 1)
-            if (part == 0) {
-                dma_a(blk, 2, as);
-                dma_b(min(blk + 1, last), bs ^ 1);
-            } else {
-                const bool tail = blk == last;  // uniform: a scalar select, no branch
-                dma_a(tail ? last : blk + 1, tail ? 2 : part - 1, as);
-            }
-            if (part == 2) frag_b(0, bs ^ 1, 0);  // the next block's
-            frag_a(0, as ^ 1, 0);
+            const int nxt = min(blk + 2, last);  // uniform; the tail reloads the last block
+            dma_a(nxt, 0, sl);
+            dma_b(nxt, sl);
+            frag_b(0, sl ^ 1, 0);  // block s + 1 (the tail's extra read is discarded)
+            frag_a(0, sl ^ 1, 0);
             mma(1);
-            if (part == 2) pin(with_b{}); else pin(a_only{});
+            pin(with_b{});
         }
     }
     // the tail's reloads land and every wave's last reads are done before the
@@ -595,8 +688,8 @@ __global__ void __launch_bounds__(WM * WN * 64) k_gemm3(const uint16_t* __restri
     __syncthreads();
 
     float* out = PARTIAL ? Y + (size_t)blockIdx.y * M * ldy : Y;
-    gemm3_store<WM, WN, FI, FJ, PRELU, !PARTIAL, 2 * ASLOT + 2 * BSLOT>(acc, lds, lane, wr, wc, m0, n0, M, N, bias, out,
-                                                                        ldy, a);
+    gemm3_store<WM, WN, FI, FJ, PRELU, !PARTIAL, 2 * ASLOT + 2 * BSLOT, PARTS>(acc, lds, lane, wr, wc, m0, n0, M, N, bias,
+                                                                               out, ldy, a);
 }
 
 }  // namespace
@@ -652,6 +745,12 @@ hipError_t mfma_split_x(const float* X, int M, int K, uint16_t* x3, int ldk, int
     return hipGetLastError();
 }
 
+hipError_t mfma_pack_x(const uint16_t* X, int M, int K, uint16_t* x1, int ldw, int* flags, hipStream_t st) {
+    if (M <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_pack1, dim3(M), dim3(256), 0, st, X, M, K, x1, ldw, flags);
+    return hipGetLastError();
+}
+
 // Tile choice: 128 x 512 (8 waves) unless a grid of 256 x 256 tiles would
 // leave more than half of the 256 CUs idle, then 128 x 128 (4 waves).
 bool mfma_big_tiles(int M, int N) { return (long long)((M + 255) / 256) * ((N + 255) / 256) >= 128; }
@@ -700,7 +799,7 @@ size_t mfma_slab_bytes(int M, int N, int K) {
     return s > 1 ? (size_t)s * M * N * sizeof(float) : 0;
 }
 
-template <bool PRELU>
+template <bool PRELU, int PARTS>
 static hipError_t launch_gemm3_t(const uint16_t* x3, int ldk, const uint16_t* wt, int ldw, int K, int nblk, int M,
                                  int N, const float* B, float* Y, int ldy, float a, float* slabs, int slices,
                                  const int* flags, const int* cq, const int* crq, hipStream_t st) {
@@ -714,27 +813,27 @@ static hipError_t launch_gemm3_t(const uint16_t* x3, int ldk, const uint16_t* wt
         const int tm = (M + 127) / 128, tn = (N + 511) / 512;
         const int gm = std::min(kGm, tm);
         if (slices <= 1)
-            hipLaunchKernelGGL((k_gemm3<1, 8, 8, 4, PRELU, false>), dim3(tm * tn), dim3(512), 0, st, x3, wt, ldk, ldw,
+            hipLaunchKernelGGL((k_gemm3<1, 8, 8, 4, PRELU, false, PARTS>), dim3(tm * tn), dim3(512), 0, st, x3, wt, ldk, ldw,
                                M, N, nblk, B, Y, ldy, a, tm, tn, gm, nblk);
         else
-            hipLaunchKernelGGL((k_gemm3<1, 8, 8, 4, false, true>), dim3(tm * tn, slices), dim3(512), 0, st, x3, wt,
+            hipLaunchKernelGGL((k_gemm3<1, 8, 8, 4, false, true, PARTS>), dim3(tm * tn, slices), dim3(512), 0, st, x3, wt,
                                ldk, ldw, M, N, nblk, nullptr, slabs, N, 0.0f, tm, tn, gm, (nblk + slices - 1) / slices);
     } else if (mfma_narrow_tiles(M, N)) {
         const int tn = (N + 255) / 256;
         if (slices <= 1)
-            hipLaunchKernelGGL((k_gemm3<1, 4, 4, 4, PRELU, false>), dim3(tn), dim3(256), 0, st, x3, wt, ldk, ldw, M, N,
+            hipLaunchKernelGGL((k_gemm3<1, 4, 4, 4, PRELU, false, PARTS>), dim3(tn), dim3(256), 0, st, x3, wt, ldk, ldw, M, N,
                                nblk, B, Y, ldy, a, 1, tn, 1, nblk);
         else
-            hipLaunchKernelGGL((k_gemm3<1, 4, 4, 4, false, true>), dim3(tn, slices), dim3(256), 0, st, x3, wt, ldk, ldw,
+            hipLaunchKernelGGL((k_gemm3<1, 4, 4, 4, false, true, PARTS>), dim3(tn, slices), dim3(256), 0, st, x3, wt, ldk, ldw,
                                M, N, nblk, nullptr, slabs, N, 0.0f, 1, tn, 1, (nblk + slices - 1) / slices);
     } else {
         const int tm = (M + 127) / 128, tn = (N + 127) / 128;
         const int gm = std::min(kGm, tm);
         if (slices <= 1)
-            hipLaunchKernelGGL((k_gemm3<2, 2, 4, 4, PRELU, false>), dim3(tm * tn), dim3(256), 0, st, x3, wt, ldk, ldw,
+            hipLaunchKernelGGL((k_gemm3<2, 2, 4, 4, PRELU, false, PARTS>), dim3(tm * tn), dim3(256), 0, st, x3, wt, ldk, ldw,
                                M, N, nblk, B, Y, ldy, a, tm, tn, gm, nblk);
         else
-            hipLaunchKernelGGL((k_gemm3<2, 2, 4, 4, false, true>), dim3(tm * tn, slices), dim3(256), 0, st, x3, wt,
+            hipLaunchKernelGGL((k_gemm3<2, 2, 4, 4, false, true, PARTS>), dim3(tm * tn, slices), dim3(256), 0, st, x3, wt,
                                ldk, ldw, M, N, nblk, nullptr, slabs, N, 0.0f, tm, tn, gm, (nblk + slices - 1) / slices);
     }
     // split K: raw partial tiles went into slabs[slice] (M x N); then
@@ -746,46 +845,72 @@ static hipError_t launch_gemm3_t(const uint16_t* x3, int ldk, const uint16_t* wt
                        reinterpret_cast<uintptr_t>(B)) & 15) == 0;
     const long long n = (long long)M * (vec ? N / 4 : N);
     if (vec)
-        hipLaunchKernelGGL((k_reduce_fix<PRELU, true>), dim3(grid_of(n, 256)), dim3(256), 0, st, slabs, slices, M, N, B,
+        hipLaunchKernelGGL((k_reduce_fix<PRELU, true, PARTS>), dim3(grid_of(n, 256)), dim3(256), 0, st, slabs, slices, M, N, B,
                            Y, ldy, a, flags, x3, K, ldk, cq, crq);
     else
-        hipLaunchKernelGGL((k_reduce_fix<PRELU, false>), dim3(grid_of(n, 256)), dim3(256), 0, st, slabs, slices, M, N,
+        hipLaunchKernelGGL((k_reduce_fix<PRELU, false, PARTS>), dim3(grid_of(n, 256)), dim3(256), 0, st, slabs, slices, M, N,
                            B, Y, ldy, a, flags, x3, K, ldk, cq, crq);
     return hipGetLastError();
+}
+
+template <int PARTS>
+static hipError_t gemm_parts(const uint16_t* xp, int ldk, const uint16_t* wt, int ldw, int K, int M, int N,
+                             const float* B, float* Y, int ldy, bool prelu, float a, float* slabs, size_t slab_bytes,
+                             const int* flags, const int* cq, const int* crq, hipStream_t st) {
+    if (M <= 0 || N <= 0) return hipSuccess;
+    const int nblk = mfma_nblk(K);
+    if (nblk < 1 || ldk != (PARTS == 3 ? mfma_ldk(K) : mfma_ldw(K)) || ldw != mfma_ldw(K)) return hipErrorInvalidValue;
+    const int slices = mfma_slices(M, N, K);
+    if (slices > 1 && (!slabs || slab_bytes < mfma_slab_bytes(M, N, K))) return hipErrorInvalidValue;
+    return prelu ? launch_gemm3_t<true, PARTS>(xp, ldk, wt, ldw, K, nblk, M, N, B, Y, ldy, a, slabs, slices, flags, cq,
+                                               crq, st)
+                 : launch_gemm3_t<false, PARTS>(xp, ldk, wt, ldw, K, nblk, M, N, B, Y, ldy, a, slabs, slices, flags,
+                                                cq, crq, st);
 }
 
 hipError_t mfma_gemm3(const uint16_t* x3, int ldk, const uint16_t* wt, int ldw, int K, int M, int N, const float* B,
                       float* Y, int ldy, bool prelu, float a, float* slabs, size_t slab_bytes, const int* flags,
                       const int* cq, const int* crq, hipStream_t st) {
-    if (M <= 0 || N <= 0) return hipSuccess;
-    const int nblk = mfma_nblk(K);
-    if (nblk < 1 || ldk != mfma_ldk(K) || ldw != mfma_ldw(K)) return hipErrorInvalidValue;
-    const int slices = mfma_slices(M, N, K);
-    if (slices > 1 && (!slabs || slab_bytes < mfma_slab_bytes(M, N, K))) return hipErrorInvalidValue;
-    return prelu ? launch_gemm3_t<true>(x3, ldk, wt, ldw, K, nblk, M, N, B, Y, ldy, a, slabs, slices, flags, cq, crq,
-                                        st)
-                 : launch_gemm3_t<false>(x3, ldk, wt, ldw, K, nblk, M, N, B, Y, ldy, a, slabs, slices, flags, cq, crq,
-                                         st);
+    return gemm_parts<3>(x3, ldk, wt, ldw, K, M, N, B, Y, ldy, prelu, a, slabs, slab_bytes, flags, cq, crq, st);
+}
+
+hipError_t mfma_gemm1(const uint16_t* x1, int ldk, const uint16_t* wt, int ldw, int K, int M, int N, const float* B,
+                      float* Y, int ldy, bool prelu, float a, float* slabs, size_t slab_bytes, const int* flags,
+                      const int* cq, const int* crq, hipStream_t st) {
+    return gemm_parts<1>(x1, ldk, wt, ldw, K, M, N, B, Y, ldy, prelu, a, slabs, slab_bytes, flags, cq, crq, st);
+}
+
+template <int PARTS>
+static hipError_t fixup_parts(const uint16_t* xp, int M, int K, int ldk, const int* cq, const int* crq, int ncols,
+                              const float* B, float* Y, int ldy, bool bias_first, bool prelu, float a,
+                              const int* flags, hipStream_t st) {
+    const dim3 grid((ncols + 255) / 256), block(256);
+#define TCSC_FIX_ARGS xp, M, K, ldk, cq, crq, ncols, B, Y, ldy, a, flags
+    if (bias_first) {
+        if (prelu)
+            hipLaunchKernelGGL((k_fixup<true, true, PARTS>), grid, block, 0, st, TCSC_FIX_ARGS);
+        else
+            hipLaunchKernelGGL((k_fixup<true, false, PARTS>), grid, block, 0, st, TCSC_FIX_ARGS);
+    } else {
+        if (prelu)
+            hipLaunchKernelGGL((k_fixup<false, true, PARTS>), grid, block, 0, st, TCSC_FIX_ARGS);
+        else
+            hipLaunchKernelGGL((k_fixup<false, false, PARTS>), grid, block, 0, st, TCSC_FIX_ARGS);
+    }
+#undef TCSC_FIX_ARGS
+    return hipGetLastError();
 }
 
 hipError_t mfma_fixup(const uint16_t* x3, int M, int K, int ldk, const int* cq, const int* crq, int ncols,
                       const float* B, float* Y, int ldy, bool bias_first, bool prelu, float a, const int* flags,
                       hipStream_t st) {
-    const dim3 grid((ncols + 255) / 256), block(256);
-#define TCSC_FIX_ARGS x3, M, K, ldk, cq, crq, ncols, B, Y, ldy, a, flags
-    if (bias_first) {
-        if (prelu)
-            hipLaunchKernelGGL((k_fixup<true, true>), grid, block, 0, st, TCSC_FIX_ARGS);
-        else
-            hipLaunchKernelGGL((k_fixup<true, false>), grid, block, 0, st, TCSC_FIX_ARGS);
-    } else {
-        if (prelu)
-            hipLaunchKernelGGL((k_fixup<false, true>), grid, block, 0, st, TCSC_FIX_ARGS);
-        else
-            hipLaunchKernelGGL((k_fixup<false, false>), grid, block, 0, st, TCSC_FIX_ARGS);
-    }
-#undef TCSC_FIX_ARGS
-    return hipGetLastError();
+    return fixup_parts<3>(x3, M, K, ldk, cq, crq, ncols, B, Y, ldy, bias_first, prelu, a, flags, st);
+}
+
+hipError_t mfma_fixup1(const uint16_t* x1, int M, int K, int ldk, const int* cq, const int* crq, int ncols,
+                       const float* B, float* Y, int ldy, bool bias_first, bool prelu, float a, const int* flags,
+                       hipStream_t st) {
+    return fixup_parts<1>(x1, M, K, ldk, cq, crq, ncols, B, Y, ldy, bias_first, prelu, a, flags, st);
 }
 
 }  // namespace tcsc

@@ -15,6 +15,8 @@
 // absolute 1e-4, which its M = 1, K = 2048 case missed by 2e-5.)
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "tcsc_internal.h"
 
 namespace tcsc {
@@ -47,20 +49,61 @@ constexpr int ring_quads() {
 //    and the sum never runs past the group;
 //  * the look-ahead loads are pinned ahead of the adds (hipcc would sink
 //    them to their first use).
-template <int MB, bool BIAS_FIRST, bool PRELU>
+// TX = uint16_t: X is bf16 bit patterns, widened (bits << 16) as it is staged:
+// the LDS image, the column walk and so the bits are those of the fp32 kernel
+// on the widened X.  16-B loads of 8 bf16 (8 per lane in flight) where K % 8
+// == 0 and X is 16-B aligned; 2-B loads otherwise.
+template <int MB, bool BIAS_FIRST, bool PRELU, typename TX = float>
 __global__ void __launch_bounds__(kBlock)
-k_small_m(const float* __restrict__ X, int M, int K, const int* __restrict__ cq, const int* __restrict__ rm,
+k_small_m(const TX* __restrict__ X, int M, int K, const int* __restrict__ cq, const int* __restrict__ rm,
           int ncols, const float* __restrict__ Bias, float* __restrict__ Y, int ldy, float a) {
     extern __shared__ float xs[];
     const int lane = threadIdx.x;
     const int Kp = csc_half(K), S = 2 * Kp;  // floats per half / per staged row pair
     // 16-B loads, 16 per lane in flight (16 KiB per wave per round trip), where
     // X's rows are 16-B aligned; 4-B loads otherwise
-    const bool vec = (K & 3) == 0 && (reinterpret_cast<uintptr_t>(X) & 15) == 0;
+    constexpr bool kBf16 = !std::is_same<TX, float>::value;
+    const bool vec = (K & (kBf16 ? 7 : 3)) == 0 && (reinterpret_cast<uintptr_t>(X) & 15) == 0;
     for (int r = 0; r < M; ++r) {
-        const float* __restrict__ xr = X + (size_t)r * K;
+        const TX* __restrict__ xr = X + (size_t)r * K;
         float* dr = xs + (size_t)r * S;
-        if (vec) {
+        if constexpr (kBf16) {
+            auto wide = [](uint32_t b) { return __uint_as_float(b << 16); };
+            if (vec) {
+                for (int k0 = 0; k0 < K; k0 += 8 * 8 * kBlock) {
+                    uint4 v[8];
+#pragma unroll
+                    for (int u = 0; u < 8; ++u)
+                        v[u] = *reinterpret_cast<const uint4*>(xr + min(k0 + 8 * (u * kBlock + lane), K - 8));
+#pragma unroll
+                    for (int u = 0; u < 8; ++u) {
+                        const int k = k0 + 8 * (u * kBlock + lane);
+                        if (k < K) {
+                            const uint32_t w[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
+#pragma unroll
+                            for (int h = 0; h < 2; ++h) {
+                                const float4 f = make_float4(wide(w[2 * h] & 0xffffu), wide(w[2 * h] >> 16),
+                                                             wide(w[2 * h + 1] & 0xffffu), wide(w[2 * h + 1] >> 16));
+                                *reinterpret_cast<float4*>(dr + k + 4 * h) = f;
+                                *reinterpret_cast<float4*>(dr + Kp + k + 4 * h) = make_float4(-f.x, -f.y, -f.z, -f.w);
+                            }
+                        }
+                    }
+                }
+            } else {
+                for (int k0 = 0; k0 < K; k0 += 8 * kBlock) {
+                    float v[8];
+#pragma unroll
+                    for (int u = 0; u < 8; ++u) v[u] = wide(xr[min(k0 + u * kBlock + lane, K - 1)]);
+#pragma unroll
+                    for (int u = 0; u < 8; ++u)
+                        if (k0 + u * kBlock + lane < K) {
+                            dr[k0 + u * kBlock + lane] = v[u];
+                            dr[Kp + k0 + u * kBlock + lane] = -v[u];
+                        }
+                }
+            }
+        } else if (vec) {
             for (int k0 = 0; k0 < K; k0 += 16 * 4 * kBlock) {
                 float4 v[16];
 #pragma unroll
@@ -154,22 +197,22 @@ k_small_m(const float* __restrict__ X, int M, int K, const int* __restrict__ cq,
     }
 }
 
-template <int MB, bool BF, bool PR>
-void launch_one(const float* X, int M, int K, const int* cq, const int* rm, int ncols, const float* B, float* Y,
+template <int MB, bool BF, bool PR, typename TX>
+void launch_one(const TX* X, int M, int K, const int* cq, const int* rm, int ncols, const float* B, float* Y,
                 int ldy, float a, hipStream_t st) {
     static const bool attr = [] {  // LDS beyond the 64 KiB default for dynamic shared memory
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_small_m<MB, BF, PR>),
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_small_m<MB, BF, PR, TX>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)small_m_lds_bytes_max());
         return true;
     }();
     (void)attr;
     const dim3 grid((ncols + kBlock - 1) / kBlock), block(kBlock);
-    hipLaunchKernelGGL((k_small_m<MB, BF, PR>), grid, block, small_m_lds_bytes(M, K), st, X, M, K, cq, rm, ncols, B,
+    hipLaunchKernelGGL((k_small_m<MB, BF, PR, TX>), grid, block, small_m_lds_bytes(M, K), st, X, M, K, cq, rm, ncols, B,
                        Y, ldy, a);
 }
 
-template <int MB>
-void launch_mb(const float* X, int M, int K, const int* cq, const int* rm, int ncols, const float* B, float* Y,
+template <int MB, typename TX>
+void launch_mb(const TX* X, int M, int K, const int* cq, const int* rm, int ncols, const float* B, float* Y,
                int ldy, bool bias_first, bool prelu, float a, hipStream_t st) {
     if (bias_first) {
         if (prelu)
@@ -186,8 +229,9 @@ void launch_mb(const float* X, int M, int K, const int* cq, const int* rm, int n
 
 }  // namespace
 
-hipError_t launch_small_m(const float* X, int M, int K, const int* cq, const int* crq, int ncols, const float* B,
-                          float* Y, int ldy, bool bias_first, bool prelu, float a, hipStream_t st) {
+template <typename TX>
+static hipError_t launch_small_any(const TX* X, int M, int K, const int* cq, const int* crq, int ncols, const float* B,
+                                   float* Y, int ldy, bool bias_first, bool prelu, float a, hipStream_t st) {
     if (M <= 0 || ncols <= 0) return hipSuccess;
     if (!small_m_fits(M, K)) return hipErrorInvalidValue;
     if (M == 1)
@@ -199,6 +243,17 @@ hipError_t launch_small_m(const float* X, int M, int K, const int* cq, const int
     else
         return hipErrorInvalidValue;
     return hipGetLastError();
+}
+
+hipError_t launch_small_m(const float* X, int M, int K, const int* cq, const int* crq, int ncols, const float* B,
+                          float* Y, int ldy, bool bias_first, bool prelu, float a, hipStream_t st) {
+    return launch_small_any(X, M, K, cq, crq, ncols, B, Y, ldy, bias_first, prelu, a, st);
+}
+
+hipError_t launch_small_m_bf16(const uint16_t* X, int M, int K, const int* cq, const int* crq, int ncols,
+                               const float* B, float* Y, int ldy, bool bias_first, bool prelu, float a,
+                               hipStream_t st) {
+    return launch_small_any(X, M, K, cq, crq, ncols, B, Y, ldy, bias_first, prelu, a, st);
 }
 
 }  // namespace tcsc

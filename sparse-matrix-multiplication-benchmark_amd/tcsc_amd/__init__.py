@@ -47,6 +47,7 @@ EXPORTED_SYMBOLS = (
     "tcsc_gpu_get_order", "tcsc_gpu_launch_info", "tcsc_gpu_launch_combine", "tcsc_gpu_build_flags",
     "tcsc_gpu_plan_workspace", "tcsc_gpu_transpose_index", "tcsc_gpu_plan_create_transposed",
     "tcsc_gpu_plan_create_transposed_device", "tcsc_gpu_sgemm_t", "tcsc_gpu_prelu_backward",
+    "tcsc_gpu_sgemm_bf16", "tcsc_gpu_launch_info_bf16",
     # include/sparse/bcsr.h
     "bcsr_from_dense", "bcsr_sgemm_basic", "bcsr_sgemm_prelu_basic", "bcsr_sgemm_avx", "bcsr_sgemm_prelu_avx",
     "bcsr_sgemm_avx2", "bcsr_free",
@@ -144,6 +145,8 @@ def lib():
     L.tcsc_gpu_plan_destroy.argtypes = [vp]
     L.tcsc_gpu_plan_destroy.restype = None
     L.tcsc_gpu_sgemm.argtypes = [vp, vp, vp, vp, i, i, i, f, vp]
+    L.tcsc_gpu_sgemm_bf16.argtypes = [vp, vp, vp, vp, i, i, i, f, vp]
+    L.tcsc_gpu_launch_info_bf16.argtypes = [vp, i, C.POINTER(i), C.POINTER(i)]
     L.tcsc_gpu_prepare_x.argtypes = [vp, vp, i, vp]
     L.tcsc_gpu_sgemm_prepared.argtypes = [vp, vp, vp, i, i, i, f, vp]
     L.tcsc_gpu_from_dense.argtypes = [vp, i, i, vp, vp, vp, vp, C.POINTER(i), C.POINTER(i), vp]
@@ -500,6 +503,14 @@ class Plan:
                "tcsc_gpu_launch_info")
         return ("gather", "fused", "mfma", "small")[path.value], slices.value
 
+    def launch_info_bf16(self, M: int) -> tuple[str, int]:
+        """(path, K slices) of an :meth:`sgemm_bf16` launch of M rows (tcsc_gpu_launch_info_bf16): the bf16
+        call has its own cost model (a one-part GEMM), so its path can differ from :meth:`launch_info`'s."""
+        path, slices = C.c_int(), C.c_int()
+        _check(lib().tcsc_gpu_launch_info_bf16(self.handle, int(M), C.byref(path), C.byref(slices)),
+               "tcsc_gpu_launch_info_bf16")
+        return ("gather", "fused", "mfma", "small")[path.value], slices.value
+
     def launch_combine(self, M: int) -> bool:
         """True when a gather launch of M rows combines its split-K slabs inside
         k_stream instead of a k_reduce launch (tcsc_gpu_launch_combine)."""
@@ -535,6 +546,15 @@ class Plan:
         _check(lib().tcsc_gpu_sgemm(self.handle, C.c_void_p(_ptr(X)), C.c_void_p(_ptr(B)), C.c_void_p(_ptr(Y)),
                                     int(M), int(ldy), VARIANT_ID[variant], float(a), C.c_void_p(stream)),
                "tcsc_gpu_sgemm")
+
+    def sgemm_bf16(self, X, B, Y, M: int, ldy: int, variant: str = "prelu_basic", a: float = 0.2,
+                   stream: int = 0) -> None:
+        """:meth:`sgemm` for bf16 activations (tcsc_gpu_sgemm_bf16): X is M x K contiguous bf16 (a
+        torch.bfloat16 tensor, or a pointer to uint16 bit patterns); B and Y stay fp32.  The bits are
+        those of sgemm on X widened to fp32 on the same path and K split."""
+        _check(lib().tcsc_gpu_sgemm_bf16(self.handle, C.c_void_p(_ptr(X)), C.c_void_p(_ptr(B)), C.c_void_p(_ptr(Y)),
+                                         int(M), int(ldy), VARIANT_ID[variant], float(a), C.c_void_p(stream)),
+               "tcsc_gpu_sgemm_bf16")
 
     def sgemm_t(self, G, DX, M: int, ldx: int, stream: int = 0) -> None:
         """dX (M x K, pitch ldx) = G (M x plan rows, contiguous) . W[:, range]^T on a transposed

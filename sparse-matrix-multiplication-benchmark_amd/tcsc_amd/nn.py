@@ -28,18 +28,21 @@ def _define():
         return torch.cuda.current_stream(device).cuda_stream
 
     class _TernaryLinearFn(torch.autograd.Function):
-        """y = act(x . W + b) on an (M x K) contiguous fp32 x; W and `a` come from the layer."""
+        """y = act(x . W + b) on an (M x K) contiguous fp32 or bf16 x (y is fp32 either way); W and `a`
+        come from the layer."""
 
         @staticmethod
         def forward(ctx, x, bias, layer):
             M, N = x.shape[0], layer.out_features
             y = torch.empty((M, N), dtype=torch.float32, device=x.device)
+            sgemm = layer.plan.sgemm_bf16 if x.dtype == torch.bfloat16 else layer.plan.sgemm
             if layer.a is None:
-                layer.plan.sgemm(x, bias, y, M, N, "basic", 0.0, _stream(x.device))
+                sgemm(x, bias, y, M, N, "basic", 0.0, _stream(x.device))
             else:
-                layer.plan.sgemm(x, bias, y, M, N, "prelu_basic", layer.a, _stream(x.device))
+                sgemm(x, bias, y, M, N, "prelu_basic", layer.a, _stream(x.device))
                 ctx.save_for_backward(y)  # the mask is the forward's own predicate on its output
             ctx.layer = layer
+            ctx.x_dtype = x.dtype
             return y
 
         @staticmethod
@@ -63,6 +66,8 @@ def _define():
             if need_dx:
                 dx = torch.empty((M, K), dtype=torch.float32, device=g.device)
                 layer._transposed().sgemm_t(dz, dx, M, K, stream)
+                if ctx.x_dtype != torch.float32:  # autograd wants the input's dtype
+                    dx = dx.to(ctx.x_dtype)
             return dx, db, None
 
     class TernaryLinear(torch.nn.Module):
@@ -76,8 +81,9 @@ def _define():
               the reference, or None for the identity activation.
         device: the GPU ordinal the plans live on.
 
-        ``forward`` takes fp32 CUDA tensors of shape (..., K) on that device and
-        returns (..., N).  The transposed plan for ``dX`` is built on the first
+        ``forward`` takes fp32 or bf16 CUDA tensors of shape (..., K) on that device
+        and returns fp32 (..., N); a bf16 x goes through ``tcsc_gpu_sgemm_bf16`` with
+        no fp32 copy, and its gradient (computed in fp32) is returned as bf16.  The transposed plan for ``dX`` is built on the first
         backward that needs it, or by :meth:`reserve`.  One module must not be
         used from several streams at once (the plans own their workspaces).
         """
@@ -124,8 +130,8 @@ def _define():
             self._transposed().reserve(max_rows)
 
         def forward(self, x):
-            if not torch.is_tensor(x) or x.dtype != torch.float32 or not x.is_cuda:
-                raise TcscError("TernaryLinear: x must be an fp32 CUDA tensor")
+            if not torch.is_tensor(x) or x.dtype not in (torch.float32, torch.bfloat16) or not x.is_cuda:
+                raise TcscError("TernaryLinear: x must be an fp32 or bf16 CUDA tensor")
             if x.device.index != self.device_index or self.bias.device != x.device:
                 raise TcscError(f"TernaryLinear: x on {x.device}, bias on {self.bias.device}, plans on cuda:"
                                 f"{self.device_index}")

@@ -10,7 +10,11 @@ density) with both times and the winner, so the default plan's density and
 M thresholds (csrc/tcsc_api.cpp kMfmaDensity, kMfmaMinM) can be set from
 measurement.
 
-  python tools/crossover.py [--shapes 2048x8192x8192,...] [--densities 0.05,0.1,...]
+--dtype bf16 runs the same sweep through tcsc_gpu_sgemm_bf16 (X rounded to
+bf16; k_pack1 + the one-part k_gemm3 on the MFMA side, k_transpose_bf16 on the
+gather's), whose cost model is its own (csrc/tcsc_api.cpp mfma_cheaper_bf16).
+
+  python tools/crossover.py [--shapes 2048x8192x8192,...] [--densities 0.05,0.1,...] [--dtype fp32|bf16]
 """
 import argparse
 import json
@@ -29,7 +33,9 @@ def main():
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--warm", type=int, default=3)
     ap.add_argument("--modes", default="gather,mfma,auto", help="plans to time (a subset of gather,mfma,auto)")
+    ap.add_argument("--dtype", default="fp32", choices=("fp32", "bf16"), help="the entry point: sgemm or sgemm_bf16")
     args = ap.parse_args()
+    bf16 = args.dtype == "bf16"
     import torch
 
     import tcsc_amd
@@ -41,13 +47,14 @@ def main():
 
     def time_plan(plan, X, B, Y, M, N):
         plan.reserve(M)
+        sgemm = plan.sgemm_bf16 if bf16 else plan.sgemm
         for _ in range(args.warm):
-            plan.sgemm(X, B, Y, M, N, "basic", 0.0, sh)
+            sgemm(X, B, Y, M, N, "basic", 0.0, sh)
         ts = []
         for _ in range(args.reps):
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record(st)
-            plan.sgemm(X, B, Y, M, N, "basic", 0.0, sh)
+            sgemm(X, B, Y, M, N, "basic", 0.0, sh)
             e1.record(st)
             e1.synchronize()
             ts.append(e0.elapsed_time(e1))
@@ -59,6 +66,8 @@ def main():
         g = torch.Generator(device=dev)
         g.manual_seed(M * 7 + K)
         X = torch.rand((M, K), generator=g, device=dev) * 2 - 1
+        if bf16:
+            X = X.to(torch.bfloat16)
         B = torch.rand((N,), generator=g, device=dev) * 2 - 1
         Y = torch.empty((M, N), device=dev)
         for d in (float(v) for v in args.densities.split(",")):
@@ -74,7 +83,7 @@ def main():
             rin = torch.empty(max(nneg, 1), dtype=torch.int32, device=dev)
             tcsc_amd.gpu_from_dense(Wd, K, N, csp, csn, rip, rin)
             del Wd
-            out = {"M": M, "K": K, "N": N, "density": d, "nnz": npos + nneg}
+            out = {"M": M, "K": K, "N": N, "density": d, "nnz": npos + nneg, "dtype": args.dtype}
             for mode in args.modes.split(","):
                 if mode == "auto":
                     os.environ.pop("TCSC_PATH", None)
@@ -82,7 +91,7 @@ def main():
                     os.environ["TCSC_PATH"] = mode
                 plan = tcsc_amd.Plan.from_device(K, N, csp, csn, rip, rin)
                 plan.reserve(M)  # the gather's K split depends on the workspace
-                path, slices = plan.launch_info(M)
+                path, slices = plan.launch_info_bf16(M) if bf16 else plan.launch_info(M)
                 out[mode + "_path"] = f"{path}/s{slices}"
                 out[mode + "_ms"] = time_plan(plan, X, B, Y, M, N)
                 plan.destroy()
