@@ -255,6 +255,74 @@ int tcsc_gpu_sgemm_bf16(const tcsc_gpu_plan *plan, const void *dX_bf16, const fl
                         float *dY, int M, int ldy, int variant, float a, void *stream);
 int tcsc_gpu_launch_info_bf16(const tcsc_gpu_plan *plan, int M, int *path, int *slices);
 
+/* ---- int8 activations with a per-row scale -------------------
+ * What ternary-weight models (BitNet b1.58 and relatives) run: X quantized to
+ * int8 per token, W about two thirds nonzero, so the MFMA path.
+ *
+ * tcsc_gpu_plan_enable_i8: on a plan that holds the bf16 MFMA image, build an
+ * int8 image of W^T beside it (cols rows of K rounded up to 128 bytes, made on
+ * the device from the bf16 image; counted in device_bytes, freed with the
+ * plan).  It is built only if every |w| <= 127 and every column's sum of |w|
+ * is below 2^24, which keeps |sum_k q w| below 2^31 for any int8 X.  Otherwise,
+ * and on a gather-only or reference-order plan, the call returns TCSC_OK and
+ * leaves the plan as it was (tcsc_gpu_plan_has_i8 then says 0, and int8 calls
+ * run the gather or the small-M path).  Idempotent; synchronises `stream`.
+ * Nothing else in the library allocates the image: a plan that never calls
+ * this behaves exactly as before.
+ *
+ * tcsc_gpu_sgemm_i8:  Y[m, j] = act(s[m] * sum_k q[m, k] W[k, j] + b[j])
+ *   dXq    : M x K row-major, contiguous int8 (any alignment, every value
+ *            -128 .. 127)
+ *   dScale : M floats s[m], or NULL for all ones
+ *   dB, dY, ldy, variant, a, stream : exactly as in tcsc_gpu_sgemm
+ * The bf16 call's guarantees: asynchronous on `stream`, allocation-free once
+ * the workspace covers M (tcsc_gpu_plan_reserve covers int8 launches as it is:
+ * X8 is a sixth of X3, there are no flags, the i32 slabs never outnumber the
+ * fp32 ones), capturable, the same argument checks answered with TCSC_E_ARG
+ * before any HIP call; forward, transposed, reference-order and column-shard
+ * plans; M > 2^22 rows on the gather as several launches.
+ * Numerics, per path:
+ *   MFMA   (the plan has the int8 image and the router picks it):
+ *          Y = act(fl(fl(float(S) * s[m]) + b[j])), S the exact i32 sum,
+ *          float(S) rounded to nearest, one multiply, one add (never fused
+ *          with it), then v < 0 ? a * v : v.  The same bits for every variant
+ *          and every K split.  Kernels: k_pack8 (X -> X8, zero padded),
+ *          k_gemm8 (v_mfma_i32_16x16x64_i8, 128-k sub-steps; the epilogue in
+ *          its store), with K split raw i32 slabs and k_reduce_i8.  No row
+ *          flags and no fixup: integers are never non-finite or tiny.
+ *   gather and small M: the bits of tcsc_gpu_sgemm on the fp32 matrix
+ *          Xs[m, k] = fl(s[m] * float(q[m, k])) on the same path and K split;
+ *          the scale is folded in while staging (k_transpose_i8, k_small_m's
+ *          int8 staging), everything after is the fp32 call's.
+ *   On every path the result is exact when s is NULL or a power of two and
+ *   |S| < 2^24; otherwise within 2^-20 (|b| + s sum |q|).
+ * Routing: the bf16 cost model with the GEMM at twice the rate and half the
+ * sub-steps per k; $TCSC_PATH, $TCSC_SLICES, $TCSC_MFMA_WGS and $TCSC_SMALL_M
+ * act as on the other calls; without the int8 image the router never names
+ * TCSC_PATH_MFMA.  tcsc_gpu_launch_info_i8 reports what an int8 call runs.
+ *
+ * tcsc_gpu_quantize_rows_i8 (k_quant_rows_i8): per row of the M x K fp32 dX,
+ *   amax = max_k |x|, dScale[m] = amax / 127.0f, inv = 127.0f / amax,
+ *   q = clamp(rintf(x * inv), -127, 127)   (amax = 0: q = 0, scale = 0)
+ * every step one rounded fp32 operation, so a host restatement gives the same
+ * bits.  Inputs must be finite (a non-finite x gives unspecified values, never
+ * a fault).  Allocates nothing, asynchronous on `stream`, capturable.
+ *
+ * tcsc_gpu_workspace_bound_i8 (host arithmetic, no plan, no device): the MFMA
+ * workspace of an int8 and of an fp32 launch of an M x K x N problem; the
+ * first never exceeds the second.
+ *
+ * Out of scope: int8 or bf16 Y, per-column weight scales, a host-pointer
+ * version, a backward pass for the int8 call, and keeping X^T narrow inside
+ * the gather's LDS ring. */
+int tcsc_gpu_plan_enable_i8(tcsc_gpu_plan *plan, void *stream);
+int tcsc_gpu_plan_has_i8(const tcsc_gpu_plan *plan);
+int tcsc_gpu_sgemm_i8(const tcsc_gpu_plan *plan, const void *dXq, const float *dScale,
+                      const float *dB, float *dY, int M, int ldy, int variant, float a, void *stream);
+int tcsc_gpu_launch_info_i8(const tcsc_gpu_plan *plan, int M, int *path, int *slices);
+int tcsc_gpu_quantize_rows_i8(const float *dX, int M, int K, void *dXq, float *dScale, void *stream);
+int tcsc_gpu_workspace_bound_i8(int M, int K, int N, size_t *i8_bytes, size_t *f32_bytes);
+
 /* Device-side tcsc_from_dense: dense K x N row-major float matrix on the
  * device -> TCSC arrays on the device, bit-exact with the reference builder
  * (tcsc.c:6-66).  Two calls: first with the four output pointers NULL to

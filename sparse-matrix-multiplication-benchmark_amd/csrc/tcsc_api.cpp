@@ -66,6 +66,10 @@ struct tcsc_gpu_plan {
     // M >= mfma_min_M may take it (use_mfma); null when the plan is gather-only.
     uint16_t* wt = nullptr;
     size_t mfma_bytes = 0;
+    // the int8 image of W^T beside it (cols x mfma8_ldw(rows) bytes), built
+    // only by tcsc_gpu_plan_enable_i8: tcsc_gpu_sgemm_i8's MFMA path
+    int8_t* w8 = nullptr;
+    size_t i8_bytes = 0;
     // the column range's rebased CSC (fast-order plans): the small-M path
     // walks it, the MFMA path's fixup recomputes flagged rows from it
     // (crq: each column's +1 / -1 rows merged in ascending k, in the quad
@@ -273,6 +277,17 @@ size_t mfma_ws_bytes(int M, int K, int N) { return mfma_slabs_off(M, K) + tcsc::
 size_t mfma1_flags_off(int M, int K) { return align256((size_t)M * tcsc::mfma_ldw(K) * 2); }
 size_t mfma1_slabs_off(int M, int K) { return mfma1_flags_off(M, K) + align256((size_t)M * sizeof(int)); }
 size_t mfma1_ws_bytes(int M, int K, int N) { return mfma1_slabs_off(M, K) + tcsc::mfma_slab_bytes(M, N, K); }
+// and for an int8 call: X8 (M x mfma8_ldw(K) bytes), no flags, the i32 slabs.
+//   mfma8_ws_bytes(M, K, N) <= mfma_ws_bytes(M, K, N) for every M, K, N:
+//   * mfma8_ldw(K) = 128 ceil(K / 128) <= 128 ceil(K / 64) <= 384 ceil(K / 64) =
+//     2 mfma_ldk(K) bytes, and align256 is monotone, so mfma8_slabs_off <=
+//     mfma_flags_off <= mfma_slabs_off;
+//   * mfma8_slices <= mfma_slices by construction (tcsc_mfma.hip) and both
+//     slabs hold 4 B per element, so mfma8_slab_bytes <= mfma_slab_bytes.
+// So tcsc_gpu_plan_workspace and tcsc_gpu_plan_reserve cover int8 launches as
+// they are (tests/test_i8_api.py sweeps the inequality).
+size_t mfma8_slabs_off(int M, int K) { return align256((size_t)M * tcsc::mfma8_ldw(K)); }
+size_t mfma8_ws_bytes(int M, int K, int N) { return mfma8_slabs_off(M, K) + tcsc::mfma8_slab_bytes(M, N, K); }
 
 // Variants 0-4 are the tcsc_sgemm_* family (sparse/tcsc.h); 5 is
 // SparseGEMM.h's sparseGEMM<float> (bias last, no activation).  Bias first
@@ -319,10 +334,31 @@ bool mfma_cheaper_bf16(const tcsc_gpu_plan* p, int M) {
     return mfma_us < gather_us;
 }
 
-// forced (TCSC_PATH=mfma: mfma_min_M 1): every launch; default: by the cost model
-bool use_mfma(const tcsc_gpu_plan* p, int M, bool bf16 = false) {
-    return p->wt && M >= p->mfma_min_M && p->rows > 0 &&
-           (p->mfma_min_M == 1 || (bf16 ? mfma_cheaper_bf16(p, M) : mfma_cheaper(p, M)));
+// The int8 call's model, derived from the bf16 one as that was from the fp32
+// fit: the same gather term, the GEMM's 2 ops per (m, k, n) at twice the bf16
+// rate (v_mfma_i32_16x16x64_i8), and half the sub-steps per k in a workgroup's
+// K walk (128-k blocks: ~4.1 ns per k), with the int8 GEMM's own K split.
+// Checked against tools/crossover.py --dtype i8.
+bool mfma_cheaper_i8(const tcsc_gpu_plan* p, int M) {
+    const double nnz = (double)(p->n_pos + p->n_neg), Kb = (double)tcsc::mfma8_ldw(p->rows);
+    const double Mp = (double)(((long long)M + tcsc::kTM - 1) / tcsc::kTM * tcsc::kTM);
+    const double gather_us = 38.0 + Mp * nnz / 23.0e6;
+    const int s = tcsc::mfma8_slices(M, p->cols, p->rows);
+    const double walk_us = Kb * (0.0244 / 6.0) / s * (tcsc::mfma_tiles(M, p->cols) * s > 256 ? 1.5 : 1.0);
+    const double reduce_us = s > 1 ? 3.0 + (s + 1.0) * M * p->cols * 4.0 / 4.0e6 : 0.0;
+    const double mfma_us = 10.0 + std::max(2.0 * M * Kb * p->cols / 3.0e9, walk_us) + reduce_us;
+    return mfma_us < gather_us;
+}
+
+// the activation type of a call: each has its own GEMM and cost model
+enum { kF32 = 0, kBf16 = 1, kI8 = 2 };
+
+// forced (TCSC_PATH=mfma: mfma_min_M 1): every launch; default: by the cost
+// model.  An int8 call needs the int8 image (tcsc_gpu_plan_enable_i8).
+bool use_mfma(const tcsc_gpu_plan* p, int M, int dt = kF32) {
+    if (!p->wt || (dt == kI8 && !p->w8) || M < p->mfma_min_M || p->rows <= 0) return false;
+    if (p->mfma_min_M == 1) return true;
+    return dt == kI8 ? mfma_cheaper_i8(p, M) : dt == kBf16 ? mfma_cheaper_bf16(p, M) : mfma_cheaper(p, M);
 }
 
 rocblas_handle rocblas_for_device(int dev) {
@@ -337,7 +373,14 @@ rocblas_handle rocblas_for_device(int dev) {
     return h;
 }
 
+void free_i8(tcsc_gpu_plan* p) {
+    if (p->w8) (void)hipFree(p->w8);
+    p->w8 = nullptr;
+    p->i8_bytes = 0;
+}
+
 void free_mfma(tcsc_gpu_plan* p) {
+    free_i8(p);  // made from the bf16 image, useless without it
     if (p->wt) (void)hipFree(p->wt);
     p->wt = nullptr;
     p->mfma_bytes = 0;
@@ -428,8 +471,8 @@ int small_max_m() {
     return std::max(0, std::min(kSmallMaxM, std::atoi(e)));
 }
 
-bool use_small(const tcsc_gpu_plan* p, int M, bool bf16 = false) {
-    return p->crq && p->rows > 0 && M >= 1 && M <= small_max_m() && !use_mfma(p, M, bf16) &&
+bool use_small(const tcsc_gpu_plan* p, int M, int dt = kF32) {
+    return p->crq && p->rows > 0 && M >= 1 && M <= small_max_m() && !use_mfma(p, M, dt) &&
            tcsc::small_m_fits(M, p->rows);
 }
 
@@ -544,8 +587,8 @@ size_t path_ws_bytes(const tcsc_gpu_plan* p, int M, int path) {
 }
 
 // bf16: the path of a tcsc_gpu_sgemm_bf16 call (its own mfma_cheaper)
-int launch_path(const tcsc_gpu_plan* p, int M, bool bf16 = false) {
-    return use_mfma(p, M, bf16) ? TCSC_PATH_MFMA : use_small(p, M, bf16) ? TCSC_PATH_SMALL : TCSC_PATH_GATHER;
+int launch_path(const tcsc_gpu_plan* p, int M, int dt = kF32) {
+    return use_mfma(p, M, dt) ? TCSC_PATH_MFMA : use_small(p, M, dt) ? TCSC_PATH_SMALL : TCSC_PATH_GATHER;
 }
 
 // Workspace of the call tcsc_gpu_sgemm makes at this M.
@@ -556,11 +599,25 @@ size_t wanted_workspace(const tcsc_gpu_plan* p, int M) { return path_ws_bytes(p,
 // for X3, the small-M path reads X in place.
 size_t wanted_workspace_bf16(const tcsc_gpu_plan* p, int M) {
     if (M <= 0 || p->cols == 0) return 0;
-    switch (launch_path(p, M, true)) {
+    switch (launch_path(p, M, kBf16)) {
         case TCSC_PATH_GATHER:
             return gather_ws_bytes(p, M);
         case TCSC_PATH_MFMA:
             return mfma1_ws_bytes(M, p->rows, p->cols);
+    }
+    return 0;
+}
+
+// And of the call tcsc_gpu_sgemm_i8 makes: the gather's again, X8 and the i32
+// slabs on the MFMA path (never more than the fp32 call's: mfma8_ws_bytes),
+// nothing for small M.
+size_t wanted_workspace_i8(const tcsc_gpu_plan* p, int M) {
+    if (M <= 0 || p->cols == 0) return 0;
+    switch (launch_path(p, M, kI8)) {
+        case TCSC_PATH_GATHER:
+            return gather_ws_bytes(p, M);
+        case TCSC_PATH_MFMA:
+            return mfma8_ws_bytes(M, p->rows, p->cols);
     }
     return 0;
 }
@@ -760,6 +817,25 @@ int sgemm_mfma_bf16(const tcsc_gpu_plan* p, const uint16_t* dX, const float* dB,
     return TCSC_OK;
 }
 
+// And for int8 X with row scales: k_pack8 (X -> X8), k_gemm8 against the int8
+// image (+ k_reduce_i8 when K is split).  No flags, no fixup.
+int sgemm_mfma_i8(const tcsc_gpu_plan* p, const int8_t* dX, const float* dScale, const float* dB, float* dY, int M,
+                  int ldy, int variant, float a, void* stream, float* ws, size_t ws_bytes) {
+    const int K = p->rows, N = p->cols, ld8 = tcsc::mfma8_ldw(K);
+    const size_t need = mfma8_ws_bytes(M, K, N);
+    if (!ws || ws_bytes < need) {
+        set_error("tcsc_gpu_sgemm_i8: workspace of %zu bytes < %zu needed for M=%d", ws ? ws_bytes : (size_t)0, need, M);
+        return TCSC_E_ARG;
+    }
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    int8_t* x8 = reinterpret_cast<int8_t*>(ws);
+    int* slabs = reinterpret_cast<int*>(reinterpret_cast<char*>(ws) + mfma8_slabs_off(M, K));
+    HIP_TRY(tcsc::mfma8_pack_x(dX, M, K, x8, ld8, st));
+    HIP_TRY(tcsc::mfma8_gemm(x8, p->w8, ld8, K, M, N, dScale, dB, dY, ldy, is_prelu(variant), a, slabs,
+                             ws_bytes - mfma8_slabs_off(M, K), st));
+    return TCSC_OK;
+}
+
 // How one sgemm_ws call is routed.  In: path < 0 lets the call choose by its
 // own M (launch_path), TCSC_PATH_GATHER pins the gather -- a caller that cuts
 // one job into several launches (run_bands, the 2^22-row pieces below) decides
@@ -772,15 +848,19 @@ struct Route {
     int slices = 0;
 };
 
-// bf16: dX_ is M x K bf16 bit patterns (tcsc_gpu_sgemm_bf16; stage 0 only), else fp32.
+// dt: dX_ is M x K fp32, bf16 bit patterns (tcsc_gpu_sgemm_bf16) or int8 with
+// the row scales dScale, null for ones (tcsc_gpu_sgemm_i8); the narrow types
+// have stage 0 only.
 int sgemm_ws(const tcsc_gpu_plan* p, const void* dX_, const float* dB, float* dY, int M, int ldy, int variant,
              float a, void* stream, float* ws, size_t ws_bytes, int stage = 0, Route* route = nullptr,
-             bool bf16 = false) {
-    const float* dX = bf16 ? nullptr : static_cast<const float*>(dX_);
+             int dt = kF32, const float* dScale = nullptr) {
+    const bool bf16 = dt == kBf16, i8 = dt == kI8;
+    const float* dX = dt == kF32 ? static_cast<const float*>(dX_) : nullptr;
     const uint16_t* dXb = bf16 ? static_cast<const uint16_t*>(dX_) : nullptr;
-    const char* who = bf16 ? "tcsc_gpu_sgemm_bf16" : "tcsc_gpu_sgemm";
-    if (bf16 && stage != 0) {
-        set_error("tcsc_gpu_sgemm_bf16: no staged form");
+    const int8_t* dXq = i8 ? static_cast<const int8_t*>(dX_) : nullptr;
+    const char* who = i8 ? "tcsc_gpu_sgemm_i8" : bf16 ? "tcsc_gpu_sgemm_bf16" : "tcsc_gpu_sgemm";
+    if (dt != kF32 && stage != 0) {
+        set_error("%s: no staged form", who);
         return TCSC_E_ARG;
     }
     if (!p || M < 0 || (stage != 1 && (ldy < p->cols || !valid_variant(variant)))) {
@@ -795,9 +875,13 @@ int sgemm_ws(const tcsc_gpu_plan* p, const void* dX_, const float* dB, float* dY
     Route own;
     if (!route) route = &own;
     const int force_slices = route->slices;
-    if (route->path != TCSC_PATH_GATHER) route->path = launch_path(p, M, bf16);
+    if (route->path != TCSC_PATH_GATHER) route->path = launch_path(p, M, dt);
     route->slices = 1;
     if (route->path == TCSC_PATH_MFMA) {
+        if (i8) {
+            route->slices = tcsc::mfma8_slices(M, p->cols, p->rows);
+            return sgemm_mfma_i8(p, dXq, dScale, dB, dY, M, ldy, variant, a, stream, ws, ws_bytes);
+        }
         route->slices = tcsc::mfma_slices(M, p->cols, p->rows);
         if (bf16) return sgemm_mfma_bf16(p, dXb, dB, dY, M, ldy, variant, a, stream, ws, ws_bytes);
         return sgemm_mfma(p, dX, dB, dY, M, ldy, variant, a, stream, ws, ws_bytes, stage);
@@ -813,6 +897,11 @@ int sgemm_ws(const tcsc_gpu_plan* p, const void* dX_, const float* dB, float* dY
         }
         if (stage == 1) {
             HIP_TRY(hipMemcpyAsync(ws, dX, xb, hipMemcpyDeviceToDevice, st));
+            return TCSC_OK;
+        }
+        if (i8) {
+            HIP_TRY(tcsc::launch_small_m_i8(dXq, dScale, M, p->rows, p->ccq, p->crq, p->cols, dB, dY, ldy, false,
+                                            is_prelu(variant), a, st));
             return TCSC_OK;
         }
         if (bf16) {
@@ -842,10 +931,11 @@ int sgemm_ws(const tcsc_gpu_plan* p, const void* dX_, const float* dB, float* dY
         for (int r0 = 0; r0 < M; r0 += kMaxLaunchRows) {
             const int r = std::min(kMaxLaunchRows, M - r0);
             Route piece{TCSC_PATH_GATHER, force_slices > 0 ? force_slices : 1};  // a short tail stays on the gather too
-            const void* xr = bf16 ? static_cast<const void*>(dXb + (size_t)r0 * p->rows)
-                                  : static_cast<const void*>(dX + (size_t)r0 * p->rows);
+            const void* xr = i8     ? static_cast<const void*>(dXq + (size_t)r0 * p->rows)
+                             : bf16 ? static_cast<const void*>(dXb + (size_t)r0 * p->rows)
+                                    : static_cast<const void*>(dX + (size_t)r0 * p->rows);
             const int rc = sgemm_ws(p, xr, dB, dY + (size_t)r0 * ldy, r, ldy, variant, a, stream, ws, ws_bytes, 0,
-                                    &piece, bf16);
+                                    &piece, dt, dScale ? dScale + r0 : nullptr);
             if (rc != TCSC_OK) return rc;
             route->slices = piece.slices;
         }
@@ -859,6 +949,8 @@ int sgemm_ws(const tcsc_gpu_plan* p, const void* dX_, const float* dB, float* dY
     tcsc::GemmArgs g;
     g.X = dX;
     g.Xb = dXb;
+    g.Xq = dXq;
+    g.Xscale = dScale;
     g.XT = p->rows > 0 ? ws : nullptr;
     g.M = M;
     g.K = p->rows;
@@ -1057,7 +1149,7 @@ int tcsc_gpu_plan_get_info(const tcsc_gpu_plan* p, tcsc_gpu_plan_info* info) {
     info->n_neg = p->n_neg;
     info->chunk_k = tcsc::kTK;
     info->n_chunks = p->n_chunks;
-    info->device_bytes = p->bytes + p->ws_bytes + p->mfma_bytes + p->csc_bytes + p->tbias_bytes +
+    info->device_bytes = p->bytes + p->ws_bytes + p->mfma_bytes + p->i8_bytes + p->csc_bytes + p->tbias_bytes +
                          (p->chain_pos ? p->chain_pos->bytes : 0) + (p->chain_neg ? p->chain_neg->bytes : 0);
     info->order = p->order;
     info->mfma_min_M = p->wt ? p->mfma_min_M : 0;
@@ -1124,18 +1216,18 @@ int tcsc_gpu_plan_workspace(const tcsc_gpu_plan* p, int M, int path, size_t* nee
     return TCSC_OK;
 }
 
-static int launch_info_impl(const char* who, const tcsc_gpu_plan* p, int M, int* path, int* slices, bool bf16) {
+static int launch_info_impl(const char* who, const tcsc_gpu_plan* p, int M, int* path, int* slices, int dt) {
     if (!p || M < 0 || !path || !slices) {
         set_error("%s: bad arguments", who);
         return TCSC_E_ARG;
     }
     *slices = 1;
-    if (use_mfma(p, M, bf16)) {
+    if (use_mfma(p, M, dt)) {
         *path = TCSC_PATH_MFMA;
-        *slices = tcsc::mfma_slices(M, p->cols, p->rows);
+        *slices = dt == kI8 ? tcsc::mfma8_slices(M, p->cols, p->rows) : tcsc::mfma_slices(M, p->cols, p->rows);
         return TCSC_OK;
     }
-    if (use_small(p, M, bf16)) {
+    if (use_small(p, M, dt)) {
         *path = TCSC_PATH_SMALL;
         return TCSC_OK;
     }
@@ -1150,11 +1242,15 @@ static int launch_info_impl(const char* who, const tcsc_gpu_plan* p, int M, int*
 }
 
 int tcsc_gpu_launch_info(const tcsc_gpu_plan* p, int M, int* path, int* slices) {
-    return launch_info_impl("tcsc_gpu_launch_info", p, M, path, slices, false);
+    return launch_info_impl("tcsc_gpu_launch_info", p, M, path, slices, kF32);
 }
 
 int tcsc_gpu_launch_info_bf16(const tcsc_gpu_plan* p, int M, int* path, int* slices) {
-    return launch_info_impl("tcsc_gpu_launch_info_bf16", p, M, path, slices, true);
+    return launch_info_impl("tcsc_gpu_launch_info_bf16", p, M, path, slices, kBf16);
+}
+
+int tcsc_gpu_launch_info_i8(const tcsc_gpu_plan* p, int M, int* path, int* slices) {
+    return launch_info_impl("tcsc_gpu_launch_info_i8", p, M, path, slices, kI8);
 }
 
 int tcsc_gpu_launch_combine(const tcsc_gpu_plan* p, int M, int* in_launch) {
@@ -1198,7 +1294,84 @@ int tcsc_gpu_sgemm_bf16(const tcsc_gpu_plan* p, const void* dX_bf16, const float
     }
     if (p) const_cast<tcsc_gpu_plan*>(p)->staged_M = -1;  // the workspace is overwritten
     return sgemm_ws(p, dX_bf16, dB, dY, M, ldy, variant, a, stream, p ? p->ws : nullptr, p ? p->ws_bytes : 0, 0,
-                    nullptr, true);
+                    nullptr, kBf16);
+}
+
+int tcsc_gpu_plan_enable_i8(tcsc_gpu_plan* p, void* stream) {
+    if (!p) {
+        set_error("tcsc_gpu_plan_enable_i8: NULL plan");
+        return TCSC_E_ARG;
+    }
+    // only beside the bf16 image of a fast-order plan; anything else stays as it was
+    if (p->w8 || !p->wt || p->order == TCSC_ORDER_REFERENCE || p->rows <= 0 || p->cols <= 0) return TCSC_OK;
+    DeviceGuard dg(p->device);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int ld8 = tcsc::mfma8_ldw(p->rows);
+    const size_t bytes = (size_t)p->cols * ld8;
+    DevBuf bad;
+    if (bad.alloc(sizeof(int)) != hipSuccess || hipMalloc(&p->w8, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        p->w8 = nullptr;
+        set_error("tcsc_gpu_plan_enable_i8: cannot allocate the int8 image (%zu bytes)", bytes);
+        return TCSC_E_NOMEM;
+    }
+    p->i8_bytes = bytes;
+    int hbad = 0, rc = TCSC_OK;
+    hipError_t e = hipMemsetAsync(bad.p, 0, sizeof(int), st);
+    if (e == hipSuccess)
+        e = tcsc::mfma8_build_w8(p->wt, p->cols, p->rows, tcsc::mfma_ldw(p->rows), p->w8, ld8, bad.as<int>(), st);
+    if (e == hipSuccess) e = hipMemcpyAsync(&hbad, bad.p, sizeof(int), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) rc = hip_fail(e, "tcsc_gpu_plan_enable_i8");
+    // a weight beyond int8, or a column whose sum of |w| could carry an i32 sum past 2^31: no image
+    if (rc != TCSC_OK || hbad) free_i8(p);
+    return rc;
+}
+
+int tcsc_gpu_plan_has_i8(const tcsc_gpu_plan* p) {
+    if (!p) {
+        set_error("tcsc_gpu_plan_has_i8: NULL plan");
+        return 0;
+    }
+    return p->w8 ? 1 : 0;
+}
+
+int tcsc_gpu_sgemm_i8(const tcsc_gpu_plan* p, const void* dXq, const float* dScale, const float* dB, float* dY, int M,
+                      int ldy, int variant, float a, void* stream) {
+    // tcsc_gpu_plan_reserve's size covers every int8 launch (mfma8_ws_bytes <=
+    // mfma_ws_bytes; the gather's need is the fp32 call's), so after it this
+    // call allocates nothing
+    if (p && M > 0 && p->cols > 0 && p->ws_bytes < wanted_workspace_i8(p, M)) {
+        const int rc = tcsc_gpu_plan_reserve(const_cast<tcsc_gpu_plan*>(p), M);
+        if (rc != TCSC_OK) return rc;
+    }
+    if (p) const_cast<tcsc_gpu_plan*>(p)->staged_M = -1;  // the workspace is overwritten
+    return sgemm_ws(p, dXq, dB, dY, M, ldy, variant, a, stream, p ? p->ws : nullptr, p ? p->ws_bytes : 0, 0, nullptr,
+                    kI8, dScale);
+}
+
+int tcsc_gpu_quantize_rows_i8(const float* dX, int M, int K, void* dXq, float* dScale, void* stream) {
+    if (M < 0 || K < 0) {
+        set_error("tcsc_gpu_quantize_rows_i8: bad arguments (M=%d K=%d)", M, K);
+        return TCSC_E_ARG;
+    }
+    if (M == 0) return TCSC_OK;
+    if (!dScale || (K > 0 && (!dX || !dXq))) {
+        set_error("tcsc_gpu_quantize_rows_i8: NULL device pointer");
+        return TCSC_E_ARG;
+    }
+    HIP_TRY(tcsc::quantize_rows_i8(dX, M, K, static_cast<int8_t*>(dXq), dScale, static_cast<hipStream_t>(stream)));
+    return TCSC_OK;
+}
+
+int tcsc_gpu_workspace_bound_i8(int M, int K, int N, size_t* i8_bytes, size_t* f32_bytes) {
+    if (M < 0 || K < 1 || N < 0) {
+        set_error("tcsc_gpu_workspace_bound_i8: bad arguments (M=%d K=%d N=%d)", M, K, N);
+        return TCSC_E_ARG;
+    }
+    if (i8_bytes) *i8_bytes = mfma8_ws_bytes(M, K, N);
+    if (f32_bytes) *f32_bytes = mfma_ws_bytes(M, K, N);
+    return TCSC_OK;
 }
 
 static int ensure_workspace(const tcsc_gpu_plan* p, int M) {

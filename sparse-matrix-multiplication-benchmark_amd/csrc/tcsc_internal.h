@@ -176,6 +176,8 @@ constexpr size_t kCombineBytes = (size_t)kCombineTiles * kCombineWords * 4;
 struct GemmArgs {
     const float* X = nullptr;
     const uint16_t* Xb = nullptr;  // bf16 X instead of X (tcsc_gpu_sgemm_bf16): the transpose widens it
+    const int8_t* Xq = nullptr;    // int8 X instead of X (tcsc_gpu_sgemm_i8): the transpose converts it and
+    const float* Xscale = nullptr; // multiplies row m by Xscale[m] (null: by one)
     float* XT = nullptr;       // K x ldxt workspace: X transposed (ldxt = M rounded up to kTM)
     int M = 0, K = 0;
     const int2* ent = nullptr;
@@ -356,6 +358,34 @@ hipError_t mfma_gemm1(const uint16_t* x1, int ldk, const uint16_t* wt, int ldw, 
 hipError_t mfma_fixup1(const uint16_t* x1, int M, int K, int ldk, const int* cq, const int* crq, int ncols,
                        const float* B, float* Y, int ldy, bool bias_first, bool prelu, float a, const int* flags,
                        hipStream_t st);
+
+// ---- int8 activations (tcsc_gpu_sgemm_i8) ---------------------
+// X8 (M x ld8) and the plan's int8 image of W^T (ncols x ld8) are rows of ld8 =
+// mfma8_ldw(K) bytes: whole 128-k blocks (one k_gemm8 sub-step: the same 128-B
+// rows k_gemm3 stages), zeros past K.
+constexpr int kMfma8Blk = 128;
+__host__ __device__ inline int mfma8_nblk(int K) { return (K + kMfma8Blk - 1) / kMfma8Blk; }
+__host__ __device__ inline int mfma8_ldw(int K) { return kMfma8Blk * mfma8_nblk(K); }
+// the K split of the int8 GEMM (never more slices than mfma_slices) and its i32 slabs
+int mfma8_slices(int M, int N, int K);
+size_t mfma8_slab_bytes(int M, int N, int K);
+// k_pack8: int8 X (M x K) -> x8 (M x ld8), zeros past K
+hipError_t mfma8_pack_x(const int8_t* X, int M, int K, int8_t* x8, int ld8, hipStream_t st);
+// k_w8_from: the int8 image from the bf16 one; *bad = 1 when a |w| > 127 or a
+// column's sum of |w| >= 2^24
+hipError_t mfma8_build_w8(const uint16_t* wt, int ncols, int K, int ldw, int8_t* w8, int ld8, int* bad,
+                          hipStream_t st);
+// k_gemm8 (+ k_reduce_i8 when K is split): Y = act(fl(fl(float(S) * scale[m]) +
+// B[j])), S the exact i32 sum; scale null = all ones
+hipError_t mfma8_gemm(const int8_t* x8, const int8_t* w8, int ld8, int K, int M, int N, const float* scale,
+                      const float* B, float* Y, int ldy, bool prelu, float a, int* slabs, size_t slab_bytes,
+                      hipStream_t st);
+// k_quant_rows_i8: per-row absmax quantization (tcsc_gpu_quantize_rows_i8)
+hipError_t quantize_rows_i8(const float* X, int M, int K, int8_t* Xq, float* scale, hipStream_t st);
+// k_small_m from int8 X: the staged image is fl(scale[m] * float(q)) (scale null = ones)
+hipError_t launch_small_m_i8(const int8_t* X, const float* scale, int M, int K, const int* cq, const int* crq,
+                             int ncols, const float* B, float* Y, int ldy, bool bias_first, bool prelu, float a,
+                             hipStream_t st);
 
 // Rewrites the flagged rows in k_stream's fast order (no-op when none is).
 hipError_t mfma_fixup(const uint16_t* x3, int M, int K, int ldk, const int* cq, const int* crq, int ncols,

@@ -352,6 +352,68 @@ __global__ void __launch_bounds__(256) k_transpose_bf16(const uint16_t* __restri
     }
 }
 
+// k_transpose from int8 X with a per-row scale (tcsc_gpu_sgemm_i8): XT[k][m] =
+// fl(scale[m] * float(X[m][k])) (scale null: float(X[m][k])), so k_stream reads
+// what it reads after an fp32 call on that matrix.  A quarter of the bytes on
+// the read side.  VEC (K % 16 == 0, X 16-B aligned): the 64 (m) x 128 (k)
+// tile, a row of it 128 B = 8 loads of 16 B (16 int8), both loads of a thread
+// in flight before the first LDS write; otherwise scalar, guarded.
+template <bool VEC>
+__global__ void __launch_bounds__(256) k_transpose_i8(const int8_t* __restrict__ X, const float* __restrict__ scale,
+                                                      int M, int K, float* __restrict__ XT, int ldxt) {
+    if (VEC) {
+        __shared__ float tv[64][129];
+        const int k0 = blockIdx.x * 128, m0 = blockIdx.y * 64;
+        const int q2 = threadIdx.x & 7, r2 = threadIdx.x >> 3;  // 8 pieces of 16 int8 per 128-wide row
+        typedef uint32_t nt4 __attribute__((ext_vector_type(4)));
+        nt4 v[2];
+        float s[2];
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const int m = m0 + r2 + 32 * i, k = k0 + 16 * q2;
+            v[i] = nt4{0u, 0u, 0u, 0u};
+            s[i] = 1.0f;
+            if (m < M && k < K) {
+                v[i] = __builtin_nontemporal_load(reinterpret_cast<const nt4*>(X + (size_t)m * K + k));
+                if (scale) s[i] = scale[m];
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const int r = r2 + 32 * i;
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+#pragma unroll
+                for (int b = 0; b < 4; ++b)
+                    tv[r][16 * q2 + 4 * j + b] = __fmul_rn(s[i], (float)(int8_t)(v[i][j] >> (8 * b)));
+        }
+        __syncthreads();
+        const int q = threadIdx.x & 15, rr = threadIdx.x >> 4;  // 16 float4 per 64-wide XT row piece
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const int kk = rr + 16 * i, k = k0 + kk;
+            if (k < K)
+                *reinterpret_cast<float4*>(XT + (size_t)k * ldxt + m0 + 4 * q) =
+                    make_float4(tv[4 * q + 0][kk], tv[4 * q + 1][kk], tv[4 * q + 2][kk], tv[4 * q + 3][kk]);
+        }
+        return;
+    }
+    __shared__ float t[64][65];
+    const int k0 = blockIdx.x * 64, m0 = blockIdx.y * 64;
+    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+        const int r = ty + 4 * i, m = m0 + r, k = k0 + tx;
+        t[r][tx] = (m < M && k < K) ? __fmul_rn(scale ? scale[m] : 1.0f, (float)X[(size_t)m * K + k]) : 0.f;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+        const int kk = ty + 4 * i, k = k0 + kk;
+        if (k < K) XT[(size_t)k * ldxt + m0 + tx] = t[tx][kk];
+    }
+}
+
 typedef int i32x16 __attribute__((ext_vector_type(16)));
 typedef __attribute__((address_space(4))) const i32x16 const_i32x16;
 // the scalar buffer's last, 4- or 8-SGPR piece (header + CAP entries is not
@@ -1658,7 +1720,14 @@ hipError_t launch_gemm(const GemmArgs& g, hipStream_t st) {
         if (!g.XT) return hipErrorInvalidValue;
         const int ldxt = ldxt_of(g.M);
         const bool vec = (g.K % 4 == 0) && ((reinterpret_cast<uintptr_t>(g.X) & 15) == 0);
-        if (g.Xb) {
+        if (g.Xq) {
+            if ((g.K % 16 == 0) && ((reinterpret_cast<uintptr_t>(g.Xq) & 15) == 0))
+                hipLaunchKernelGGL(k_transpose_i8<true>, dim3((g.K + 127) / 128, ldxt / 64), dim3(256), 0, st, g.Xq,
+                                   g.Xscale, g.M, g.K, g.XT, ldxt);
+            else
+                hipLaunchKernelGGL(k_transpose_i8<false>, dim3((g.K + 63) / 64, ldxt / 64), dim3(256), 0, st, g.Xq,
+                                   g.Xscale, g.M, g.K, g.XT, ldxt);
+        } else if (g.Xb) {
             if ((g.K % 8 == 0) && ((reinterpret_cast<uintptr_t>(g.Xb) & 15) == 0))
                 hipLaunchKernelGGL(k_transpose_bf16<true>, dim3((g.K + 127) / 128, ldxt / 64), dim3(256), 0, st, g.Xb,
                                    g.M, g.K, g.XT, ldxt);

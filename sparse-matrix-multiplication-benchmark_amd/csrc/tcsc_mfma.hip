@@ -692,6 +692,389 @@ __global__ void __launch_bounds__(WM * WN * 64) k_gemm3(const uint16_t* __restri
                                                                                out, ldy, a);
 }
 
+// ---------------------------------------------------------------------------
+// int8 activations (tcsc_gpu_sgemm_i8).  X8 (M x ld8 bytes) and
+// the plan's int8 image of W^T (N x ld8), ld8 = mfma8_ldw(K): rows of whole
+// 128-k blocks, zeros past K.  Integers are never non-finite or tiny: no row
+// flags, no fixup; the i32 sums are exact, so every K split gives one result.
+// ---------------------------------------------------------------------------
+typedef int i32x4 __attribute__((ext_vector_type(4)));
+
+// act(fl(fl(float(S) * s) + b)): one conversion (round to nearest), one
+// multiply, one add that must not contract with it, then the PReLU.
+template <bool PRELU>
+__device__ __forceinline__ float i8_out(int S, float s, float b, float a) {
+    // (__fmul_rn / __fadd_rn are plain * and + to hipcc, which would fuse them)
+#pragma clang fp contract(off)
+    const float p = (float)S * s;
+    const float v = p + b;
+    return PRELU ? ((v < 0.0f) ? a * v : v) : v;
+}
+
+// int8 X (M x K, pitch K) -> X8 (M x ld8 bytes): the row as it is, zeros past
+// K, one workgroup per row.  VEC (K % 16 == 0, X 16-B aligned): kSplitU 16-B
+// loads in flight per thread, 16-B stores; otherwise byte by byte.
+__global__ void __launch_bounds__(256) k_pack8(const int8_t* __restrict__ X, int M, int K, int8_t* __restrict__ X8,
+                                              int ld8) {
+    const int row = blockIdx.x;
+    const int8_t* src = X + (size_t)row * K;
+    int8_t* dst = X8 + (size_t)row * ld8;
+    const bool vec = (K & 15) == 0 && (reinterpret_cast<uintptr_t>(X) & 15) == 0;
+    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+    if (vec) {
+        const int ko = K / 16;
+        for (int q0 = threadIdx.x; q0 < ko; q0 += kSplitU * blockDim.x) {
+            u32x4 w[kSplitU];
+#pragma unroll
+            for (int u = 0; u < kSplitU; ++u) {
+                const int q = q0 + u * blockDim.x;
+                if (q < ko) w[u] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(src + 16 * q));
+            }
+#pragma unroll
+            for (int u = 0; u < kSplitU; ++u) {
+                const int q = q0 + u * blockDim.x;
+                if (q >= ko) break;
+                *reinterpret_cast<u32x4*>(dst + 16 * q) = w[u];
+            }
+        }
+    } else {
+        for (int k = threadIdx.x; k < K; k += blockDim.x) dst[k] = src[k];
+    }
+    for (int i = K + threadIdx.x; i < ld8; i += blockDim.x) dst[i] = 0;
+}
+
+// The int8 image from the bf16 one: WT (ncols x ldw bf16, small integers) ->
+// W8 (ncols x ld8 bytes, zeros past K), one workgroup per column of W.  *bad =
+// 1 when a weight is outside [-127, 127] or a column's sum of |w| reaches 2^24
+// (then |sum_k q w| could pass 2^31 for some int8 X).
+__global__ void __launch_bounds__(256) k_w8_from(const uint16_t* __restrict__ WT, int ncols, int K, int ldw,
+                                                int8_t* __restrict__ W8, int ld8, int* __restrict__ bad) {
+    __shared__ unsigned long long tot[256];
+    const int j = blockIdx.x;
+    const uint16_t* src = WT + (size_t)j * ldw;
+    int8_t* dst = W8 + (size_t)j * ld8;
+    unsigned long long sum = 0;
+    bool wide = false;
+    for (int k = threadIdx.x; k < ld8; k += blockDim.x) {
+        int w = 0;
+        if (k < K) w = (int)u2f((uint32_t)src[k] << 16);
+        const int m = w < 0 ? -w : w;
+        wide |= m > 127;
+        sum += (unsigned long long)m;
+        dst[k] = (int8_t)w;
+    }
+    tot[threadIdx.x] = sum;
+    wide = __syncthreads_or(wide);
+    for (int s = 128; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) tot[threadIdx.x] += tot[threadIdx.x + s];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0 && (wide || tot[0] >= (1ull << 24))) *bad = 1;
+}
+
+// Split K: the i32 slabs added as integers (any order gives the same sum),
+// then the unsplit epilogue's arithmetic.  VEC: 4 columns per thread (N % 4 ==
+// 0, ldy % 4 == 0, 16-B aligned slabs and Y), all slices' loads in flight.
+template <bool PRELU, bool VEC>
+__global__ void __launch_bounds__(256) k_reduce_i8(const int* __restrict__ ws, int slices, int M, int N,
+                                                   const float* __restrict__ scale, const float* __restrict__ Bias,
+                                                   float* __restrict__ Y, int ldy, float a) {
+    constexpr int W = VEC ? 4 : 1;
+    const int nq = N / W;
+    const long long total = (long long)M * nq;
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total;
+         i += (long long)gridDim.x * blockDim.x) {
+        const int row = (int)(i / nq), col = W * (int)(i % nq);
+        const size_t slab = (size_t)M * N, e = (size_t)row * N + col;
+        int p[16][W];
+#pragma unroll
+        for (int s = 0; s < 16; ++s)
+            if (s < slices) {
+                if constexpr (VEC) {
+                    const i32x4 q = __builtin_nontemporal_load(reinterpret_cast<const i32x4*>(ws + s * slab + e));
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) p[s][u] = q[u];
+                } else {
+                    p[s][0] = ws[s * slab + e];
+                }
+            }
+        const float sc = scale ? scale[row] : 1.0f;
+        float v[W];
+#pragma unroll
+        for (int u = 0; u < W; ++u) {
+            int t = 0;
+#pragma unroll
+            for (int s = 0; s < 16; ++s)
+                if (s < slices) t += p[s][u];
+            v[u] = i8_out<PRELU>(t, sc, Bias[col + u], a);
+        }
+        float* dst = Y + (size_t)row * ldy + col;
+        if constexpr (VEC) {
+            const f32x4 o = {v[0], v[1], v[2], v[3]};
+            __builtin_nontemporal_store(o, reinterpret_cast<f32x4*>(dst));
+        } else {
+            dst[0] = v[0];
+        }
+    }
+}
+
+// The k_gemm8 epilogue: gemm3_store's staging (the raw i32 sums parked in the
+// LDS, read back as whole rows, 16-B stores).  PARTIAL: the raw sums go into
+// the i32 slab (Yi, pitch ldy); otherwise Y = i8_out(S, scale[row], bias[col]).
+template <int WM, int WN, int FI, int FJ, bool PRELU, bool PARTIAL, int LDSB>
+__device__ __forceinline__ void gemm8_store(const i32x4 (&acc)[FI][FJ], char* lds, int lane, int wr, int wc, int m0,
+                                            int n0, int M, int N, const float* __restrict__ scale,
+                                            const float* __restrict__ bias, float* __restrict__ Y, int ldy, float a) {
+    constexpr int TM = WM * FI * 16, TN = WN * FJ * 16, NW = WM * WN;
+    constexpr int PR = 64, SROW = TN + 4, LPR = TN / 4;  // rows per pass, staged row, lanes per row
+    static_assert(PR * SROW * 4 <= LDSB && TM % PR == 0 && (64 % LPR == 0 || LPR % 64 == 0), "epilogue staging");
+    static_assert((NW * 64) % LPR == 0, "a lane keeps its columns across the read-back");
+    int* stg = reinterpret_cast<int*>(lds);
+    const bool vec = (ldy & 3) == 0 && (reinterpret_cast<uintptr_t>(Y) & 15) == 0;
+    const int c4 = 4 * (threadIdx.x % LPR), col = n0 + c4;
+    f32x4 bq = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (!PARTIAL)
+#pragma unroll
+        for (int u = 0; u < 4; ++u) bq[u] = col + u < N ? bias[col + u] : 0.0f;
+#pragma unroll
+    for (int p = 0; p < TM / PR; ++p) {
+#pragma unroll
+        for (int i = 0; i < FI; ++i) {
+            if (((wr * FI + i) * 16) / PR != p) continue;  // uniform
+            const int rb = (wr * FI + i) * 16 - p * PR + 4 * (lane >> 4);
+#pragma unroll
+            for (int j = 0; j < FJ; ++j) {
+                const int c = (wc * FJ + j) * 16 + (lane & 15);
+#pragma unroll
+                for (int rg = 0; rg < 4; ++rg) stg[(rb + rg) * SROW + c] = acc[i][j][rg];
+            }
+        }
+        __syncthreads();
+        for (int e = threadIdx.x; e < PR * LPR; e += NW * 64) {
+            const int r = e / LPR;
+            const int row = m0 + p * PR + r;
+            if (row >= M) continue;
+            const i32x4 s = *reinterpret_cast<const i32x4*>(stg + r * SROW + c4);
+            if constexpr (PARTIAL) {
+                int* dst = reinterpret_cast<int*>(Y) + (size_t)row * ldy + col;
+                if (vec && col + 3 < N) {
+                    __builtin_nontemporal_store(s, reinterpret_cast<i32x4*>(dst));
+                } else {
+#pragma unroll
+                    for (int u = 0; u < 4; ++u)
+                        if (col + u < N) __builtin_nontemporal_store(s[u], dst + u);
+                }
+            } else {
+                const float sc = scale ? scale[row] : 1.0f;
+                f32x4 v;
+#pragma unroll
+                for (int u = 0; u < 4; ++u) v[u] = i8_out<PRELU>(s[u], sc, bq[u], a);
+                float* dst = Y + (size_t)row * ldy + col;
+                if (vec && col + 3 < N) {
+                    __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(dst));
+                } else {
+#pragma unroll
+                    for (int u = 0; u < 4; ++u)
+                        if (col + u < N) __builtin_nontemporal_store(v[u], dst + u);
+                }
+            }
+        }
+        __syncthreads();  // the staging is reused by the next pass
+    }
+}
+
+// k_gemm8: k_gemm3's one-part form on int8 (a sibling, so the bf16 kernels'
+// code stays what it was).  A sub-step is a 128-k block: the same 128-byte
+// rows, 1-KiB pieces, 16-B DMA granules, swizzle, rings and half-step
+// pipeline; a lane's 16-B fragment holds 16 int8 for
+// v_mfma_i32_16x16x64_i8, two of them (kh 0, 1) per row and sub-step.  A and W
+// are read with the same lane -> byte mapping, so both operands hold the same
+// k values whichever they are, and an integer dot product does not depend on
+// their order.  ldk = ldw = mfma8_ldw(K) bytes.  PARTIAL: raw i32 sums into
+// slab blockIdx.y of Y (M x ldy ints), added by k_reduce_i8.
+template <int WM, int WN, int FI, int FJ, bool PRELU, bool PARTIAL>
+__global__ void __launch_bounds__(WM * WN * 64) k_gemm8(const int8_t* __restrict__ A, const int8_t* __restrict__ Bt,
+                                                      int ldk, int ldw, int M, int N, int nblk,
+                                                      const float* __restrict__ scale,
+                                                      const float* __restrict__ bias, float* __restrict__ Y, int ldy,
+                                                      float a, int tiles_m, int tiles_n, int gm, int bps) {
+    static_assert(!(PARTIAL && PRELU), "a partial slab carries raw sums");
+    constexpr int TM = WM * FI * 16, TN = WN * FJ * 16, NW = WM * WN;
+    constexpr int PA = TM / 8, PB = TN / 8;  // 1-KiB pieces of a slot
+    constexpr int ASLOT = PA * 1024, BSLOT = PB * 1024, BOFF = 2 * ASLOT;
+    constexpr int PAW = PA / NW, PBW = PB / NW;  // pieces each wave moves per A / B slot
+    static_assert(PA % NW == 0 && PB % NW == 0, "whole pieces per wave");
+    __shared__ __attribute__((aligned(1024))) char lds[2 * ASLOT + 2 * BSLOT];
+
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int wr = wave / WN, wc = wave % WN;
+
+    int m0, n0;
+    gemm3_tile<TM, TN>(tiles_m, tiles_n, gm, m0, n0);
+
+    // per-lane byte offsets of this wave's DMA pieces (rows clamped into the matrix)
+    const int row_in = lane >> 3, gsel = (lane & 7) ^ row_in;
+    uint32_t offa[PAW];
+#pragma unroll
+    for (int i = 0; i < PAW; ++i)
+        offa[i] = (uint32_t)(min(8 * (wave * PAW + i) + row_in, M - 1 - m0) * ldk + 16 * gsel);
+    const char* abase = reinterpret_cast<const char*>(A + (size_t)m0 * ldk);
+    const char* bbase = reinterpret_cast<const char*>(Bt + (size_t)n0 * ldw);
+    auto dma_a = [&](int blk, int slot) {  // X8's 128-k block `blk`
+        const char* g = abase + (size_t)kMfma8Blk * blk;
+#pragma unroll
+        for (int i = 0; i < PAW; ++i)
+            __builtin_amdgcn_global_load_lds(reinterpret_cast<const void*>(g + offa[i]),
+                                             (__attribute__((address_space(3))) void*)(lds + slot * ASLOT +
+                                                                                       (wave * PAW + i) * 1024),
+                                             16, 0, 0);
+    };
+    auto dma_b = [&](int blk, int slot) {  // W8's 128-k block `blk` (offsets recomputed, as k_gemm3 does)
+        const char* g = bbase + (size_t)kMfma8Blk * blk;
+#pragma unroll
+        for (int i = 0; i < PBW; ++i)
+            __builtin_amdgcn_global_load_lds(reinterpret_cast<const void*>(
+                                                 g + (uint32_t)(min(8 * (wave * PBW + i) + row_in, N - 1 - n0) * ldw +
+                                                                16 * gsel)),
+                                             (__attribute__((address_space(3))) void*)(lds + BOFF + slot * BSLOT +
+                                                                                       (wave * PBW + i) * 1024),
+                                             16, 0, 0);
+    };
+
+    // fragment read offsets inside a 16-row block (k_gemm3's swizzle)
+    int foff[2];
+#pragma unroll
+    for (int kh = 0; kh < 2; ++kh)
+        foff[kh] = ((lane & 15) >> 3) * 1024 + 16 * (8 * (lane & 7) + ((4 * kh + (lane >> 4)) ^ (lane & 7)));
+
+    i32x4 acc[FI][FJ];
+#pragma unroll
+    for (int i = 0; i < FI; ++i)
+#pragma unroll
+        for (int j = 0; j < FJ; ++j) acc[i][j] = i32x4{0, 0, 0, 0};
+
+    i32x4 af[2][FI], bfr[2][FJ];
+    auto frag_a = [&](int set, int aslot, int kh) {
+        const char* sa = lds + aslot * ASLOT;
+#pragma unroll
+        for (int i = 0; i < FI; ++i)
+            af[set][i] = *reinterpret_cast<const i32x4*>(sa + ((wr * FI + i) * 2) * 1024 + foff[kh]);
+    };
+    auto frag_b = [&](int set, int bslot, int kh) {
+        const char* sb = lds + BOFF + bslot * BSLOT;
+#pragma unroll
+        for (int j = 0; j < FJ; ++j)
+            bfr[set][j] = *reinterpret_cast<const i32x4*>(sb + ((wc * FJ + j) * 2) * 1024 + foff[kh]);
+    };
+    auto mma = [&](int set) {
+#pragma unroll
+        for (int i = 0; i < FI; ++i)
+#pragma unroll
+            for (int j = 0; j < FJ; ++j)
+                acc[i][j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(af[set][i], bfr[set][j], acc[i][j], 0, 0, 0);
+    };
+
+    // the half steps pinned as in k_gemm3: one read per MFMA pair
+    constexpr int NM = FI * FJ, NR = FI + FJ;
+    static_assert(2 * NR <= NM, "one read per MFMA pair");
+    auto pin = [&]() {
+#pragma unroll
+        for (int k = 0; k < NR; ++k) {
+            __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);  // MFMA
+            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);  // DS read
+        }
+        if constexpr (NM > 2 * NR) __builtin_amdgcn_sched_group_barrier(0x008, NM - 2 * NR, 0);
+        __builtin_amdgcn_sched_barrier(0);
+    };
+    // this workgroup's 128-k blocks (the host makes every slice non-empty)
+    const int b0 = PARTIAL ? (int)blockIdx.y * bps : 0;
+    const int b1 = PARTIAL ? min(nblk, b0 + bps) : nblk;
+    const int last = b1 - 1;
+    dma_a(b0, 0);
+    dma_b(b0, 0);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    dma_a(min(b0 + 1, last), 1);
+    dma_b(min(b0 + 1, last), 1);
+    frag_b(0, 0, 0);
+    frag_a(0, 0, 0);
+    for (int blk = b0; blk < b1; ++blk) {
+        const int sl = (blk - b0) & 1;
+        frag_b(1, sl, 1);
+        frag_a(1, sl, 1);
+        mma(0);
+        pin();
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+        __builtin_amdgcn_sched_barrier(0);
+        const int nxt = min(blk + 2, last);  // uniform; the tail reloads the last block
+        dma_a(nxt, sl);
+        dma_b(nxt, sl);
+        frag_b(0, sl ^ 1, 0);  // block s + 1 (the tail's extra read is discarded)
+        frag_a(0, sl ^ 1, 0);
+        mma(1);
+        pin();
+    }
+    // the tail's reloads land and every wave's last reads are done before the
+    // epilogue reuses the LDS
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+
+    float* out = PARTIAL ? reinterpret_cast<float*>(reinterpret_cast<int*>(Y) + (size_t)blockIdx.y * M * ldy) : Y;
+    gemm8_store<WM, WN, FI, FJ, PRELU, PARTIAL, 2 * ASLOT + 2 * BSLOT>(acc, lds, lane, wr, wc, m0, n0, M, N, scale, bias,
+                                                                       out, ldy, a);
+}
+
+// tcsc_gpu_quantize_rows_i8: per row, amax = max |x|, scale = amax / 127, inv
+// = 127 / amax, q = clamp(rint(x * inv), -127, 127); amax = 0: q = 0, scale =
+// 0.  Every step is one correctly rounded fp32 operation.  One workgroup per
+// row, the row read twice (the second time from the L2).  VEC (K % 4 == 0, X
+// 16-B and Xq 4-B aligned): 16-B loads, 4-B stores of four q.
+template <bool VEC>
+__global__ void __launch_bounds__(256) k_quant_rows_i8(const float* __restrict__ X, int M, int K,
+                                                      int8_t* __restrict__ Xq, float* __restrict__ scale) {
+    __shared__ float red[256];
+    const int row = blockIdx.x;
+    const float* src = X + (size_t)row * K;
+    int8_t* dst = Xq + (size_t)row * K;
+    float amax = 0.0f;
+    if (VEC) {
+        for (int q = threadIdx.x; q < K / 4; q += blockDim.x) {
+            const f32x4 w = *reinterpret_cast<const f32x4*>(src + 4 * q);
+#pragma unroll
+            for (int u = 0; u < 4; ++u) amax = fmaxf(amax, fabsf(w[u]));
+        }
+    } else {
+        for (int k = threadIdx.x; k < K; k += blockDim.x) amax = fmaxf(amax, fabsf(src[k]));
+    }
+    red[threadIdx.x] = amax;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) red[threadIdx.x] = fmaxf(red[threadIdx.x], red[threadIdx.x + s]);
+        __syncthreads();
+    }
+    amax = red[0];
+    const bool zero = !(amax > 0.0f);
+    const float inv = zero ? 0.0f : __fdiv_rn(127.0f, amax);
+    if (threadIdx.x == 0) scale[row] = zero ? 0.0f : __fdiv_rn(amax, 127.0f);
+    auto quant = [&](float x) {
+        const float r = fminf(fmaxf(rintf(__fmul_rn(x, inv)), -127.0f), 127.0f);
+        return (int)r;
+    };
+    if (VEC) {
+        for (int q = threadIdx.x; q < K / 4; q += blockDim.x) {
+            const f32x4 w = *reinterpret_cast<const f32x4*>(src + 4 * q);
+            uint32_t o = 0;
+#pragma unroll
+            for (int u = 0; u < 4; ++u) o |= ((uint32_t)quant(w[u]) & 0xffu) << (8 * u);
+            *reinterpret_cast<uint32_t*>(dst + 4 * q) = o;
+        }
+    } else {
+        for (int k = threadIdx.x; k < K; k += blockDim.x) dst[k] = (int8_t)quant(src[k]);
+    }
+}
+
 }  // namespace
 
 hipError_t csc_prepare(const int* csp, const int* csn, const int* rip, const int* rin, int col_begin, int ncols,
@@ -911,6 +1294,112 @@ hipError_t mfma_fixup1(const uint16_t* x1, int M, int K, int ldk, const int* cq,
                        const float* B, float* Y, int ldy, bool bias_first, bool prelu, float a, const int* flags,
                        hipStream_t st) {
     return fixup_parts<1>(x1, M, K, ldk, cq, crq, ncols, B, Y, ldy, bias_first, prelu, a, flags, st);
+}
+
+// ---- int8 (tcsc_gpu_sgemm_i8) ------------------------------------------------
+
+// mfma_slices' logic counted in 128-k blocks: the same workgroup targets, a
+// slice at least 4 blocks (the 512 k of mfma_slices' 8 blocks of 64), and
+// never more slices than the fp32 call takes at this shape: the i32 slabs then
+// fit the fp32 call's slab space (4 B per element either way), which is what
+// keeps the int8 workspace inside the reserved one.
+int mfma8_slices(int M, int N, int K) {
+    if (M <= 0 || N <= 0) return 1;
+    const long long tiles = mfma_tiles(M, N);
+    const int nblk = mfma8_nblk(K);
+    const long long s = std::min<long long>({mfma_split_target(mfma_big_tiles(M, N), mfma_narrow_tiles(M, N)) / tiles,
+                                             16, nblk / 4, mfma_slices(M, N, K)});
+    if (s < 2) return 1;
+    const int bps = (int)((nblk + s - 1) / s);
+    return (nblk + bps - 1) / bps;
+}
+
+size_t mfma8_slab_bytes(int M, int N, int K) {
+    const int s = mfma8_slices(M, N, K);
+    return s > 1 ? (size_t)s * M * N * sizeof(int) : 0;
+}
+
+hipError_t mfma8_pack_x(const int8_t* X, int M, int K, int8_t* x8, int ld8, hipStream_t st) {
+    if (M <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_pack8, dim3(M), dim3(256), 0, st, X, M, K, x8, ld8);
+    return hipGetLastError();
+}
+
+hipError_t mfma8_build_w8(const uint16_t* wt, int ncols, int K, int ldw, int8_t* w8, int ld8, int* bad,
+                          hipStream_t st) {
+    if (ncols <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_w8_from, dim3(ncols), dim3(256), 0, st, wt, ncols, K, ldw, w8, ld8, bad);
+    return hipGetLastError();
+}
+
+hipError_t quantize_rows_i8(const float* X, int M, int K, int8_t* Xq, float* scale, hipStream_t st) {
+    if (M <= 0) return hipSuccess;
+    const bool vec = K % 4 == 0 && (reinterpret_cast<uintptr_t>(X) & 15) == 0 && (reinterpret_cast<uintptr_t>(Xq) & 3) == 0;
+    if (vec)
+        hipLaunchKernelGGL(k_quant_rows_i8<true>, dim3(M), dim3(256), 0, st, X, M, K, Xq, scale);
+    else
+        hipLaunchKernelGGL(k_quant_rows_i8<false>, dim3(M), dim3(256), 0, st, X, M, K, Xq, scale);
+    return hipGetLastError();
+}
+
+template <bool PRELU>
+static hipError_t launch_gemm8_t(const int8_t* x8, const int8_t* w8, int ld8, int nblk, int M, int N,
+                                 const float* scale, const float* B, float* Y, int ldy, float a, int* slabs,
+                                 int slices, hipStream_t st) {
+    constexpr int kGm = 4;  // bands of 4 row tiles, as launch_gemm3_t
+    float* sl = reinterpret_cast<float*>(slabs);
+    const int bps = (nblk + slices - 1) / std::max(slices, 1);
+    if (mfma_big_tiles(M, N)) {
+        const int tm = (M + 127) / 128, tn = (N + 511) / 512;
+        const int gm = std::min(kGm, tm);
+        if (slices <= 1)
+            hipLaunchKernelGGL((k_gemm8<1, 8, 8, 4, PRELU, false>), dim3(tm * tn), dim3(512), 0, st, x8, w8, ld8, ld8, M, N,
+                               nblk, scale, B, Y, ldy, a, tm, tn, gm, nblk);
+        else
+            hipLaunchKernelGGL((k_gemm8<1, 8, 8, 4, false, true>), dim3(tm * tn, slices), dim3(512), 0, st, x8, w8, ld8,
+                               ld8, M, N, nblk, nullptr, nullptr, sl, N, 0.0f, tm, tn, gm, bps);
+    } else if (mfma_narrow_tiles(M, N)) {
+        const int tn = (N + 255) / 256;
+        if (slices <= 1)
+            hipLaunchKernelGGL((k_gemm8<1, 4, 4, 4, PRELU, false>), dim3(tn), dim3(256), 0, st, x8, w8, ld8, ld8, M, N, nblk,
+                               scale, B, Y, ldy, a, 1, tn, 1, nblk);
+        else
+            hipLaunchKernelGGL((k_gemm8<1, 4, 4, 4, false, true>), dim3(tn, slices), dim3(256), 0, st, x8, w8, ld8, ld8, M,
+                               N, nblk, nullptr, nullptr, sl, N, 0.0f, 1, tn, 1, bps);
+    } else {
+        const int tm = (M + 127) / 128, tn = (N + 127) / 128;
+        const int gm = std::min(kGm, tm);
+        if (slices <= 1)
+            hipLaunchKernelGGL((k_gemm8<2, 2, 4, 4, PRELU, false>), dim3(tm * tn), dim3(256), 0, st, x8, w8, ld8, ld8, M, N,
+                               nblk, scale, B, Y, ldy, a, tm, tn, gm, nblk);
+        else
+            hipLaunchKernelGGL((k_gemm8<2, 2, 4, 4, false, true>), dim3(tm * tn, slices), dim3(256), 0, st, x8, w8, ld8,
+                               ld8, M, N, nblk, nullptr, nullptr, sl, N, 0.0f, tm, tn, gm, bps);
+    }
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess || slices <= 1) return e;
+    const bool vec = N % 4 == 0 && ldy % 4 == 0 &&
+                     ((reinterpret_cast<uintptr_t>(Y) | reinterpret_cast<uintptr_t>(slabs)) & 15) == 0;
+    const long long n = (long long)M * (vec ? N / 4 : N);
+    if (vec)
+        hipLaunchKernelGGL((k_reduce_i8<PRELU, true>), dim3(grid_of(n, 256)), dim3(256), 0, st, slabs, slices, M, N, scale,
+                           B, Y, ldy, a);
+    else
+        hipLaunchKernelGGL((k_reduce_i8<PRELU, false>), dim3(grid_of(n, 256)), dim3(256), 0, st, slabs, slices, M, N, scale,
+                           B, Y, ldy, a);
+    return hipGetLastError();
+}
+
+hipError_t mfma8_gemm(const int8_t* x8, const int8_t* w8, int ld8, int K, int M, int N, const float* scale,
+                      const float* B, float* Y, int ldy, bool prelu, float a, int* slabs, size_t slab_bytes,
+                      hipStream_t st) {
+    if (M <= 0 || N <= 0) return hipSuccess;
+    const int nblk = mfma8_nblk(K);
+    if (nblk < 1 || ld8 != mfma8_ldw(K)) return hipErrorInvalidValue;
+    const int slices = mfma8_slices(M, N, K);
+    if (slices > 1 && (!slabs || slab_bytes < mfma8_slab_bytes(M, N, K))) return hipErrorInvalidValue;
+    return prelu ? launch_gemm8_t<true>(x8, w8, ld8, nblk, M, N, scale, B, Y, ldy, a, slabs, slices, st)
+                 : launch_gemm8_t<false>(x8, w8, ld8, nblk, M, N, scale, B, Y, ldy, a, slabs, slices, st);
 }
 
 }  // namespace tcsc

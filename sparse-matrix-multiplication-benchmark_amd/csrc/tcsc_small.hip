@@ -53,21 +53,64 @@ constexpr int ring_quads() {
 // the LDS image, the column walk and so the bits are those of the fp32 kernel
 // on the widened X.  16-B loads of 8 bf16 (8 per lane in flight) where K % 8
 // == 0 and X is 16-B aligned; 2-B loads otherwise.
+// TX = int8_t (tcsc_gpu_sgemm_i8): X is int8 with a per-row scale (Scale, null
+// = ones; read by this form only, and last among the arguments so the other
+// forms' code is what it was): the staged value is fl(Scale[r] * float(x)), so
+// the bits are those of the fp32 kernel on that matrix.  16-B loads of 16 int8
+// (4 per lane in flight) where K % 16 == 0 and X is 16-B aligned; 1-B loads
+// otherwise.
 template <int MB, bool BIAS_FIRST, bool PRELU, typename TX = float>
 __global__ void __launch_bounds__(kBlock)
 k_small_m(const TX* __restrict__ X, int M, int K, const int* __restrict__ cq, const int* __restrict__ rm,
-          int ncols, const float* __restrict__ Bias, float* __restrict__ Y, int ldy, float a) {
+          int ncols, const float* __restrict__ Bias, float* __restrict__ Y, int ldy, float a,
+          const float* __restrict__ Scale) {
     extern __shared__ float xs[];
     const int lane = threadIdx.x;
     const int Kp = csc_half(K), S = 2 * Kp;  // floats per half / per staged row pair
     // 16-B loads, 16 per lane in flight (16 KiB per wave per round trip), where
     // X's rows are 16-B aligned; 4-B loads otherwise
-    constexpr bool kBf16 = !std::is_same<TX, float>::value;
-    const bool vec = (K & (kBf16 ? 7 : 3)) == 0 && (reinterpret_cast<uintptr_t>(X) & 15) == 0;
+    constexpr bool kBf16 = std::is_same<TX, uint16_t>::value, kI8 = std::is_same<TX, int8_t>::value;
+    const bool vec = (K & (kI8 ? 15 : kBf16 ? 7 : 3)) == 0 && (reinterpret_cast<uintptr_t>(X) & 15) == 0;
     for (int r = 0; r < M; ++r) {
         const TX* __restrict__ xr = X + (size_t)r * K;
         float* dr = xs + (size_t)r * S;
-        if constexpr (kBf16) {
+        if constexpr (kI8) {
+            const float sc = Scale ? Scale[r] : 1.0f;
+            auto conv = [&](uint32_t w, int b) { return __fmul_rn(sc, (float)(int8_t)(w >> (8 * b))); };
+            if (vec) {
+                for (int k0 = 0; k0 < K; k0 += 4 * 16 * kBlock) {
+                    uint4 v[4];
+#pragma unroll
+                    for (int u = 0; u < 4; ++u)
+                        v[u] = *reinterpret_cast<const uint4*>(xr + min(k0 + 16 * (u * kBlock + lane), K - 16));
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) {
+                        const int k = k0 + 16 * (u * kBlock + lane);
+                        if (k < K) {
+                            const uint32_t w[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
+#pragma unroll
+                            for (int h = 0; h < 4; ++h) {
+                                const float4 f = make_float4(conv(w[h], 0), conv(w[h], 1), conv(w[h], 2), conv(w[h], 3));
+                                *reinterpret_cast<float4*>(dr + k + 4 * h) = f;
+                                *reinterpret_cast<float4*>(dr + Kp + k + 4 * h) = make_float4(-f.x, -f.y, -f.z, -f.w);
+                            }
+                        }
+                    }
+                }
+            } else {
+                for (int k0 = 0; k0 < K; k0 += 8 * kBlock) {
+                    float v[8];
+#pragma unroll
+                    for (int u = 0; u < 8; ++u) v[u] = __fmul_rn(sc, (float)xr[min(k0 + u * kBlock + lane, K - 1)]);
+#pragma unroll
+                    for (int u = 0; u < 8; ++u)
+                        if (k0 + u * kBlock + lane < K) {
+                            dr[k0 + u * kBlock + lane] = v[u];
+                            dr[Kp + k0 + u * kBlock + lane] = -v[u];
+                        }
+                }
+            }
+        } else if constexpr (kBf16) {
             auto wide = [](uint32_t b) { return __uint_as_float(b << 16); };
             if (vec) {
                 for (int k0 = 0; k0 < K; k0 += 8 * 8 * kBlock) {
@@ -199,7 +242,7 @@ k_small_m(const TX* __restrict__ X, int M, int K, const int* __restrict__ cq, co
 
 template <int MB, bool BF, bool PR, typename TX>
 void launch_one(const TX* X, int M, int K, const int* cq, const int* rm, int ncols, const float* B, float* Y,
-                int ldy, float a, hipStream_t st) {
+                int ldy, float a, const float* scale, hipStream_t st) {
     static const bool attr = [] {  // LDS beyond the 64 KiB default for dynamic shared memory
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_small_m<MB, BF, PR, TX>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)small_m_lds_bytes_max());
@@ -208,22 +251,22 @@ void launch_one(const TX* X, int M, int K, const int* cq, const int* rm, int nco
     (void)attr;
     const dim3 grid((ncols + kBlock - 1) / kBlock), block(kBlock);
     hipLaunchKernelGGL((k_small_m<MB, BF, PR, TX>), grid, block, small_m_lds_bytes(M, K), st, X, M, K, cq, rm, ncols, B,
-                       Y, ldy, a);
+                       Y, ldy, a, scale);
 }
 
 template <int MB, typename TX>
 void launch_mb(const TX* X, int M, int K, const int* cq, const int* rm, int ncols, const float* B, float* Y,
-               int ldy, bool bias_first, bool prelu, float a, hipStream_t st) {
+               int ldy, bool bias_first, bool prelu, float a, const float* scale, hipStream_t st) {
     if (bias_first) {
         if (prelu)
-            launch_one<MB, true, true>(X, M, K, cq, rm, ncols, B, Y, ldy, a, st);
+            launch_one<MB, true, true>(X, M, K, cq, rm, ncols, B, Y, ldy, a, scale, st);
         else
-            launch_one<MB, true, false>(X, M, K, cq, rm, ncols, B, Y, ldy, a, st);
+            launch_one<MB, true, false>(X, M, K, cq, rm, ncols, B, Y, ldy, a, scale, st);
     } else {
         if (prelu)
-            launch_one<MB, false, true>(X, M, K, cq, rm, ncols, B, Y, ldy, a, st);
+            launch_one<MB, false, true>(X, M, K, cq, rm, ncols, B, Y, ldy, a, scale, st);
         else
-            launch_one<MB, false, false>(X, M, K, cq, rm, ncols, B, Y, ldy, a, st);
+            launch_one<MB, false, false>(X, M, K, cq, rm, ncols, B, Y, ldy, a, scale, st);
     }
 }
 
@@ -231,15 +274,16 @@ void launch_mb(const TX* X, int M, int K, const int* cq, const int* rm, int ncol
 
 template <typename TX>
 static hipError_t launch_small_any(const TX* X, int M, int K, const int* cq, const int* crq, int ncols, const float* B,
-                                   float* Y, int ldy, bool bias_first, bool prelu, float a, hipStream_t st) {
+                                   float* Y, int ldy, bool bias_first, bool prelu, float a, hipStream_t st,
+                                   const float* scale = nullptr) {
     if (M <= 0 || ncols <= 0) return hipSuccess;
     if (!small_m_fits(M, K)) return hipErrorInvalidValue;
     if (M == 1)
-        launch_mb<1>(X, M, K, cq, crq, ncols, B, Y, ldy, bias_first, prelu, a, st);
+        launch_mb<1>(X, M, K, cq, crq, ncols, B, Y, ldy, bias_first, prelu, a, scale, st);
     else if (M <= 2)
-        launch_mb<2>(X, M, K, cq, crq, ncols, B, Y, ldy, bias_first, prelu, a, st);
+        launch_mb<2>(X, M, K, cq, crq, ncols, B, Y, ldy, bias_first, prelu, a, scale, st);
     else if (M <= 4)
-        launch_mb<4>(X, M, K, cq, crq, ncols, B, Y, ldy, bias_first, prelu, a, st);
+        launch_mb<4>(X, M, K, cq, crq, ncols, B, Y, ldy, bias_first, prelu, a, scale, st);
     else
         return hipErrorInvalidValue;
     return hipGetLastError();
@@ -254,6 +298,12 @@ hipError_t launch_small_m_bf16(const uint16_t* X, int M, int K, const int* cq, c
                                const float* B, float* Y, int ldy, bool bias_first, bool prelu, float a,
                                hipStream_t st) {
     return launch_small_any(X, M, K, cq, crq, ncols, B, Y, ldy, bias_first, prelu, a, st);
+}
+
+hipError_t launch_small_m_i8(const int8_t* X, const float* scale, int M, int K, const int* cq, const int* crq,
+                             int ncols, const float* B, float* Y, int ldy, bool bias_first, bool prelu, float a,
+                             hipStream_t st) {
+    return launch_small_any(X, M, K, cq, crq, ncols, B, Y, ldy, bias_first, prelu, a, st, scale);
 }
 
 }  // namespace tcsc

@@ -48,6 +48,8 @@ EXPORTED_SYMBOLS = (
     "tcsc_gpu_plan_workspace", "tcsc_gpu_transpose_index", "tcsc_gpu_plan_create_transposed",
     "tcsc_gpu_plan_create_transposed_device", "tcsc_gpu_sgemm_t", "tcsc_gpu_prelu_backward",
     "tcsc_gpu_sgemm_bf16", "tcsc_gpu_launch_info_bf16",
+    "tcsc_gpu_plan_enable_i8", "tcsc_gpu_plan_has_i8", "tcsc_gpu_sgemm_i8", "tcsc_gpu_launch_info_i8",
+    "tcsc_gpu_quantize_rows_i8", "tcsc_gpu_workspace_bound_i8",
     # include/sparse/bcsr.h
     "bcsr_from_dense", "bcsr_sgemm_basic", "bcsr_sgemm_prelu_basic", "bcsr_sgemm_avx", "bcsr_sgemm_prelu_avx",
     "bcsr_sgemm_avx2", "bcsr_free",
@@ -147,6 +149,12 @@ def lib():
     L.tcsc_gpu_sgemm.argtypes = [vp, vp, vp, vp, i, i, i, f, vp]
     L.tcsc_gpu_sgemm_bf16.argtypes = [vp, vp, vp, vp, i, i, i, f, vp]
     L.tcsc_gpu_launch_info_bf16.argtypes = [vp, i, C.POINTER(i), C.POINTER(i)]
+    L.tcsc_gpu_plan_enable_i8.argtypes = [vp, vp]
+    L.tcsc_gpu_plan_has_i8.argtypes = [vp]
+    L.tcsc_gpu_sgemm_i8.argtypes = [vp, vp, vp, vp, vp, i, i, i, f, vp]
+    L.tcsc_gpu_launch_info_i8.argtypes = [vp, i, C.POINTER(i), C.POINTER(i)]
+    L.tcsc_gpu_quantize_rows_i8.argtypes = [vp, i, i, vp, vp, vp]
+    L.tcsc_gpu_workspace_bound_i8.argtypes = [i, i, i, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
     L.tcsc_gpu_prepare_x.argtypes = [vp, vp, i, vp]
     L.tcsc_gpu_sgemm_prepared.argtypes = [vp, vp, vp, i, i, i, f, vp]
     L.tcsc_gpu_from_dense.argtypes = [vp, i, i, vp, vp, vp, vp, C.POINTER(i), C.POINTER(i), vp]
@@ -556,6 +564,32 @@ class Plan:
                                          int(M), int(ldy), VARIANT_ID[variant], float(a), C.c_void_p(stream)),
                "tcsc_gpu_sgemm_bf16")
 
+    def enable_i8(self, stream: int = 0) -> bool:
+        """Build the int8 image of W beside the bf16 MFMA image (tcsc_gpu_plan_enable_i8) and return
+        :attr:`has_i8`: False on a gather-only or reference-order plan, or when a weight does not fit int8 --
+        :meth:`sgemm_i8` then runs the gather or the small-M path.  Idempotent; synchronises the stream."""
+        _check(lib().tcsc_gpu_plan_enable_i8(self.handle, C.c_void_p(stream)), "tcsc_gpu_plan_enable_i8")
+        return self.has_i8
+
+    @property
+    def has_i8(self) -> bool:
+        return bool(lib().tcsc_gpu_plan_has_i8(self.handle))
+
+    def launch_info_i8(self, M: int) -> tuple[str, int]:
+        """(path, K slices) of an :meth:`sgemm_i8` launch of M rows (tcsc_gpu_launch_info_i8)."""
+        path, slices = C.c_int(), C.c_int()
+        _check(lib().tcsc_gpu_launch_info_i8(self.handle, int(M), C.byref(path), C.byref(slices)),
+               "tcsc_gpu_launch_info_i8")
+        return ("gather", "fused", "mfma", "small")[path.value], slices.value
+
+    def sgemm_i8(self, Xq, scale, B, Y, M: int, ldy: int, variant: str = "prelu_basic", a: float = 0.2,
+                 stream: int = 0) -> None:
+        """Y = act(scale[m] * (Xq . W) + B) for int8 activations (tcsc_gpu_sgemm_i8): Xq is M x K contiguous
+        int8 (a torch.int8 tensor or a pointer), scale M floats or None for all ones; B and Y are fp32."""
+        _check(lib().tcsc_gpu_sgemm_i8(self.handle, C.c_void_p(_ptr(Xq)), C.c_void_p(_ptr(scale)),
+                                       C.c_void_p(_ptr(B)), C.c_void_p(_ptr(Y)), int(M), int(ldy),
+                                       VARIANT_ID[variant], float(a), C.c_void_p(stream)), "tcsc_gpu_sgemm_i8")
+
     def sgemm_t(self, G, DX, M: int, ldx: int, stream: int = 0) -> None:
         """dX (M x K, pitch ldx) = G (M x plan rows, contiguous) . W[:, range]^T on a transposed
         plan (tcsc_gpu_sgemm_t); TcscError on a plan that :meth:`transposed` did not make."""
@@ -614,6 +648,15 @@ def gpu_transpose_index(rows: int, cols: int, d_csp, d_csn, d_rip, d_rin, col_be
                                           int(col_end), C.c_void_p(_ptr(d_t_csp)), C.c_void_p(_ptr(d_t_csn)),
                                           C.c_void_p(_ptr(d_t_rip)), C.c_void_p(_ptr(d_t_rin)), C.c_void_p(stream)),
            "tcsc_gpu_transpose_index")
+
+
+def quantize_rows_i8(X, Xq, scale, M: int, K: int, stream: int = 0) -> None:
+    """Per-row absmax quantization on the device (tcsc_gpu_quantize_rows_i8): X is M x K contiguous fp32;
+    Xq (M x K int8) and scale (M floats) are written: scale = amax / 127, q = clamp(rint(x * (127 / amax)),
+    -127, 127), a row of zeros gives q = 0 and scale = 0."""
+    _check(lib().tcsc_gpu_quantize_rows_i8(C.c_void_p(_ptr(X)), int(M), int(K), C.c_void_p(_ptr(Xq)),
+                                           C.c_void_p(_ptr(scale)), C.c_void_p(stream)),
+           "tcsc_gpu_quantize_rows_i8")
 
 
 def prelu_backward(G, Y, a: float, DZ, DB, M: int, N: int, ldg: int | None = None, ldy: int | None = None,

@@ -14,7 +14,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from . import Plan, TcscError, TcscMatrix, prelu_backward
+from . import Plan, TcscError, TcscMatrix, prelu_backward, quantize_rows_i8
 
 __all__ = ["TernaryLinear"]
 
@@ -115,6 +115,7 @@ def _define():
             self.bias = torch.nn.Parameter(b)
             self.plan = Plan(self._W, 0, self.out_features, self.device_index, _stream(dev))
             self.transposed_plan = None  # built by the first backward that needs dX, or by reserve()
+            self._i8_rows, self._i8_xq, self._i8_scale = 0, None, None  # forward_int8's buffers
 
         def _transposed(self) -> Plan:
             if self.transposed_plan is None:
@@ -122,12 +123,54 @@ def _define():
                 self.transposed_plan = Plan.transposed(self._W, 0, self.out_features, self.device_index, _stream(dev))
             return self.transposed_plan
 
-        def reserve(self, max_rows: int) -> None:
+        def reserve(self, max_rows: int, int8: bool = False) -> None:
             """Workspaces of both plans for up to max_rows rows (the flattened leading
             dimensions), building the transposed plan if it is absent: afterwards a
-            forward + backward step allocates nothing in the library and can be captured."""
+            forward + backward step allocates nothing in the library and can be captured.
+            int8=True also builds the plan's int8 image (``Plan.enable_i8``) and the
+            buffers :meth:`forward_int8` quantizes into, for up to max_rows rows."""
             self.plan.reserve(max_rows)
             self._transposed().reserve(max_rows)
+            if int8:
+                self.plan.enable_i8(_stream(torch.device("cuda", self.device_index)))
+                self._i8_buffers(max_rows)
+
+        def _i8_buffers(self, rows: int):
+            """(Xq, scale) for `rows` rows: kept from the last reserve, grown when a call needs more."""
+            if self._i8_rows < rows:
+                dev = torch.device("cuda", self.device_index)
+                self._i8_xq = torch.empty((rows, self.in_features), dtype=torch.int8, device=dev)
+                self._i8_scale = torch.empty(rows, dtype=torch.float32, device=dev)
+                self._i8_rows = rows
+            return self._i8_xq, self._i8_scale
+
+        def forward_int8(self, x):
+            """Inference with int8 activations: the rows of the fp32 x are quantized per row
+            (``tcsc_amd.quantize_rows_i8``) into buffers the layer keeps, then ``Plan.sgemm_i8`` computes
+            ``act(scale * (q . W) + bias)`` on the current stream.  On the int8 MFMA path after
+            ``reserve(rows, int8=True)``; without the image the gather serves the call.  No backward:
+            raises when grad is enabled and x requires grad."""
+            if not torch.is_tensor(x) or x.dtype != torch.float32 or not x.is_cuda:
+                raise TcscError("TernaryLinear.forward_int8: x must be an fp32 CUDA tensor")
+            if torch.is_grad_enabled() and x.requires_grad:
+                raise TcscError("TernaryLinear.forward_int8 is inference only: x requires grad")
+            if x.device.index != self.device_index or self.bias.device != x.device:
+                raise TcscError(f"TernaryLinear: x on {x.device}, bias on {self.bias.device}, plans on cuda:"
+                                f"{self.device_index}")
+            if x.dim() < 1 or x.shape[-1] != self.in_features:
+                raise TcscError(f"TernaryLinear: x has shape {tuple(x.shape)}, expected (..., {self.in_features})")
+            lead = x.shape[:-1]
+            x2 = x.detach().reshape(-1, self.in_features).contiguous()
+            M, K, N = x2.shape[0], self.in_features, self.out_features
+            xq, scale = self._i8_buffers(M)
+            stream = _stream(x.device)
+            y = torch.empty((M, N), dtype=torch.float32, device=x.device)
+            quantize_rows_i8(x2, xq, scale, M, K, stream)
+            if self.a is None:
+                self.plan.sgemm_i8(xq, scale, self.bias.detach(), y, M, N, "basic", 0.0, stream)
+            else:
+                self.plan.sgemm_i8(xq, scale, self.bias.detach(), y, M, N, "prelu_basic", self.a, stream)
+            return y.reshape(*lead, N)
 
         def forward(self, x):
             if not torch.is_tensor(x) or x.dtype not in (torch.float32, torch.bfloat16) or not x.is_cuda:

@@ -14,7 +14,12 @@ measurement.
 bf16; k_pack1 + the one-part k_gemm3 on the MFMA side, k_transpose_bf16 on the
 gather's), whose cost model is its own (csrc/tcsc_api.cpp mfma_cheaper_bf16).
 
-  python tools/crossover.py [--shapes 2048x8192x8192,...] [--densities 0.05,0.1,...] [--dtype fp32|bf16]
+--dtype i8 runs it through tcsc_gpu_sgemm_i8 (X quantized per row by
+tcsc_gpu_quantize_rows_i8, the scales passed along; every plan calls
+enable_i8, so the MFMA side is k_pack8 + k_gemm8 and the gather's staging is
+k_transpose_i8), with its own model again (mfma_cheaper_i8).
+
+  python tools/crossover.py [--shapes 2048x8192x8192,...] [--densities 0.05,0.1,...] [--dtype fp32|bf16|i8]
 """
 import argparse
 import json
@@ -33,9 +38,10 @@ def main():
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--warm", type=int, default=3)
     ap.add_argument("--modes", default="gather,mfma,auto", help="plans to time (a subset of gather,mfma,auto)")
-    ap.add_argument("--dtype", default="fp32", choices=("fp32", "bf16"), help="the entry point: sgemm or sgemm_bf16")
+    ap.add_argument("--dtype", default="fp32", choices=("fp32", "bf16", "i8"),
+                    help="the entry point: sgemm, sgemm_bf16 or sgemm_i8")
     args = ap.parse_args()
-    bf16 = args.dtype == "bf16"
+    bf16, i8 = args.dtype == "bf16", args.dtype == "i8"
     import torch
 
     import tcsc_amd
@@ -48,6 +54,11 @@ def main():
     def time_plan(plan, X, B, Y, M, N):
         plan.reserve(M)
         sgemm = plan.sgemm_bf16 if bf16 else plan.sgemm
+        if i8:
+            Xq, S = X
+
+            def sgemm(_, B, Y, M, N, variant, a, sh):
+                plan.sgemm_i8(Xq, S, B, Y, M, N, variant, a, sh)
         for _ in range(args.warm):
             sgemm(X, B, Y, M, N, "basic", 0.0, sh)
         ts = []
@@ -68,6 +79,11 @@ def main():
         X = torch.rand((M, K), generator=g, device=dev) * 2 - 1
         if bf16:
             X = X.to(torch.bfloat16)
+        if i8:
+            Xq = torch.empty((M, K), dtype=torch.int8, device=dev)
+            S = torch.empty(M, device=dev)
+            tcsc_amd.quantize_rows_i8(X, Xq, S, M, K, sh)
+            X = (Xq, S)
         B = torch.rand((N,), generator=g, device=dev) * 2 - 1
         Y = torch.empty((M, N), device=dev)
         for d in (float(v) for v in args.densities.split(",")):
@@ -91,7 +107,10 @@ def main():
                     os.environ["TCSC_PATH"] = mode
                 plan = tcsc_amd.Plan.from_device(K, N, csp, csn, rip, rin)
                 plan.reserve(M)  # the gather's K split depends on the workspace
-                path, slices = plan.launch_info_bf16(M) if bf16 else plan.launch_info(M)
+                if i8:
+                    plan.enable_i8(sh)
+                path, slices = (plan.launch_info_i8(M) if i8 else plan.launch_info_bf16(M) if bf16
+                                else plan.launch_info(M))
                 out[mode + "_path"] = f"{path}/s{slices}"
                 out[mode + "_ms"] = time_plan(plan, X, B, Y, M, N)
                 plan.destroy()
