@@ -146,6 +146,20 @@ int tcsc_gpu_launch_info(const tcsc_gpu_plan *plan, int M, int *path, int *slice
  * uses k_reduce. */
 int tcsc_gpu_launch_combine(const tcsc_gpu_plan *plan, int M, int *in_launch);
 
+/* The gather kernel's geometry a tcsc_gpu_sgemm of M rows takes:
+ * *cols_per_wave = 16 (k_stream: 256 columns per workgroup), 22 (k_stream_w:
+ * 352 columns per workgroup; unsplit K, the fast order, a plan whose
+ * tcsc_gpu_plan_reserve built the second copy of the entry streams) or 0 when
+ * the launch is not on TCSC_PATH_GATHER.  The two compute the same bits; the
+ * choice is a rounds model, tcsc_gpu_wide_pays, unless TCSC_GEO=16|22 forces
+ * one (22 is an error where K is split by TCSC_SLICES, the order is the
+ * reference's or the plan has no wide streams). */
+int tcsc_gpu_launch_geometry(const tcsc_gpu_plan *plan, int M, int *cols_per_wave);
+/* The rounds model itself (pure; no device needed): 1 when M rows x ncols
+ * columns on num_cus CUs take fewer column-rounds with 352-column workgroups
+ * than with 256-column ones, weighted by the measured cost per column. */
+int tcsc_gpu_wide_pays(int M, int ncols, int num_cus);
+
 /* Allocate the plan's workspace for launches of up to `max_M` rows: X^T
  * (K x max_M rounded up to 256 floats; the kernel streams X^T rows into LDS)
  * plus, where the gather's cost model or the MFMA GEMM's grid splits K over

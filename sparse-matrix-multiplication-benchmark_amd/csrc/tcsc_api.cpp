@@ -84,6 +84,16 @@ struct tcsc_gpu_plan {
     unsigned* csync = nullptr;
     mutable bool csync_dirty = false;
     int num_cus = 0;
+    // the second copy of the entry streams, re-grouped for the 22-column
+    // geometry (k_stream_w, DESIGN.md §4 "Two geometries"): built from ent /
+    // sptr by tcsc_gpu_plan_reserve (or the reserve a launch falls into) where
+    // wide_pays holds for a reserved M or $TCSC_GEO=22 asks for it; fast-order
+    // plans only
+    int2* ent_w = nullptr;
+    int* sptr_w = nullptr;
+    long long n_entries_w = 0;
+    int n_groups_w = 0;
+    size_t wide_bytes = 0;
     // transposed plans (tcsc_gpu_plan_create_transposed*): `cols` zeros, the
     // bias tcsc_gpu_sgemm_t hands to the launch; null on every other plan
     float* tbias = nullptr;
@@ -763,6 +773,122 @@ class DeviceGuard {
     bool ok_ = false;
 };
 
+// ---- the two gather geometries (DESIGN.md §4 "Two geometries") --------------
+// A launch of M rows over ncols columns runs ceil(M / 256) x ceil(ncols / w)
+// workgroups of w columns, one per CU at a time, so it takes
+//   rounds(w) = ceil(ceil(M / 256) * ceil(ncols / w) / num_cus)
+// passes over the chip, each about as long as one workgroup's K walk, which
+// costs in proportion to the workgroup's columns.  The 22-column geometry (w =
+// 352) pays where   rounds(352) * 352 * alpha < rounds(256) * 256,
+// alpha = the measured cost per column of a wide workgroup over a narrow one.
+// Fitted on cfg 4, both kernels of one library alternating on one MI355X
+// (profiles/wide_ab_kernels.txt, HIP events, 3 rounds): k_stream 1.1819 ms in
+// 4 rounds of 256 columns, k_stream_w 1.1216 ms in 3 rounds of 352:
+//   alpha = (1.1216 / (3 * 352)) / (1.1819 / (4 * 256)) = 0.920.
+// Fitted at 98 % sparsity, where a wave's chunk stream (21 entries) fits the
+// wide loop's 30-entry scalar buffer; denser W was not measured.
+constexpr double kWideAlpha = 0.92;
+bool wide_pays(int M, int ncols, int num_cus) {
+    if (M <= 0 || ncols <= 0 || num_cus <= 0) return false;
+    const long long rt = ((long long)M + tcsc::kTM - 1) / tcsc::kTM;
+    auto rounds = [&](int w) { return (rt * ((ncols + w - 1) / w) + num_cus - 1) / num_cus; };
+    return (double)(rounds(tcsc::kWideWgCols) * tcsc::kWideWgCols) * kWideAlpha <
+           (double)(rounds(tcsc::kWgCols) * tcsc::kWgCols);
+}
+
+// $TCSC_GEO=16|22 forces a geometry (tests, A/B); read per call.  0: the rounds model.
+int geo_override() {
+    const char* s = std::getenv("TCSC_GEO");
+    const int v = s ? std::atoi(s) : 0;
+    return v == tcsc::kCW || v == tcsc::kWideCW ? v : 0;
+}
+
+// Whether tcsc_gpu_plan_reserve(max_M) builds the wide streams: a fast-order
+// forward plan with entries whose launch of some M <= max_M would take them (the
+// model is not monotone in M, so every row-tile count is asked), or $TCSC_GEO=22.
+bool wide_wanted(const tcsc_gpu_plan* p, int max_M) {
+    if (p->order != TCSC_ORDER_FAST || p->tbias || p->rows <= 0 || p->cols <= 0 || max_M <= 0 || !p->ent || !p->sptr)
+        return false;  // the backward pass's transposed plans keep the 16-column kernel
+    const int f = geo_override();
+    if (f == tcsc::kWideCW) return true;
+    if (f == tcsc::kCW) return false;
+    const int top = std::min(max_M, 1 << 22);
+    for (long long M = tcsc::kTM; M < top + tcsc::kTM; M += tcsc::kTM)
+        if (wide_pays((int)std::min<long long>(M, top), p->cols, p->num_cus)) return true;
+    return false;
+}
+
+// The second copy of the entry streams, from the plan's own (tcsc_wide.hip).
+// Synchronises; a failure to allocate is no error (the 16-column kernel
+// serves every launch).
+int build_wide(tcsc_gpu_plan* p) {
+    if (p->ent_w) return TCSC_OK;
+    DeviceGuard dg(p->device);
+    hipStream_t st = nullptr;
+    const int nch = p->n_chunks, G = p->n_groups, ncols = p->cols, Gw = tcsc::wide_groups_for(ncols);
+    const long long nc = (long long)nch * ncols, ng = (long long)nch * Gw;
+    if (nch <= 0 || ng + 1 > 0x7fffffffLL) return TCSC_OK;
+    DevBuf cnt, cptr, gcnt, tmp;
+    size_t tb1 = 0, tb2 = 0;
+    HIP_TRY(tcsc::plan_scan_tmp_bytes(nc + 1, &tb1));
+    HIP_TRY(tcsc::plan_scan_tmp_bytes(ng + 1, &tb2));
+    const size_t tb = std::max(tb1, tb2);
+    int* sptr_w = nullptr;
+    if (cnt.alloc((size_t)(nc + 1) * sizeof(int)) != hipSuccess || cptr.alloc((size_t)(nc + 1) * sizeof(int)) != hipSuccess ||
+        gcnt.alloc((size_t)(ng + 1) * sizeof(int)) != hipSuccess || tmp.alloc(tb) != hipSuccess ||
+        hipMalloc(&sptr_w, (size_t)(ng + 1) * sizeof(int)) != hipSuccess) {
+        (void)hipGetLastError();
+        return TCSC_OK;
+    }
+    std::unique_ptr<int, void (*)(int*)> sptr_guard(sptr_w, [](int* q) { (void)hipFree(q); });
+    HIP_TRY(hipDeviceSynchronize());  // the plan's streams are complete (built on the creator's stream)
+    HIP_TRY(tcsc::wide_counts(p->ent, p->sptr, G, nch, ncols, Gw, cnt.as<int>(), cptr.as<int>(), gcnt.as<int>(), sptr_w,
+                              tmp.p, tb, st));
+    int total = 0;
+    HIP_TRY(hipMemcpyAsync(&total, sptr_w + ng, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    int2* ent_w = nullptr;
+    if (hipMalloc(&ent_w, (size_t)(total + tcsc::kEntGuard) * sizeof(int2)) != hipSuccess) {
+        (void)hipGetLastError();
+        return TCSC_OK;
+    }
+    hipError_t e = tcsc::wide_fill(p->ent, p->sptr, G, nch, ncols, Gw, cptr.as<int>(), sptr_w, ent_w, total, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);  // the scratch is freed on return
+    if (e != hipSuccess) {
+        (void)hipFree(ent_w);
+        return hip_fail(e, "build_wide");
+    }
+    p->ent_w = ent_w;
+    p->sptr_w = sptr_guard.release();
+    p->n_entries_w = total;
+    p->n_groups_w = Gw;
+    p->wide_bytes = (size_t)(ng + 1) * sizeof(int) + (size_t)(total + tcsc::kEntGuard) * sizeof(int2);
+    return TCSC_OK;
+}
+
+// The geometry of a gather launch of M rows (kCW or kWideCW), given the K
+// split it would run with the 16-column kernel and whether the caller forces
+// one; -1 with the error set where $TCSC_GEO=22 cannot be had.
+int launch_geo(const tcsc_gpu_plan* p, int M, int slices, int forced_slices, const char* who) {
+    const int f = geo_override();
+    if (f == tcsc::kWideCW) {
+        if (p->order != TCSC_ORDER_FAST || forced_slices > 1) {
+            set_error("%s: TCSC_GEO=22 needs the fast order and an unsplit K (order %s, %d slices forced)", who,
+                      p->order == TCSC_ORDER_FAST ? "fast" : "reference", forced_slices);
+            return -1;
+        }
+        if (p->rows <= 0) return tcsc::kCW;  // nothing to gather: the bias alone, either kernel
+        if (!p->ent_w) {
+            set_error("%s: TCSC_GEO=22 but the plan has no wide streams (tcsc_gpu_plan_reserve builds them)", who);
+            return -1;
+        }
+        return tcsc::kWideCW;
+    }
+    if (f == tcsc::kCW || !p->ent_w || p->order != TCSC_ORDER_FAST) return tcsc::kCW;
+    if (tcsc::normalized_slices(p->rows, slices) != 1) return tcsc::kCW;
+    return wide_pays(M, p->cols, p->num_cus) ? tcsc::kWideCW : tcsc::kCW;
+}
+
 }  // namespace
 
 namespace {
@@ -984,6 +1110,19 @@ int sgemm_ws(const tcsc_gpu_plan* p, const void* dX_, const float* dB, float* dY
     g.stage = stage;
     if (g.order == 0)  // what tcsc::launch_gemm picks with this workspace; the reference orders walk K in order
         route->slices = tcsc::choose_slices(M, g.ncols, g.K, g.nnz, g.n_groups, g.ws ? g.ws_bytes : 0, g.force_slices);
+    // the 22-column kernel where the rounds model (or $TCSC_GEO) says so: unsplit K, the wide streams
+    if (stage != 1) {
+        const int geo = launch_geo(p, M, route->slices, g.force_slices, who);
+        if (geo < 0) return TCSC_E_ARG;
+        if (geo == tcsc::kWideCW) {
+            g.geo = geo;
+            g.ent = p->ent_w;
+            g.sptr = p->sptr_w;
+            g.n_entries = p->n_entries_w;
+            g.n_groups = p->n_groups_w;
+            route->slices = 1;
+        }
+    }
     // the plan's own workspace (device API) with its combine words: the
     // in-launch split-K combine (tcsc::launch_gemm decides if it applies)
     if (ws == p->ws && p->csync) {
@@ -1149,7 +1288,7 @@ int tcsc_gpu_plan_get_info(const tcsc_gpu_plan* p, tcsc_gpu_plan_info* info) {
     info->n_neg = p->n_neg;
     info->chunk_k = tcsc::kTK;
     info->n_chunks = p->n_chunks;
-    info->device_bytes = p->bytes + p->ws_bytes + p->mfma_bytes + p->i8_bytes + p->csc_bytes + p->tbias_bytes +
+    info->device_bytes = p->bytes + p->ws_bytes + p->mfma_bytes + p->i8_bytes + p->csc_bytes + p->tbias_bytes + p->wide_bytes +
                          (p->chain_pos ? p->chain_pos->bytes : 0) + (p->chain_neg ? p->chain_neg->bytes : 0);
     info->order = p->order;
     info->mfma_min_M = p->wt ? p->mfma_min_M : 0;
@@ -1171,6 +1310,8 @@ void tcsc_gpu_plan_destroy(tcsc_gpu_plan* p) {
     if (p->ws) (void)hipFree(p->ws);
     if (p->csync) (void)hipFree(p->csync);
     if (p->tbias) (void)hipFree(p->tbias);
+    if (p->ent_w) (void)hipFree(p->ent_w);
+    if (p->sptr_w) (void)hipFree(p->sptr_w);
     free_mfma(p);
     free_csc(p);
     tcsc_gpu_plan_destroy(p->chain_pos);
@@ -1190,6 +1331,12 @@ int tcsc_gpu_plan_reserve(tcsc_gpu_plan* p, int max_M) {
         HIP_TRY(hipMemset(p->csync, 0, tcsc::kCombineBytes));
         HIP_TRY(hipDeviceSynchronize());
         if (!p->num_cus) HIP_TRY(hipDeviceGetAttribute(&p->num_cus, hipDeviceAttributeMultiprocessorCount, p->device));
+    }
+    // the wide streams, where a launch of some M <= max_M takes them: built
+    // here so that no launch after this call allocates or synchronises
+    if (!p->ent_w && wide_wanted(p, max_M)) {
+        const int rc = build_wide(p);
+        if (rc != TCSC_OK) return rc;
     }
     if (want <= p->ws_bytes) return TCSC_OK;
     DeviceGuard dg(p->device);
@@ -1251,6 +1398,24 @@ int tcsc_gpu_launch_info_bf16(const tcsc_gpu_plan* p, int M, int* path, int* sli
 
 int tcsc_gpu_launch_info_i8(const tcsc_gpu_plan* p, int M, int* path, int* slices) {
     return launch_info_impl("tcsc_gpu_launch_info_i8", p, M, path, slices, kI8);
+}
+
+int tcsc_gpu_wide_pays(int M, int ncols, int num_cus) { return wide_pays(M, ncols, num_cus) ? 1 : 0; }
+
+int tcsc_gpu_launch_geometry(const tcsc_gpu_plan* p, int M, int* cols_per_wave) {
+    if (!p || M < 0 || !cols_per_wave) {
+        set_error("tcsc_gpu_launch_geometry: bad arguments");
+        return TCSC_E_ARG;
+    }
+    *cols_per_wave = 0;  // not a gather launch
+    int path = 0, slices = 1;
+    const int rc = tcsc_gpu_launch_info(p, M, &path, &slices);
+    if (rc != TCSC_OK) return rc;
+    if (path != TCSC_PATH_GATHER) return TCSC_OK;
+    const int geo = launch_geo(p, std::min(M, 1 << 22), slices, slices_override(), "tcsc_gpu_launch_geometry");
+    if (geo < 0) return TCSC_E_ARG;
+    *cols_per_wave = geo;
+    return TCSC_OK;
 }
 
 int tcsc_gpu_launch_combine(const tcsc_gpu_plan* p, int M, int* in_launch) {

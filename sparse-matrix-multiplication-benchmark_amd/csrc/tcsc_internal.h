@@ -134,6 +134,19 @@ static_assert(kNBuf >= 2 && kNBuf <= 5, "ring of 2 (DMA(c+1) before gather(c)) o
 static_assert(4 * kCW <= 255, "slot index must fit the 8-bit gpr_idx field");
 static_assert(64 * 16 <= 1024, "lane byte offset (16*lane) must fit the 10 low address bits");
 
+// ---- the wide geometry (tcsc_wide.hip, DESIGN.md §4 "Two geometries") ------
+// 16 waves x 22 columns = 352 columns per workgroup: k_stream_w, unsplit K and
+// the fast order only.  Same chunks, ring, entry format and header as above;
+// slot = column inside the wave (0..21), the header's batch is kWideBatch.
+constexpr int kWideCW = 22;
+constexpr int kWideBatch = 3;
+constexpr int kWideWgCols = kWaves * kWideCW;
+__host__ __device__ constexpr int wide_group_col0(int g) { return (g / kWaves) * kWideWgCols + (g % kWaves) * kWideCW; }
+// groups with at least one of ncols columns
+__host__ __device__ constexpr int wide_groups_for(int ncols) {
+    return (ncols / kWideWgCols) * kWaves + (ncols % kWideWgCols + kWideCW - 1) / kWideCW;
+}
+
 // Input TCSC arrays (device pointers, absolute offsets as in tcsc_t) and the
 // column range a plan covers.
 struct PlanDev {
@@ -190,6 +203,9 @@ struct GemmArgs {
     const int* sptr2 = nullptr;
     long long n_entries2 = 0;
     int n_groups = 0;
+    // columns per wave: kCW (k_stream) or kWideCW (k_stream_w: ent, sptr, n_entries and n_groups
+    // are the wide streams; unsplit K, order 0)
+    int geo = kCW;
     int ncols = 0;
     long long nnz = 0;
     const float* B = nullptr;
@@ -226,6 +242,18 @@ void pf_stream_params(long long n_entries, int n_groups, int n_chunks, int* dist
 size_t workspace_bytes(int M, int ncols, int slices);
 size_t xt_bytes(int M, int K);
 hipError_t launch_gemm(const GemmArgs& g, hipStream_t st);
+// The wide geometry (tcsc_wide.hip).  wide_counts / wide_fill re-group a
+// plan's 16-column streams (ent, sptr: G groups x nch chunks) into Gw =
+// wide_groups_for(ncols) 22-column ones: cnt, cptr (nch*ncols + 1 ints each)
+// and gcnt (Gw*nch + 1) are scratch, tmp serves plan_scan_tmp_bytes of either
+// length; sptr_w (Gw*nch + 1) ends in the entry count, and ent_w holds that
+// many entries + kEntGuard.  launch_stream_wide is launch_gemm's gather
+// launch for GemmArgs::geo == kWideCW.
+hipError_t wide_counts(const int2* ent, const int* sptr, int G, int nch, int ncols, int Gw, int* cnt, int* cptr,
+                       int* gcnt, int* sptr_w, void* tmp, size_t tmp_bytes, hipStream_t st);
+hipError_t wide_fill(const int2* ent, const int* sptr, int G, int nch, int ncols, int Gw, const int* cptr,
+                     const int* sptr_w, int2* ent_w, long long n_entries, hipStream_t st);
+hipError_t launch_stream_wide(const GemmArgs& g, hipStream_t st);
 // tcsc_from_dense on the device
 // tile counts cp/cn ([row tile][col], dense_tile_rows(rows) rows per tile)
 // turned into per-column tile offsets in place; column totals into totp/totn

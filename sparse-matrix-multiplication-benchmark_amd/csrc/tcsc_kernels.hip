@@ -1744,6 +1744,7 @@ hipError_t launch_gemm(const GemmArgs& g, hipStream_t st) {
         if (e != hipSuccess) return e;
     }
     if (g.stage == 1) return hipSuccess;
+    if (g.geo == kWideCW) return launch_stream_wide(g, st);  // the 22-column kernel (tcsc_wide.hip): one K slice
     const int s = choose_slices(g.M, g.ncols, g.K, g.nnz, g.n_groups, g.ws ? g.ws_bytes : 0, g.force_slices);
     if (g.bias_first) return g.prelu ? launch_t<true, true>(g, s, st) : launch_t<true, false>(g, s, st);
     return g.prelu ? launch_t<false, true>(g, s, st) : launch_t<false, false>(g, s, st);

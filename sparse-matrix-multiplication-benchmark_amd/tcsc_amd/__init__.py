@@ -50,6 +50,7 @@ EXPORTED_SYMBOLS = (
     "tcsc_gpu_sgemm_bf16", "tcsc_gpu_launch_info_bf16",
     "tcsc_gpu_plan_enable_i8", "tcsc_gpu_plan_has_i8", "tcsc_gpu_sgemm_i8", "tcsc_gpu_launch_info_i8",
     "tcsc_gpu_quantize_rows_i8", "tcsc_gpu_workspace_bound_i8",
+    "tcsc_gpu_launch_geometry", "tcsc_gpu_wide_pays",
     # include/sparse/bcsr.h
     "bcsr_from_dense", "bcsr_sgemm_basic", "bcsr_sgemm_prelu_basic", "bcsr_sgemm_avx", "bcsr_sgemm_prelu_avx",
     "bcsr_sgemm_avx2", "bcsr_free",
@@ -142,6 +143,8 @@ def lib():
     L.tcsc_gpu_plan_get_info.argtypes = [vp, C.POINTER(plan_info_t)]
     L.tcsc_gpu_launch_info.argtypes = [vp, i, C.POINTER(i), C.POINTER(i)]
     L.tcsc_gpu_launch_combine.argtypes = [vp, i, C.POINTER(i)]
+    L.tcsc_gpu_launch_geometry.argtypes = [vp, i, C.POINTER(i)]
+    L.tcsc_gpu_wide_pays.argtypes = [i, i, i]
     L.tcsc_gpu_plan_reserve.argtypes = [vp, i]
     L.tcsc_gpu_plan_workspace.argtypes = [vp, i, i, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
     L.tcsc_gpu_plan_destroy.argtypes = [vp]
@@ -532,6 +535,13 @@ class Plan:
         v = C.c_int()
         _check(lib().tcsc_gpu_launch_combine(self.handle, int(M), C.byref(v)), "tcsc_gpu_launch_combine")
         return {2: "bands", 3: "pairwise", 4: "pairwise-split"}.get(v.value)
+
+    def launch_geometry(self, M: int) -> int:
+        """Columns per wave of a gather launch of M rows: 16 (k_stream), 22 (k_stream_w, the wide
+        geometry) or 0 when the launch is not on the gather path (tcsc_gpu_launch_geometry)."""
+        v = C.c_int()
+        _check(lib().tcsc_gpu_launch_geometry(self.handle, int(M), C.byref(v)), "tcsc_gpu_launch_geometry")
+        return v.value
 
     def reserve(self, max_M: int) -> None:
         """Allocate the workspace (X^T + split-K slabs) for launches of up to max_M rows."""

@@ -2,6 +2,7 @@
 """Generate the gather loop of kernel K1 (k_stream) for one register geometry.
 
     gen_gather_asm.py [--cw 16] [--batch 4] [--cap 24] [--budget 128] [--depth 1] [--tail 1] [-o path]
+    gen_gather_asm.py --cw 22 --batch 3 --cap 30 --prefix TCSCW -o .../csrc/gather_asm_w22.inc   (the wide geometry)
 
 Why generated: the loop is a fully unrolled, software-pipelined sequence of
 positions whose register names are static per position; writing it by hand
@@ -55,7 +56,7 @@ import sys
 
 class Geo:
     def __init__(self, cw, batch, cap, budget, depth=1, touch=0, tail=1, hdr=4, pf=0):
-        assert cw % 4 == 0 and cap % batch == 0 and 36 + hdr + 2 * cap <= 100
+        assert cw >= 1 and cap % batch == 0 and 36 + hdr + 2 * cap <= 100
         assert hdr == 4 and (hdr + 2 * cap) % 4 == 0
         assert 1 <= depth and depth * batch <= 15, "lgkmcnt counts to 15"
         self.cw, self.batch, self.cap, self.budget, self.depth = cw, batch, cap, budget, depth
@@ -282,10 +283,32 @@ def emit(f, name, lines):
     f.write('    ""\n')
 
 
-def write_inc(path, g):
+def acc_vectors(g):
+    """Widths of the accumulator asm operands (register tuples the compiler
+    can pin: 32, 16 or 8 VGPRs).  4*CW a multiple of 32 or 16: equal vectors
+    (an array in the kernel); otherwise a mixed set, widest first (CW = 22: 88
+    = 32 + 32 + 16 + 8; the kernel holds them as a struct v0, v1, ...)."""
+    n = 4 * g.cw
+    if n % 32 == 0:
+        return [32] * (n // 32), False
+    if n % 16 == 0:
+        return [16] * (n // 16), False
+    ws = []
+    for w in (32, 16, 8, 4):
+        while n >= w:
+            ws.append(w)
+            n -= w
+    assert n == 0
+    return ws, True
+
+
+def write_inc(path, g, prefix="TCSC"):
+    """prefix: the first part of every macro name the file defines, so two
+    generated loops can be included into one library without colliding."""
     global ABL
-    aw = 32 if (4 * g.cw) % 32 == 0 else 16  # accumulator vector width (asm operands)
-    nvec = 4 * g.cw // aw
+    P = prefix
+    widths, mixed = acc_vectors(g)
+    aw, nvec = widths[0], len(widths)
     ndw = g.hdr + 2 * g.cap      # scalar buffer: header + entries
     nsv = ndw // 16              # 16-SGPR vectors of the buffer
     stail = ndw % 16             # + one 4- or 8-SGPR vector
@@ -296,31 +319,36 @@ def write_inc(path, g):
                 f"tail={int(g.tail)}: "
                 f"acc v[{g.acc}:{g.acc + 4 * g.cw - 1}], X v[{g.xbase}:{g.xbase + g.nx - 1}], "
                 f"stream s[{g.sbase}:{g.slast}]\n")
-        f.write(f"#define TCSC_GEN_CW {g.cw}\n#define TCSC_GEN_BATCH {g.batch}\n#define TCSC_GEN_CAP {g.cap}\n")
-        f.write(f"#define TCSC_GEN_HDR {g.hdr}\n")
-        f.write(f"#define TCSC_GEN_BUDGET {g.budget}\n#define TCSC_ACC_W {aw}\n#define TCSC_ACC_VECS {nvec}\n#define TCSC_SBUF_VECS {nsv}\n")
-        f.write(f"#define TCSC_SBUF_TAIL {stail}\n")
-        f.write(f"#define TCSC_GEN_TAIL {int(g.tail)}\n")
-        ops = ", ".join(f'"+{{v[{g.acc + aw * i}:{g.acc + aw * i + aw - 1}]}}"(acc[{i}])' for i in range(nvec))
-        f.write(f"#define TCSC_ACC_OPERANDS(acc) {ops}\n")
+        f.write(f"#define {P}_GEN_CW {g.cw}\n#define {P}_GEN_BATCH {g.batch}\n#define {P}_GEN_CAP {g.cap}\n")
+        f.write(f"#define {P}_GEN_HDR {g.hdr}\n")
+        f.write(f"#define {P}_GEN_BUDGET {g.budget}\n#define {P}_ACC_W {aw}\n#define {P}_ACC_VECS {nvec}\n#define {P}_SBUF_VECS {nsv}\n")
+        f.write(f"#define {P}_SBUF_TAIL {stail}\n")
+        f.write(f"#define {P}_GEN_TAIL {int(g.tail)}\n")
+        ops, r = [], g.acc
+        for i, w in enumerate(widths):
+            ops.append(f'"+{{v[{r}:{r + w - 1}]}}"(acc.v{i})' if mixed else f'"+{{v[{r}:{r + w - 1}]}}"(acc[{i}])')
+            r += w
+        if mixed:
+            f.write(f"#define {P}_ACC_WIDTHS " + ", ".join(str(w) for w in widths) + "\n")
+        f.write(f"#define {P}_ACC_OPERANDS(acc) " + ", ".join(ops) + "\n")
         sops = ", ".join(f'"+{{s[{g.sbuf + 16 * i}:{g.sbuf + 16 * i + 15}]}}"(sb[{i}])' for i in range(nsv))
         if stail:
             t0 = g.sbuf + 16 * nsv
             sops += f', "+{{s[{t0}:{t0 + stail - 1}]}}"(sbt)'
-        f.write(f"#define TCSC_SBUF_OPERANDS(sb, sbt) {sops}\n")
+        f.write(f"#define {P}_SBUF_OPERANDS(sb, sbt) {sops}\n")
         ptr = g.ptr
-        f.write(f'#define TCSC_PTR_OPERAND(p) "+{{s[{ptr}:{ptr + 1}]}}"(p)\n')
+        f.write(f'#define {P}_PTR_OPERAND(p) "+{{s[{ptr}:{ptr + 1}]}}"(p)\n')
         if g.touch:
-            f.write(f'#define TCSC_JUNK_OPERAND(j) [junk] "+{{s{ptr + 2}}}"(j)\n')
+            f.write(f'#define {P}_JUNK_OPERAND(j) [junk] "+{{s{ptr + 2}}}"(j)\n')
         else:
-            f.write('#define TCSC_JUNK_OPERAND(j) [junk] "+s"(j)\n')
-        f.write(f"#define TCSC_GEN_TOUCH {g.touch}\n")
-        f.write(f"#define TCSC_GEN_PF {g.pf}\n")
+            f.write(f'#define {P}_JUNK_OPERAND(j) [junk] "+s"(j)\n')
+        f.write(f"#define {P}_GEN_TOUCH {g.touch}\n")
+        f.write(f"#define {P}_GEN_PF {g.pf}\n")
         clob = ['"memory"', '"scc"']
         clob += [f'"v{r}"' for r in range(g.xbase, g.xbase + g.nx)]
         if SGN == 1:
             clob += [f'"s{r}"' for r in range(SGN_BASE, SGN_BASE + 2 * g.batch)]
-        f.write("#define TCSC_GATHER_CLOBBERS " + ", ".join(clob) + "\n")
+        f.write(f"#define {P}_GATHER_CLOBBERS " + ", ".join(clob) + "\n")
         f.write("#if !defined(TCSC_ABLATION) || TCSC_ABLATION == 0 || TCSC_ABLATION >= 6\n")
         for a in (0, 1, 3, 4, 5):
             if a:
@@ -330,8 +358,8 @@ def write_inc(path, g):
             # s_set_gpr_idx_on/idx write M0[7:0]: the loop saves and restores
             # M0 (operand %[m0sv]), so no compiler-managed M0 value is lost
             # (M0 is a reserved register: a clobber would not be honoured)
-            emit(f, "TCSC_GATHER_ASM", ["s_mov_b32 %[m0sv], m0"] + body + ["s_mov_b32 m0, %[m0sv]"] if body else [])
-        f.write("#else\n#define TCSC_GATHER_ASM \"\"\n#endif\n")
+            emit(f, f"{P}_GATHER_ASM", ["s_mov_b32 %[m0sv], m0"] + body + ["s_mov_b32 m0, %[m0sv]"] if body else [])
+        f.write(f"#else\n#define {P}_GATHER_ASM \"\"\n#endif\n")
         ABL = 0
 
 
@@ -348,12 +376,13 @@ def main():
     ap.add_argument("--pf", type=int, default=0, help="scalar-cache lines prefetched for a stream that will reload")
     ap.add_argument("--sgn", type=int, default=0, help="1/2: rebuild the +-1 multiplier from a sign bit (2 SALU per entry; 2: a batch ahead)")
     here = os.path.dirname(os.path.abspath(__file__))
+    ap.add_argument("--prefix", default="TCSC", help="first part of the generated macro names")
     ap.add_argument("-o", default=os.path.join(here, "..", "sparse-matrix-multiplication-benchmark_amd", "csrc",
                                                "gather_asm.inc"))
     a = ap.parse_args()
     global SGN
     SGN = a.sgn
-    write_inc(a.o, Geo(a.cw, a.batch, a.cap, a.budget, a.depth, a.touch, a.tail, a.hdr, a.pf))
+    write_inc(a.o, Geo(a.cw, a.batch, a.cap, a.budget, a.depth, a.touch, a.tail, a.hdr, a.pf), a.prefix)
     print(a.o)
 
 
