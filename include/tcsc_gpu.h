@@ -243,7 +243,7 @@ int tcsc_gpu_sgemm_prepared(const tcsc_gpu_plan *plan, const float *dB, float *d
  * contract is tcsc_gpu_sgemm's on the widened X: bit-exact on integer-valued
  * inputs, within 2^-20 (|b| + sum |x|) otherwise; on one path and K split the
  * bits are those of tcsc_gpu_sgemm(X widened to fp32).
- *   gather : k_transpose_bf16 widens X into the same fp32 X^T; k_stream, the
+ *   gather : k_transpose's bf16 form widens X into the same fp32 X^T; k_stream, the
  *            reduce and the in-launch combine are the fp32 call's
  *   small  : k_small_m stages the widened rows (M <= 4)
  *   MFMA   : k_pack1 (X -> X1, M x 64-k blocks of bf16, and the row flags
@@ -306,8 +306,8 @@ int tcsc_gpu_launch_info_bf16(const tcsc_gpu_plan *plan, int M, int *path, int *
  *          flags and no fixup: integers are never non-finite or tiny.
  *   gather and small M: the bits of tcsc_gpu_sgemm on the fp32 matrix
  *          Xs[m, k] = fl(s[m] * float(q[m, k])) on the same path and K split;
- *          the scale is folded in while staging (k_transpose_i8, k_small_m's
- *          int8 staging), everything after is the fp32 call's.
+ *          the scale is folded in while staging (the int8 forms of k_transpose
+ *          and of k_small_m's staging), everything after is the fp32 call's.
  *   On every path the result is exact when s is NULL or a power of two and
  *   |S| < 2^24; otherwise within 2^-20 (|b| + s sum |q|).
  * Routing: the bf16 cost model with the GEMM at twice the rate and half the

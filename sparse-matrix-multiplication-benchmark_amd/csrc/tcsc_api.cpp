@@ -276,28 +276,70 @@ int path_mode() {  // 0 auto, 1 gather only, 2 mfma forced
 
 size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
-// workspace of one MFMA launch: X3 (M x mfma_ldk(K) bf16), M row flags, and
-// the split-K slabs of a small grid (tcsc::mfma_slices; none for big tiles)
-size_t mfma_flags_off(int M, int K) { return align256((size_t)M * tcsc::mfma_ldk(K) * 2); }
-size_t mfma_slabs_off(int M, int K) { return mfma_flags_off(M, K) + align256((size_t)M * sizeof(int)); }
-size_t mfma_ws_bytes(int M, int K, int N) { return mfma_slabs_off(M, K) + tcsc::mfma_slab_bytes(M, N, K); }
-// the same for a bf16 call: X1 (M x mfma_ldw(K) bf16, a third of X3), the
-// flags, the same slabs -- never more than the fp32 call's, so what
-// tcsc_gpu_plan_workspace reports and tcsc_gpu_plan_reserve allocates covers it
-size_t mfma1_flags_off(int M, int K) { return align256((size_t)M * tcsc::mfma_ldw(K) * 2); }
-size_t mfma1_slabs_off(int M, int K) { return mfma1_flags_off(M, K) + align256((size_t)M * sizeof(int)); }
-size_t mfma1_ws_bytes(int M, int K, int N) { return mfma1_slabs_off(M, K) + tcsc::mfma_slab_bytes(M, N, K); }
-// and for an int8 call: X8 (M x mfma8_ldw(K) bytes), no flags, the i32 slabs.
-//   mfma8_ws_bytes(M, K, N) <= mfma_ws_bytes(M, K, N) for every M, K, N:
+// What the fp32, bf16 and int8 calls differ in on the host, indexed by the
+// activation type (tcsc::kF32 / kBf16 / kI8); everything below that routes,
+// sizes or stages a call reads it from here.  The kernels' side is XSrc
+// (tcsc_xsrc.h).
+using tcsc::kBf16;
+using tcsc::kF32;
+using tcsc::kI8;
+struct XType {
+    const char* sgemm;  // the entry point, as error messages name it
+    size_t elem;        // bytes of one element of X
+    // MFMA path: the packed X (X3: [h | m | l] blocks of bf16; X1: the bf16 row;
+    // X8: the int8 row) is M rows of ldx(K) elements of pack_elem bytes, W's
+    // image has rows of ldw(K) elements
+    int (*ldx)(int K);
+    size_t pack_elem;
+    int (*ldw)(int K);
+    bool flags;  // the pack flags the rows its format cannot carry and a fixup recomputes them
+    int (*slices)(int M, int N, int K);  // the GEMM's K split
+    size_t slab_elem;                    // bytes of one element of its split-K slabs
+    // cost model of the GEMM (mfma_cheaper): ops per (m, k, n), ops per
+    // microsecond, microseconds per k of one workgroup's K walk
+    double ops, rate, walk_us;
+};
+// fp32: the bf16 x3 GEMM's 6 flops per (m, k, n) at ~1.5 PFLOP/s, ~24 ns per k.
+// bf16: one part instead of three -- 2 flops, a third of the sub-steps in the
+// walk (~8.1 ns per k); derived from the fp32 fit, checked against
+// tools/crossover.py --dtype bf16.  int8: 2 ops at twice the
+// bf16 rate (v_mfma_i32_16x16x64_i8) and half the bf16 sub-steps per k (128-k
+// blocks: ~4.1 ns per k), with the int8 GEMM's own K split; checked against
+// tools/crossover.py --dtype i8.
+constexpr XType kXTypes[3] = {
+    // sgemm, elem, ldx, pack_elem, ldw, flags, slices, slab_elem, ops, rate, walk_us
+    {"tcsc_gpu_sgemm", 4, tcsc::mfma_ldk, 2, tcsc::mfma_ldw, true, tcsc::mfma_slices, 4, 6.0, 1.5e9, 0.0244},
+    {"tcsc_gpu_sgemm_bf16", 2, tcsc::mfma_ldw, 2, tcsc::mfma_ldw, true, tcsc::mfma_slices, 4, 2.0, 1.5e9,
+     0.0244 / 3.0},
+    {"tcsc_gpu_sgemm_i8", 1, tcsc::mfma8_ldw, 1, tcsc::mfma8_ldw, false, tcsc::mfma8_slices, 4, 2.0, 3.0e9,
+     0.0244 / 6.0},
+};
+
+// Workspace of one MFMA launch: [packed X][M row flags, where the type keeps
+// them][split-K slabs of a small grid (XType::slices; none for big tiles)],
+// each part rounded up to 256 bytes.
+// The bf16 call's never exceeds the fp32 call's (X1 is a third of X3, the rest
+// is the same), and neither does the int8 call's, for every M, K, N:
 //   * mfma8_ldw(K) = 128 ceil(K / 128) <= 128 ceil(K / 64) <= 384 ceil(K / 64) =
-//     2 mfma_ldk(K) bytes, and align256 is monotone, so mfma8_slabs_off <=
-//     mfma_flags_off <= mfma_slabs_off;
+//     2 mfma_ldk(K) bytes, and align256 is monotone, so int8's slabs_off <=
+//     fp32's flags_off <= fp32's slabs_off;
 //   * mfma8_slices <= mfma_slices by construction (tcsc_mfma.hip) and both
-//     slabs hold 4 B per element, so mfma8_slab_bytes <= mfma_slab_bytes.
-// So tcsc_gpu_plan_workspace and tcsc_gpu_plan_reserve cover int8 launches as
-// they are (tests/test_i8_api.py sweeps the inequality).
-size_t mfma8_slabs_off(int M, int K) { return align256((size_t)M * tcsc::mfma8_ldw(K)); }
-size_t mfma8_ws_bytes(int M, int K, int N) { return mfma8_slabs_off(M, K) + tcsc::mfma8_slab_bytes(M, N, K); }
+//     slabs hold 4 B per element, so int8's slabs are no larger.
+// So tcsc_gpu_plan_workspace and tcsc_gpu_plan_reserve, which size the MFMA
+// path for fp32, cover bf16 and int8 launches as they are (tests/test_i8_api.py
+// sweeps the inequality).
+struct MfmaWs {
+    size_t flags_off, slabs_off, bytes;
+};
+MfmaWs mfma_ws(int dt, int M, int K, int N) {
+    const XType& d = kXTypes[dt];
+    MfmaWs w;
+    w.flags_off = align256((size_t)M * d.ldx(K) * d.pack_elem);
+    w.slabs_off = w.flags_off + (d.flags ? align256((size_t)M * sizeof(int)) : 0);
+    const int s = d.slices(M, N, K);
+    w.bytes = w.slabs_off + (s > 1 ? (size_t)s * M * N * d.slab_elem : 0);
+    return w;
+}
 
 // Variants 0-4 are the tcsc_sgemm_* family (sparse/tcsc.h); 5 is
 // SparseGEMM.h's sparseGEMM<float> (bias last, no activation).  Bias first
@@ -311,64 +353,33 @@ bool is_prelu(int v) { return v >= TCSC_VARIANT_PRELU_BASIC && v <= TCSC_VARIANT
 //  * gather: ~38 us fixed + one add per nonzero and row of the 256-row tiles
 //    it runs (M rounded up to 256) at ~23 T adds/s;
 //  * MFMA: ~10 us fixed (k_split3, k_fixup, launches) + the larger of the
-//    bf16 x3 GEMM's 6 flops per (m, k, n) at ~1.5 PFLOP/s and the K walk of
-//    one workgroup (~24 ns per k, the slice's share when K is split; x1.5
-//    with two workgroups per CU), + for a split K the slab reduce (~3 us +
-//    the slabs read and Y written at ~4 TB/s).
+//    GEMM's ops per (m, k, n) at its rate (XType: fp32's bf16 x3 GEMM is 6
+//    flops at ~1.5 PFLOP/s) and the K walk of one workgroup (fp32 ~24 ns per
+//    k, the slice's share when K is split; x1.5 with two workgroups per CU),
+//    + for a split K the slab reduce (~3 us + the slabs read and Y written at
+//    ~4 TB/s).
 // With these constants the default plan is within 1.02x of the faster
-// forced path at every measured point.
-bool mfma_cheaper(const tcsc_gpu_plan* p, int M) {
-    const double nnz = (double)(p->n_pos + p->n_neg), Kb = (double)tcsc::mfma_ldw(p->rows);
+// forced path at every measured point.  The gather term, the fixed cost and
+// the reduce are the same for every activation type (only the gather's
+// transpose reads less).
+bool mfma_cheaper(const tcsc_gpu_plan* p, int M, int dt) {
+    const XType& d = kXTypes[dt];
+    const double nnz = (double)(p->n_pos + p->n_neg), Kb = (double)d.ldw(p->rows);
     const double Mp = (double)(((long long)M + tcsc::kTM - 1) / tcsc::kTM * tcsc::kTM);
     const double gather_us = 38.0 + Mp * nnz / 23.0e6;
-    const int s = tcsc::mfma_slices(M, p->cols, p->rows);
-    const double walk_us = Kb * 0.0244 / s * (tcsc::mfma_tiles(M, p->cols) * s > 256 ? 1.5 : 1.0);
+    const int s = d.slices(M, p->cols, p->rows);
+    const double walk_us = Kb * d.walk_us / s * (tcsc::mfma_tiles(M, p->cols) * s > 256 ? 1.5 : 1.0);
     const double reduce_us = s > 1 ? 3.0 + (s + 1.0) * M * p->cols * 4.0 / 4.0e6 : 0.0;
-    const double mfma_us = 10.0 + std::max(6.0 * M * Kb * p->cols / 1.5e9, walk_us) + reduce_us;
+    const double mfma_us = 10.0 + std::max(d.ops * M * Kb * p->cols / d.rate, walk_us) + reduce_us;
     return mfma_us < gather_us;
 }
-
-// The bf16 call's model: the same gather (only its transpose reads less), the
-// GEMM with one part instead of three -- 2 flops per (m, k, n), and a third of
-// the sub-steps in a workgroup's K walk (~8.1 ns per k).  The fixed cost and
-// the reduce are the fp32 call's.  Derived from the fp32 fit, checked against
-// tools/crossover.py --dtype bf16.
-bool mfma_cheaper_bf16(const tcsc_gpu_plan* p, int M) {
-    const double nnz = (double)(p->n_pos + p->n_neg), Kb = (double)tcsc::mfma_ldw(p->rows);
-    const double Mp = (double)(((long long)M + tcsc::kTM - 1) / tcsc::kTM * tcsc::kTM);
-    const double gather_us = 38.0 + Mp * nnz / 23.0e6;
-    const int s = tcsc::mfma_slices(M, p->cols, p->rows);
-    const double walk_us = Kb * (0.0244 / 3.0) / s * (tcsc::mfma_tiles(M, p->cols) * s > 256 ? 1.5 : 1.0);
-    const double reduce_us = s > 1 ? 3.0 + (s + 1.0) * M * p->cols * 4.0 / 4.0e6 : 0.0;
-    const double mfma_us = 10.0 + std::max(2.0 * M * Kb * p->cols / 1.5e9, walk_us) + reduce_us;
-    return mfma_us < gather_us;
-}
-
-// The int8 call's model, derived from the bf16 one as that was from the fp32
-// fit: the same gather term, the GEMM's 2 ops per (m, k, n) at twice the bf16
-// rate (v_mfma_i32_16x16x64_i8), and half the sub-steps per k in a workgroup's
-// K walk (128-k blocks: ~4.1 ns per k), with the int8 GEMM's own K split.
-// Checked against tools/crossover.py --dtype i8.
-bool mfma_cheaper_i8(const tcsc_gpu_plan* p, int M) {
-    const double nnz = (double)(p->n_pos + p->n_neg), Kb = (double)tcsc::mfma8_ldw(p->rows);
-    const double Mp = (double)(((long long)M + tcsc::kTM - 1) / tcsc::kTM * tcsc::kTM);
-    const double gather_us = 38.0 + Mp * nnz / 23.0e6;
-    const int s = tcsc::mfma8_slices(M, p->cols, p->rows);
-    const double walk_us = Kb * (0.0244 / 6.0) / s * (tcsc::mfma_tiles(M, p->cols) * s > 256 ? 1.5 : 1.0);
-    const double reduce_us = s > 1 ? 3.0 + (s + 1.0) * M * p->cols * 4.0 / 4.0e6 : 0.0;
-    const double mfma_us = 10.0 + std::max(2.0 * M * Kb * p->cols / 3.0e9, walk_us) + reduce_us;
-    return mfma_us < gather_us;
-}
-
-// the activation type of a call: each has its own GEMM and cost model
-enum { kF32 = 0, kBf16 = 1, kI8 = 2 };
 
 // forced (TCSC_PATH=mfma: mfma_min_M 1): every launch; default: by the cost
 // model.  An int8 call needs the int8 image (tcsc_gpu_plan_enable_i8).
 bool use_mfma(const tcsc_gpu_plan* p, int M, int dt = kF32) {
     if (!p->wt || (dt == kI8 && !p->w8) || M < p->mfma_min_M || p->rows <= 0) return false;
     if (p->mfma_min_M == 1) return true;
-    return dt == kI8 ? mfma_cheaper_i8(p, M) : dt == kBf16 ? mfma_cheaper_bf16(p, M) : mfma_cheaper(p, M);
+    return mfma_cheaper(p, M, dt);
 }
 
 rocblas_handle rocblas_for_device(int dev) {
@@ -587,7 +598,7 @@ size_t path_ws_bytes(const tcsc_gpu_plan* p, int M, int path) {
         case TCSC_PATH_GATHER:
             return gather_ws_bytes(p, M);
         case TCSC_PATH_MFMA:
-            return p->wt && M >= p->mfma_min_M && p->rows > 0 ? mfma_ws_bytes(M, p->rows, p->cols) : 0;
+            return p->wt && M >= p->mfma_min_M && p->rows > 0 ? mfma_ws(kF32, M, p->rows, p->cols).bytes : 0;
         case TCSC_PATH_SMALL:  // staged X (prepare_x)
             return p->crq && p->rows > 0 && M <= small_max_m() && tcsc::small_m_fits(M, p->rows)
                        ? align256((size_t)M * p->rows * sizeof(float))
@@ -596,40 +607,21 @@ size_t path_ws_bytes(const tcsc_gpu_plan* p, int M, int path) {
     return 0;
 }
 
-// bf16: the path of a tcsc_gpu_sgemm_bf16 call (its own mfma_cheaper)
+// the path of a call of type dt (each type has its own cost model)
 int launch_path(const tcsc_gpu_plan* p, int M, int dt = kF32) {
     return use_mfma(p, M, dt) ? TCSC_PATH_MFMA : use_small(p, M, dt) ? TCSC_PATH_SMALL : TCSC_PATH_GATHER;
 }
 
-// Workspace of the call tcsc_gpu_sgemm makes at this M.
-size_t wanted_workspace(const tcsc_gpu_plan* p, int M) { return path_ws_bytes(p, M, launch_path(p, M)); }
-
-// Workspace of the call tcsc_gpu_sgemm_bf16 makes at this M: the gather's is
-// the fp32 call's (the same fp32 X^T and slabs), the MFMA path's holds X1
-// for X3, the small-M path reads X in place.
-size_t wanted_workspace_bf16(const tcsc_gpu_plan* p, int M) {
+// Workspace of the call of type dt at this M.  The gather's is the same for
+// every type (the same fp32 X^T and slabs), the MFMA path holds the type's
+// packed X, and on the small-M path only the fp32 call has a staged form
+// (tcsc_gpu_prepare_x's copy of X): the narrow types read X in place.
+size_t wanted_workspace(const tcsc_gpu_plan* p, int M, int dt = kF32) {
     if (M <= 0 || p->cols == 0) return 0;
-    switch (launch_path(p, M, kBf16)) {
-        case TCSC_PATH_GATHER:
-            return gather_ws_bytes(p, M);
-        case TCSC_PATH_MFMA:
-            return mfma1_ws_bytes(M, p->rows, p->cols);
-    }
-    return 0;
-}
-
-// And of the call tcsc_gpu_sgemm_i8 makes: the gather's again, X8 and the i32
-// slabs on the MFMA path (never more than the fp32 call's: mfma8_ws_bytes),
-// nothing for small M.
-size_t wanted_workspace_i8(const tcsc_gpu_plan* p, int M) {
-    if (M <= 0 || p->cols == 0) return 0;
-    switch (launch_path(p, M, kI8)) {
-        case TCSC_PATH_GATHER:
-            return gather_ws_bytes(p, M);
-        case TCSC_PATH_MFMA:
-            return mfma8_ws_bytes(M, p->rows, p->cols);
-    }
-    return 0;
+    const int path = launch_path(p, M, dt);
+    if (path == TCSC_PATH_MFMA) return mfma_ws(dt, M, p->rows, p->cols).bytes;
+    if (path == TCSC_PATH_SMALL && dt != kF32) return 0;
+    return path_ws_bytes(p, M, path);
 }
 
 // tcsc_gpu_plan_reserve(max_M): the largest need of any M <= max_M on any path
@@ -892,73 +884,54 @@ int launch_geo(const tcsc_gpu_plan* p, int M, int slices, int forced_slices, con
 }  // namespace
 
 namespace {
-// The MFMA path (stage 0: all; 1: split only; 2: GEMM + fixup on the staged
-// X3): k_split3 (X -> X3 + row flags), k_gemm3 (Y = act(X3 . WT^T + B),
-// the bias and PReLU in its store), k_fixup (the flagged rows, exact).
-int sgemm_mfma(const tcsc_gpu_plan* p, const float* dX, const float* dB, float* dY, int M, int ldy, int variant,
-               float a, void* stream, float* ws, size_t ws_bytes, int stage) {
-    const int K = p->rows, N = p->cols, ldk = tcsc::mfma_ldk(K);
-    const size_t need = mfma_ws_bytes(M, K, N);
-    if (!ws || ws_bytes < need) {
-        set_error("tcsc_gpu_sgemm: workspace of %zu bytes < %zu needed for M=%d", ws ? ws_bytes : (size_t)0, need, M);
+// The MFMA path: pack X into the type's GEMM operand in the workspace, run
+// the GEMM against W's image (the bias and PReLU in its store), and where the
+// type keeps row flags rewrite the flagged rows exactly.
+//   fp32: k_split3 (X -> X3 + flags), k_gemm3, k_fixup; stage 1 is the split
+//         only, stage 2 the GEMM + fixup on the staged X3 (fp32 alone has stages)
+//   bf16: k_pack1 (X -> X1 + flags, k_split3's rule), the one-part k_gemm3 and k_fixup
+//   int8: k_pack8 (X -> X8), k_gemm8 against the int8 image (+ k_reduce_i8 when
+//         K is split) with the row scales; no flags, no fixup
+int sgemm_mfma(const tcsc_gpu_plan* p, const void* dX, int dt, const float* dScale, const float* dB, float* dY, int M,
+               int ldy, int variant, float a, void* stream, float* ws, size_t ws_bytes, int stage) {
+    const XType& d = kXTypes[dt];
+    const int K = p->rows, N = p->cols, ldx = d.ldx(K), ldw = d.ldw(K);
+    const MfmaWs w = mfma_ws(dt, M, K, N);
+    if (!ws || ws_bytes < w.bytes) {
+        set_error("%s: workspace of %zu bytes < %zu needed for M=%d", d.sgemm, ws ? ws_bytes : (size_t)0, w.bytes, M);
         return TCSC_E_ARG;
     }
     hipStream_t st = static_cast<hipStream_t>(stream);
-    uint16_t* x3 = reinterpret_cast<uint16_t*>(ws);
-    int* flags = reinterpret_cast<int*>(reinterpret_cast<char*>(ws) + mfma_flags_off(M, K));
-    float* slabs = reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + mfma_slabs_off(M, K));
-    if (stage != 2) HIP_TRY(tcsc::mfma_split_x(dX, M, K, x3, ldk, flags, st));
-    if (stage == 1) return TCSC_OK;
+    char* base = reinterpret_cast<char*>(ws);
+    uint16_t* xp = reinterpret_cast<uint16_t*>(base);
+    int* flags = reinterpret_cast<int*>(base + w.flags_off);
+    void* slabs = base + w.slabs_off;
+    const size_t slab_bytes = ws_bytes - w.slabs_off;
     const bool prelu = is_prelu(variant);
-    HIP_TRY(tcsc::mfma_gemm3(x3, ldk, p->wt, tcsc::mfma_ldw(K), K, M, N, dB, dY, ldy, prelu, a, slabs,
-                             ws_bytes - mfma_slabs_off(M, K), flags, p->ccq, p->crq, st));
+    switch (dt) {
+        case kF32:
+            if (stage != 2) HIP_TRY(tcsc::mfma_split_x(static_cast<const float*>(dX), M, K, xp, ldx, flags, st));
+            if (stage == 1) return TCSC_OK;
+            HIP_TRY(tcsc::mfma_gemm3(xp, ldx, p->wt, ldw, K, M, N, dB, dY, ldy, prelu, a, static_cast<float*>(slabs),
+                                     slab_bytes, flags, p->ccq, p->crq, st));
+            break;
+        case kBf16:
+            HIP_TRY(tcsc::mfma_pack_x(static_cast<const uint16_t*>(dX), M, K, xp, ldx, flags, st));
+            HIP_TRY(tcsc::mfma_gemm1(xp, ldx, p->wt, ldw, K, M, N, dB, dY, ldy, prelu, a, static_cast<float*>(slabs),
+                                     slab_bytes, flags, p->ccq, p->crq, st));
+            break;
+        case kI8:
+            HIP_TRY(tcsc::mfma8_pack_x(static_cast<const int8_t*>(dX), M, K, reinterpret_cast<int8_t*>(base), ldx, st));
+            HIP_TRY(tcsc::mfma8_gemm(reinterpret_cast<const int8_t*>(base), p->w8, ldx, K, M, N, dScale, dB, dY, ldy,
+                                     prelu, a, static_cast<int*>(slabs), slab_bytes, st));
+            break;
+    }
     // fast order: bias after the sum for every variant; a
     // split K rewrote the flagged rows in its reduce already
-    if (tcsc::mfma_slices(M, N, K) <= 1)
-        HIP_TRY(tcsc::mfma_fixup(x3, M, K, ldk, p->ccq, p->crq, N, dB, dY, ldy, false, prelu, a, flags, st));
-    return TCSC_OK;
-}
-
-// The same for bf16 X: k_pack1 (X -> X1 + row flags, k_split3's rule), the
-// one-part k_gemm3, the one-part k_fixup.
-int sgemm_mfma_bf16(const tcsc_gpu_plan* p, const uint16_t* dX, const float* dB, float* dY, int M, int ldy,
-                    int variant, float a, void* stream, float* ws, size_t ws_bytes) {
-    const int K = p->rows, N = p->cols, ldw = tcsc::mfma_ldw(K);
-    const size_t need = mfma1_ws_bytes(M, K, N);
-    if (!ws || ws_bytes < need) {
-        set_error("tcsc_gpu_sgemm_bf16: workspace of %zu bytes < %zu needed for M=%d", ws ? ws_bytes : (size_t)0, need,
-                  M);
-        return TCSC_E_ARG;
+    if (d.flags && d.slices(M, N, K) <= 1) {
+        const auto fixup = dt == kF32 ? tcsc::mfma_fixup : tcsc::mfma_fixup1;
+        HIP_TRY(fixup(xp, M, K, ldx, p->ccq, p->crq, N, dB, dY, ldy, false, prelu, a, flags, st));
     }
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    uint16_t* x1 = reinterpret_cast<uint16_t*>(ws);
-    int* flags = reinterpret_cast<int*>(reinterpret_cast<char*>(ws) + mfma1_flags_off(M, K));
-    float* slabs = reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + mfma1_slabs_off(M, K));
-    HIP_TRY(tcsc::mfma_pack_x(dX, M, K, x1, ldw, flags, st));
-    const bool prelu = is_prelu(variant);
-    HIP_TRY(tcsc::mfma_gemm1(x1, ldw, p->wt, ldw, K, M, N, dB, dY, ldy, prelu, a, slabs,
-                             ws_bytes - mfma1_slabs_off(M, K), flags, p->ccq, p->crq, st));
-    if (tcsc::mfma_slices(M, N, K) <= 1)
-        HIP_TRY(tcsc::mfma_fixup1(x1, M, K, ldw, p->ccq, p->crq, N, dB, dY, ldy, false, prelu, a, flags, st));
-    return TCSC_OK;
-}
-
-// And for int8 X with row scales: k_pack8 (X -> X8), k_gemm8 against the int8
-// image (+ k_reduce_i8 when K is split).  No flags, no fixup.
-int sgemm_mfma_i8(const tcsc_gpu_plan* p, const int8_t* dX, const float* dScale, const float* dB, float* dY, int M,
-                  int ldy, int variant, float a, void* stream, float* ws, size_t ws_bytes) {
-    const int K = p->rows, N = p->cols, ld8 = tcsc::mfma8_ldw(K);
-    const size_t need = mfma8_ws_bytes(M, K, N);
-    if (!ws || ws_bytes < need) {
-        set_error("tcsc_gpu_sgemm_i8: workspace of %zu bytes < %zu needed for M=%d", ws ? ws_bytes : (size_t)0, need, M);
-        return TCSC_E_ARG;
-    }
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    int8_t* x8 = reinterpret_cast<int8_t*>(ws);
-    int* slabs = reinterpret_cast<int*>(reinterpret_cast<char*>(ws) + mfma8_slabs_off(M, K));
-    HIP_TRY(tcsc::mfma8_pack_x(dX, M, K, x8, ld8, st));
-    HIP_TRY(tcsc::mfma8_gemm(x8, p->w8, ld8, K, M, N, dScale, dB, dY, ldy, is_prelu(variant), a, slabs,
-                             ws_bytes - mfma8_slabs_off(M, K), st));
     return TCSC_OK;
 }
 
@@ -974,17 +947,13 @@ struct Route {
     int slices = 0;
 };
 
-// dt: dX_ is M x K fp32, bf16 bit patterns (tcsc_gpu_sgemm_bf16) or int8 with
-// the row scales dScale, null for ones (tcsc_gpu_sgemm_i8); the narrow types
-// have stage 0 only.
-int sgemm_ws(const tcsc_gpu_plan* p, const void* dX_, const float* dB, float* dY, int M, int ldy, int variant,
+// dX is M x K of type dt (with the int8 type the row scales dScale, null for
+// ones); the narrow types have stage 0 only.
+int sgemm_ws(const tcsc_gpu_plan* p, const void* dX, const float* dB, float* dY, int M, int ldy, int variant,
              float a, void* stream, float* ws, size_t ws_bytes, int stage = 0, Route* route = nullptr,
              int dt = kF32, const float* dScale = nullptr) {
-    const bool bf16 = dt == kBf16, i8 = dt == kI8;
-    const float* dX = dt == kF32 ? static_cast<const float*>(dX_) : nullptr;
-    const uint16_t* dXb = bf16 ? static_cast<const uint16_t*>(dX_) : nullptr;
-    const int8_t* dXq = i8 ? static_cast<const int8_t*>(dX_) : nullptr;
-    const char* who = i8 ? "tcsc_gpu_sgemm_i8" : bf16 ? "tcsc_gpu_sgemm_bf16" : "tcsc_gpu_sgemm";
+    const XType& d = kXTypes[dt];
+    const char* who = d.sgemm;
     if (dt != kF32 && stage != 0) {
         set_error("%s: no staged form", who);
         return TCSC_E_ARG;
@@ -994,7 +963,7 @@ int sgemm_ws(const tcsc_gpu_plan* p, const void* dX_, const float* dB, float* dY
         return TCSC_E_ARG;
     }
     if (M == 0 || p->cols == 0) return TCSC_OK;
-    if ((stage != 1 && (!dY || !dB)) || (stage != 2 && !dX_ && p->rows > 0)) {
+    if ((stage != 1 && (!dY || !dB)) || (stage != 2 && !dX && p->rows > 0)) {
         set_error("%s: NULL device pointer", who);
         return TCSC_E_ARG;
     }
@@ -1004,13 +973,8 @@ int sgemm_ws(const tcsc_gpu_plan* p, const void* dX_, const float* dB, float* dY
     if (route->path != TCSC_PATH_GATHER) route->path = launch_path(p, M, dt);
     route->slices = 1;
     if (route->path == TCSC_PATH_MFMA) {
-        if (i8) {
-            route->slices = tcsc::mfma8_slices(M, p->cols, p->rows);
-            return sgemm_mfma_i8(p, dXq, dScale, dB, dY, M, ldy, variant, a, stream, ws, ws_bytes);
-        }
-        route->slices = tcsc::mfma_slices(M, p->cols, p->rows);
-        if (bf16) return sgemm_mfma_bf16(p, dXb, dB, dY, M, ldy, variant, a, stream, ws, ws_bytes);
-        return sgemm_mfma(p, dX, dB, dY, M, ldy, variant, a, stream, ws, ws_bytes, stage);
+        route->slices = d.slices(M, p->cols, p->rows);
+        return sgemm_mfma(p, dX, dt, dScale, dB, dY, M, ldy, variant, a, stream, ws, ws_bytes, stage);
     }
     if (route->path == TCSC_PATH_SMALL) {
         // stage 1 stages X as is (the kernel reads X rows directly), stage 2 reads the staged copy
@@ -1025,18 +989,8 @@ int sgemm_ws(const tcsc_gpu_plan* p, const void* dX_, const float* dB, float* dY
             HIP_TRY(hipMemcpyAsync(ws, dX, xb, hipMemcpyDeviceToDevice, st));
             return TCSC_OK;
         }
-        if (i8) {
-            HIP_TRY(tcsc::launch_small_m_i8(dXq, dScale, M, p->rows, p->ccq, p->crq, p->cols, dB, dY, ldy, false,
-                                            is_prelu(variant), a, st));
-            return TCSC_OK;
-        }
-        if (bf16) {
-            HIP_TRY(tcsc::launch_small_m_bf16(dXb, M, p->rows, p->ccq, p->crq, p->cols, dB, dY, ldy, false,
-                                              is_prelu(variant), a, st));
-            return TCSC_OK;
-        }
-        HIP_TRY(tcsc::launch_small_m(stage == 2 ? ws : dX, M, p->rows, p->ccq, p->crq, p->cols, dB, dY, ldy, false,
-                                     is_prelu(variant), a, st));
+        HIP_TRY(tcsc::launch_small_m(stage == 2 ? ws : dX, dt, dScale, M, p->rows, p->ccq, p->crq, p->cols, dB, dY, ldy,
+                                     false, is_prelu(variant), a, st));
         return TCSC_OK;
     }
     // gather-path limits: X^T row tiles of 64 rows on the transpose grid's y
@@ -1057,9 +1011,7 @@ int sgemm_ws(const tcsc_gpu_plan* p, const void* dX_, const float* dB, float* dY
         for (int r0 = 0; r0 < M; r0 += kMaxLaunchRows) {
             const int r = std::min(kMaxLaunchRows, M - r0);
             Route piece{TCSC_PATH_GATHER, force_slices > 0 ? force_slices : 1};  // a short tail stays on the gather too
-            const void* xr = i8     ? static_cast<const void*>(dXq + (size_t)r0 * p->rows)
-                             : bf16 ? static_cast<const void*>(dXb + (size_t)r0 * p->rows)
-                                    : static_cast<const void*>(dX + (size_t)r0 * p->rows);
+            const void* xr = static_cast<const char*>(dX) + (size_t)r0 * p->rows * d.elem;
             const int rc = sgemm_ws(p, xr, dB, dY + (size_t)r0 * ldy, r, ldy, variant, a, stream, ws, ws_bytes, 0,
                                     &piece, dt, dScale ? dScale + r0 : nullptr);
             if (rc != TCSC_OK) return rc;
@@ -1074,8 +1026,7 @@ int sgemm_ws(const tcsc_gpu_plan* p, const void* dX_, const float* dB, float* dY
     }
     tcsc::GemmArgs g;
     g.X = dX;
-    g.Xb = dXb;
-    g.Xq = dXq;
+    g.xtype = dt;
     g.Xscale = dScale;
     g.XT = p->rows > 0 ? ws : nullptr;
     g.M = M;
@@ -1371,7 +1322,7 @@ static int launch_info_impl(const char* who, const tcsc_gpu_plan* p, int M, int*
     *slices = 1;
     if (use_mfma(p, M, dt)) {
         *path = TCSC_PATH_MFMA;
-        *slices = dt == kI8 ? tcsc::mfma8_slices(M, p->cols, p->rows) : tcsc::mfma_slices(M, p->cols, p->rows);
+        *slices = kXTypes[dt].slices(M, p->cols, p->rows);
         return TCSC_OK;
     }
     if (use_small(p, M, dt)) {
@@ -1437,29 +1388,29 @@ int tcsc_gpu_launch_combine(const tcsc_gpu_plan* p, int M, int* in_launch) {
     return TCSC_OK;
 }
 
-int tcsc_gpu_sgemm(const tcsc_gpu_plan* p, const float* dX, const float* dB, float* dY, int M, int ldy,
-                   int variant, float a, void* stream) {
-    // grow the workspace on first use at a larger M (tcsc_gpu_plan_reserve
-    // up front keeps this call allocation-free and graph-capturable)
-    if (p && M > 0 && p->cols > 0 && p->ws_bytes < wanted_workspace(p, M)) {
+// tcsc_gpu_sgemm{,_bf16,_i8}: grow the workspace on first use at a larger M
+// (tcsc_gpu_plan_reserve up front keeps the call allocation-free and
+// graph-capturable: its size covers every launch of every type, mfma_ws),
+// then run on it.
+static int sgemm_entry(const tcsc_gpu_plan* p, const void* dX, int dt, const float* dScale, const float* dB, float* dY,
+                       int M, int ldy, int variant, float a, void* stream) {
+    if (p && M > 0 && p->cols > 0 && p->ws_bytes < wanted_workspace(p, M, dt)) {
         const int rc = tcsc_gpu_plan_reserve(const_cast<tcsc_gpu_plan*>(p), M);
         if (rc != TCSC_OK) return rc;
     }
-    if (p) const_cast<tcsc_gpu_plan*>(p)->staged_M = -1;  // this call's X^T replaces any staged one
-    return sgemm_ws(p, dX, dB, dY, M, ldy, variant, a, stream, p ? p->ws : nullptr, p ? p->ws_bytes : 0);
+    if (p) const_cast<tcsc_gpu_plan*>(p)->staged_M = -1;  // this call's X^T or packed X replaces any staged one
+    return sgemm_ws(p, dX, dB, dY, M, ldy, variant, a, stream, p ? p->ws : nullptr, p ? p->ws_bytes : 0, 0, nullptr, dt,
+                    dScale);
+}
+
+int tcsc_gpu_sgemm(const tcsc_gpu_plan* p, const float* dX, const float* dB, float* dY, int M, int ldy,
+                   int variant, float a, void* stream) {
+    return sgemm_entry(p, dX, kF32, nullptr, dB, dY, M, ldy, variant, a, stream);
 }
 
 int tcsc_gpu_sgemm_bf16(const tcsc_gpu_plan* p, const void* dX_bf16, const float* dB, float* dY, int M, int ldy,
                         int variant, float a, void* stream) {
-    // tcsc_gpu_plan_reserve's size covers every bf16 launch (never more than
-    // the fp32 call's need on the same path), so after it this call allocates nothing
-    if (p && M > 0 && p->cols > 0 && p->ws_bytes < wanted_workspace_bf16(p, M)) {
-        const int rc = tcsc_gpu_plan_reserve(const_cast<tcsc_gpu_plan*>(p), M);
-        if (rc != TCSC_OK) return rc;
-    }
-    if (p) const_cast<tcsc_gpu_plan*>(p)->staged_M = -1;  // the workspace is overwritten
-    return sgemm_ws(p, dX_bf16, dB, dY, M, ldy, variant, a, stream, p ? p->ws : nullptr, p ? p->ws_bytes : 0, 0,
-                    nullptr, kBf16);
+    return sgemm_entry(p, dX_bf16, kBf16, nullptr, dB, dY, M, ldy, variant, a, stream);
 }
 
 int tcsc_gpu_plan_enable_i8(tcsc_gpu_plan* p, void* stream) {
@@ -1503,16 +1454,7 @@ int tcsc_gpu_plan_has_i8(const tcsc_gpu_plan* p) {
 
 int tcsc_gpu_sgemm_i8(const tcsc_gpu_plan* p, const void* dXq, const float* dScale, const float* dB, float* dY, int M,
                       int ldy, int variant, float a, void* stream) {
-    // tcsc_gpu_plan_reserve's size covers every int8 launch (mfma8_ws_bytes <=
-    // mfma_ws_bytes; the gather's need is the fp32 call's), so after it this
-    // call allocates nothing
-    if (p && M > 0 && p->cols > 0 && p->ws_bytes < wanted_workspace_i8(p, M)) {
-        const int rc = tcsc_gpu_plan_reserve(const_cast<tcsc_gpu_plan*>(p), M);
-        if (rc != TCSC_OK) return rc;
-    }
-    if (p) const_cast<tcsc_gpu_plan*>(p)->staged_M = -1;  // the workspace is overwritten
-    return sgemm_ws(p, dXq, dB, dY, M, ldy, variant, a, stream, p ? p->ws : nullptr, p ? p->ws_bytes : 0, 0, nullptr,
-                    kI8, dScale);
+    return sgemm_entry(p, dXq, kI8, dScale, dB, dY, M, ldy, variant, a, stream);
 }
 
 int tcsc_gpu_quantize_rows_i8(const float* dX, int M, int K, void* dXq, float* dScale, void* stream) {
@@ -1534,8 +1476,8 @@ int tcsc_gpu_workspace_bound_i8(int M, int K, int N, size_t* i8_bytes, size_t* f
         set_error("tcsc_gpu_workspace_bound_i8: bad arguments (M=%d K=%d N=%d)", M, K, N);
         return TCSC_E_ARG;
     }
-    if (i8_bytes) *i8_bytes = mfma8_ws_bytes(M, K, N);
-    if (f32_bytes) *f32_bytes = mfma_ws_bytes(M, K, N);
+    if (i8_bytes) *i8_bytes = mfma_ws(kI8, M, K, N).bytes;
+    if (f32_bytes) *f32_bytes = mfma_ws(kF32, M, K, N).bytes;
     return TCSC_OK;
 }
 

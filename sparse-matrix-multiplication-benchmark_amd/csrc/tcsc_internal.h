@@ -186,11 +186,16 @@ constexpr int kCombineTiles = 4096;
 constexpr int kCombineWords = 32;  // per tile: 2 + Z (Z <= 16) used
 constexpr size_t kCombineBytes = (size_t)kCombineTiles * kCombineWords * 4;
 
+// The activation type of a call: X is M x K fp32 (tcsc_gpu_sgemm), bf16 bit
+// patterns (tcsc_gpu_sgemm_bf16) or int8 with a per-row scale
+// (tcsc_gpu_sgemm_i8).  The host's descriptor of each is kXTypes
+// (tcsc_api.cpp), the kernels' is XSrc (tcsc_xsrc.h).
+enum { kF32 = 0, kBf16 = 1, kI8 = 2 };
+
 struct GemmArgs {
-    const float* X = nullptr;
-    const uint16_t* Xb = nullptr;  // bf16 X instead of X (tcsc_gpu_sgemm_bf16): the transpose widens it
-    const int8_t* Xq = nullptr;    // int8 X instead of X (tcsc_gpu_sgemm_i8): the transpose converts it and
-    const float* Xscale = nullptr; // multiplies row m by Xscale[m] (null: by one)
+    const void* X = nullptr;        // M x K of xtype; the transpose converts it into the fp32 X^T and
+    int xtype = kF32;
+    const float* Xscale = nullptr;  // multiplies an int8 row m by Xscale[m] (null: by one)
     float* XT = nullptr;       // K x ldxt workspace: X transposed (ldxt = M rounded up to kTM)
     int M = 0, K = 0;
     const int2* ent = nullptr;
@@ -280,7 +285,8 @@ hipError_t sort_columns(const int* in, int* out, int n, int ncols, const int* of
                         hipStream_t st);
 // X (M x K) -> XT (K x ldxt), rows m >= M zero; ldxt = ldxt_for(M) (M rounded up to kTM)
 int ldxt_for(int M);
-hipError_t launch_transpose(const float* X, int M, int K, float* XT, int ldxt, hipStream_t st);
+hipError_t launch_transpose(const void* X, int M, int K, float* XT, int ldxt, hipStream_t st, int xtype = kF32,
+                            const float* scale = nullptr);
 
 // ---- per-column CSC copy of a plan's range (small-M path, MFMA fixup) ------
 // The merged list: each column's +1 and -1 rows in ascending order (the fast
@@ -349,13 +355,12 @@ inline size_t small_m_lds_bytes(int M, int K) { return (size_t)M * 2 * (size_t)c
 inline bool small_m_fits(int M, int K) { return M >= 1 && M <= 4 && small_m_lds_bytes(M, K) <= small_m_lds_bytes_max(); }
 // Y[m, j] = act(sum over column j's merged rows of +-X[m,k], ascending k,
 // then + B[j]) for m < M <= 4: one lane per column over the merged CSC copy,
-// the fast order's exact arithmetic (bit-identical to k_stream unsplit).
-hipError_t launch_small_m(const float* X, int M, int K, const int* cq, const int* crq, int ncols, const float* B,
-                          float* Y, int ldy, bool bias_first, bool prelu, float a, hipStream_t st);
-// the same from bf16 X (bit patterns): the staged image is the widened fp32 one
-hipError_t launch_small_m_bf16(const uint16_t* X, int M, int K, const int* cq, const int* crq, int ncols,
-                               const float* B, float* Y, int ldy, bool bias_first, bool prelu, float a,
-                               hipStream_t st);
+// the fast order's exact arithmetic (bit-identical to k_stream unsplit).  X is
+// of xtype: the staged image is the fp32 one of the widened bf16 X, or
+// fl(scale[m] * float(q)) of an int8 X (scale null = ones; int8 only).
+hipError_t launch_small_m(const void* X, int xtype, const float* scale, int M, int K, const int* cq, const int* crq,
+                          int ncols, const float* B, float* Y, int ldy, bool bias_first, bool prelu, float a,
+                          hipStream_t st);
 // X (M x K) -> x3 (M x ldk bf16, [h | m | l | 0..]); flags[m] = 1 for the
 // rows the fixup recomputes, 0 otherwise (every row, every call).
 hipError_t mfma_split_x(const float* X, int M, int K, uint16_t* x3, int ldk, int* flags, hipStream_t st);
@@ -410,10 +415,6 @@ hipError_t mfma8_gemm(const int8_t* x8, const int8_t* w8, int ld8, int K, int M,
                       hipStream_t st);
 // k_quant_rows_i8: per-row absmax quantization (tcsc_gpu_quantize_rows_i8)
 hipError_t quantize_rows_i8(const float* X, int M, int K, int8_t* Xq, float* scale, hipStream_t st);
-// k_small_m from int8 X: the staged image is fl(scale[m] * float(q)) (scale null = ones)
-hipError_t launch_small_m_i8(const int8_t* X, const float* scale, int M, int K, const int* cq, const int* crq,
-                             int ncols, const float* B, float* Y, int ldy, bool bias_first, bool prelu, float a,
-                             hipStream_t st);
 
 // Rewrites the flagged rows in k_stream's fast order (no-op when none is).
 hipError_t mfma_fixup(const uint16_t* x3, int M, int K, int ldk, const int* cq, const int* crq, int ncols,

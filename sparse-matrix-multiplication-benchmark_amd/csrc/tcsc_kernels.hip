@@ -43,6 +43,7 @@
 #include <type_traits>
 
 #include "tcsc_internal.h"
+#include "tcsc_xsrc.h"
 
 namespace tcsc {
 
@@ -236,156 +237,49 @@ __global__ void k_rebase(const int* __restrict__ cs, int col_begin, int ncols, i
 // X (M x K, row-major) -> XT (K x ldxt), ldxt = M rounded up to kTM; the
 // rows m in [M, ldxt) are written as 0.  64x64 tiles through LDS (the +1
 // column keeps the column reads conflict-free).  HBM-bound: 2*M*K*4 bytes
-// per call.  VEC (K % 4 == 0, X 16-B aligned): 16-B loads along k and
-// 16-B stores along m; otherwise scalar, guarded.
-template <bool VEC>
-__global__ void __launch_bounds__(256) k_transpose(const float* __restrict__ X, int M, int K, float* __restrict__ XT,
-                                                   int ldxt) {
+// per fp32 call.  TX is X's type (XSrc, tcsc_xsrc.h): bf16 is widened and
+// int8 multiplied by its row's scale (read by that form only) on the way into
+// the same fp32 XT, so k_stream reads what it reads after an fp32 call on
+// the converted matrix, for a half or a quarter of the bytes on the read side.
+// VEC (XSrc::vec_ok): 16-B loads along k and 16-B stores along m; otherwise
+// scalar, guarded.
+template <bool VEC, typename TX>
+__global__ void __launch_bounds__(256) k_transpose(const TX* __restrict__ X, const float* __restrict__ scale, int M,
+                                                   int K, float* __restrict__ XT, int ldxt) {
+    using XS = XSrc<TX>;
     if (VEC) {
-        // 64 (m) x 128 (k) tile: 512-B row reads, all 8 float4 loads of a
-        // thread in flight before the first LDS write.  Row stride 129 keeps
-        // the column reads conflict-free (129 = 1 mod 64 banks).
+        // 64 (m) x 128 (k) tile: a row of it is kPieces 16-B loads, and all
+        // kLoads loads of a thread (8 fp32, 4 bf16, 2 int8) are in flight before
+        // the first LDS write.  Row stride 129 keeps the column reads
+        // conflict-free (129 = 1 mod 64 banks).
+        constexpr int kV = XS::kVec, kPieces = 128 / kV, kStep = 256 / kPieces, kLoads = 64 / kStep;
+        static_assert(kStep == 2 * kV && kLoads == 32 / kV, "one tile per 256 threads");
         __shared__ float tv[64][129];
         const int k0 = blockIdx.x * 128, m0 = blockIdx.y * 64;
-        const int q2 = threadIdx.x & 31, r2 = threadIdx.x >> 5;  // 32 float4 per 128-wide row
-        float4 v[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const int m = m0 + r2 + 8 * i, k = k0 + 4 * q2;
-            v[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (m < M && k < K) {
-                typedef float nt4 __attribute__((ext_vector_type(4)));
-                const nt4 w = __builtin_nontemporal_load(reinterpret_cast<const nt4*>(X + (size_t)m * K + k));
-                v[i] = make_float4(w.x, w.y, w.z, w.w);
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const int r = r2 + 8 * i;
-            tv[r][4 * q2 + 0] = v[i].x;
-            tv[r][4 * q2 + 1] = v[i].y;
-            tv[r][4 * q2 + 2] = v[i].z;
-            tv[r][4 * q2 + 3] = v[i].w;
-        }
-        __syncthreads();
-        const int q = threadIdx.x & 15, rr = threadIdx.x >> 4;  // 16 float4 per 64-wide XT row piece
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const int kk = rr + 16 * i, k = k0 + kk;
-            if (k < K)
-                *reinterpret_cast<float4*>(XT + (size_t)k * ldxt + m0 + 4 * q) =
-                    make_float4(tv[4 * q + 0][kk], tv[4 * q + 1][kk], tv[4 * q + 2][kk], tv[4 * q + 3][kk]);
-        }
-        return;
-    }
-    __shared__ float t[64][65];
-    const int k0 = blockIdx.x * 64, m0 = blockIdx.y * 64;
-    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-        const int r = ty + 4 * i, m = m0 + r, k = k0 + tx;
-        t[r][tx] = (m < M && k < K) ? X[(size_t)m * K + k] : 0.f;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-        const int kk = ty + 4 * i, k = k0 + kk;
-        if (k < K) XT[(size_t)k * ldxt + m0 + tx] = t[tx][kk];
-    }
-}
-
-// k_transpose from bf16 X (bit patterns; tcsc_gpu_sgemm_bf16): widened with
-// bits << 16 into the same fp32 XT (rows m in [M, ldxt) zero), so k_stream
-// reads what it reads after an fp32 call on the widened X.  Half the bytes on
-// the read side.  VEC (K % 8 == 0, X 16-B aligned): the same 64 (m) x 128 (k)
-// tile, a row of it 256 B = 16 loads of 16 B (8 bf16), all 4 loads of a thread
-// in flight before the first LDS write; otherwise scalar, guarded.
-template <bool VEC>
-__global__ void __launch_bounds__(256) k_transpose_bf16(const uint16_t* __restrict__ X, int M, int K,
-                                                        float* __restrict__ XT, int ldxt) {
-    auto wide = [](uint32_t b) { return __uint_as_float(b << 16); };
-    if (VEC) {
-        __shared__ float tv[64][129];
-        const int k0 = blockIdx.x * 128, m0 = blockIdx.y * 64;
-        const int q2 = threadIdx.x & 15, r2 = threadIdx.x >> 4;  // 16 pieces of 8 bf16 per 128-wide row
+        const int q2 = threadIdx.x % kPieces, r2 = threadIdx.x / kPieces;
         typedef uint32_t nt4 __attribute__((ext_vector_type(4)));
-        nt4 v[4];
+        // held as four words each: an array of the loaded ext-vectors hipcc merges (the fp32 form's eight
+        // into one 32-dword value) and copies whole at every guard -- 228 VGPRs instead of 38
+        uint4 v[kLoads];
+        float s[kLoads];
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int m = m0 + r2 + 16 * i, k = k0 + 8 * q2;
-            v[i] = nt4{0u, 0u, 0u, 0u};
-            if (m < M && k < K) v[i] = __builtin_nontemporal_load(reinterpret_cast<const nt4*>(X + (size_t)m * K + k));
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int r = r2 + 16 * i;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                tv[r][8 * q2 + 2 * j + 0] = wide(v[i][j] & 0xffffu);
-                tv[r][8 * q2 + 2 * j + 1] = wide(v[i][j] >> 16);
-            }
-        }
-        __syncthreads();
-        const int q = threadIdx.x & 15, rr = threadIdx.x >> 4;  // 16 float4 per 64-wide XT row piece
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const int kk = rr + 16 * i, k = k0 + kk;
-            if (k < K)
-                *reinterpret_cast<float4*>(XT + (size_t)k * ldxt + m0 + 4 * q) =
-                    make_float4(tv[4 * q + 0][kk], tv[4 * q + 1][kk], tv[4 * q + 2][kk], tv[4 * q + 3][kk]);
-        }
-        return;
-    }
-    __shared__ float t[64][65];
-    const int k0 = blockIdx.x * 64, m0 = blockIdx.y * 64;
-    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-        const int r = ty + 4 * i, m = m0 + r, k = k0 + tx;
-        t[r][tx] = (m < M && k < K) ? wide(X[(size_t)m * K + k]) : 0.f;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-        const int kk = ty + 4 * i, k = k0 + kk;
-        if (k < K) XT[(size_t)k * ldxt + m0 + tx] = t[tx][kk];
-    }
-}
-
-// k_transpose from int8 X with a per-row scale (tcsc_gpu_sgemm_i8): XT[k][m] =
-// fl(scale[m] * float(X[m][k])) (scale null: float(X[m][k])), so k_stream reads
-// what it reads after an fp32 call on that matrix.  A quarter of the bytes on
-// the read side.  VEC (K % 16 == 0, X 16-B aligned): the 64 (m) x 128 (k)
-// tile, a row of it 128 B = 8 loads of 16 B (16 int8), both loads of a thread
-// in flight before the first LDS write; otherwise scalar, guarded.
-template <bool VEC>
-__global__ void __launch_bounds__(256) k_transpose_i8(const int8_t* __restrict__ X, const float* __restrict__ scale,
-                                                      int M, int K, float* __restrict__ XT, int ldxt) {
-    if (VEC) {
-        __shared__ float tv[64][129];
-        const int k0 = blockIdx.x * 128, m0 = blockIdx.y * 64;
-        const int q2 = threadIdx.x & 7, r2 = threadIdx.x >> 3;  // 8 pieces of 16 int8 per 128-wide row
-        typedef uint32_t nt4 __attribute__((ext_vector_type(4)));
-        nt4 v[2];
-        float s[2];
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int m = m0 + r2 + 32 * i, k = k0 + 16 * q2;
-            v[i] = nt4{0u, 0u, 0u, 0u};
+        for (int i = 0; i < kLoads; ++i) {
+            const int m = m0 + r2 + kStep * i, k = k0 + kV * q2;
+            v[i] = make_uint4(0u, 0u, 0u, 0u);
             s[i] = 1.0f;
             if (m < M && k < K) {
-                v[i] = __builtin_nontemporal_load(reinterpret_cast<const nt4*>(X + (size_t)m * K + k));
-                if (scale) s[i] = scale[m];
+                const nt4 w = __builtin_nontemporal_load(reinterpret_cast<const nt4*>(X + (size_t)m * K + k));
+                v[i] = make_uint4(w.x, w.y, w.z, w.w);
+                s[i] = XS::row_scale(scale, m);
             }
         }
 #pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int r = r2 + 32 * i;
+        for (int i = 0; i < kLoads; ++i) {
+            const int r = r2 + kStep * i;
+            float f[kV];
+            XS::unpack(v[i], s[i], f);
 #pragma unroll
-            for (int j = 0; j < 4; ++j)
-#pragma unroll
-                for (int b = 0; b < 4; ++b)
-                    tv[r][16 * q2 + 4 * j + b] = __fmul_rn(s[i], (float)(int8_t)(v[i][j] >> (8 * b)));
+            for (int e = 0; e < kV; ++e) tv[r][kV * q2 + e] = f[e];
         }
         __syncthreads();
         const int q = threadIdx.x & 15, rr = threadIdx.x >> 4;  // 16 float4 per 64-wide XT row piece
@@ -404,7 +298,12 @@ __global__ void __launch_bounds__(256) k_transpose_i8(const int8_t* __restrict__
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
         const int r = ty + 4 * i, m = m0 + r, k = k0 + tx;
-        t[r][tx] = (m < M && k < K) ? __fmul_rn(scale ? scale[m] : 1.0f, (float)X[(size_t)m * K + k]) : 0.f;
+        float x = 0.f;
+        if (m < M && k < K) {
+            const float s = XS::row_scale(scale, m);  // first: hipcc then sign-extends int8 in the load itself
+            x = XS::conv(X[(size_t)m * K + k], s);
+        }
+        t[r][tx] = x;
     }
     __syncthreads();
 #pragma unroll
@@ -1718,29 +1617,7 @@ hipError_t launch_gemm(const GemmArgs& g, hipStream_t st) {
     if (g.M <= 0 || g.ncols <= 0) return hipSuccess;
     if (g.K > 0 && g.stage != 2) {
         if (!g.XT) return hipErrorInvalidValue;
-        const int ldxt = ldxt_of(g.M);
-        const bool vec = (g.K % 4 == 0) && ((reinterpret_cast<uintptr_t>(g.X) & 15) == 0);
-        if (g.Xq) {
-            if ((g.K % 16 == 0) && ((reinterpret_cast<uintptr_t>(g.Xq) & 15) == 0))
-                hipLaunchKernelGGL(k_transpose_i8<true>, dim3((g.K + 127) / 128, ldxt / 64), dim3(256), 0, st, g.Xq,
-                                   g.Xscale, g.M, g.K, g.XT, ldxt);
-            else
-                hipLaunchKernelGGL(k_transpose_i8<false>, dim3((g.K + 63) / 64, ldxt / 64), dim3(256), 0, st, g.Xq,
-                                   g.Xscale, g.M, g.K, g.XT, ldxt);
-        } else if (g.Xb) {
-            if ((g.K % 8 == 0) && ((reinterpret_cast<uintptr_t>(g.Xb) & 15) == 0))
-                hipLaunchKernelGGL(k_transpose_bf16<true>, dim3((g.K + 127) / 128, ldxt / 64), dim3(256), 0, st, g.Xb,
-                                   g.M, g.K, g.XT, ldxt);
-            else
-                hipLaunchKernelGGL(k_transpose_bf16<false>, dim3((g.K + 63) / 64, ldxt / 64), dim3(256), 0, st, g.Xb,
-                                   g.M, g.K, g.XT, ldxt);
-        } else if (vec)
-            hipLaunchKernelGGL(k_transpose<true>, dim3((g.K + 127) / 128, ldxt / 64), dim3(256), 0, st, g.X, g.M, g.K,
-                               g.XT, ldxt);
-        else
-            hipLaunchKernelGGL(k_transpose<false>, dim3((g.K + 63) / 64, ldxt / 64), dim3(256), 0, st, g.X, g.M,
-                               g.K, g.XT, ldxt);
-        hipError_t e = hipGetLastError();
+        const hipError_t e = launch_transpose(g.X, g.M, g.K, g.XT, ldxt_of(g.M), st, g.xtype, g.Xscale);
         if (e != hipSuccess) return e;
     }
     if (g.stage == 1) return hipSuccess;
@@ -1854,14 +1731,28 @@ extern "C" __attribute__((visibility("default"))) int tcsc_debug_wgtimes(void* d
 }
 #endif
 
-hipError_t launch_transpose(const float* X, int M, int K, float* XT, int ldxt, hipStream_t st) {
-    if (M <= 0 || K <= 0) return hipSuccess;
-    const bool vec = (K % 4 == 0) && ((reinterpret_cast<uintptr_t>(X) & 15) == 0);
-    if (vec)
-        hipLaunchKernelGGL(k_transpose<true>, dim3((K + 127) / 128, ldxt / 64), dim3(256), 0, st, X, M, K, XT, ldxt);
+template <typename TX>
+static hipError_t transpose_t(const void* X_, const float* scale, int M, int K, float* XT, int ldxt, hipStream_t st) {
+    const TX* X = static_cast<const TX*>(X_);
+    if (XSrc<TX>::vec_ok(X, K))
+        hipLaunchKernelGGL((k_transpose<true, TX>), dim3((K + 127) / 128, ldxt / 64), dim3(256), 0, st, X, scale, M, K,
+                           XT, ldxt);
     else
-        hipLaunchKernelGGL(k_transpose<false>, dim3((K + 63) / 64, ldxt / 64), dim3(256), 0, st, X, M, K, XT, ldxt);
+        hipLaunchKernelGGL((k_transpose<false, TX>), dim3((K + 63) / 64, ldxt / 64), dim3(256), 0, st, X, scale, M, K,
+                           XT, ldxt);
     return hipGetLastError();
+}
+
+hipError_t launch_transpose(const void* X, int M, int K, float* XT, int ldxt, hipStream_t st, int xtype,
+                            const float* scale) {
+    if (M <= 0 || K <= 0) return hipSuccess;
+    switch (xtype) {
+        case kBf16:
+            return transpose_t<uint16_t>(X, scale, M, K, XT, ldxt, st);
+        case kI8:
+            return transpose_t<int8_t>(X, scale, M, K, XT, ldxt, st);
+    }
+    return transpose_t<float>(X, scale, M, K, XT, ldxt, st);
 }
 
 }  // namespace tcsc

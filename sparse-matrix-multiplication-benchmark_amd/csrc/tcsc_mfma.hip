@@ -1166,16 +1166,18 @@ int mfma_split_target(bool big, bool narrow) {
     return e ? std::atoi(e) : big ? 256 : narrow ? 1024 : 512;
 }
 
-int mfma_slices(int M, int N, int K) {
+// The rule for a K of nblk blocks: a slice at least min_blk blocks, at most cap slices.
+static int split_k(int M, int N, int nblk, int min_blk, int cap) {
     if (M <= 0 || N <= 0) return 1;
     const long long tiles = mfma_tiles(M, N);
-    const int nblk = mfma_nblk(K);
-    const long long s =
-        std::min<long long>({mfma_split_target(mfma_big_tiles(M, N), mfma_narrow_tiles(M, N)) / tiles, 16, nblk / 8});
+    const long long s = std::min<long long>(
+        {mfma_split_target(mfma_big_tiles(M, N), mfma_narrow_tiles(M, N)) / tiles, cap, nblk / min_blk});
     if (s < 2) return 1;
     const int bps = (int)((nblk + s - 1) / s);
     return (nblk + bps - 1) / bps;
 }
+
+int mfma_slices(int M, int N, int K) { return split_k(M, N, mfma_nblk(K), 8, 16); }
 
 size_t mfma_slab_bytes(int M, int N, int K) {
     const int s = mfma_slices(M, N, K);
@@ -1303,16 +1305,7 @@ hipError_t mfma_fixup1(const uint16_t* x1, int M, int K, int ldk, const int* cq,
 // never more slices than the fp32 call takes at this shape: the i32 slabs then
 // fit the fp32 call's slab space (4 B per element either way), which is what
 // keeps the int8 workspace inside the reserved one.
-int mfma8_slices(int M, int N, int K) {
-    if (M <= 0 || N <= 0) return 1;
-    const long long tiles = mfma_tiles(M, N);
-    const int nblk = mfma8_nblk(K);
-    const long long s = std::min<long long>({mfma_split_target(mfma_big_tiles(M, N), mfma_narrow_tiles(M, N)) / tiles,
-                                             16, nblk / 4, mfma_slices(M, N, K)});
-    if (s < 2) return 1;
-    const int bps = (int)((nblk + s - 1) / s);
-    return (nblk + bps - 1) / bps;
-}
+int mfma8_slices(int M, int N, int K) { return split_k(M, N, mfma8_nblk(K), 4, std::min(16, mfma_slices(M, N, K))); }
 
 size_t mfma8_slab_bytes(int M, int N, int K) {
     const int s = mfma8_slices(M, N, K);

@@ -15,9 +15,8 @@
 // absolute 1e-4, which its M = 1, K = 2048 case missed by 2e-5.)
 #include <hip/hip_runtime.h>
 
-#include <type_traits>
-
 #include "tcsc_internal.h"
+#include "tcsc_xsrc.h"
 
 namespace tcsc {
 namespace {
@@ -37,8 +36,8 @@ constexpr int ring_quads() {
 //    -X | 0..] (2*Kp floats, tcsc_internal.h): an entry of the list (4k, or
 //    4Kp + 4k for a -1 row, or 4K for padding) is then directly the byte
 //    offset of +-X[m, k], so an add is one ds_read and one v_add (negation is
-//    exact: acc + (-x) is the gather's fma(x, -1, acc)); the staging keeps 16
-//    16-B loads per lane in flight, addresses clamped instead of branched
+//    exact: acc + (-x) is the gather's fma(x, -1, acc)); the staging keeps a
+//    pass's 16-B loads per lane in flight, addresses clamped instead of branched
 //    around (a load under a runtime condition makes hipcc branch around it
 //    and drain vmcnt per load);
 //  * the list (the 64 columns of this workgroup interleaved by 16-B quads,
@@ -49,115 +48,46 @@ constexpr int ring_quads() {
 //    and the sum never runs past the group;
 //  * the look-ahead loads are pinned ahead of the adds (hipcc would sink
 //    them to their first use).
-// TX = uint16_t: X is bf16 bit patterns, widened (bits << 16) as it is staged:
-// the LDS image, the column walk and so the bits are those of the fp32 kernel
-// on the widened X.  16-B loads of 8 bf16 (8 per lane in flight) where K % 8
-// == 0 and X is 16-B aligned; 2-B loads otherwise.
-// TX = int8_t (tcsc_gpu_sgemm_i8): X is int8 with a per-row scale (Scale, null
-// = ones; read by this form only, and last among the arguments so the other
-// forms' code is what it was): the staged value is fl(Scale[r] * float(x)), so
-// the bits are those of the fp32 kernel on that matrix.  16-B loads of 16 int8
-// (4 per lane in flight) where K % 16 == 0 and X is 16-B aligned; 1-B loads
-// otherwise.
+// TX (XSrc, tcsc_xsrc.h) is X's type: bf16 bit patterns are widened and int8
+// multiplied by its row's scale (Scale, null = ones; read by that form only,
+// and last among the arguments so the fp32 form's code is what it was) as
+// they are staged: the LDS image, the column walk and so the bits are those
+// of the fp32 kernel on the converted X.  16-B loads of kVec elements, 64 /
+// kVec per lane in flight (a pass of 4096 k for every type), where
+// XSrc::vec_ok holds; single elements, 8 in flight, otherwise.
 template <int MB, bool BIAS_FIRST, bool PRELU, typename TX = float>
 __global__ void __launch_bounds__(kBlock)
 k_small_m(const TX* __restrict__ X, int M, int K, const int* __restrict__ cq, const int* __restrict__ rm,
           int ncols, const float* __restrict__ Bias, float* __restrict__ Y, int ldy, float a,
           const float* __restrict__ Scale) {
+    using XS = XSrc<TX>;
+    constexpr int kV = XS::kVec, kU = 64 / kV;  // elements per 16-B load, loads per lane in flight
     extern __shared__ float xs[];
     const int lane = threadIdx.x;
     const int Kp = csc_half(K), S = 2 * Kp;  // floats per half / per staged row pair
-    // 16-B loads, 16 per lane in flight (16 KiB per wave per round trip), where
-    // X's rows are 16-B aligned; 4-B loads otherwise
-    constexpr bool kBf16 = std::is_same<TX, uint16_t>::value, kI8 = std::is_same<TX, int8_t>::value;
-    const bool vec = (K & (kI8 ? 15 : kBf16 ? 7 : 3)) == 0 && (reinterpret_cast<uintptr_t>(X) & 15) == 0;
+    const bool vec = XS::vec_ok(X, K);
     for (int r = 0; r < M; ++r) {
         const TX* __restrict__ xr = X + (size_t)r * K;
         float* dr = xs + (size_t)r * S;
-        if constexpr (kI8) {
-            const float sc = Scale ? Scale[r] : 1.0f;
-            auto conv = [&](uint32_t w, int b) { return __fmul_rn(sc, (float)(int8_t)(w >> (8 * b))); };
-            if (vec) {
-                for (int k0 = 0; k0 < K; k0 += 4 * 16 * kBlock) {
-                    uint4 v[4];
+        const float sc = XS::row_scale(Scale, r);
+        if (vec) {
+            for (int k0 = 0; k0 < K; k0 += kU * kV * kBlock) {
+                uint4 v[kU];
 #pragma unroll
-                    for (int u = 0; u < 4; ++u)
-                        v[u] = *reinterpret_cast<const uint4*>(xr + min(k0 + 16 * (u * kBlock + lane), K - 16));
+                for (int u = 0; u < kU; ++u)
+                    v[u] = *reinterpret_cast<const uint4*>(xr + min(k0 + kV * (u * kBlock + lane), K - kV));
 #pragma unroll
-                    for (int u = 0; u < 4; ++u) {
-                        const int k = k0 + 16 * (u * kBlock + lane);
-                        if (k < K) {
-                            const uint32_t w[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
-#pragma unroll
-                            for (int h = 0; h < 4; ++h) {
-                                const float4 f = make_float4(conv(w[h], 0), conv(w[h], 1), conv(w[h], 2), conv(w[h], 3));
-                                *reinterpret_cast<float4*>(dr + k + 4 * h) = f;
-                                *reinterpret_cast<float4*>(dr + Kp + k + 4 * h) = make_float4(-f.x, -f.y, -f.z, -f.w);
-                            }
-                        }
-                    }
-                }
-            } else {
-                for (int k0 = 0; k0 < K; k0 += 8 * kBlock) {
-                    float v[8];
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) v[u] = __fmul_rn(sc, (float)xr[min(k0 + u * kBlock + lane, K - 1)]);
-#pragma unroll
-                    for (int u = 0; u < 8; ++u)
-                        if (k0 + u * kBlock + lane < K) {
-                            dr[k0 + u * kBlock + lane] = v[u];
-                            dr[Kp + k0 + u * kBlock + lane] = -v[u];
-                        }
-                }
-            }
-        } else if constexpr (kBf16) {
-            auto wide = [](uint32_t b) { return __uint_as_float(b << 16); };
-            if (vec) {
-                for (int k0 = 0; k0 < K; k0 += 8 * 8 * kBlock) {
-                    uint4 v[8];
-#pragma unroll
-                    for (int u = 0; u < 8; ++u)
-                        v[u] = *reinterpret_cast<const uint4*>(xr + min(k0 + 8 * (u * kBlock + lane), K - 8));
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) {
-                        const int k = k0 + 8 * (u * kBlock + lane);
-                        if (k < K) {
-                            const uint32_t w[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
-#pragma unroll
-                            for (int h = 0; h < 2; ++h) {
-                                const float4 f = make_float4(wide(w[2 * h] & 0xffffu), wide(w[2 * h] >> 16),
-                                                             wide(w[2 * h + 1] & 0xffffu), wide(w[2 * h + 1] >> 16));
-                                *reinterpret_cast<float4*>(dr + k + 4 * h) = f;
-                                *reinterpret_cast<float4*>(dr + Kp + k + 4 * h) = make_float4(-f.x, -f.y, -f.z, -f.w);
-                            }
-                        }
-                    }
-                }
-            } else {
-                for (int k0 = 0; k0 < K; k0 += 8 * kBlock) {
-                    float v[8];
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) v[u] = wide(xr[min(k0 + u * kBlock + lane, K - 1)]);
-#pragma unroll
-                    for (int u = 0; u < 8; ++u)
-                        if (k0 + u * kBlock + lane < K) {
-                            dr[k0 + u * kBlock + lane] = v[u];
-                            dr[Kp + k0 + u * kBlock + lane] = -v[u];
-                        }
-                }
-            }
-        } else if (vec) {
-            for (int k0 = 0; k0 < K; k0 += 16 * 4 * kBlock) {
-                float4 v[16];
-#pragma unroll
-                for (int u = 0; u < 16; ++u)
-                    v[u] = *reinterpret_cast<const float4*>(xr + min(k0 + 4 * (u * kBlock + lane), K - 4));
-#pragma unroll
-                for (int u = 0; u < 16; ++u) {
-                    const int k = k0 + 4 * (u * kBlock + lane);
+                for (int u = 0; u < kU; ++u) {
+                    const int k = k0 + kV * (u * kBlock + lane);
                     if (k < K) {
-                        *reinterpret_cast<float4*>(dr + k) = v[u];
-                        *reinterpret_cast<float4*>(dr + Kp + k) = make_float4(-v[u].x, -v[u].y, -v[u].z, -v[u].w);
+                        float f[kV];
+                        XS::unpack(v[u], sc, f);
+#pragma unroll
+                        for (int h = 0; h < kV; h += 4) {
+                            *reinterpret_cast<float4*>(dr + k + h) = make_float4(f[h], f[h + 1], f[h + 2], f[h + 3]);
+                            *reinterpret_cast<float4*>(dr + Kp + k + h) =
+                                make_float4(-f[h], -f[h + 1], -f[h + 2], -f[h + 3]);
+                        }
                     }
                 }
             }
@@ -165,7 +95,7 @@ k_small_m(const TX* __restrict__ X, int M, int K, const int* __restrict__ cq, co
             for (int k0 = 0; k0 < K; k0 += 8 * kBlock) {
                 float v[8];
 #pragma unroll
-                for (int u = 0; u < 8; ++u) v[u] = xr[min(k0 + u * kBlock + lane, K - 1)];
+                for (int u = 0; u < 8; ++u) v[u] = XS::conv(xr[min(k0 + u * kBlock + lane, K - 1)], sc);
 #pragma unroll
                 for (int u = 0; u < 8; ++u)
                     if (k0 + u * kBlock + lane < K) {
@@ -273,37 +203,31 @@ void launch_mb(const TX* X, int M, int K, const int* cq, const int* rm, int ncol
 }  // namespace
 
 template <typename TX>
-static hipError_t launch_small_any(const TX* X, int M, int K, const int* cq, const int* crq, int ncols, const float* B,
-                                   float* Y, int ldy, bool bias_first, bool prelu, float a, hipStream_t st,
-                                   const float* scale = nullptr) {
-    if (M <= 0 || ncols <= 0) return hipSuccess;
-    if (!small_m_fits(M, K)) return hipErrorInvalidValue;
+static hipError_t launch_small_t(const void* X_, const float* scale, int M, int K, const int* cq, const int* crq,
+                                 int ncols, const float* B, float* Y, int ldy, bool bias_first, bool prelu, float a,
+                                 hipStream_t st) {
+    const TX* X = static_cast<const TX*>(X_);
     if (M == 1)
         launch_mb<1>(X, M, K, cq, crq, ncols, B, Y, ldy, bias_first, prelu, a, scale, st);
     else if (M <= 2)
         launch_mb<2>(X, M, K, cq, crq, ncols, B, Y, ldy, bias_first, prelu, a, scale, st);
-    else if (M <= 4)
-        launch_mb<4>(X, M, K, cq, crq, ncols, B, Y, ldy, bias_first, prelu, a, scale, st);
     else
-        return hipErrorInvalidValue;
+        launch_mb<4>(X, M, K, cq, crq, ncols, B, Y, ldy, bias_first, prelu, a, scale, st);
     return hipGetLastError();
 }
 
-hipError_t launch_small_m(const float* X, int M, int K, const int* cq, const int* crq, int ncols, const float* B,
-                          float* Y, int ldy, bool bias_first, bool prelu, float a, hipStream_t st) {
-    return launch_small_any(X, M, K, cq, crq, ncols, B, Y, ldy, bias_first, prelu, a, st);
-}
-
-hipError_t launch_small_m_bf16(const uint16_t* X, int M, int K, const int* cq, const int* crq, int ncols,
-                               const float* B, float* Y, int ldy, bool bias_first, bool prelu, float a,
-                               hipStream_t st) {
-    return launch_small_any(X, M, K, cq, crq, ncols, B, Y, ldy, bias_first, prelu, a, st);
-}
-
-hipError_t launch_small_m_i8(const int8_t* X, const float* scale, int M, int K, const int* cq, const int* crq,
-                             int ncols, const float* B, float* Y, int ldy, bool bias_first, bool prelu, float a,
-                             hipStream_t st) {
-    return launch_small_any(X, M, K, cq, crq, ncols, B, Y, ldy, bias_first, prelu, a, st, scale);
+hipError_t launch_small_m(const void* X, int xtype, const float* scale, int M, int K, const int* cq, const int* crq,
+                          int ncols, const float* B, float* Y, int ldy, bool bias_first, bool prelu, float a,
+                          hipStream_t st) {
+    if (M <= 0 || ncols <= 0) return hipSuccess;
+    if (!small_m_fits(M, K)) return hipErrorInvalidValue;  // M <= 4 and the row pairs fit the LDS
+    switch (xtype) {
+        case kBf16:
+            return launch_small_t<uint16_t>(X, nullptr, M, K, cq, crq, ncols, B, Y, ldy, bias_first, prelu, a, st);
+        case kI8:
+            return launch_small_t<int8_t>(X, scale, M, K, cq, crq, ncols, B, Y, ldy, bias_first, prelu, a, st);
+    }
+    return launch_small_t<float>(X, nullptr, M, K, cq, crq, ncols, B, Y, ldy, bias_first, prelu, a, st);
 }
 
 }  // namespace tcsc

@@ -505,22 +505,21 @@ class Plan:
         _check(lib().tcsc_gpu_plan_get_info(self.handle, C.byref(inf)), "tcsc_gpu_plan_get_info")
         return {k: getattr(inf, k) for k, _ in plan_info_t._fields_}
 
+    def _launch_info(self, name: str, M: int) -> tuple[str, int]:
+        path, slices = C.c_int(), C.c_int()
+        _check(getattr(lib(), name)(self.handle, int(M), C.byref(path), C.byref(slices)), name)
+        return ("gather", "fused", "mfma", "small")[path.value], slices.value
+
     def launch_info(self, M: int) -> tuple[str, int]:
         """(path, K slices) of a launch of M rows: path is 'gather' (k_transpose +
         k_stream), 'mfma' or 'small' (include/tcsc_gpu.h tcsc_gpu_launch_info; value 1,
         the retired persistent k_fused, is never returned)."""
-        path, slices = C.c_int(), C.c_int()
-        _check(lib().tcsc_gpu_launch_info(self.handle, int(M), C.byref(path), C.byref(slices)),
-               "tcsc_gpu_launch_info")
-        return ("gather", "fused", "mfma", "small")[path.value], slices.value
+        return self._launch_info("tcsc_gpu_launch_info", M)
 
     def launch_info_bf16(self, M: int) -> tuple[str, int]:
         """(path, K slices) of an :meth:`sgemm_bf16` launch of M rows (tcsc_gpu_launch_info_bf16): the bf16
         call has its own cost model (a one-part GEMM), so its path can differ from :meth:`launch_info`'s."""
-        path, slices = C.c_int(), C.c_int()
-        _check(lib().tcsc_gpu_launch_info_bf16(self.handle, int(M), C.byref(path), C.byref(slices)),
-               "tcsc_gpu_launch_info_bf16")
-        return ("gather", "fused", "mfma", "small")[path.value], slices.value
+        return self._launch_info("tcsc_gpu_launch_info_bf16", M)
 
     def launch_combine(self, M: int) -> bool:
         """True when a gather launch of M rows combines its split-K slabs inside
@@ -587,10 +586,7 @@ class Plan:
 
     def launch_info_i8(self, M: int) -> tuple[str, int]:
         """(path, K slices) of an :meth:`sgemm_i8` launch of M rows (tcsc_gpu_launch_info_i8)."""
-        path, slices = C.c_int(), C.c_int()
-        _check(lib().tcsc_gpu_launch_info_i8(self.handle, int(M), C.byref(path), C.byref(slices)),
-               "tcsc_gpu_launch_info_i8")
-        return ("gather", "fused", "mfma", "small")[path.value], slices.value
+        return self._launch_info("tcsc_gpu_launch_info_i8", M)
 
     def sgemm_i8(self, Xq, scale, B, Y, M: int, ldy: int, variant: str = "prelu_basic", a: float = 0.2,
                  stream: int = 0) -> None:

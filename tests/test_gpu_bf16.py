@@ -102,7 +102,7 @@ def int_case(o, M, K, N, density):
         X = o.integers((M, K), seed + 1, rng=128)
         B = o.integers((N,), seed + 2)
         assert np.array_equal(widen(bf16_bits(X)), X) and np.abs(X).max() <= 128
-        # fp64 holds these integer sums exactly (K <= 1100: below 2^24), so this is the int64 result
+        # fp64 holds these integer sums exactly (K <= 4112: below 2^24), so this is the int64 result
         lin64 = (X.astype(np.float64) @ Wd.astype(np.float64) + B.astype(np.float64)).astype(np.int64)
         assert np.abs(lin64).max() < 2 ** 24
         lin = lin64.astype(np.float32)
@@ -121,8 +121,13 @@ def exact(case, variant):
 
 
 # (M, K, N, density, TCSC_PATH, the path both calls must report)
-GATHER = [(70, 96, 80, 0.1, "gather", "gather"), (70, 101, 80, 0.1, "gather", "gather")]
-SMALL = [(M, K, 130, 0.1, None, "small") for M in (1, 3, 4) for K in (96, 101)]
+# K = 144: a multiple of 16 past one 128-k tile -- the vector transpose's second k tile is mostly past K (its load
+# and store guards), with a ragged second row tile.  K = 4112: a multiple of 16 past 4096 -- the small-M vector
+# staging takes a second pass, on clamped addresses (small_m_fits(4, 4112): 131,712 bytes).
+GATHER = [(70, 96, 80, 0.1, "gather", "gather"), (70, 101, 80, 0.1, "gather", "gather"),
+          (70, 144, 80, 0.1, "gather", "gather")]
+SMALL = [(M, K, 130, 0.1, None, "small") for M in (1, 3, 4) for K in (96, 101)] + \
+        [(M, 4112, 130, 0.1, None, "small") for M in (1, 4)]
 MFMA = [(200, 700, 300, 0.5, "mfma", "mfma"), (200, 701, 300, 0.5, "mfma", "mfma"),
         (40, 1100, 300, 0.5, "mfma", "mfma"), (2048, 200, 4096, 0.5, "mfma", "mfma")]
 

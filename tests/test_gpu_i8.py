@@ -249,9 +249,13 @@ def test_split_k_invariance(gpu, oracle, env, block):
 
 # ---- 4. gather and small M: the bits of the fp32 call on Xs = s * q ----------------------------------------------------
 
+# K = 144: a multiple of 16 past one 128-k tile -- the vector transpose's second k tile is mostly past K (its load
+# and store guards), with a ragged second row tile.  K = 4112: a multiple of 16 past 4096 -- the small-M vector
+# staging takes a second pass, on clamped addresses (small_m_fits(4, 4112): 131,712 bytes).
 GATHER = [(70, 96, 80, 0.1, "gather", "gather"), (70, 101, 80, 0.1, "gather", "gather"),
-          (70, 112, 80, 0.1, "gather", "gather")]
-SMALL = [(M, K, 130, 0.1, None, "small") for M in (1, 3, 4) for K in (96, 101, 112)]
+          (70, 112, 80, 0.1, "gather", "gather"), (70, 144, 80, 0.1, "gather", "gather")]
+SMALL = [(M, K, 130, 0.1, None, "small") for M in (1, 3, 4) for K in (96, 101, 112)] + \
+        [(M, 4112, 130, 0.1, None, "small") for M in (1, 4)]
 
 
 def ids(cases):

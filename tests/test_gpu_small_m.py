@@ -114,7 +114,7 @@ def test_specials_and_off_switch(gpu, oracle, monkeypatch):
     W.free()
 
 
-@pytest.mark.parametrize("K", [1, 5, 4093, 4096])
+@pytest.mark.parametrize("K", [1, 5, 4093, 4096, 4112])
 def test_ragged_k_and_unaligned_x_equal_gather(gpu, oracle, monkeypatch, K):
     """The staging's two forms -- 16-B loads where K % 4 == 0 and X is 16-B
     aligned, 4-B loads otherwise (K = 1, 5, 4093, or X one float off a 16-B

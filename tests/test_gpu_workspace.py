@@ -15,6 +15,9 @@ result with a fresh plan reserved at exactly that M, with the oracle, and
 with a graph replay.
 """
 import functools
+import importlib.util
+import json
+import os
 
 import numpy as np
 import pytest
@@ -165,6 +168,43 @@ def test_query_rejects_bad_arguments_and_reports_absent_paths(torch_gpu, monkeyp
     assert L.tcsc_gpu_plan_workspace(plan.handle, 8, -1, None, None) == 0
     plan.destroy()
     W.free()
+
+
+# ---- what the cost models decide ---------------------------------------------
+
+def load_gen_routing():
+    """tests/golden/gen_routing.py: the plans and the record the table was made with."""
+    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "gen_routing.py")
+    spec = importlib.util.spec_from_file_location("gen_routing", path)
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+GEN_ROUTING = load_gen_routing()
+
+
+@pytest.mark.parametrize("shape", GEN_ROUTING.SHAPES, ids=lambda s: f"K{s[0]}-N{s[1]}")
+def test_routing_and_workspace_equal_the_recorded_table(torch_gpu, monkeypatch, shape):
+    """tests/golden/routing_table.json holds, for fast-order plans of four shapes at six densities, with and
+    without the int8 image, and 17 values of M: the path and K split of the fp32, bf16 and int8 calls, the
+    workspace of the auto path and of each path, the gather geometry, and what reserve(4096) holds -- recorded
+    once from the three per-type cost models and workspace layouts.  Every entry must be what it was."""
+    for k in GEN_ROUTING.KNOBS:
+        monkeypatch.delenv(k, raising=False)
+    with open(GEN_ROUTING.TABLE) as f:
+        table = json.load(f)
+    got = GEN_ROUTING.record(tcsc_amd, *shape)
+    assert len(got) == 2 * len(GEN_ROUTING.DENSITIES) and set(got) <= set(table)
+    names = ("M", "path", "slices", "bf16 path", "bf16 slices", "i8 path", "i8 slices", "workspace", "gather ws",
+             "mfma ws", "small ws", "geometry")
+    for key, g in got.items():
+        want = table[key]
+        assert g["reserved"] == want["reserved"], f"{key}: reserve({GEN_ROUTING.RESERVE_M})"
+        assert len(g["rows"]) == len(want["rows"]) == len(GEN_ROUTING.MS)
+        for grow, wrow in zip(g["rows"], want["rows"]):
+            assert grow == wrow, f"{key} M={wrow[0]}: " + ", ".join(
+                f"{n} {a} (recorded {b})" for n, a, b in zip(names, grow, wrow) if a != b)
 
 
 # ---- launches ---------------------------------------------------------------

@@ -8,10 +8,11 @@ import ctypes as C
 import os
 import re
 
+import numpy as np
 import pytest
 
 import tcsc_amd
-from conftest import ROOT
+from conftest import GOLDEN, ROOT
 
 NEW_SYMBOLS = ("tcsc_gpu_plan_enable_i8", "tcsc_gpu_plan_has_i8", "tcsc_gpu_sgemm_i8", "tcsc_gpu_launch_info_i8",
                "tcsc_gpu_quantize_rows_i8")
@@ -99,18 +100,21 @@ def bound(lib, M, K, N):
     return i8.value, f32.value
 
 
+# the sweep: small and ragged M, every K residue class that changes a block count, N around the tile widths
+Ms = [1, 4, 5, 17, 63, 64, 65, 96, 127, 128, 129, 200, 256, 257, 1000, 2048, 4097]
+Ks = [1, 63, 64, 65, 127, 128, 129, 300, 511, 512, 513, 1023, 1100, 2047, 2048, 2049, 3000, 4095, 8192, 8193, 16384,
+      20000, 100003]
+Ns = [1, 64, 130, 255, 256, 257, 300, 512, 600, 1024, 4096, 8192, 16384]
+
+
 @pytest.mark.parametrize("wgs", [None, "0", "64", "4096"])
 def test_int8_workspace_never_exceeds_the_fp32_calls(built_lib, monkeypatch, wgs):
-    """mfma8_ws_bytes <= mfma_ws_bytes over a sweep of shapes (small and ragged M, every K residue class that
-    changes a block count, N around the tile widths), whatever $TCSC_MFMA_WGS asks of the two K splits."""
+    """The int8 MFMA workspace <= the fp32 call's (mfma_ws, csrc/tcsc_api.cpp) over the sweep, whatever
+    $TCSC_MFMA_WGS asks of the two K splits."""
     if wgs is None:
         monkeypatch.delenv("TCSC_MFMA_WGS", raising=False)
     else:
         monkeypatch.setenv("TCSC_MFMA_WGS", wgs)
-    Ms = [1, 4, 5, 17, 63, 64, 65, 96, 127, 128, 129, 200, 256, 257, 1000, 2048, 4097]
-    Ks = [1, 63, 64, 65, 127, 128, 129, 300, 511, 512, 513, 1023, 1100, 2047, 2048, 2049, 3000, 4095, 8192, 8193, 16384,
-          20000, 100003]
-    Ns = [1, 64, 130, 255, 256, 257, 300, 512, 600, 1024, 4096, 8192, 16384]
     splits = 0
     for M in Ms:
         for K in Ks:
@@ -125,6 +129,23 @@ def test_int8_workspace_never_exceeds_the_fp32_calls(built_lib, monkeypatch, wgs
         assert splits == 0
     else:
         assert splits > 0  # the sweep reaches shapes whose K is split
+
+
+@pytest.mark.parametrize("wgs", [None, "0", "64", "4096"])
+def test_workspace_bound_equals_the_recorded_sweep(built_lib, monkeypatch, wgs):
+    """Both sizes over the same sweep are what the per-type workspace layouts gave before they became one function
+    (tests/golden/routing/i8_workspace_bound.npz, written by tests/golden/gen_routing.py --bound)."""
+    if wgs is None:
+        monkeypatch.delenv("TCSC_MFMA_WGS", raising=False)
+    else:
+        monkeypatch.setenv("TCSC_MFMA_WGS", wgs)
+    z = np.load(os.path.join(GOLDEN, "routing", "i8_workspace_bound.npz"))
+    assert list(z["Ms"]) == Ms and list(z["Ks"]) == Ks and list(z["Ns"]) == Ns
+    recorded = z["wgs_" + (wgs or "unset")]
+    got = np.array([[[bound(built_lib, M, K, N) for N in Ns] for K in Ks] for M in Ms], np.int64)
+    bad = np.argwhere((got != recorded).any(axis=-1))
+    assert bad.size == 0, (f"{len(bad)} shapes differ, first M={Ms[bad[0][0]]} K={Ks[bad[0][1]]} N={Ns[bad[0][2]]}: "
+                           f"{got[tuple(bad[0])]} (recorded {recorded[tuple(bad[0])]})")
 
 
 def test_workspace_bound_rejects_bad_shapes(built_lib):

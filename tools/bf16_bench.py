@@ -10,9 +10,9 @@ HIP events around windows of back-to-back launches after a warm-up (median of
   cast        torch's X.float() of the bf16 X: what a bf16 caller of the fp32
               entry point pays on top of `fp32`
   kernels     per-kernel mean microseconds of either call from torch's profiler
-              (k_split3 / k_pack1, k_gemm3, k_fixup or k_reduce_fix; k_transpose /
-              k_transpose_bf16, k_stream, ...), a few calls each, apart from
-              the timed windows
+              (k_split3 / k_pack1, k_gemm3, k_fixup or k_reduce_fix; k_transpose --
+              its bf16 instantiation reported as k_transpose_bf16 --, k_stream,
+              ...), a few calls each, apart from the timed windows
 
 The two calls must agree: `check` records whether the bf16 call's bits equal
 the fp32 call's on the widened X.  One JSON line goes to --out (default
@@ -24,6 +24,7 @@ fails, it never falls back.
 import argparse
 import json
 import os
+import re
 import statistics
 import sys
 
@@ -35,8 +36,23 @@ from tcsc_amd import workloads  # noqa: E402
 
 A = 0.2
 # the library's kernels by name, longer names first where one is a prefix of another
-KERNELS = ("k_transpose_bf16", "k_transpose", "k_stream", "k_reduce_fix", "k_reduce4", "k_reduce", "k_split3",
-           "k_pack1", "k_gemm3", "k_fixup", "k_small_m")
+KERNELS = ("k_transpose", "k_stream", "k_reduce_fix", "k_reduce4", "k_reduce", "k_split3", "k_pack1", "k_gemm3",
+           "k_fixup", "k_small_m")
+# k_transpose<VEC, TX> is one template: its instantiations are reported apart by X's type (demangled, or the
+# type's letter in the mangled name), under the names the three kernels had, so old and new profiles compare
+# (and a library from before the template, given through $TCSC_AMD_LIB, reports under the same keys)
+TRANSPOSE = re.compile(r"k_transpose(?:_(bf16|i8)|<\w+, ([a-z ]+)>|ILb[01]E([fta]))")
+TRANSPOSE_KEY = {"float": "k_transpose", "f": "k_transpose", "unsigned short": "k_transpose_bf16",
+                 "t": "k_transpose_bf16", "signed char": "k_transpose_i8", "a": "k_transpose_i8"}
+
+
+def kernel_name(key):
+    """The reporting name of a profiler event, None when it is not one of the library's kernels."""
+    m = TRANSPOSE.search(key)
+    if m:
+        old, demangled, letter = m.groups()
+        return "k_transpose_" + old if old else TRANSPOSE_KEY.get(demangled or letter, "k_transpose")
+    return next((k for k in KERNELS if k in key), None)  # demangled or not
 
 
 def timed(torch, fn, reps, min_window_s=0.05):
@@ -76,7 +92,7 @@ def kernel_split(torch, fn, calls=5):
         torch.cuda.synchronize()
     out = {}
     for ev in prof.key_averages():
-        name = next((k for k in KERNELS if k in ev.key), None)  # demangled or not
+        name = kernel_name(ev.key)
         if name is None:
             continue
         total = getattr(ev, "device_time_total", None)

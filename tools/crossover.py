@@ -11,13 +11,14 @@ M thresholds (csrc/tcsc_api.cpp kMfmaDensity, kMfmaMinM) can be set from
 measurement.
 
 --dtype bf16 runs the same sweep through tcsc_gpu_sgemm_bf16 (X rounded to
-bf16; k_pack1 + the one-part k_gemm3 on the MFMA side, k_transpose_bf16 on the
-gather's), whose cost model is its own (csrc/tcsc_api.cpp mfma_cheaper_bf16).
+bf16; k_pack1 + the one-part k_gemm3 on the MFMA side, k_transpose's bf16 form
+on the gather's), whose cost model has its own constants (csrc/tcsc_api.cpp:
+mfma_cheaper reads them from kXTypes).
 
 --dtype i8 runs it through tcsc_gpu_sgemm_i8 (X quantized per row by
 tcsc_gpu_quantize_rows_i8, the scales passed along; every plan calls
 enable_i8, so the MFMA side is k_pack8 + k_gemm8 and the gather's staging is
-k_transpose_i8), with its own model again (mfma_cheaper_i8).
+k_transpose's int8 form), with its own constants again (kXTypes' int8 entry).
 
   python tools/crossover.py [--shapes 2048x8192x8192,...] [--densities 0.05,0.1,...] [--dtype fp32|bf16|i8]
 """

@@ -37,9 +37,9 @@ from tcsc_amd import workloads  # noqa: E402
 import bf16_bench  # noqa: E402  (timed(), kernel_split(): the same windows and profiler)
 
 A = 0.2
-bf16_bench.KERNELS = ("k_transpose_bf16", "k_transpose_i8", "k_transpose", "k_stream", "k_reduce_fix", "k_reduce_i8",
-                      "k_reduce4", "k_reduce", "k_split3", "k_pack1", "k_pack8", "k_gemm3", "k_gemm8", "k_fixup",
-                      "k_small_m", "k_quant_rows_i8")
+# (the transposes are told apart by bf16_bench.kernel_name: k_transpose, k_transpose_bf16, k_transpose_i8)
+bf16_bench.KERNELS = ("k_transpose", "k_stream", "k_reduce_fix", "k_reduce_i8", "k_reduce4", "k_reduce", "k_split3",
+                      "k_pack1", "k_pack8", "k_gemm3", "k_gemm8", "k_fixup", "k_small_m", "k_quant_rows_i8")
 
 
 def bench_cfg(torch, cfg, reps):
