@@ -142,8 +142,9 @@ int tcsc_gpu_launch_info(const tcsc_gpu_plan *plan, int M, int *path, int *slice
  *   2  inside the k_stream launch, by row bands (>= 3 slices, the grid fits
  *      the chip at one workgroup per CU, >= 64 workgroups)
  *   0  by k_reduce after it, or nothing is split.
- * Y and bias are assumed 16-B aligned with ldy = N; otherwise the launch
- * uses k_reduce. */
+ * A Y or bias that is not 16-B aligned, or an ldy that is no multiple of 4,
+ * makes the launch fall back to k_reduce after k_stream; the query has no
+ * pointers to look at and reports the aligned case. */
 int tcsc_gpu_launch_combine(const tcsc_gpu_plan *plan, int M, int *in_launch);
 
 /* The gather kernel's geometry a tcsc_gpu_sgemm of M rows takes:

@@ -1,0 +1,1060 @@
+// tcsc_host.cpp -- the host-pointer half of the C ABI of libtcsc_amd.so:
+// include/sparse/tcsc.h, the reference's host-pointer API (sparse/tcsc.h:19-48),
+// and include/sparse_gemm.h, implemented on top of the device API
+// (tcsc_api.cpp): per-tcsc_t plan cache on every GPU used, per-call H2D of X
+// and B, one launch per column block, D2H of each block straight into Y's
+// columns.  It sees of the device layer what tcsc_plan.h declares: a plan is an
+// opaque handle here, and how a call is routed and sized comes from route_call().
+//
+// Error policy: the reference's kernels return void and cannot fail.  Here a
+// HIP failure is recorded (tcsc_gpu_last_error()), printed on stderr and --
+// unless TCSC_ON_ERROR=continue -- aborts, because silently leaving Y
+// unwritten would be worse than the reference's behaviour.
+#include <hip/hip_runtime.h>
+#include <sched.h>
+
+#include <algorithm>
+#include <array>
+#include <chrono>
+#include <atomic>
+#include <condition_variable>
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <deque>
+#include <functional>
+#include <limits>
+#include <memory>
+#include <mutex>
+#include <string>
+#include <thread>
+#include <unordered_map>
+#include <vector>
+
+#include "../../include/sparse/tcsc.h"
+#include "../../include/sparse_gemm.h"
+#include "../../include/tcsc_gpu.h"
+#include "tcsc_plan.h"
+
+// ===========================================================================
+// Host-pointer API (include/sparse/tcsc.h)
+// ===========================================================================
+namespace {
+
+using tcsc::current_order;
+using tcsc::device_count_raw;
+using tcsc::DeviceGuard;
+using tcsc::fmix64;
+using tcsc::hash_finish;
+using tcsc::hash_groups;
+using tcsc::hash_ints;
+using tcsc::hip_fail;
+using tcsc::plan_create_impl;
+using tcsc::Route;
+using tcsc::route_call;
+using tcsc::RoutePins;
+using tcsc::set_error;
+using tcsc::sgemm_ws;
+using tcsc::tcsc_fingerprint;
+
+// One column block of W on one device (column axis), or one device's plan of
+// the whole W (row axis: the calls split M over the devices instead).
+struct Shard {
+    int device = 0;
+    int c0 = 0, c1 = 0;
+    tcsc_gpu_plan* plan = nullptr;
+    // the path and K split of the last launch on this shard, for $TCSC_HOST_PATHS
+    // (written by the one thread that runs the shard's device)
+    mutable int ran_path = -1, ran_slices = 1;
+};
+
+// How the host API spreads a call over the GPUs ($TCSC_SHARD_AXIS, read when
+// a tcsc_t is first cached).  cols (default, the north star's layout,
+// SURVEY.md §8e): block s of S owns the columns [N*s/S, N*(s+1)/S) of W, B
+// and Y, every device receives all of X, and each block's Y lands in its
+// columns of the caller's Y (a pitched D2H copy: the host-side concat).
+// rows: block s owns rows [M*s/S, M*(s+1)/S) of X and Y and uses its
+// device's plan of the whole W -- each device receives only its rows of X,
+// so the PCIe traffic of X is 1/S of the column split's (the better choice
+// when X dominates the copies, e.g. cfg 4 through host pointers).  Either
+// way no data moves between the GPUs and every element is summed as by one
+// launch.
+enum { kAxisRows = 0, kAxisCols = 1 };
+int shard_axis() {
+    const char* e = std::getenv("TCSC_SHARD_AXIS");
+    return (e && std::strcmp(e, "rows") == 0) ? kAxisRows : kAxisCols;
+}
+
+// Host API exact mode (the default; TCSC_HOST_FAST=1 turns it off).  The
+// reference's harness validates tcsc_sgemm_basic / _optimized against its
+// dense oracle, dense.c:64-77 gemm_basic (y = 0; y += X*W over ascending k;
+// Y = y + B), with an absolute 1e-4 (main.cpp:307-333, dense.c:42-59), and
+// the three PReLU variants against each other (main.cpp:357-366).  So every
+// host call sums in exactly that order: the fast order with K never split
+// (the gather with one K-slice, or the small-M path), never the MFMA path,
+// whose bf16 x3 sums are rounded in its own blocked order.
+// The outputs are then gemm_basic's bits (+ PReLU) on every shape, shard count
+// and shard axis.  With TCSC_HOST_FAST=1 host calls take the device API's
+// fastest paths (the MFMA path where the cost model picks it, split K): within
+// the fp32 bound.
+bool host_exact() {
+    const char* e = std::getenv("TCSC_HOST_FAST");
+    return !(e && std::atoi(e) != 0);
+}
+
+struct CacheEntry {
+    // fingerprint: the shape, the array addresses and a hash of the array
+    // contents (tcsc_fingerprint), checked on every call, so rebuilding the
+    // arrays in place or reusing freed addresses for another matrix gets a
+    // fresh plan
+    int rows = 0, cols = 0, n_pos = 0, n_neg = 0;
+    const int *csp = nullptr, *csn = nullptr, *rip = nullptr, *rin = nullptr;
+    uint64_t content = 0;
+    int order = TCSC_ORDER_FAST;  // the summation order the shards' plans were built for
+    int axis = kAxisCols;         // shard_axis() when built
+    int blocks = 1;               // S: row or column blocks per call
+    bool exact = true;            // host_exact() when built: no MFMA image, K never split
+    unsigned traced = 0;          // variants already reported under $TCSC_HOST_PATHS
+    std::vector<Shard> shards;    // cols: one per column block; rows: one per device used
+};
+
+// Per-device staging buffers for X, B and Y of the host API, and the copy
+// streams, events and pinned host slots of the banded pipeline (run_device).
+constexpr int kPinSlots = 3;
+struct DevState {
+    hipStream_t stream = nullptr, s_in = nullptr, s_out = nullptr;
+    float *x = nullptr, *b = nullptr, *y = nullptr, *ws = nullptr;
+    size_t x_cap = 0, b_cap = 0, y_cap = 0, ws_cap = 0;
+    std::vector<hipEvent_t> ev_in, ev_k, ev_out;
+    char* hx[kPinSlots] = {};  // pinned host staging: band b's X in hx[b % kPinSlots]
+    char* hy[kPinSlots] = {};  // and its Y in hy[b % kPinSlots]
+    size_t hx_cap = 0, hy_cap = 0;
+};
+
+// Host copy workers for the pinned staging.  One thread copies pageable
+// memory at 20-29 GB/s, 8 reach ~110-120 GB/s (tools/pcie_bench.cpp on the
+// MI355X box), above the 57 GB/s a PCIe direction takes, so the staging
+// copies keep up with the DMA.  $TCSC_HOST_THREADS sets the count (default
+// 8).  Callers from several threads at once (the pipeline's input and
+// output sides, several devices) share the queue.  The pool is never torn
+// down: its threads sleep on the queue until the process ends.
+class CopyPool {
+  public:
+    explicit CopyPool(int n) {
+        for (int i = 0; i < n; ++i) std::thread([this] { work(); }).detach();
+        n_ = n;
+    }
+    int size() const { return n_; }
+    // rows x row_bytes from src (pitch sp) to dst (pitch dp), split over the
+    // workers; returns once every piece is copied
+    void copy2d(char* dst, size_t dp, const char* src, size_t sp, size_t row_bytes, size_t rows) {
+        if (!rows || !row_bytes) return;
+        if (dp == row_bytes && sp == row_bytes) {  // contiguous: one long row
+            row_bytes *= rows;
+            rows = 1;
+        }
+        std::vector<std::function<void()>> parts;
+        const size_t kMin = 1 << 20;  // pieces of >= 1 MiB
+        if (rows >= (size_t)n_) {
+            for (int t = 0; t < n_; ++t) {
+                const size_t r0 = rows * t / n_, r1 = rows * (t + 1) / n_;
+                parts.push_back([=] {
+                    for (size_t r = r0; r < r1; ++r) std::memcpy(dst + r * dp, src + r * sp, row_bytes);
+                });
+            }
+        } else {
+            const size_t per = std::max(kMin, (row_bytes * rows + n_ - 1) / n_);
+            for (size_t r = 0; r < rows; ++r)
+                for (size_t o = 0; o < row_bytes; o += per) {
+                    const size_t len = std::min(per, row_bytes - o);
+                    parts.push_back([=] { std::memcpy(dst + r * dp + o, src + r * sp + o, len); });
+                }
+        }
+        run(parts);
+    }
+
+    struct Done {
+        std::mutex mu;
+        std::condition_variable cv;
+        int left = 0;
+    };
+    using Handle = std::shared_ptr<Done>;  // outlives the last worker's notify
+
+    // queue every function in `parts` on the workers; wait() for them
+    Handle submit(const std::vector<std::function<void()>>& parts) {
+        auto done = std::make_shared<Done>();
+        done->left = (int)parts.size();
+        if (!done->left) return done;
+        {
+            std::lock_guard<std::mutex> lk(mu_);
+            for (auto& f : parts)
+                q_.push_back([f, done] {
+                    f();
+                    std::lock_guard<std::mutex> dl(done->mu);
+                    if (--done->left == 0) done->cv.notify_all();
+                });
+        }
+        if (parts.size() >= (size_t)n_)
+            cv_.notify_all();
+        else  // wake only as many workers as there are pieces
+            for (size_t i = 0; i < parts.size(); ++i) cv_.notify_one();
+        return done;
+    }
+    static void wait(const Handle& done) {
+        std::unique_lock<std::mutex> dl(done->mu);
+        done->cv.wait(dl, [&] { return done->left == 0; });
+    }
+    void run(const std::vector<std::function<void()>>& parts) { wait(submit(parts)); }
+
+  private:
+    void work() {
+        for (;;) {
+            std::function<void()> f;
+            {
+                std::unique_lock<std::mutex> lk(mu_);
+                cv_.wait(lk, [&] { return !q_.empty(); });
+                f = std::move(q_.front());
+                q_.pop_front();
+            }
+            f();
+        }
+    }
+    int n_ = 0;
+    std::mutex mu_;
+    std::condition_variable cv_;
+    std::deque<std::function<void()>> q_;
+};
+
+// CPUs this process may run on (its affinity mask): the reference's
+// benchmark.sh runs the harness under `taskset -c 0` (benchmark.sh:36), and
+// copy workers confined to one core would be slower than the runtime's own
+// pageable copies.
+int usable_cpus() {
+    static const int n = [] {
+        cpu_set_t set;
+        CPU_ZERO(&set);
+        if (sched_getaffinity(0, sizeof set, &set) != 0) return 1;
+        return std::max(1, CPU_COUNT(&set));
+    }();
+    return n;
+}
+
+// Two pools per device, one per direction: with one shared FIFO a band's
+// input copy queues behind the previous band's output copy and the pipeline
+// serialises; with one pool for all devices, 8 concurrent device pipelines
+// (one host thread per GPU) would queue behind each other.  Each device's
+// pools get min(8, usable CPUs / (2 x visible devices)) workers, at least 1
+// ($TCSC_HOST_THREADS overrides the count).  A third, process-wide pool sums
+// the plan-cache fingerprint while the call already runs (host_sgemm), so it
+// never waits behind the pipeline's copies.
+
+CopyPool& copy_pool(int side, int dev = 0) {
+    static std::mutex mu;
+    static std::vector<std::array<CopyPool*, 2>> per_dev;
+    static CopyPool* hash_pool = nullptr;
+    std::lock_guard<std::mutex> lk(mu);
+    if (side == 2) {
+        // the hash workers run while the copy pools mostly wait on PCIe: all usable CPUs, up to 16
+        if (!hash_pool) hash_pool = new CopyPool(std::max(1, std::min(16, usable_cpus())));
+        return *hash_pool;
+    }
+    if (dev < 0) dev = 0;
+    if ((int)per_dev.size() <= dev) per_dev.resize(dev + 1, {nullptr, nullptr});
+    if (!per_dev[dev][side]) {
+        const int ndev = std::max(1, device_count_raw());
+        int n = std::max(1, std::min(8, usable_cpus() / (2 * ndev)));
+        if (const char* e = std::getenv("TCSC_HOST_THREADS")) n = std::max(1, std::min(64, std::atoi(e)));
+        per_dev[dev][side] = new CopyPool(n);
+    }
+    return *per_dev[dev][side];
+}
+
+// tcsc_fingerprint (same value) with the row-index arrays' 8-int groups
+// summed on the hash workers; start() returns at once, get() waits.  ~50 us
+// for 0.5 M indices and ~190 us for 8 M on the box -- most of a small call's
+// time -- so host_sgemm starts it, runs the call on the plan cached for the
+// same arrays, and only then compares.
+class AsyncFingerprint {
+  public:
+    explicit AsyncFingerprint(const tcsc_t* W) : W_(W) {
+        const long long kMinPar = 1 << 16;  // below, waking the workers costs more than it saves
+        if ((long long)W->n_elem_pos + W->n_elem_neg < kMinPar || usable_cpus() < 2) {
+            value_ = tcsc_fingerprint(W);
+            done_ = true;
+            return;
+        }
+        CopyPool& pool = copy_pool(2);
+        // ~256 K indices per piece: small arrays wake few workers
+        const long long total = (long long)W->n_elem_pos + W->n_elem_neg;
+        T_ = (int)std::max(1LL, std::min((long long)pool.size(), total >> 18));
+        part_.assign(2 * T_, std::array<uint64_t, 4>{0, 0, 0, 0});
+        std::vector<std::function<void()>> fs;
+        const int* arr[2] = {W->row_index_pos, W->row_index_neg};
+        const long long n[2] = {W->n_elem_pos, W->n_elem_neg};
+        for (int a = 0; a < 2; ++a) {
+            if (!arr[a] || n[a] <= 0) continue;
+            const uint32_t* u = reinterpret_cast<const uint32_t*>(arr[a]);
+            const long long groups = n[a] / 8;
+            for (int t = 0; t < T_; ++t)
+                fs.push_back([this, u, groups, a, t] {
+                    hash_groups(u, 8 * (groups * t / T_), 8 * (groups * (t + 1) / T_), part_[a * T_ + t].data());
+                });
+        }
+        handle_ = pool.submit(fs);
+    }
+    uint64_t get() {
+        if (done_) return value_;
+        CopyPool::wait(handle_);
+        uint64_t h = fmix64(((uint64_t)(uint32_t)W_->rows << 32) | (uint32_t)W_->cols);
+        h = hash_ints(W_->col_start_pos, (long long)W_->cols + 1, h);
+        h = hash_ints(W_->col_start_neg, (long long)W_->cols + 1, h);
+        const int* arr[2] = {W_->row_index_pos, W_->row_index_neg};
+        const long long n[2] = {W_->n_elem_pos, W_->n_elem_neg};
+        for (int a = 0; a < 2; ++a) {
+            h = fmix64(h ^ (uint64_t)n[a]);
+            if (!arr[a] || n[a] <= 0) continue;
+            uint64_t acc[4] = {0, 0, 0, 0};
+            for (int t = 0; t < T_; ++t)
+                for (int j = 0; j < 4; ++j) acc[j] += part_[a * T_ + t][j];
+            h = hash_finish(reinterpret_cast<const uint32_t*>(arr[a]), n[a], h, acc);
+        }
+        value_ = h;
+        done_ = true;
+        return h;
+    }
+    ~AsyncFingerprint() {
+        if (!done_) CopyPool::wait(handle_);  // the workers write into part_
+    }
+
+  private:
+    const tcsc_t* W_;
+    int T_ = 0;
+    std::vector<std::array<uint64_t, 4>> part_;
+    CopyPool::Handle handle_;
+    uint64_t value_ = 0;
+    bool done_ = false;
+};
+
+int ensure_pinned(char* (&slots)[kPinSlots], size_t* cap, size_t bytes) {
+    if (*cap >= bytes && slots[0]) return TCSC_OK;
+    for (auto& p : slots) {
+        if (p) (void)hipHostFree(p);
+        p = nullptr;
+    }
+    *cap = 0;
+    for (auto& p : slots) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&p), bytes, hipHostMallocDefault));
+    *cap = bytes;
+    return TCSC_OK;
+}
+
+std::mutex g_mu;  // guards everything below (host API is re-entrant, not concurrent-fast)
+std::unordered_map<const tcsc_t*, CacheEntry> g_cache;
+std::vector<DevState> g_dev;
+int g_shards_override = 0;
+
+void destroy_entry(CacheEntry& e) {
+    for (auto& s : e.shards) tcsc_gpu_plan_destroy(s.plan);
+    e.shards.clear();
+}
+
+bool fingerprint_matches(const CacheEntry& e, const tcsc_t* W, uint64_t content) {
+    return e.rows == W->rows && e.cols == W->cols && e.n_pos == W->n_elem_pos && e.n_neg == W->n_elem_neg &&
+           e.csp == W->col_start_pos && e.csn == W->col_start_neg && e.rip == W->row_index_pos &&
+           e.rin == W->row_index_neg && e.content == content && e.order == current_order() &&
+           e.axis == shard_axis() && e.exact == host_exact();
+}
+
+[[noreturn]] void die() {
+    std::fprintf(stderr, "[tcsc_amd] fatal: %s\n", tcsc::error_msg());
+    std::abort();
+}
+
+void report(int rc) {
+    if (rc == TCSC_OK) return;
+    const char* pol = std::getenv("TCSC_ON_ERROR");
+    if (pol && std::strcmp(pol, "continue") == 0) {
+        std::fprintf(stderr, "[tcsc_amd] error: %s\n", tcsc::error_msg());
+        return;
+    }
+    die();
+}
+
+int ensure(float** p, size_t* cap, size_t bytes) {
+    if (*cap >= bytes && *p) return TCSC_OK;
+    if (*p) (void)hipFree(*p);
+    *p = nullptr;
+    *cap = 0;
+    size_t want = bytes < 256 ? 256 : bytes;
+    HIP_TRY(hipMalloc(p, want));
+    *cap = want;
+    return TCSC_OK;
+}
+
+int num_shards_locked(int ndev) {
+    if (g_shards_override > 0) return g_shards_override;
+    int n = ndev;
+    if (const char* s = std::getenv("TCSC_NUM_GPUS")) {
+        int v = std::atoi(s);
+        if (v > 0 && v < n) n = v;
+    }
+    return n < 1 ? 1 : n;
+}
+
+// The cached entry of W if everything but the content hash matches (shape,
+// counts, array addresses, order, axis), else null.
+CacheEntry* find_structural_locked(const tcsc_t* W) {
+    auto it = g_cache.find(W);
+    if (it == g_cache.end()) return nullptr;
+    const CacheEntry& e = it->second;
+    return fingerprint_matches(e, W, e.content) ? &it->second : nullptr;
+}
+
+int get_entry_locked(const tcsc_t* W, uint64_t content, CacheEntry** out) {
+    const int ndev = device_count_raw();
+    if (ndev <= 0) {
+        set_error("no HIP device visible: the TCSC kernels need a gfx950 GPU");
+        return TCSC_E_NODEV;
+    }
+    if ((int)g_dev.size() < ndev) g_dev.resize(ndev);
+    auto it = g_cache.find(W);
+    if (it != g_cache.end()) {
+        if (fingerprint_matches(it->second, W, content)) {
+            *out = &it->second;
+            return TCSC_OK;
+        }
+        destroy_entry(it->second);
+        g_cache.erase(it);
+    }
+    CacheEntry e;
+    e.rows = W->rows;
+    e.cols = W->cols;
+    e.n_pos = W->n_elem_pos;
+    e.n_neg = W->n_elem_neg;
+    e.csp = W->col_start_pos;
+    e.csn = W->col_start_neg;
+    e.rip = W->row_index_pos;
+    e.rin = W->row_index_neg;
+    e.content = content;
+    e.order = current_order();
+    e.axis = shard_axis();
+    e.exact = host_exact();
+    int S = num_shards_locked(ndev);
+    if (e.axis == kAxisCols && S > W->cols && W->cols > 0) S = W->cols;
+    if (S < 1) S = 1;
+    e.blocks = S;
+    const int nplans = e.axis == kAxisRows ? std::min(S, ndev) : S;
+    for (int s = 0; s < nplans; ++s) {
+        Shard sh;
+        sh.device = s % ndev;
+        sh.c0 = e.axis == kAxisRows ? 0 : (int)((long long)W->cols * s / S);
+        sh.c1 = e.axis == kAxisRows ? W->cols : (int)((long long)W->cols * (s + 1) / S);
+        DevState& ds = g_dev[sh.device];
+        {
+            DeviceGuard dg(sh.device);
+            if (!ds.stream) HIP_TRY(hipStreamCreateWithFlags(&ds.stream, hipStreamNonBlocking));
+        }
+        int rc = plan_create_impl(W, sh.c0, sh.c1, sh.device, ds.stream, !e.exact, &sh.plan);
+        if (rc != TCSC_OK) {
+            destroy_entry(e);
+            return rc;
+        }
+        e.shards.push_back(sh);
+    }
+    auto res = g_cache.emplace(W, std::move(e));
+    *out = &res.first->second;
+    return TCSC_OK;
+}
+
+// One block of a call: rows [m0, m1) x the plan's columns [c0, c1).
+struct Job {
+    const Shard* sh;
+    int m0, m1;
+};
+
+// Row bands of one job for the copy/compute pipeline (run_bands): X arrives
+// from pageable host memory and Y goes back to it, ~10 ms of PCIe at cfg 4
+// against 1.3 ms of kernels.  Split into bands (whole 256-row tiles), band
+// b's kernels run while band b+1's X and band b-1's Y cross PCIe in both
+// directions.  Measured (tools/host_pipe_sweep.py, 8 copy workers per
+// direction): 8 bands are best from 64 MB of X up (cfg 4: 11.1 -> 7.4-8.4 ms
+// through torch's HIP runtime, 11.2 -> 9.2 ms in the native driver, where 16
+// bands of 16 MB lose the H2D/D2H overlap again; 2048x8192: 3.0 -> 2.3 ms);
+// below ~48 MB the single-shot pageable copies win (cfg 2: 0.82 ms against
+// 0.86-1.0 banded).  Only where the whole job takes the gather path, and
+// then every band runs the gather with the split-K factor of the whole job
+// (run_bands pins both: a band of M / n rows asked on its own may prefer the
+// MFMA path, the cost model is not monotone in M): each element is summed in
+// the same order as by one launch, so the bits do not change.
+// TCSC_HOST_BANDS=1 turns the pipeline off, =n asks for n.
+int host_bands(const Route& job, int M, int K) {
+    if (job.path != TCSC_PATH_GATHER || K <= 0) return 1;
+    const double xbytes = (double)M * K * sizeof(float), MiB = 1024.0 * 1024;
+    // the pipeline's copies need CPUs: none of it under `taskset -c 0` (benchmark.sh:36)
+    int nb = (xbytes < 48 * MiB || usable_cpus() < 4) ? 1 : std::max(4, std::min(8, (int)(xbytes / (8 * MiB))));
+    if (const char* e = std::getenv("TCSC_HOST_BANDS")) nb = std::min(std::atoi(e), 64);
+    nb = std::min(nb, M / tcsc::kTM);  // whole row tiles
+    return nb < 2 ? 1 : nb;
+}
+
+int ensure_events(std::vector<hipEvent_t>& v, size_t n, unsigned flags = hipEventDisableTiming) {
+    while (v.size() < n) {
+        hipEvent_t e;
+        HIP_TRY(hipEventCreateWithFlags(&e, flags));
+        v.push_back(e);
+    }
+    return TCSC_OK;
+}
+
+// One large job as a pipeline of row bands (host_bands) through pinned host
+// slots.  Pageable copies reach ~56 GB/s for H2D and D2H together, because
+// the runtime stages them through its own buffers one direction at a time;
+// pinned copies run both directions at once (97 GB/s, tools/pcie_bench.cpp).
+// So band b's X goes pageable -> hx[b % 3] on the copy workers, then H2D on
+// s_in; the kernels run on the compute stream; its Y goes D2H into
+// hy[b % 3] on s_out, and an output thread moves it into the caller's Y
+// while the next bands are in flight.  The input side reuses an X slot once
+// its H2D is done (ev_in); it reuses a Y slot once the output thread has
+// drained it (`drained`).  Every band runs with the split-K factor of the
+// whole job, so the bits equal one launch's.
+constexpr int kNoPinned = -1;  // run_bands: no pinned slots, take the unbanded path
+int run_bands(int dev, DevState& ds, const Shard& sh, int m0, int M, int nb, const float* X, const float* B, float* Y,
+              int N, int K, int variant, float a, const Route& job) {
+    const tcsc_gpu_plan* p = sh.plan;
+    const int nc = sh.c1 - sh.c0;
+    hipStream_t st = ds.stream;
+    int rc;
+    // every band on the whole job's path (host_bands: the gather) and K split
+    RoutePins pin;
+    pin.path = job.path;
+    pin.slices = job.slices;
+    pin.plan_ws = false;
+    const int rows_per = (M + nb - 1) / nb;
+    const int bm = (rows_per + tcsc::kTM - 1) / tcsc::kTM * tcsc::kTM;
+    const int nbands = (M + bm - 1) / bm;
+    const size_t xrow = (size_t)K * sizeof(float), yrow = (size_t)nc * sizeof(float);
+    const size_t wsb = route_call(p, bm, tcsc::kF32, tcsc::kUnbounded, pin).ws_bytes;
+    if ((rc = ensure(&ds.x, &ds.x_cap, (size_t)M * xrow)) != TCSC_OK) return rc;
+    if ((rc = ensure(&ds.ws, &ds.ws_cap, wsb)) != TCSC_OK) return rc;
+    if (ensure_pinned(ds.hx, &ds.hx_cap, (size_t)bm * xrow) != TCSC_OK ||
+        ensure_pinned(ds.hy, &ds.hy_cap, (size_t)bm * yrow) != TCSC_OK) {
+        // no pinned memory to be had (a locked-memory limit): the caller
+        // takes the single-copy path instead, with the same bits
+        (void)hipGetLastError();
+        tcsc::set_error_msg("");
+        return kNoPinned;
+    }
+    if (!ds.s_in) HIP_TRY(hipStreamCreateWithFlags(&ds.s_in, hipStreamNonBlocking));
+    if (!ds.s_out) HIP_TRY(hipStreamCreateWithFlags(&ds.s_out, hipStreamNonBlocking));
+    // the host waits on ev_in / ev_out sleep instead of spinning next to the copy workers
+    const unsigned host_wait = hipEventDisableTiming | hipEventBlockingSync;
+    if ((rc = ensure_events(ds.ev_in, nbands, host_wait)) != TCSC_OK ||
+        (rc = ensure_events(ds.ev_k, nbands)) != TCSC_OK || (rc = ensure_events(ds.ev_out, nbands, host_wait)) != TCSC_OK)
+        return rc;
+    HIP_TRY(hipMemcpyAsync(ds.b, B + sh.c0, yrow, hipMemcpyHostToDevice, st));
+    // $TCSC_HOST_TRACE: per-band timeline on stderr (ms since the call entered run_bands)
+    static const bool trace = std::getenv("TCSC_HOST_TRACE") != nullptr;
+    const auto T0 = std::chrono::steady_clock::now();
+    auto now_ms = [&] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - T0).count(); };
+    std::vector<double> t_in0(nbands), t_in1(nbands), t_out0(nbands), t_out1(nbands), t_wy(nbands);
+    CopyPool& pool_in = copy_pool(0, dev);
+    CopyPool& pool_out = copy_pool(1, dev);
+    auto band = [&](int b, int* r0, int* r1) {
+        *r0 = b * bm;
+        *r1 = std::min(M, *r0 + bm);
+    };
+
+    // output side: band by band, wait for its D2H, copy it into Y's rows/columns
+    std::mutex mu;
+    std::condition_variable cv;
+    int drained = 0, enqueued = 0;  // bands copied out / bands whose D2H is enqueued
+    bool stop = false;
+    int out_rc = TCSC_OK;
+    std::string out_err;
+    std::thread out([&] {
+        for (int b = 0; b < nbands; ++b) {
+            {
+                std::unique_lock<std::mutex> lk(mu);
+                cv.wait(lk, [&] { return enqueued > b || stop; });
+                if (enqueued <= b) return;
+            }
+            const hipError_t e = hipEventSynchronize(ds.ev_out[b]);
+            if (e != hipSuccess) {
+                out_rc = hip_fail(e, "hipEventSynchronize (band D2H)");
+                out_err = tcsc::error_msg();
+                std::lock_guard<std::mutex> lk(mu);
+                drained = nbands;  // unblock the input side
+                cv.notify_all();
+                return;
+            }
+            int r0, r1;
+            band(b, &r0, &r1);
+            t_out0[b] = now_ms();
+            pool_out.copy2d(reinterpret_cast<char*>(Y + (size_t)(m0 + r0) * N + sh.c0), (size_t)N * sizeof(float),
+                        ds.hy[b % kPinSlots], yrow, yrow, (size_t)(r1 - r0));
+            t_out1[b] = now_ms();
+            std::lock_guard<std::mutex> lk(mu);
+            drained = b + 1;
+            cv.notify_all();
+        }
+    });
+    auto finish = [&](int r) {
+        {
+            std::lock_guard<std::mutex> lk(mu);
+            stop = true;
+        }
+        cv.notify_all();
+        out.join();
+        if (r == TCSC_OK && out_rc != TCSC_OK) {
+            tcsc::set_error_msg(out_err.c_str());
+            return out_rc;
+        }
+        return r;
+    };
+
+    // input side
+    for (int b = 0; b < nbands; ++b) {
+        const int slot = b % kPinSlots;
+        int r0, r1;
+        band(b, &r0, &r1);
+        const hipError_t e = b >= kPinSlots ? hipEventSynchronize(ds.ev_in[b - kPinSlots]) : hipSuccess;
+        if (e != hipSuccess) return finish(hip_fail(e, "hipEventSynchronize (band H2D)"));
+        t_in0[b] = now_ms();
+        pool_in.copy2d(ds.hx[slot], xrow, reinterpret_cast<const char*>(X + (size_t)(m0 + r0) * K), xrow, xrow,
+                    (size_t)(r1 - r0));
+        t_in1[b] = now_ms();
+        float* xb = ds.x + (size_t)r0 * K;
+        hipError_t he = hipMemcpyAsync(xb, ds.hx[slot], (size_t)(r1 - r0) * xrow, hipMemcpyHostToDevice, ds.s_in);
+        if (he == hipSuccess) he = hipEventRecord(ds.ev_in[b], ds.s_in);
+        if (he == hipSuccess) he = hipStreamWaitEvent(st, ds.ev_in[b], 0);
+        if (he != hipSuccess) return finish(hip_fail(he, "band H2D"));
+        // the whole job's path (host_bands: the gather) and K split: a band of bm rows
+        // chooses neither for itself, and ds.ws is sized for exactly this
+        Route route;
+        if ((rc = sgemm_ws(p, xb, ds.b, ds.y + (size_t)r0 * nc, r1 - r0, nc, variant, a, st, ds.ws, ds.ws_cap, 0, pin,
+                           &route)) != TCSC_OK)
+            return finish(rc);
+        sh.ran_path = route.path;
+        sh.ran_slices = route.slices;
+        he = hipEventRecord(ds.ev_k[b], st);
+        if (he == hipSuccess) he = hipStreamWaitEvent(ds.s_out, ds.ev_k[b], 0);
+        if (he != hipSuccess) return finish(hip_fail(he, "band kernels"));
+        {  // the Y slot must have been copied out (band b - kPinSlots)
+            std::unique_lock<std::mutex> lk(mu);
+            cv.wait(lk, [&] { return drained >= b - kPinSlots + 1; });
+        }
+        t_wy[b] = now_ms();
+        he = hipMemcpyAsync(ds.hy[slot], ds.y + (size_t)r0 * nc, (size_t)(r1 - r0) * yrow, hipMemcpyDeviceToHost,
+                            ds.s_out);
+        if (he == hipSuccess) he = hipEventRecord(ds.ev_out[b], ds.s_out);
+        if (he != hipSuccess) return finish(hip_fail(he, "band D2H"));
+        {
+            std::lock_guard<std::mutex> lk(mu);
+            enqueued = b + 1;
+        }
+        cv.notify_all();
+    }
+    rc = finish(TCSC_OK);
+    if (trace) {
+        for (int b = 0; b < nbands; ++b)
+            std::fprintf(stderr, "[tcsc_amd] band %d: X copy %.3f-%.3f, D2H enqueued %.3f, Y copy %.3f-%.3f ms\n", b,
+                         t_in0[b], t_in1[b], t_wy[b], t_out0[b], t_out1[b]);
+        std::fprintf(stderr, "[tcsc_amd] bands done %.3f ms\n", now_ms());
+    }
+    if (rc != TCSC_OK) return rc;
+    HIP_TRY(hipStreamSynchronize(st));
+    return TCSC_OK;
+}
+
+// Everything one device does for one call, job by job: H2D of the job's rows
+// of X (skipped when the previous job staged the same rows), H2D of the bias
+// slice, the launch, D2H of the (m1-m0) x (c1-c0) block into Y.  A large job
+// runs as a pipeline of row bands over three streams (host_bands).
+int run_device(int dev, const std::vector<Job>& jobs, const float* X, const float* B, float* Y, int N, int K,
+               int variant, float a, bool exact) {
+    DeviceGuard dg(dev);
+    DevState& ds = g_dev[dev];
+    hipStream_t st = ds.stream;
+    int rc, staged0 = -1, staged1 = -1;
+    for (const Job& j : jobs) {
+        const Shard* sh = j.sh;
+        const int nc = sh->c1 - sh->c0, M = j.m1 - j.m0;
+        if (nc == 0 || M == 0) continue;
+        // the whole job's route, decided once: exact mode pins one K slice (its plans have no MFMA
+        // image, so the path is the gather or the small-M one); every band and launch below runs it
+        RoutePins pin;
+        pin.slices = exact ? 1 : 0;
+        pin.plan_ws = false;
+        const Route job = route_call(sh->plan, M, tcsc::kF32, tcsc::kUnbounded, pin);
+        const int nb = (j.m0 != staged0 || j.m1 != staged1) ? host_bands(job, M, K) : 1;
+        if ((rc = ensure(&ds.b, &ds.b_cap, (size_t)nc * sizeof(float))) != TCSC_OK) return rc;
+        if ((rc = ensure(&ds.y, &ds.y_cap, (size_t)M * nc * sizeof(float))) != TCSC_OK) return rc;
+        if (nb > 1) {
+            rc = run_bands(dev, ds, *j.sh, j.m0, M, nb, X, B, Y, N, K, variant, a, job);
+            if (rc == TCSC_OK) {
+                staged0 = j.m0;
+                staged1 = j.m1;
+                continue;
+            }
+            if (rc != kNoPinned) return rc;
+        }
+        if (j.m0 != staged0 || j.m1 != staged1) {
+            const size_t xb = (size_t)M * K * sizeof(float);
+            if ((rc = ensure(&ds.x, &ds.x_cap, xb)) != TCSC_OK) return rc;
+            if (xb) HIP_TRY(hipMemcpyAsync(ds.x, X + (size_t)j.m0 * K, xb, hipMemcpyHostToDevice, st));
+            staged0 = j.m0;
+            staged1 = j.m1;
+        }
+        const size_t wsb = job.ws_bytes;
+        if (wsb && (rc = ensure(&ds.ws, &ds.ws_cap, wsb)) != TCSC_OK) return rc;
+        HIP_TRY(hipMemcpyAsync(ds.b, B + sh->c0, (size_t)nc * sizeof(float), hipMemcpyHostToDevice, st));
+        pin.path = job.path;
+        pin.slices = job.slices;
+        Route route;
+        if ((rc = sgemm_ws(sh->plan, ds.x, ds.b, ds.y, M, nc, variant, a, st, ds.ws, ds.ws_cap, 0, pin, &route)) !=
+            TCSC_OK)
+            return rc;
+        sh->ran_path = route.path;
+        sh->ran_slices = route.slices;
+        HIP_TRY(hipMemcpy2DAsync(Y + (size_t)j.m0 * N + sh->c0, (size_t)N * sizeof(float), ds.y,
+                                 (size_t)nc * sizeof(float), (size_t)nc * sizeof(float), M, hipMemcpyDeviceToHost,
+                                 st));
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    return TCSC_OK;
+}
+
+// $TCSC_HOST_PATHS: one stderr line per matrix and variant (its first call),
+// naming the path and K-split each block took (recorded by run_device /
+// run_bands when they launched, not recomputed here), so a failed validation
+// in a harness run (tests/test_reference_main_gpu.py) says which code computed it.
+void trace_paths(CacheEntry& e, int variant, int M, int N, int K) {
+    static const bool on = std::getenv("TCSC_HOST_PATHS") != nullptr;
+    if (!on || variant < 0 || variant >= 32 || (e.traced & (1u << variant))) return;
+    e.traced |= 1u << variant;
+    static const char* kNames[] = {"basic", "optimized", "prelu_basic", "prelu_separate", "prelu_onthego",
+                                   "sparse_gemm"};
+    std::string paths;
+    for (const Shard& sh : e.shards) {
+        // what run_device / run_bands ran on this shard (its last block, when it served several)
+        const char* path = sh.ran_path == TCSC_PATH_MFMA    ? "mfma"
+                           : sh.ran_path == TCSC_PATH_SMALL ? "small"
+                           : sh.ran_path == TCSC_PATH_GATHER ? "gather"
+                                                             : "none";
+        char buf[96];
+        std::snprintf(buf, sizeof buf, "%s%s/s%d", paths.empty() ? "" : ",", path, sh.ran_slices);
+        paths += buf;
+    }
+    std::fprintf(stderr, "[tcsc_amd] path: %s M=%d N=%d K=%d blocks=%d axis=%s exact=%d -> %s\n",
+                 variant <= TCSC_VARIANT_SPARSE_GEMM ? kNames[variant] : "?", M, N, K, e.blocks,
+                 e.axis == kAxisRows ? "rows" : "cols", e.exact ? 1 : 0, paths.c_str());
+}
+
+void host_sgemm(int variant, const float* X, const tcsc_t* W, const float* B, float a, float* Y, int M, int N,
+                int K) {
+    if (M <= 0 || N <= 0) return;
+    if (!W || W->cols != N || W->rows != K || !Y || !B || (!X && K > 0)) {
+        set_error("tcsc_sgemm: shape mismatch (W %dx%d, M=%d N=%d K=%d) or NULL", W ? W->rows : -1,
+                  W ? W->cols : -1, M, N, K);
+        report(TCSC_E_ARG);
+        return;
+    }
+    static const bool trace = std::getenv("TCSC_HOST_TRACE") != nullptr;
+    const auto t0 = std::chrono::steady_clock::now();
+    auto us = [&] { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count(); };
+    std::lock_guard<std::mutex> lk(g_mu);
+    if (device_count_raw() <= 0) {
+        set_error("no HIP device visible: the TCSC kernels need a gfx950 GPU");
+        report(TCSC_E_NODEV);
+        return;
+    }
+    // The content fingerprint (AsyncFingerprint) is summed while the call
+    // runs on the plan cached for the same arrays; if the arrays turn out to
+    // have changed in place, the plan is rebuilt and the call run again, so
+    // Y is only ever left holding the current W's product.
+    AsyncFingerprint fp(W);
+    CacheEntry* e = find_structural_locked(W);
+    const bool speculative = e != nullptr;
+    int rc = TCSC_OK;
+    if (!speculative && (rc = get_entry_locked(W, fp.get(), &e)) != TCSC_OK) {
+        report(rc);
+        return;
+    }
+    auto run = [&](CacheEntry* ce) -> int {
+        // the call's blocks, grouped by device
+        std::vector<std::vector<Job>> per_dev(g_dev.size());
+        if (ce->axis == kAxisRows) {
+            const int S = ce->blocks, P = (int)ce->shards.size();
+            for (int s = 0; s < S; ++s) {
+                const Shard* sh = &ce->shards[s % P];
+                per_dev[sh->device].push_back(
+                    Job{sh, (int)((long long)M * s / S), (int)((long long)M * (s + 1) / S)});
+            }
+        } else {
+            for (const auto& s : ce->shards) per_dev[s.device].push_back(Job{&s, 0, M});
+        }
+        std::vector<int> used;
+        for (size_t d = 0; d < per_dev.size(); ++d)
+            if (!per_dev[d].empty()) used.push_back((int)d);
+        if (used.size() == 1) return run_device(used[0], per_dev[used[0]], X, B, Y, N, K, variant, a, ce->exact);
+        std::vector<int> rcs(used.size(), TCSC_OK);
+        std::vector<std::string> errs(used.size());
+        std::vector<std::thread> th;
+        for (size_t i = 0; i < used.size(); ++i)
+            th.emplace_back([&, i] {
+                rcs[i] = run_device(used[i], per_dev[used[i]], X, B, Y, N, K, variant, a, ce->exact);
+                if (rcs[i] != TCSC_OK) errs[i] = tcsc::error_msg();  // thread-local
+            });
+        for (auto& t : th) t.join();
+        for (size_t i = 0; i < used.size(); ++i)
+            if (rcs[i] != TCSC_OK) {
+                tcsc::set_error_msg(errs[i].c_str());
+                return rcs[i];
+            }
+        return TCSC_OK;
+    };
+    rc = run(e);
+    bool rerun = false;
+    if (speculative && fp.get() != e->content) {  // W's arrays changed in place: stale plan
+        rerun = true;
+        if ((rc = get_entry_locked(W, fp.get(), &e)) == TCSC_OK) rc = run(e);
+        if (rc != TCSC_OK) {
+            // Y holds the stale plan's product (or part of the rerun's): never leave
+            // that behind under TCSC_ON_ERROR=continue -- quiet NaN everywhere
+            const float qnan = std::numeric_limits<float>::quiet_NaN();
+            for (size_t i = 0; i < (size_t)M * N; ++i) Y[i] = qnan;
+        }
+    }
+    if (trace)
+        std::fprintf(stderr, "[tcsc_amd] host call: %.1f us (%s%s)\n", us(),
+                     speculative ? "cached plan, fingerprint overlapped" : "plan built", rerun ? ", rerun" : "");
+    if (rc == TCSC_OK) trace_paths(*e, variant, M, N, K);
+    report(rc);
+}
+
+// --- SparseGEMM.h's raw-array API (include/sparse_gemm.h) ------------------
+// Its calls carry no tcsc_t, so each distinct col_start_pos array gets a
+// library-owned tcsc_t view; the view goes through host_sgemm like any
+// tcsc_t, so the plan cache's content fingerprint catches arrays that were
+// rebuilt in place or freed and reused.  The reference's harness builds a
+// new SparseFormat per case (SparseGEMM.cpp:101) and never says when one
+// dies, so only the kRawViews most recently used views keep their plans.
+constexpr size_t kRawViews = 8;
+std::mutex g_raw_mu;  // taken before g_mu, never after it
+std::deque<std::pair<const int*, std::unique_ptr<tcsc_t>>> g_raw;  // most recent first
+
+void raw_sgemm(int variant, const float* X, const int* csp, const int* csn, const int* rip, const int* rin,
+               const float* b, float* Y, int M, int N, int K, float a) {
+    if (M <= 0 || N <= 0) return;
+    if (!csp || !csn || K < 0) {
+        set_error("sparseGEMM: NULL col_start array or K=%d", K);
+        report(TCSC_E_ARG);
+        return;
+    }
+    std::lock_guard<std::mutex> rk(g_raw_mu);
+    auto it = std::find_if(g_raw.begin(), g_raw.end(), [&](const auto& e) { return e.first == csp; });
+    std::unique_ptr<tcsc_t> view;
+    if (it != g_raw.end()) {
+        view = std::move(it->second);
+        g_raw.erase(it);
+    } else {
+        view.reset(new tcsc_t{});
+        if (g_raw.size() >= kRawViews) {  // drop the least recently used view and its plans
+            std::lock_guard<std::mutex> lk(g_mu);
+            auto c = g_cache.find(g_raw.back().second.get());
+            if (c != g_cache.end()) {
+                destroy_entry(c->second);
+                g_cache.erase(c);
+            }
+            g_raw.pop_back();
+        }
+    }
+    tcsc_t* v = view.get();
+    g_raw.emplace_front(csp, std::move(view));
+    // the reference's loops run k over [col_start[n], col_start[n+1]) of the
+    // row arrays, so col_start[N] entries of each are addressable
+    v->rows = K;
+    v->cols = N;
+    v->n_elem_pos = csp[N];
+    v->n_elem_neg = csn[N];
+    v->col_start_pos = const_cast<int*>(csp);
+    v->col_start_neg = const_cast<int*>(csn);
+    v->row_index_pos = const_cast<int*>(rip);
+    v->row_index_neg = const_cast<int*>(rin);
+    if ((csp[N] > 0 && !rip) || (csn[N] > 0 && !rin)) {
+        set_error("sparseGEMM: NULL row_index array with %d / %d entries", csp[N], csn[N]);
+        report(TCSC_E_ARG);
+        return;
+    }
+    host_sgemm(variant, X, v, b, a, Y, M, N, K);
+}
+
+// GEMM / GEMM_PReLU (SparseGEMM.h:121-149) on host pointers: the dense
+// baseline through tcsc_gpu_dense_sgemm on the current device, with
+// per-device staging buffers that grow as needed.
+struct DenseStage {
+    float *x = nullptr, *w = nullptr, *b = nullptr, *y = nullptr;
+    size_t x_cap = 0, w_cap = 0, b_cap = 0, y_cap = 0;
+};
+std::vector<DenseStage> g_dense;
+
+void host_dense(int variant, const float* X, const float* W, const float* b, float* Y, int M, int N, int K, float a) {
+    if (M <= 0 || N <= 0) return;
+    if (K < 0 || !Y || !b || (K > 0 && (!X || !W))) {
+        set_error("GEMM: bad arguments (M=%d N=%d K=%d) or NULL", M, N, K);
+        report(TCSC_E_ARG);
+        return;
+    }
+    std::lock_guard<std::mutex> lk(g_mu);
+    const int ndev = device_count_raw();
+    int dev = 0, rc = TCSC_OK;
+    if (ndev <= 0) {
+        set_error("no HIP device visible: GEMM needs a gfx950 GPU");
+        report(TCSC_E_NODEV);
+        return;
+    }
+    if (hipGetDevice(&dev) != hipSuccess || dev >= ndev) dev = 0;
+    if ((int)g_dev.size() < ndev) g_dev.resize(ndev);
+    if ((int)g_dense.size() < ndev) g_dense.resize(ndev);
+    DevState& ds = g_dev[dev];
+    DenseStage& d = g_dense[dev];
+    auto run = [&]() -> int {
+        DeviceGuard dg(dev);
+        if (!ds.stream) HIP_TRY(hipStreamCreateWithFlags(&ds.stream, hipStreamNonBlocking));
+        const size_t xb = (size_t)M * K * sizeof(float), wb = (size_t)K * N * sizeof(float);
+        int r;
+        if ((r = ensure(&d.x, &d.x_cap, xb)) != TCSC_OK || (r = ensure(&d.w, &d.w_cap, wb)) != TCSC_OK ||
+            (r = ensure(&d.b, &d.b_cap, (size_t)N * sizeof(float))) != TCSC_OK ||
+            (r = ensure(&d.y, &d.y_cap, (size_t)M * N * sizeof(float))) != TCSC_OK)
+            return r;
+        if (xb) HIP_TRY(hipMemcpyAsync(d.x, X, xb, hipMemcpyHostToDevice, ds.stream));
+        if (wb) HIP_TRY(hipMemcpyAsync(d.w, W, wb, hipMemcpyHostToDevice, ds.stream));
+        HIP_TRY(hipMemcpyAsync(d.b, b, (size_t)N * sizeof(float), hipMemcpyHostToDevice, ds.stream));
+        if ((r = tcsc_gpu_dense_sgemm(d.x, d.w, d.b, d.y, M, N, K, N, variant, a, ds.stream)) != TCSC_OK) return r;
+        HIP_TRY(hipMemcpyAsync(Y, d.y, (size_t)M * N * sizeof(float), hipMemcpyDeviceToHost, ds.stream));
+        HIP_TRY(hipStreamSynchronize(ds.stream));
+        return TCSC_OK;
+    };
+    rc = run();
+    report(rc);
+}
+
+}  // namespace
+
+namespace tcsc {
+void report_status(int rc) { report(rc); }
+}  // namespace tcsc
+
+extern "C" {
+
+void tcsc_gpu_cache_clear(void) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    for (auto& kv : g_cache) destroy_entry(kv.second);
+    g_cache.clear();
+}
+
+int tcsc_gpu_num_shards(void) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    return num_shards_locked(device_count_raw());
+}
+
+void tcsc_gpu_set_num_shards(int shards) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    g_shards_override = shards > 0 ? shards : 0;
+    for (auto& kv : g_cache) destroy_entry(kv.second);
+    g_cache.clear();
+}
+
+void tcsc_sgemm_basic(const dense_t X, const tcsc_t* W, const dense_t B, dense_t Y, int M, int N, int K) {
+    host_sgemm(TCSC_VARIANT_BASIC, X, W, B, 0.0f, Y, M, N, K);
+}
+
+void tcsc_sgemm_optimized(const dense_t X, const tcsc_t* W, const dense_t B, dense_t Y, int M, int N, int K) {
+    host_sgemm(TCSC_VARIANT_OPTIMIZED, X, W, B, 0.0f, Y, M, N, K);
+}
+
+void tcsc_sgemm_prelu_basic(const dense_t X, const tcsc_t* W, const dense_t B, float a, dense_t Y, int M, int N,
+                            int K) {
+    host_sgemm(TCSC_VARIANT_PRELU_BASIC, X, W, B, a, Y, M, N, K);
+}
+
+void tcsc_sgemm_prelu_optimized_separate(const dense_t X, const tcsc_t* W, const dense_t B, float a, dense_t Y,
+                                         int M, int N, int K) {
+    host_sgemm(TCSC_VARIANT_PRELU_SEPARATE, X, W, B, a, Y, M, N, K);
+}
+
+void tcsc_sgemm_prelu_optimized_onthego(const dense_t X, const tcsc_t* W, const dense_t B, float a, dense_t Y,
+                                        int M, int N, int K) {
+    host_sgemm(TCSC_VARIANT_PRELU_ONTHEGO, X, W, B, a, Y, M, N, K);
+}
+
+void tcsc_free(tcsc_t* W) {
+    if (!W) return;
+    {
+        std::lock_guard<std::mutex> lk(g_mu);
+        auto it = g_cache.find(W);
+        if (it != g_cache.end()) {
+            destroy_entry(it->second);
+            g_cache.erase(it);
+        }
+    }
+    std::free(W->col_start_pos);
+    std::free(W->col_start_neg);
+    std::free(W->row_index_pos);
+    std::free(W->row_index_neg);
+    std::free(W);
+}
+
+}  // extern "C"
+
+// SparseGEMM.h drop-in (include/sparse_gemm.h)
+extern "C" {
+
+void tcsc_sparse_gemm(const float* X, const int* col_start_pos, const int* col_start_neg, const int* row_index_pos,
+                      const int* row_index_neg, const float* b, float* Y, int M, int N, int K) {
+    raw_sgemm(TCSC_VARIANT_SPARSE_GEMM, X, col_start_pos, col_start_neg, row_index_pos, row_index_neg, b, Y, M, N, K,
+              0.0f);
+}
+
+void tcsc_sparse_gemm_prelu(const float* X, const int* col_start_pos, const int* col_start_neg,
+                            const int* row_index_pos, const int* row_index_neg, const float* b, float* Y, int M,
+                            int N, int K, float a) {
+    // y = 0 + sum(+1) - sum(-1); y += b; PReLU (SparseGEMM.h:156-165) is
+    // tcsc_sgemm_prelu_basic's order and predicate (tcsc.c:149-162)
+    raw_sgemm(TCSC_VARIANT_PRELU_BASIC, X, col_start_pos, col_start_neg, row_index_pos, row_index_neg, b, Y, M, N, K,
+              a);
+}
+
+void tcsc_dense_gemm(const float* X, const float* W, const float* b, float* Y, int M, int N, int K) {
+    host_dense(TCSC_VARIANT_SPARSE_GEMM, X, W, b, Y, M, N, K, 0.0f);
+}
+
+void tcsc_dense_gemm_prelu(const float* X, const float* W, const float* b, float* Y, int M, int N, int K, float a) {
+    host_dense(TCSC_VARIANT_PRELU_BASIC, X, W, b, Y, M, N, K, a);
+}
+
+}  // extern "C"
+
+// Self-test hooks (tests/native/tcsc_selftest.h): the worker pools without
+// a GPU.  Compiled only into the sanitizer builds (-DTCSC_SELFTEST), never
+// exported by the product library.
+#ifdef TCSC_SELFTEST
+extern "C" {
+
+int tcsc_selftest_fingerprint(const tcsc_t* W) {
+    if (!W) return -1;
+    AsyncFingerprint fp(W);
+    return fp.get() == tcsc_fingerprint(W) ? 0 : 1;
+}
+
+int tcsc_selftest_copy2d(void* dst, size_t dp, const void* src, size_t sp, size_t row_bytes, size_t rows, int dev,
+                         int side) {
+    if ((!dst || !src) && rows && row_bytes) return -1;
+    if (side != 0 && side != 1) return -1;
+    copy_pool(side, dev).copy2d(static_cast<char*>(dst), dp, static_cast<const char*>(src), sp, row_bytes, rows);
+    return 0;
+}
+
+}  // extern "C"
+#endif  // TCSC_SELFTEST

@@ -1,5 +1,5 @@
-// tcsc_internal.h -- shared between the kernels (tcsc_kernels.hip) and the
-// C-ABI layer (tcsc_api.cpp).  Not part of the public ABI.
+// tcsc_internal.h -- shared between the kernels (the .hip files) and the C-ABI
+// layer (tcsc_api.cpp, tcsc_host.cpp).  Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -212,7 +212,6 @@ struct GemmArgs {
     // are the wide streams; unsplit K, order 0)
     int geo = kCW;
     int ncols = 0;
-    long long nnz = 0;
     const float* B = nullptr;
     float* Y = nullptr;
     int ldy = 0;
@@ -221,12 +220,23 @@ struct GemmArgs {
     bool prelu = false;
     float* ws = nullptr;       // split-K partial slabs (may be null: no split)
     size_t ws_bytes = 0;
-    int force_slices = 0;      // 0 = cost model
+    // the route the API layer decided (tcsc_api.cpp route_call); launch_gemm
+    // checks that it can run as given and launches it
+    int slices = 1;            // K slices = grid z: whole chunks, none empty (normalized_slices)
+    int combine = 0;           // combine_mode's answer for this grid: 0, or 2, 3, 4 with the tile words in ccnt
     int stage = 0;             // 0: transpose + gather, 1: transpose only, 2: gather only (X^T prepared)
-    int num_cus = 0;           // CUs of the device (the in-launch combine needs the grid resident)
     unsigned* ccnt = nullptr;  // the split-K combine's tile words (kCombineBytes), null = k_reduce4
     int combine_giveup = 0;    // test knob (TCSC_COMBINE_GIVEUP=1): every slice but the last arrival gives up at once
 };
+// whether the split-K combine may use 16-B loads and stores on Y, B and the slabs
+inline bool stores16(const GemmArgs& g) {
+    return g.ncols % 4 == 0 && g.ldy % 4 == 0 &&
+           ((reinterpret_cast<uintptr_t>(g.Y) | reinterpret_cast<uintptr_t>(g.ws) | reinterpret_cast<uintptr_t>(g.B)) & 15) == 0;
+}
+// Gather-path limits: X^T row tiles of 64 rows on the transpose grid's y axis
+// (<= 65536 blocks) and 32-bit per-lane DMA offsets within a chunk (kTK rows
+// of ldxt floats): at most 2^22 rows per launch.
+constexpr int kMaxLaunchRows = 1 << 22;
 
 // Plan building
 hipError_t plan_scan_tmp_bytes(long long n, size_t* bytes);
@@ -240,7 +250,7 @@ int choose_slices(int M, int ncols, int K, long long nnz, int n_groups, size_t w
 // pairwise in split halves (2 slices, the grid resident at once)
 int combine_mode(int slices, long long wgs, long long tiles, long long slab_floats, int num_cus, bool have_words,
                  bool vec);
-int normalized_slices(int K, int slices);  // the K split launch_gemm actually runs
+int normalized_slices(int K, int slices);  // `slices` rounded to whole chunks: the K split a launch runs
 // stream prefetch of a plan of n_entries entries over n_groups x n_chunks
 // streams: *dist bytes ahead, *lines 128-B lines (TCSC_PF_DIST / TCSC_PF_LINES override)
 void pf_stream_params(long long n_entries, int n_groups, int n_chunks, int* dist, int* lines);
@@ -437,9 +447,9 @@ hipError_t transpose_sign(const int* cs, const int* ri, int col_begin, int ncols
 hipError_t launch_prelu_bwd(const float* G, int ldg, const float* Y, int ldy, float a, float* DZ, int lddz, float* DB,
                             int M, int N, hipStream_t st);
 
-// Error channel shared by every entry point of the library (tcsc_api.cpp):
-// the message behind tcsc_gpu_last_error(), and the host API's policy
-// (stderr + abort unless TCSC_ON_ERROR=continue).
+// Error channel shared by every entry point of the library: the message
+// behind tcsc_gpu_last_error() (tcsc_api.cpp), and the host API's policy
+// (tcsc_host.cpp: stderr + abort unless TCSC_ON_ERROR=continue).
 void set_error_msg(const char* msg);
 const char* error_msg();
 void report_status(int rc);

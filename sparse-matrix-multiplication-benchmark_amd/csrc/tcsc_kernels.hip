@@ -1549,12 +1549,26 @@ int normalized_slices(int K, int slices) {
     return (nch + cps - 1) / cps;
 }
 
+// Whether the route in g (slices, combine) can run as it stands: whole chunks
+// and no empty slice, the reference orders unsplit, slabs for every slice,
+// and an in-launch combine only with its tile words, 16-B stores and the
+// slice count of its form.
+static bool route_legal(const GemmArgs& g) {
+    const int nch = (g.K + kTK - 1) / kTK, s = g.slices;
+    if (s == 1) return g.combine == 0;
+    if (s < 1 || g.order != 0 || !g.ws || g.ws_bytes < workspace_bytes(g.M, g.ncols, s)) return false;
+    if ((long long)(s - 1) * ((nch + s - 1) / s) >= nch) return false;
+    if (g.combine == 0) return true;
+    const long long tiles = (long long)((g.n_groups + kWaves - 1) / kWaves) * ((g.M + kTM - 1) / kTM);
+    if (!g.ccnt || !stores16(g) || s > 16 || tiles > kCombineTiles) return false;
+    return g.combine == 2 || ((g.combine == 3 || g.combine == 4) && s == 2);
+}
+
 template <bool BF, bool PR>
-static hipError_t launch_t(const GemmArgs& g, int slices, hipStream_t st) {
+static hipError_t launch_t(const GemmArgs& g, hipStream_t st) {
     const int nch = (g.K + kTK - 1) / kTK;
-    if (g.order != 0) slices = 1;  // the reference orders walk K in order
-    int cps = nch > 0 ? (nch + slices - 1) / slices : 1;
-    slices = nch > 0 ? (nch + cps - 1) / cps : 1;
+    const int slices = g.slices;
+    const int cps = nch > 0 ? (nch + slices - 1) / slices : 1;
     const int ldxt = ldxt_of(g.M);
     dim3 grid((g.n_groups + kWaves - 1) / kWaves, (g.M + kTM - 1) / kTM, slices);
     dim3 block(kWaves * 64);
@@ -1579,11 +1593,8 @@ static hipError_t launch_t(const GemmArgs& g, int slices, hipStream_t st) {
         return hipGetLastError();
     }
     const long long total = (long long)g.M * g.ncols;
-    const bool vec = slices <= 16 && g.ncols % 4 == 0 && g.ldy % 4 == 0 &&
-                     ((reinterpret_cast<uintptr_t>(g.Y) | reinterpret_cast<uintptr_t>(g.ws) |
-                       reinterpret_cast<uintptr_t>(g.B)) & 15) == 0;
-    const int cm = combine_mode(slices, (long long)grid.x * grid.y * grid.z, (long long)grid.x * grid.y, total,
-                                g.num_cus, g.ccnt != nullptr, vec);
+    const bool vec = slices <= 16 && stores16(g);
+    const int cm = g.combine;
     if (cm == 3 || cm == 4) {  // pairwise: no residency needed (3); the split halves on a resident grid (4)
         const int split = cm == 4 ? 2 : 0;
         hipLaunchKernelGGL((k_stream<BF, PR, 3, 0>), grid, block, 0, st, g.XT, ldxt, g.M, g.K, g.ent, g.sptr,
@@ -1622,9 +1633,9 @@ hipError_t launch_gemm(const GemmArgs& g, hipStream_t st) {
     }
     if (g.stage == 1) return hipSuccess;
     if (g.geo == kWideCW) return launch_stream_wide(g, st);  // the 22-column kernel (tcsc_wide.hip): one K slice
-    const int s = choose_slices(g.M, g.ncols, g.K, g.nnz, g.n_groups, g.ws ? g.ws_bytes : 0, g.force_slices);
-    if (g.bias_first) return g.prelu ? launch_t<true, true>(g, s, st) : launch_t<true, false>(g, s, st);
-    return g.prelu ? launch_t<false, true>(g, s, st) : launch_t<false, false>(g, s, st);
+    if (!route_legal(g)) return hipErrorInvalidValue;
+    if (g.bias_first) return g.prelu ? launch_t<true, true>(g, st) : launch_t<true, false>(g, st);
+    return g.prelu ? launch_t<false, true>(g, st) : launch_t<false, false>(g, st);
 }
 
 int dense_tile_rows(int rows) {

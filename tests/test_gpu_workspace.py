@@ -207,6 +207,34 @@ def test_routing_and_workspace_equal_the_recorded_table(torch_gpu, monkeypatch, 
                 f"{n} {a} (recorded {b})" for n, a, b in zip(names, grow, wrow) if a != b)
 
 
+@pytest.mark.parametrize("name", list(GEN_ROUTING.KNOB_PLANS))
+def test_knob_routes_equal_the_recorded_table(torch_gpu, monkeypatch, name):
+    """tests/golden/routing_knobs.json holds the forced and special routes of three small plans (the one whose
+    split-K slabs peak inside the reserved range, one with the MFMA image, tests/test_gpu_wide.py's with its
+    wide streams), each as a fast-order, a reference-order and a transposed plan, under every TCSC_SLICES,
+    TCSC_GEO and TCSC_COMBINE of gen_routing.py and seven values of M: path and K split, geometry (or the
+    text of the refusal of TCSC_GEO=22), combine mode, the workspace of each path and what reserve(512) holds.
+    Queries only, nothing is launched.  Every entry must be what it was."""
+    for k in GEN_ROUTING.KNOBS + GEN_ROUTING.KNOB_ENV:
+        monkeypatch.delenv(k, raising=False)  # record_knobs sets the knobs itself and leaves them cleared
+    with open(GEN_ROUTING.KNOB_TABLE) as f:
+        table = json.load(f)
+    order = tcsc_amd.get_order()
+    got = GEN_ROUTING.record_knobs(tcsc_amd, name)
+    assert tcsc_amd.get_order() == order
+    per_plan = len(GEN_ROUTING.KNOB_KINDS) * len(GEN_ROUTING.KNOB_SLICES) * len(GEN_ROUTING.KNOB_GEO) * \
+        len(GEN_ROUTING.KNOB_COMBINE)
+    assert len(got) == per_plan and set(got) <= set(table) and len(table) == per_plan * len(GEN_ROUTING.KNOB_PLANS)
+    names = ("M", "path", "slices", "geometry", "combine", "workspace", "gather ws", "mfma ws", "small ws")
+    for key, g in got.items():
+        want = table[key]
+        assert g["reserved"] == want["reserved"], f"{key}: reserve({GEN_ROUTING.KNOB_RESERVE_M})"
+        assert len(g["rows"]) == len(want["rows"]) == len(GEN_ROUTING.KNOB_MS)
+        for grow, wrow in zip(g["rows"], want["rows"]):
+            assert grow == wrow, f"{key} M={wrow[0]}: " + ", ".join(
+                f"{n} {a} (recorded {b})" for n, a, b in zip(names, grow, wrow) if a != b)
+
+
 # ---- launches ---------------------------------------------------------------
 
 def bits(t):
@@ -304,6 +332,62 @@ def test_launch_history_mfma_plan(torch_gpu, monkeypatch):
     W, plan, paths, held, _ = run_sequence(torch_gpu, 1024, 512, 0.5, 256, (256, 64, 17, 5, 4, 130))
     assert paths[0] == "mfma" and paths[1] == "mfma" and paths[4] == "small", paths
     plan.destroy()
+    W.free()
+
+
+@pytest.mark.parametrize("K,N,density", [(512, 4096, 0.02), (1024, 512, 0.5)], ids=["slabs", "image"])
+def test_pinned_split_launches_what_the_route_says(torch_gpu, monkeypatch, K, N, density):
+    """TCSC_SLICES = 1, 2, 4 at plan creation, reserve(512) and launch, M = 339 and 64: the launch runs in the
+    workspace the route sized (the plan never reallocates), and its rows have the bits of a launch with the
+    knob unset at the largest M' <= 512 where the cost model itself takes the same path and K split (a row's
+    sum depends on the split, not on how many rows run beside it; on the MFMA path, whose tiles depend on M,
+    only M' = M counts).  Where no such M' exists the fp32 bound against the fp64 oracle is all there is; it
+    is asked in either case."""
+    torch = torch_gpu
+    for k in ("TCSC_SLICES", "TCSC_PATH", "TCSC_SMALL_M", "TCSC_MFMA_WGS", "TCSC_GEO", "TCSC_COMBINE"):
+        monkeypatch.delenv(k, raising=False)
+    dev = torch.device("cuda:0")
+    c = launch_case(K, N, density, 512)
+    dX, dB = torch.from_numpy(c["X"]).to(dev), torch.from_numpy(c["B"]).to(dev)
+    W = strided_w(K, N, density)
+
+    def launch(plan, M):
+        Y = torch.full((M, N), float("nan"), device=dev)
+        plan.sgemm(dX, dB, Y, M, N, "prelu_basic", 0.2)
+        torch.cuda.synchronize()
+        return Y
+
+    free = tcsc_amd.Plan(W)  # the cost model's own choices
+    free.reserve(512)
+    chosen = {M: free.launch_info(M) for M in range(1, 513)}
+    same_bits = 0
+    for slices in (1, 2, 4):
+        monkeypatch.setenv("TCSC_SLICES", str(slices))
+        plan = tcsc_amd.Plan(W)
+        plan.reserve(512)
+        held = plan.info()["device_bytes"]
+        for M in (339, 64):
+            route = plan.launch_info(M)
+            assert route[0] == "mfma" or route == ("gather", slices), route
+            assert plan.workspace(M)[0] <= plan.workspace(M)[1]
+            Y = launch(plan, M)
+            assert plan.info()["device_bytes"] == held, f"TCSC_SLICES={slices} M={M}: the plan reallocated"
+            ok, ratio = pyoracle.check_close(Y.cpu().numpy(), c["Y64"][:M], c["S64"][:M], 0.2)
+            print(f"TCSC_SLICES={slices} M={M}: {route}, worst err/bound {ratio:.3g}")
+            assert ok, f"TCSC_SLICES={slices} M={M}: worst err/bound = {ratio:.3g}"
+            twins = [m for m, r in chosen.items() if r == route and (route[0] == "gather" or m == M)]
+            if twins:
+                monkeypatch.delenv("TCSC_SLICES")
+                m = max(twins)
+                F = launch(free, m)
+                monkeypatch.setenv("TCSC_SLICES", str(slices))
+                rows = min(m, M)
+                np.testing.assert_array_equal(bits(Y[:rows]), bits(F[:rows]),
+                                              err_msg=f"TCSC_SLICES={slices} M={M} vs the cost model's M={m}")
+                same_bits += 1
+        plan.destroy()
+    assert same_bits > 0, "no forced route met a route the cost model chose"
+    free.destroy()
     W.free()
 
 
