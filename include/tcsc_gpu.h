@@ -127,7 +127,9 @@ enum tcsc_path {
     TCSC_PATH_GATHER = 0,
     TCSC_PATH_FUSED = 1, /* retired (round 5): the persistent k_fused left the library; never returned */
     TCSC_PATH_MFMA = 2,
-    TCSC_PATH_SMALL = 3
+    TCSC_PATH_SMALL = 3,
+    TCSC_PATH_DECODE = 4 /* k_decode8: int8 calls of M <= 16 rows on a plan with the 2-bit image
+                            (tcsc_gpu_plan_enable_w2); never an fp32 or bf16 call */
 };
 int tcsc_gpu_launch_info(const tcsc_gpu_plan *plan, int M, int *path, int *slices);
 
@@ -183,6 +185,8 @@ void tcsc_gpu_plan_destroy(tcsc_gpu_plan *plan);
  * TCSC_PATH_MFMA, TCSC_PATH_SMALL: what that path would need at this M
  * whatever the cost model prefers, 0 where the plan cannot run it (no MFMA
  * image, M below mfma_min_M, M > 4 or an X too long for the small-M path).
+ * TCSC_PATH_DECODE may be named too: k_decode8 needs no workspace, so its need
+ * is 0 at every M.
  * The gather's need is its X^T plus the split-K slabs of the split the cost
  * model (or $TCSC_SLICES) picks with room to spare.  After
  * tcsc_gpu_plan_reserve(max_M), need <= reserved for every M <= max_M and
@@ -337,6 +341,68 @@ int tcsc_gpu_sgemm_i8(const tcsc_gpu_plan *plan, const void *dXq, const float *d
 int tcsc_gpu_launch_info_i8(const tcsc_gpu_plan *plan, int M, int *path, int *slices);
 int tcsc_gpu_quantize_rows_i8(const float *dX, int M, int K, void *dXq, float *dScale, void *stream);
 int tcsc_gpu_workspace_bound_i8(int M, int K, int N, size_t *i8_bytes, size_t *f32_bytes);
+
+/* ---- int8 decode: M <= 16 rows on a 2-bit image of W ----------
+ * Token generation of a ternary-weight model is an int8 call of one row, or of
+ * a batch of a few.  At M <= 16 the whole product is one 16-row MFMA tile per
+ * 16 columns and the call is a stream of W, so what counts is the bytes of W
+ * read: the merged CSC copy holds 4 bytes per nonzero (k_small_m, M <= 4), the
+ * int8 image 1 byte per weight (k_gemm8), a ternary weight needs 2 bits.
+ *
+ * tcsc_gpu_plan_enable_w2: on a plan that holds the int8 image
+ * (tcsc_gpu_plan_has_i8), build a 2-bit image of W beside it, on the device
+ * from the int8 one (k_w2_from); counted in device_bytes, freed with the plan
+ * and with the int8 image.  It is built only if every weight is -1, 0 or +1
+ * (duplicate indices in W can make |w| = 2) and K < 2^22, which keeps every
+ * i32 sum of the kernel below 2^31 for any int8 X.  Otherwise, and on a plan
+ * without the int8 image, the call returns TCSC_OK and leaves the plan as it
+ * was: tcsc_gpu_plan_has_w2 says 0 and every call behaves as before.
+ * Idempotent; synchronises `stream`.  Nothing else in the library builds the
+ * image: a plan that never calls this routes and computes exactly as before.
+ *
+ * Layout of the image: tiles of 16 columns x 256 k, 1 KiB each, column-tile
+ * major then k-block, tcsc_gpu_w2_image_bytes = ceil(N/16) ceil(K/256) 1024
+ * bytes in all (host arithmetic: no plan, no device).  One wave reads a tile as
+ * 64 lanes x 16 contiguous bytes; lane l owns column 16 t + (l & 15) and the k
+ * quarter l >> 4; dword i of its 16 bytes holds the 16 weights
+ * k = 256 kb + 64 i + 16 (l >> 4) + j, j = 0 .. 15 -- the bytes of the lane's
+ * v_mfma_i32_16x16x64_i8 fragment in step i of the block.  The code of weight
+ * j is c = w + 1 at bit 8 (j & 3) + 2 (j >> 2), so the int8 fragment's dword d
+ * is (p >> 2d) & 0x03030303.  Padding (k >= K, column >= N) holds c = 1.
+ *
+ * The call: tcsc_gpu_sgemm_i8 as it is.  Where the route is TCSC_PATH_DECODE,
+ * k_decode8 computes
+ *   Y[m, j] = act(fl(fl(float(S) * s[m]) + b[j])),   m < M <= 16, j < cols
+ * with S the exact i32 sum: sum_k q c by MFMA minus the row sums sum_k q (one
+ * more MFMA per step against a fragment of ones), as integers.  The epilogue is
+ * the int8 MFMA path's own function, so the bits are k_gemm8's for every
+ * variant and every scale, and do not depend on how K is split over the waves.
+ * One launch: X is read in place (16-B loads where dXq is 16-B aligned and
+ * K % 16 == 0, guarded byte loads otherwise; rows >= M are never read), the
+ * waves of a workgroup split K and add their partial sums through the LDS.  No
+ * workspace (tcsc_gpu_plan_workspace reports 0 for this path), no atomics, no
+ * allocation, no synchronisation: capturable.  Only rows < M and columns < cols
+ * are stored, with pitch ldy.
+ *
+ * Routing: only int8 calls on a plan with the 2-bit image take the path, and
+ * only at 1 <= M <= 16.  By default it is taken where tcsc_gpu_decode_pays
+ * (host arithmetic) says 1:
+ *   1 <= M <= 16 and (M > 4, or the small-M path does not fit this (M, K), or
+ *   16 nnz > K N)
+ * -- the last clause compares the 4 bytes per nonzero of the merged CSC copy
+ * with a quarter byte per weight.  $TCSC_DECODE, read per call: 0 never takes
+ * the path, 1 takes it at every M <= 16 where the image exists, unset follows
+ * the rule.  Where it applies it precedes the MFMA path and the small-M path.
+ * tcsc_gpu_launch_info_i8 names the path; tcsc_gpu_launch_info and _bf16 never
+ * do.
+ *
+ * Out of scope: M > 16; dropping the bf16 and int8 images on decode-only plans;
+ * bf16 or int8 Y; a host-pointer version; building the 2-bit image without the
+ * int8 one. */
+int tcsc_gpu_plan_enable_w2(tcsc_gpu_plan *plan, void *stream);
+int tcsc_gpu_plan_has_w2(const tcsc_gpu_plan *plan);
+int tcsc_gpu_w2_image_bytes(int K, int N, size_t *bytes);
+int tcsc_gpu_decode_pays(int M, int K, int N, long long nnz);
 
 /* Device-side tcsc_from_dense: dense K x N row-major float matrix on the
  * device -> TCSC arrays on the device, bit-exact with the reference builder

@@ -57,6 +57,11 @@ struct tcsc_gpu_plan {
     // only by tcsc_gpu_plan_enable_i8: tcsc_gpu_sgemm_i8's MFMA path
     int8_t* w8 = nullptr;
     size_t i8_bytes = 0;
+    // the 2-bit image of a ternary W made from it (w2_image_bytes(rows, cols)),
+    // built only by tcsc_gpu_plan_enable_w2: int8 calls of M <= 16 rows stream
+    // it (k_decode8)
+    uint32_t* w2 = nullptr;
+    size_t w2_bytes = 0;
     // the column range's rebased CSC (fast-order plans): the small-M path
     // walks it, the MFMA path's fixup recomputes flagged rows from it
     // (crq: each column's +1 / -1 rows merged in ascending k, in the quad
@@ -403,7 +408,14 @@ rocblas_handle rocblas_for_device(int dev) {
     return h;
 }
 
+void free_w2(tcsc_gpu_plan* p) {
+    if (p->w2) (void)hipFree(p->w2);
+    p->w2 = nullptr;
+    p->w2_bytes = 0;
+}
+
 void free_i8(tcsc_gpu_plan* p) {
+    free_w2(p);  // made from the int8 image, useless without it
     if (p->w8) (void)hipFree(p->w8);
     p->w8 = nullptr;
     p->i8_bytes = 0;
@@ -506,6 +518,31 @@ bool has_small(const tcsc_gpu_plan* p, int M) {  // the plan can run M rows on t
 }
 bool use_small(const tcsc_gpu_plan* p, int M, int dt = kF32) { return has_small(p, M) && !use_mfma(p, M, dt); }
 
+// The decode path (tcsc_decode.hip): int8 calls of M <= 16 rows
+// on a plan with the 2-bit image.  The default rule compares the bytes of W a
+// call reads: above 4 rows the alternative is k_gemm8 on the int8 image, 1 byte
+// per weight against a quarter; up to 4 rows it is k_small_m on the merged CSC
+// copy, 4 bytes per nonzero against a quarter byte per weight -- unless X does
+// not fit the small-M path's LDS, which leaves k_gemm8 or the gather.
+bool decode_pays(int M, int K, int N, long long nnz) {
+    if (M < 1 || M > tcsc::kDecodeMaxM) return false;
+    return M > kSmallMaxM || !tcsc::small_m_fits(M, K) || 16 * nnz > (long long)K * N;
+}
+// $TCSC_DECODE, read per call: 0 never, 1 at every M <= 16 where the image exists, unset the rule
+int decode_knob() {
+    const char* e = std::getenv("TCSC_DECODE");
+    if (!e || !*e) return -1;
+    return std::atoi(e) != 0 ? 1 : 0;
+}
+bool has_decode(const tcsc_gpu_plan* p, int M, int dt) {  // the plan can run M rows of type dt on the decode path
+    return dt == kI8 && p->w2 && M >= 1 && M <= tcsc::kDecodeMaxM;
+}
+bool use_decode(const tcsc_gpu_plan* p, int M, int dt) {
+    if (!has_decode(p, M, dt)) return false;
+    const int knob = decode_knob();
+    return knob >= 0 ? knob == 1 : decode_pays(M, p->rows, p->cols, p->n_pos + p->n_neg);
+}
+
 // Adds the MFMA image to a fast-order plan when the path mode and the density
 // call for it.  Not building it is never an error: the gather serves every M.
 int maybe_build_mfma(tcsc_gpu_plan* p, const int* csp, const int* csn, const int* rip, const int* rin, int col_begin,
@@ -600,6 +637,7 @@ size_t path_ws_bytes(const tcsc_gpu_plan* p, int M, int path) {
 
 // the path of a call of type dt (each type has its own cost model)
 int launch_path(const tcsc_gpu_plan* p, int M, int dt = kF32) {
+    if (use_decode(p, M, dt)) return TCSC_PATH_DECODE;
     return use_mfma(p, M, dt) ? TCSC_PATH_MFMA : use_small(p, M, dt) ? TCSC_PATH_SMALL : TCSC_PATH_GATHER;
 }
 
@@ -879,6 +917,7 @@ Route tcsc::route_call(const tcsc_gpu_plan* p, int M, int dt, size_t ws_avail, c
         r.ws_bytes = mfma_ws(dt, M, K, N).bytes;
         return r;
     }
+    if (r.path == TCSC_PATH_DECODE) return r;  // one launch that reads X in place: no workspace, K split inside the workgroup
     if (r.path == TCSC_PATH_SMALL) {
         // only the fp32 call has a staged form (tcsc_gpu_prepare_x's copy of X): the narrow types read X in place
         if (has_small(p, M) && dt == kF32) r.ws_bytes = align256((size_t)M * K * sizeof(float));
@@ -994,9 +1033,15 @@ int tcsc::sgemm_ws(const tcsc_gpu_plan* p, const void* dX, const float* dB, floa
     // stage 1 only transposes: a geometry that cannot be had is the launch's error (stage 2)
     const Route r = route_call(p, M, dt, ws ? ws_bytes : 0, pins, stage != 1 ? who : nullptr);
     if (ran) *ran = r;
-    if ((r.path == TCSC_PATH_MFMA && !has_mfma(p, M, dt)) || (r.path == TCSC_PATH_SMALL && !has_small(p, M))) {
+    if ((r.path == TCSC_PATH_MFMA && !has_mfma(p, M, dt)) || (r.path == TCSC_PATH_SMALL && !has_small(p, M)) ||
+        (r.path == TCSC_PATH_DECODE && !has_decode(p, M, dt))) {
         set_error("%s: the plan cannot run M=%d on the pinned path %d", who, M, r.path);
         return TCSC_E_ARG;
+    }
+    if (r.path == TCSC_PATH_DECODE) {
+        HIP_TRY(tcsc::decode_gemm(static_cast<const int8_t*>(dX), p->w2, p->rows, M, p->cols, dScale, dB, dY, ldy,
+                                  is_prelu(variant), a, p->num_cus, static_cast<hipStream_t>(stream)));
+        return TCSC_OK;
     }
     if (r.path == TCSC_PATH_MFMA)
         return sgemm_mfma(p, dX, dt, dScale, dB, dY, M, ldy, variant, a, stream, ws, ws_bytes, stage);
@@ -1250,7 +1295,7 @@ int tcsc_gpu_plan_get_info(const tcsc_gpu_plan* p, tcsc_gpu_plan_info* info) {
     info->n_neg = p->n_neg;
     info->chunk_k = tcsc::kTK;
     info->n_chunks = p->n_chunks;
-    info->device_bytes = p->bytes + p->ws_bytes + p->mfma_bytes + p->i8_bytes + p->csc_bytes + p->tbias_bytes + p->wide_bytes +
+    info->device_bytes = p->bytes + p->ws_bytes + p->mfma_bytes + p->i8_bytes + p->w2_bytes + p->csc_bytes + p->tbias_bytes + p->wide_bytes +
                          (p->chain_pos ? p->chain_pos->bytes : 0) + (p->chain_neg ? p->chain_neg->bytes : 0);
     info->order = p->order;
     info->mfma_min_M = p->wt ? p->mfma_min_M : 0;
@@ -1316,7 +1361,7 @@ int tcsc_gpu_plan_reserve(tcsc_gpu_plan* p, int max_M) {
 
 int tcsc_gpu_plan_workspace(const tcsc_gpu_plan* p, int M, int path, size_t* need, size_t* reserved) {
     if (!p || M < 0 || (path != TCSC_PATH_AUTO && path != TCSC_PATH_GATHER && path != TCSC_PATH_MFMA &&
-                        path != TCSC_PATH_SMALL)) {
+                        path != TCSC_PATH_SMALL && path != TCSC_PATH_DECODE)) {
         set_error("tcsc_gpu_plan_workspace: bad arguments (M=%d path=%d)", M, path);
         return TCSC_E_ARG;
     }
@@ -1441,6 +1486,58 @@ int tcsc_gpu_plan_has_i8(const tcsc_gpu_plan* p) {
     }
     return p->w8 ? 1 : 0;
 }
+
+int tcsc_gpu_plan_enable_w2(tcsc_gpu_plan* p, void* stream) {
+    if (!p) {
+        set_error("tcsc_gpu_plan_enable_w2: NULL plan");
+        return TCSC_E_ARG;
+    }
+    // only beside the int8 image, and only where every i32 sum of k_decode8 stays below 2^31
+    if (p->w2 || !p->w8 || p->rows <= 0 || p->rows >= tcsc::kDecodeMaxK || p->cols <= 0) return TCSC_OK;
+    DeviceGuard dg(p->device);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const size_t bytes = tcsc::w2_image_bytes(p->rows, p->cols);
+    DevBuf bad;
+    if (bad.alloc(sizeof(int)) != hipSuccess || hipMalloc(&p->w2, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        p->w2 = nullptr;
+        set_error("tcsc_gpu_plan_enable_w2: cannot allocate the 2-bit image (%zu bytes)", bytes);
+        return TCSC_E_NOMEM;
+    }
+    p->w2_bytes = bytes;
+    int hbad = 0, rc = TCSC_OK;
+    hipError_t e = hipMemsetAsync(bad.p, 0, sizeof(int), st);
+    if (e == hipSuccess)
+        e = tcsc::decode_build_w2(p->w8, p->cols, p->rows, tcsc::mfma8_ldw(p->rows), p->w2, bad.as<int>(), st);
+    if (e == hipSuccess) e = hipMemcpyAsync(&hbad, bad.p, sizeof(int), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    // the grid rule of k_decode8 (decode_tiles_per_wg) wants the CU count
+    if (e == hipSuccess && !p->num_cus)
+        e = hipDeviceGetAttribute(&p->num_cus, hipDeviceAttributeMultiprocessorCount, p->device);
+    if (e != hipSuccess) rc = hip_fail(e, "tcsc_gpu_plan_enable_w2");
+    // a weight that is not -1, 0 or +1 (a duplicated index): no image
+    if (rc != TCSC_OK || hbad) free_w2(p);
+    return rc;
+}
+
+int tcsc_gpu_plan_has_w2(const tcsc_gpu_plan* p) {
+    if (!p) {
+        set_error("tcsc_gpu_plan_has_w2: NULL plan");
+        return 0;
+    }
+    return p->w2 ? 1 : 0;
+}
+
+int tcsc_gpu_w2_image_bytes(int K, int N, size_t* bytes) {
+    if (K < 0 || N < 0 || !bytes) {
+        set_error("tcsc_gpu_w2_image_bytes: bad arguments (K=%d N=%d)", K, N);
+        return TCSC_E_ARG;
+    }
+    *bytes = tcsc::w2_image_bytes(K, N);
+    return TCSC_OK;
+}
+
+int tcsc_gpu_decode_pays(int M, int K, int N, long long nnz) { return decode_pays(M, K, N, nnz) ? 1 : 0; }
 
 int tcsc_gpu_sgemm_i8(const tcsc_gpu_plan* p, const void* dXq, const float* dScale, const float* dB, float* dY, int M,
                       int ldy, int variant, float a, void* stream) {

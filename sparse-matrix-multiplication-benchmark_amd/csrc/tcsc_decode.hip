@@ -1,0 +1,232 @@
+// tcsc_decode.hip -- the int8 decode path: tcsc_gpu_sgemm_i8
+// calls of M <= 16 rows on a 2-bit image of a ternary W.
+//
+// At M <= 16 the product is one 16-row v_mfma_i32_16x16x64_i8 tile per 16
+// columns, and the call is a stream of W.  The int8 image (k_gemm8) holds 1
+// byte per weight and the merged CSC copy (k_small_m) 4 bytes per nonzero; a
+// ternary weight needs 2 bits.  k_w2_from packs the int8 image into tiles of
+// 16 columns x 256 k (1 KiB, the layout of tcsc_internal.h) and k_decode8
+// streams them: a workgroup owns T adjacent column tiles, its 8 waves split K
+// by 256-k blocks, every wave expands its 16 bytes of a tile into four int8
+// fragments (one shift and one mask per dword) and issues four MFMAs per tile,
+// and the partial sums meet in the LDS.
+//
+// The codes are c = w + 1, so the MFMAs give sum_k q c; one more MFMA per step
+// against a fragment of ones gives the row sums sum_k q in the accumulator's
+// own layout, and the difference is the exact S = sum_k q w as an integer.
+// The epilogue is i8_out, k_gemm8's own: the same bits as the int8 MFMA path.
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "tcsc_i8_out.h"
+#include "tcsc_internal.h"
+
+namespace tcsc {
+namespace {
+
+typedef int i32x4 __attribute__((ext_vector_type(4)));
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+
+// Waves per workgroup (the K split) and, for A/B builds, a fixed number of
+// column tiles per workgroup (0: decode_tiles_per_wg's rule).  DESIGN.md §17
+// has the measurements behind 8 and the rule.
+#ifndef TCSC_DEC_WAVES
+#define TCSC_DEC_WAVES 8
+#endif
+#ifndef TCSC_DEC_TILES
+#define TCSC_DEC_TILES 0
+#endif
+constexpr int kDecWaves = TCSC_DEC_WAVES;
+constexpr int kDecTiles = TCSC_DEC_TILES;
+static_assert(kDecWaves >= 1 && kDecWaves <= 16 && kDecWaves * 4 * 1024 <= 64 * 1024, "the LDS reduce of 4 tiles");
+static_assert(kDecTiles == 0 || kDecTiles == 1 || kDecTiles == 2 || kDecTiles == 4, "1, 2 or 4 tiles");
+
+// The 2-bit image from the int8 one (W8: ncols x ld8 bytes, zeros past K).  One
+// thread per dword of the image, so a wave writes 1 KiB of contiguous memory;
+// the reads are 16 contiguous bytes of one column (a build-time kernel).
+__global__ void __launch_bounds__(256) k_w2_from(const int8_t* __restrict__ W8, int ncols, int K, int ld8, int nkb,
+                                                size_t dwords, uint32_t* __restrict__ W2, int* __restrict__ bad) {
+    for (size_t g = blockIdx.x * (size_t)blockDim.x + threadIdx.x; g < dwords; g += (size_t)gridDim.x * blockDim.x) {
+        const size_t tile = g >> 8;  // 256 dwords per tile
+        const int l = (int)(g >> 2) & 63, i = (int)g & 3;
+        const int t = (int)(tile / nkb), kb = (int)(tile % nkb);
+        const int col = kW2Cols * t + (l & 15), k0 = kW2Blk * kb + 64 * i + 16 * (l >> 4);
+        uint32_t p = 0x55555555u;  // c = 1 everywhere: weight 0
+        if (col < ncols && k0 < K) {
+            const int8_t* src = W8 + (size_t)col * ld8 + k0;
+            p = 0;
+#pragma unroll
+            for (int j = 0; j < 16; ++j) {
+                const int w = k0 + j < K ? (int)src[j] : 0;  // k0 + 15 < ld8: ld8 and k0 are multiples of 16
+                if (w < -1 || w > 1) *bad = 1;
+                p |= (uint32_t)((w + 1) & 3) << (8 * (j & 3) + 2 * (j >> 2));
+            }
+        }
+        W2[g] = p;
+    }
+}
+
+// k_decode8.  Grid: ceil(col tiles / T) workgroups of kDecWaves waves.  Wave w
+// takes the 256-k blocks w, w + 8, ...: of each it loads the X fragments once
+// (4 x 16 B per lane: row l & 15, k quarter l >> 4; rows >= M and k >= K are
+// zeros and never read) and, per column tile, 16 B of image.  The next block's
+// loads are issued before this block's MFMAs.  ALIGNED: X is 16-B aligned and
+// K % 16 == 0, so a fragment is one 16-B load that lies wholly below K or
+// wholly past it; otherwise its 16 bytes are loaded one by one, each guarded.
+// K tails and column tails need nothing in the tile loop: the image's padding
+// is weight 0 (code 1, cancelled by the row sums: X is zero there anyway) and
+// columns >= N are computed and not stored.
+template <int T, bool ALIGNED, bool PRELU>
+__global__ void __launch_bounds__(kDecWaves * 64) k_decode8(const int8_t* __restrict__ X,
+                                                             const uint32_t* __restrict__ W2, int K, int M, int N,
+                                                             int nkb, int ntiles, const float* __restrict__ scale,
+                                                             const float* __restrict__ bias, float* __restrict__ Y,
+                                                             int ldy, float a) {
+    __shared__ int red[kDecWaves * T * 256];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int t0 = blockIdx.x * T;
+    const int xr = lane & 15, kq = lane >> 4;
+    const bool row_ok = xr < M;
+    const int8_t* xrow = X + (size_t)(row_ok ? xr : 0) * K;
+
+    // this wave's 16 bytes of tile (t, kb) are at wp[t] + 64 * kb (16-B units); a workgroup's last
+    // tiles past the matrix read the last tile again (uniform) and are not stored
+    const u32x4* wp[T];
+#pragma unroll
+    for (int t = 0; t < T; ++t)
+        wp[t] = reinterpret_cast<const u32x4*>(W2) + (size_t)min(t0 + t, ntiles - 1) * nkb * 64 + lane;
+
+    auto load = [&](int kb, i32x4 (&xf)[4], u32x4 (&p)[T]) {
+#pragma unroll
+        for (int t = 0; t < T; ++t) p[t] = __builtin_nontemporal_load(wp[t] + (size_t)kb * 64);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int k = kW2Blk * kb + 64 * i + 16 * kq;
+            xf[i] = i32x4{0, 0, 0, 0};
+            if constexpr (ALIGNED) {
+                if (row_ok && k < K) xf[i] = *reinterpret_cast<const i32x4*>(xrow + k);
+            } else {
+                if (row_ok && k < K) {
+#pragma unroll
+                    for (int j = 0; j < 16; ++j) {
+                        const uint32_t b = k + j < K ? (uint32_t)(uint8_t)xrow[k + j] : 0u;
+                        xf[i][j >> 2] |= (int)(b << (8 * (j & 3)));
+                    }
+                }
+            }
+        }
+    };
+
+    i32x4 acc[T], rs = i32x4{0, 0, 0, 0};
+#pragma unroll
+    for (int t = 0; t < T; ++t) acc[t] = i32x4{0, 0, 0, 0};
+    const i32x4 ones = i32x4{0x01010101, 0x01010101, 0x01010101, 0x01010101};
+
+    i32x4 xf[4], xn[4];
+    u32x4 p[T], pn[T];
+    int kb = wave;
+    if (kb < nkb) load(kb, xf, p);
+    while (kb < nkb) {  // uniform
+        const int nx = kb + kDecWaves;
+        if (nx < nkb) load(nx, xn, pn);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            rs = __builtin_amdgcn_mfma_i32_16x16x64_i8(xf[i], ones, rs, 0, 0, 0);
+#pragma unroll
+            for (int t = 0; t < T; ++t) {
+                const uint32_t q = p[t][i];
+                const i32x4 b = i32x4{(int)(q & 0x03030303u), (int)((q >> 2) & 0x03030303u),
+                                      (int)((q >> 4) & 0x03030303u), (int)((q >> 6) & 0x03030303u)};
+                acc[t] = __builtin_amdgcn_mfma_i32_16x16x64_i8(xf[i], b, acc[t], 0, 0, 0);
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) xf[i] = xn[i];
+#pragma unroll
+        for (int t = 0; t < T; ++t) p[t] = pn[t];
+        kb = nx;
+    }
+
+    // S of this wave's K share, in the accumulator layout (register r of lane l: row 4 (l >> 4) + r,
+    // column l & 15); a wave without blocks adds zeros
+#pragma unroll
+    for (int t = 0; t < T; ++t)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) red[(wave * T + t) * 256 + r * 64 + lane] = acc[t][r] - rs[r];
+    __syncthreads();
+    // one thread per output, a row's 16 T columns on consecutive threads
+    for (int o = threadIdx.x; o < T * 256; o += kDecWaves * 64) {
+        const int row = o / (16 * T), cg = o % (16 * T), t = cg >> 4, c = cg & 15;
+        const int col = (t0 + t) * kW2Cols + c;
+        if (row >= M || col >= N) continue;
+        int S = 0;
+#pragma unroll
+        for (int w = 0; w < kDecWaves; ++w) S += red[(w * T + t) * 256 + (row & 3) * 64 + (row >> 2) * 16 + c];
+        const float sc = scale ? scale[row] : 1.0f;
+        Y[(size_t)row * ldy + col] = i8_out<PRELU>(S, sc, bias[col], a);
+    }
+}
+
+template <int T, bool ALIGNED>
+void launch_decode(const int8_t* X, const uint32_t* w2, int K, int M, int N, const float* scale, const float* B,
+                   float* Y, int ldy, bool prelu, float a, hipStream_t st) {
+    const int ntiles = w2_col_tiles(N), nkb = w2_kblocks(K);
+    const dim3 grid((ntiles + T - 1) / T), block(kDecWaves * 64);
+    if (prelu)
+        hipLaunchKernelGGL((k_decode8<T, ALIGNED, true>), grid, block, 0, st, X, w2, K, M, N, nkb, ntiles, scale, B, Y,
+                           ldy, a);
+    else
+        hipLaunchKernelGGL((k_decode8<T, ALIGNED, false>), grid, block, 0, st, X, w2, K, M, N, nkb, ntiles, scale, B, Y,
+                           ldy, a);
+}
+
+}  // namespace
+
+hipError_t decode_build_w2(const int8_t* w8, int ncols, int K, int ld8, uint32_t* w2, int* bad, hipStream_t st) {
+    if (ncols <= 0 || K <= 0 || ld8 < K || ld8 % 16) return hipErrorInvalidValue;
+    const int nkb = w2_kblocks(K);
+    const size_t dwords = w2_image_bytes(K, ncols) / 4;
+    const size_t blocks = (dwords + 255) / 256;
+    hipLaunchKernelGGL(k_w2_from, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, st, w8, ncols, K, ld8,
+                       nkb, dwords, w2, bad);
+    return hipGetLastError();
+}
+
+// Column tiles per workgroup.  A workgroup reads all of X (M K bytes, from the
+// L2) and 4 T K bytes of image (from HBM): T >= M / 4 keeps the first at or
+// below the second.  But T tiles per workgroup leave ceil(tiles / T)
+// workgroups, and below one per CU the stream has too few loads in flight, so
+// T is halved until the grid covers the chip (or T = 1).
+int decode_tiles_per_wg(int M, int N, int num_cus) {
+    if (kDecTiles) return kDecTiles;
+    const int ntiles = w2_col_tiles(N), cus = num_cus > 0 ? num_cus : 256;
+    int T = M > 8 ? 4 : M > 4 ? 2 : 1;
+    while (T > 1 && (ntiles + T - 1) / T < cus) T >>= 1;
+    return T;
+}
+
+hipError_t decode_gemm(const int8_t* X, const uint32_t* w2, int K, int M, int N, const float* scale, const float* B,
+                       float* Y, int ldy, bool prelu, float a, int num_cus, hipStream_t st) {
+    if (M < 1 || M > kDecodeMaxM || K < 1 || K >= kDecodeMaxK || N < 1 || !X || !w2 || !B || !Y || ldy < N)
+        return hipErrorInvalidValue;
+    const bool aligned = K % 16 == 0 && (reinterpret_cast<uintptr_t>(X) & 15) == 0;
+    const int T = decode_tiles_per_wg(M, N, num_cus);
+#define TCSC_DECODE_LAUNCH(TT)                                                        \
+    if (aligned)                                                                      \
+        launch_decode<TT, true>(X, w2, K, M, N, scale, B, Y, ldy, prelu, a, st);      \
+    else                                                                              \
+        launch_decode<TT, false>(X, w2, K, M, N, scale, B, Y, ldy, prelu, a, st)
+    if (T == 4) {
+        TCSC_DECODE_LAUNCH(4);
+    } else if (T == 2) {
+        TCSC_DECODE_LAUNCH(2);
+    } else {
+        TCSC_DECODE_LAUNCH(1);
+    }
+#undef TCSC_DECODE_LAUNCH
+    return hipGetLastError();
+}
+
+}  // namespace tcsc

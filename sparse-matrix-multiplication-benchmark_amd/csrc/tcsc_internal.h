@@ -426,6 +426,33 @@ hipError_t mfma8_gemm(const int8_t* x8, const int8_t* w8, int ld8, int K, int M,
 // k_quant_rows_i8: per-row absmax quantization (tcsc_gpu_quantize_rows_i8)
 hipError_t quantize_rows_i8(const float* X, int M, int K, int8_t* Xq, float* scale, hipStream_t st);
 
+// ---- int8 decode path (tcsc_decode.hip) -------------------------
+// The 2-bit image of a ternary W: tiles of kW2Cols columns x kW2Blk k, 1 KiB
+// each, column-tile major then k-block.  Lane l of the wave that reads a tile
+// owns bytes 16 l .. 16 l + 15: column 16 t + (l & 15), k quarter l >> 4; its
+// dword i holds the 16 weights k = 256 kb + 64 i + 16 (l >> 4) + j, j = 0 .. 15,
+// the bytes of its v_mfma_i32_16x16x64_i8 fragment in step i of the block (the
+// mapping of k_gemm8's fragments).  Code c = w + 1 of weight j sits at bit
+// 8 (j & 3) + 2 (j >> 2), so the fragment's dword d is (p >> 2d) & 0x03030303.
+// Padding (k >= K, column >= N) holds c = 1, weight 0.
+constexpr int kW2Cols = 16;
+constexpr int kW2Blk = 256;
+constexpr int kW2TileBytes = 1024;
+constexpr int kDecodeMaxM = 16;      // one 16-row MFMA tile
+constexpr int kDecodeMaxK = 1 << 22; // K below it: |sum q c| <= 128 * 2 * K < 2^31
+__host__ __device__ inline int w2_col_tiles(int N) { return (N + kW2Cols - 1) / kW2Cols; }
+__host__ __device__ inline int w2_kblocks(int K) { return (K + kW2Blk - 1) / kW2Blk; }
+inline size_t w2_image_bytes(int K, int N) { return (size_t)w2_col_tiles(N) * w2_kblocks(K) * kW2TileBytes; }
+// k_w2_from: the 2-bit image from the int8 one (ncols x ld8); *bad = 1 when a
+// weight is not -1, 0 or +1
+hipError_t decode_build_w2(const int8_t* w8, int ncols, int K, int ld8, uint32_t* w2, int* bad, hipStream_t st);
+// column tiles per workgroup of a k_decode8 launch (1, 2 or 4)
+int decode_tiles_per_wg(int M, int N, int num_cus);
+// k_decode8: Y = act(fl(fl(float(S) * scale[m]) + B[j])) for m < M <= 16, S the
+// exact i32 sum; X is M x K int8 of any alignment, read in place
+hipError_t decode_gemm(const int8_t* X, const uint32_t* w2, int K, int M, int N, const float* scale, const float* B,
+                       float* Y, int ldy, bool prelu, float a, int num_cus, hipStream_t st);
+
 // Rewrites the flagged rows in k_stream's fast order (no-op when none is).
 hipError_t mfma_fixup(const uint16_t* x3, int M, int K, int ldk, const int* cq, const int* crq, int ncols,
                       const float* B, float* Y, int ldy, bool bias_first, bool prelu, float a, const int* flags,

@@ -35,6 +35,7 @@
 #include <cstdlib>
 #include <type_traits>
 
+#include "tcsc_i8_out.h"
 #include "tcsc_internal.h"
 
 namespace tcsc {
@@ -700,16 +701,8 @@ __global__ void __launch_bounds__(WM * WN * 64) k_gemm3(const uint16_t* __restri
 // ---------------------------------------------------------------------------
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 
-// act(fl(fl(float(S) * s) + b)): one conversion (round to nearest), one
-// multiply, one add that must not contract with it, then the PReLU.
-template <bool PRELU>
-__device__ __forceinline__ float i8_out(int S, float s, float b, float a) {
-    // (__fmul_rn / __fadd_rn are plain * and + to hipcc, which would fuse them)
-#pragma clang fp contract(off)
-    const float p = (float)S * s;
-    const float v = p + b;
-    return PRELU ? ((v < 0.0f) ? a * v : v) : v;
-}
+// The epilogue arithmetic, act(fl(fl(float(S) * s) + b)), is i8_out of
+// tcsc_i8_out.h: k_decode8 (tcsc_decode.hip) runs the same definition.
 
 // int8 X (M x K, pitch K) -> X8 (M x ld8 bytes): the row as it is, zeros past
 // K, one workgroup per row.  VEC (K % 16 == 0, X 16-B aligned): kSplitU 16-B

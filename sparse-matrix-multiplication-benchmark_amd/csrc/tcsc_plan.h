@@ -58,8 +58,8 @@ int plan_create_impl(const tcsc_t* W, int col_begin, int col_end, int device, vo
 
 // ---- the route of one call ---------------------------------------------------
 // Everything that launches, sizes or reports a call of M rows takes these from
-// route_call(), which alone asks the cost models (use_mfma / use_small,
-// choose_slices, wide_pays, combine_mode).
+// route_call(), which alone asks the cost models (use_decode / use_mfma /
+// use_small, choose_slices, wide_pays, combine_mode).
 struct Route {
     int path = TCSC_PATH_GATHER;
     // The K split as launched: the MFMA GEMM's, or the 16-column gather's
@@ -78,7 +78,7 @@ struct Route {
 // cost models are not monotone in M, and a piece on another path or split
 // would sum in another order, in a workspace sized for the job's.
 struct RoutePins {
-    int path = TCSC_PATH_AUTO;  // AUTO: the cost models choose; GATHER can always be pinned, MFMA and SMALL for sizing
+    int path = TCSC_PATH_AUTO;  // AUTO: the cost models choose; GATHER can always be pinned, MFMA, SMALL and DECODE for sizing
     int slices = 0;             // > 0: the gather's K split (else $TCSC_SLICES, else the cost model)
     bool plan_ws = true;        // the launch runs on the plan's own workspace, beside its combine words
     bool vec = true;            // Y, B and the slabs are 16-B aligned and ldy % 4 == 0

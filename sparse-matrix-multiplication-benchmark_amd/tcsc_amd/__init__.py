@@ -50,6 +50,7 @@ EXPORTED_SYMBOLS = (
     "tcsc_gpu_sgemm_bf16", "tcsc_gpu_launch_info_bf16",
     "tcsc_gpu_plan_enable_i8", "tcsc_gpu_plan_has_i8", "tcsc_gpu_sgemm_i8", "tcsc_gpu_launch_info_i8",
     "tcsc_gpu_quantize_rows_i8", "tcsc_gpu_workspace_bound_i8",
+    "tcsc_gpu_plan_enable_w2", "tcsc_gpu_plan_has_w2", "tcsc_gpu_w2_image_bytes", "tcsc_gpu_decode_pays",
     "tcsc_gpu_launch_geometry", "tcsc_gpu_wide_pays",
     # include/sparse/bcsr.h
     "bcsr_from_dense", "bcsr_sgemm_basic", "bcsr_sgemm_prelu_basic", "bcsr_sgemm_avx", "bcsr_sgemm_prelu_avx",
@@ -158,6 +159,10 @@ def lib():
     L.tcsc_gpu_launch_info_i8.argtypes = [vp, i, C.POINTER(i), C.POINTER(i)]
     L.tcsc_gpu_quantize_rows_i8.argtypes = [vp, i, i, vp, vp, vp]
     L.tcsc_gpu_workspace_bound_i8.argtypes = [i, i, i, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+    L.tcsc_gpu_plan_enable_w2.argtypes = [vp, vp]
+    L.tcsc_gpu_plan_has_w2.argtypes = [vp]
+    L.tcsc_gpu_w2_image_bytes.argtypes = [i, i, C.POINTER(C.c_size_t)]
+    L.tcsc_gpu_decode_pays.argtypes = [i, i, i, C.c_longlong]
     L.tcsc_gpu_prepare_x.argtypes = [vp, vp, i, vp]
     L.tcsc_gpu_sgemm_prepared.argtypes = [vp, vp, vp, i, i, i, f, vp]
     L.tcsc_gpu_from_dense.argtypes = [vp, i, i, vp, vp, vp, vp, C.POINTER(i), C.POINTER(i), vp]
@@ -508,7 +513,7 @@ class Plan:
     def _launch_info(self, name: str, M: int) -> tuple[str, int]:
         path, slices = C.c_int(), C.c_int()
         _check(getattr(lib(), name)(self.handle, int(M), C.byref(path), C.byref(slices)), name)
-        return ("gather", "fused", "mfma", "small")[path.value], slices.value
+        return ("gather", "fused", "mfma", "small", "decode")[path.value], slices.value
 
     def launch_info(self, M: int) -> tuple[str, int]:
         """(path, K slices) of a launch of M rows: path is 'gather' (k_transpose +
@@ -546,13 +551,14 @@ class Plan:
         """Allocate the workspace (X^T + split-K slabs) for launches of up to max_M rows."""
         _check(lib().tcsc_gpu_plan_reserve(self.handle, int(max_M)), "tcsc_gpu_plan_reserve")
 
-    PATH_ID = {None: -1, "gather": 0, "mfma": 2, "small": 3}
+    PATH_ID = {None: -1, "gather": 0, "mfma": 2, "small": 3, "decode": 4}
 
     def workspace(self, M: int, path: str | None = None) -> tuple[int, int]:
         """(bytes a launch of M rows wants, bytes reserved now): host arithmetic, no
         launch.  path None: the path launch_info(M) names; 'gather', 'mfma' or
         'small': that path's need at M whatever the cost model prefers, 0 where the
-        plan cannot run it (tcsc_gpu_plan_workspace)."""
+        plan cannot run it; 'decode': always 0, the decode path reads X in place
+        (tcsc_gpu_plan_workspace)."""
         need, reserved = C.c_size_t(), C.c_size_t()
         _check(lib().tcsc_gpu_plan_workspace(self.handle, int(M), self.PATH_ID[path], C.byref(need),
                                              C.byref(reserved)), "tcsc_gpu_plan_workspace")
@@ -585,8 +591,21 @@ class Plan:
         return bool(lib().tcsc_gpu_plan_has_i8(self.handle))
 
     def launch_info_i8(self, M: int) -> tuple[str, int]:
-        """(path, K slices) of an :meth:`sgemm_i8` launch of M rows (tcsc_gpu_launch_info_i8)."""
+        """(path, K slices) of an :meth:`sgemm_i8` launch of M rows (tcsc_gpu_launch_info_i8); the path may be
+        'decode' (k_decode8 on the 2-bit image: M <= 16 after :meth:`enable_w2`)."""
         return self._launch_info("tcsc_gpu_launch_info_i8", M)
+
+    def enable_w2(self, stream: int = 0) -> bool:
+        """Build the 2-bit image of a ternary W beside the int8 image (tcsc_gpu_plan_enable_w2) and return
+        :attr:`has_w2`: False on a plan without the int8 image, when a weight is not -1, 0 or +1 (a duplicated
+        index) or K >= 2^22 -- :meth:`sgemm_i8` then runs as before.  With the image, int8 calls of M <= 16 rows
+        may take the decode path (:func:`decode_pays`, $TCSC_DECODE).  Idempotent; synchronises the stream."""
+        _check(lib().tcsc_gpu_plan_enable_w2(self.handle, C.c_void_p(stream)), "tcsc_gpu_plan_enable_w2")
+        return self.has_w2
+
+    @property
+    def has_w2(self) -> bool:
+        return bool(lib().tcsc_gpu_plan_has_w2(self.handle))
 
     def sgemm_i8(self, Xq, scale, B, Y, M: int, ldy: int, variant: str = "prelu_basic", a: float = 0.2,
                  stream: int = 0) -> None:
@@ -663,6 +682,20 @@ def quantize_rows_i8(X, Xq, scale, M: int, K: int, stream: int = 0) -> None:
     _check(lib().tcsc_gpu_quantize_rows_i8(C.c_void_p(_ptr(X)), int(M), int(K), C.c_void_p(_ptr(Xq)),
                                            C.c_void_p(_ptr(scale)), C.c_void_p(stream)),
            "tcsc_gpu_quantize_rows_i8")
+
+
+def w2_image_bytes(K: int, N: int) -> int:
+    """Bytes of the 2-bit image of a K x N ternary W: ceil(N/16) * ceil(K/256) * 1024 (tcsc_gpu_w2_image_bytes;
+    host arithmetic, no device)."""
+    b = C.c_size_t()
+    _check(lib().tcsc_gpu_w2_image_bytes(int(K), int(N), C.byref(b)), "tcsc_gpu_w2_image_bytes")
+    return b.value
+
+
+def decode_pays(M: int, K: int, N: int, nnz: int) -> bool:
+    """The default rule for the decode path (tcsc_gpu_decode_pays; host arithmetic): 1 <= M <= 16 and (M > 4, or
+    the small-M path does not fit (M, K), or 16 * nnz > K * N)."""
+    return bool(lib().tcsc_gpu_decode_pays(int(M), int(K), int(N), int(nnz)))
 
 
 def prelu_backward(G, Y, a: float, DZ, DB, M: int, N: int, ldg: int | None = None, ldy: int | None = None,

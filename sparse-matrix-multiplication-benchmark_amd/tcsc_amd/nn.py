@@ -123,17 +123,24 @@ def _define():
                 self.transposed_plan = Plan.transposed(self._W, 0, self.out_features, self.device_index, _stream(dev))
             return self.transposed_plan
 
-        def reserve(self, max_rows: int, int8: bool = False) -> None:
+        def reserve(self, max_rows: int, int8: bool = False, decode: bool = False) -> None:
             """Workspaces of both plans for up to max_rows rows (the flattened leading
             dimensions), building the transposed plan if it is absent: afterwards a
             forward + backward step allocates nothing in the library and can be captured.
             int8=True also builds the plan's int8 image (``Plan.enable_i8``) and the
-            buffers :meth:`forward_int8` quantizes into, for up to max_rows rows."""
+            buffers :meth:`forward_int8` quantizes into, for up to max_rows rows.
+            decode=True (with int8=True) also builds the 2-bit image (``Plan.enable_w2``):
+            :meth:`forward_int8` calls of up to 16 rows then stream it (the decode path)."""
+            if decode and not int8:
+                raise TcscError("TernaryLinear.reserve: decode=True needs int8=True (the 2-bit image is made from "
+                                "the int8 one)")
             self.plan.reserve(max_rows)
             self._transposed().reserve(max_rows)
             if int8:
                 self.plan.enable_i8(_stream(torch.device("cuda", self.device_index)))
                 self._i8_buffers(max_rows)
+            if decode:
+                self.plan.enable_w2(_stream(torch.device("cuda", self.device_index)))
 
         def _i8_buffers(self, rows: int):
             """(Xq, scale) for `rows` rows: kept from the last reserve, grown when a call needs more."""

@@ -53,6 +53,13 @@ lib/abl/libtcsc_amd_dma%.so: $(SRC)/tcsc_kernels.hip $(call ab_rest,$(K_OBJ)) $(
 	$(HIPCC) $(HIPFLAGS) -DTCSC_DMA_WAVES=$(word 1,$(subst _, ,$*)) -DTCSC_DMA_EARLY=$(word 2,$(subst _, ,$*)) -c $(SRC)/tcsc_kernels.hip -o $(OBJ)/abl/k_dma$*.o
 	$(call ab_link,$(K_OBJ),$(OBJ)/abl/k_dma$*.o)
 
+# decode-kernel variants (A/B): lib/abl/libtcsc_amd_dec<waves>_<tiles>.so, waves per
+# workgroup and column tiles per workgroup (0 = the product's rule); the same results, other timings
+lib/abl/libtcsc_amd_dec%.so: $(SRC)/tcsc_decode.hip $(call ab_rest,$(OBJ)/tcsc_decode.o) $(HDRS)
+	@mkdir -p lib/abl $(OBJ)/abl
+	$(HIPCC) $(HIPFLAGS) -DTCSC_DEC_WAVES=$(word 1,$(subst _, ,$*)) -DTCSC_DEC_TILES=$(word 2,$(subst _, ,$*)) -c $(SRC)/tcsc_decode.hip -o $(OBJ)/abl/dec$*.o
+	$(call ab_link,$(OBJ)/tcsc_decode.o,$(OBJ)/abl/dec$*.o)
+
 # the same without the X staging (gather cost alone): lib/abl/libtcsc_amd_abl<N>_nd.so
 ablation-nodma: $(foreach a,0 1 3 4 5,lib/abl/libtcsc_amd_abl$(a)_nd.so)
 
