@@ -396,13 +396,85 @@ int tcsc_gpu_workspace_bound_i8(int M, int K, int N, size_t *i8_bytes, size_t *f
  * tcsc_gpu_launch_info_i8 names the path; tcsc_gpu_launch_info and _bf16 never
  * do.
  *
- * Out of scope: M > 16; dropping the bf16 and int8 images on decode-only plans;
- * bf16 or int8 Y; a host-pointer version; building the 2-bit image without the
- * int8 one. */
+ * Out of scope: bf16 or int8 Y; a host-pointer version.  (M > 16 on the image,
+ * plans that hold nothing else, and the image without the int8 one: packed
+ * plans, below.) */
 int tcsc_gpu_plan_enable_w2(tcsc_gpu_plan *plan, void *stream);
 int tcsc_gpu_plan_has_w2(const tcsc_gpu_plan *plan);
 int tcsc_gpu_w2_image_bytes(int K, int N, size_t *bytes);
 int tcsc_gpu_decode_pays(int M, int K, int N, long long nnz);
+
+/* ---- packed plans: int8 calls at every M from the 2-bit image alone
+ * A plan that decodes as above still holds every format of W: the gather's
+ * entry streams (about 8 bytes per nonzero), the merged CSC copy (4 per
+ * nonzero), the bf16 image (2 per weight), the int8 image (1) and the 2-bit
+ * image (1/4).  A packed plan holds the last one and nothing else of W.
+ *
+ * tcsc_gpu_plan_create_packed / _packed_device: the arguments of
+ * tcsc_gpu_plan_create / _create_device.  The image is built on the device
+ * straight from the TCSC arrays (k_w2_from_tcsc; integer adds only, so no
+ * order of execution shows in it) and is byte for byte the one
+ * tcsc_gpu_plan_enable_i8 + _enable_w2 build for the same W and column range:
+ * the layout above, padding code 1, a +1 and a -1 at one position cancel, and
+ * the order inside a column does not matter.  Straight after creation
+ * tcsc_gpu_plan_get_info(...).device_bytes == tcsc_gpu_w2_image_bytes(K, cols)
+ * exactly; nnz, n_pos, n_neg, rows, cols and col_begin are filled, mfma_min_M
+ * is 17, chunk_k is the library's constant and n_chunks is 0.  TCSC_E_ARG with
+ * a message, and no plan, for: a position whose summed weight is outside
+ * {-1, 0, +1} (a duplicated index), K < 1 or K >= 2^22, a col_start that is no
+ * range or a row outside [0, K), and a reference-order request
+ * ($TCSC_ORDER=reference or tcsc_gpu_set_order) -- a packed plan has no other
+ * format to fall back to.  $TCSC_PATH is not read.  Synchronises `stream`.
+ *
+ * tcsc_gpu_sgemm_i8 on a packed plan (the numeric contract of the int8 MFMA
+ * path, Y = act(fl(fl(float(S) * s[m]) + b[j])) with S the exact i32 sum: the
+ * bits of k_gemm8 on an ordinary plan of the same W, for every variant, K
+ * split and tile shape):
+ *   1 <= M <= 16  TCSC_PATH_DECODE, k_decode8 as it is -- whatever
+ *                 tcsc_gpu_decode_pays or $TCSC_DECODE say: there is nothing
+ *                 else to run
+ *   M >= 17       TCSC_PATH_MFMA: k_pack8 (X -> X8), then k_gemm8w2, k_gemm8
+ *                 with the B fragments loaded from the 2-bit image straight
+ *                 into registers and turned into signed bytes there (no row
+ *                 sums), on k_gemm8's tiles and K split (mfma8_slices;
+ *                 $TCSC_MFMA_WGS acts as on other plans), with K split raw i32
+ *                 slabs and k_reduce_i8
+ *   M > 2^22      several launches of at most 2^22 rows on one workspace
+ * tcsc_gpu_launch_info_i8 reports this; tcsc_gpu_plan_reserve and
+ * tcsc_gpu_plan_workspace size X8 and the slabs for every M <= max_M (0 for the
+ * decode path), after which calls allocate nothing and can be captured.
+ * $TCSC_PATH=gather has nothing to select and is ignored.
+ * Everything that needs a format the plan lacks returns TCSC_E_ARG with a
+ * message naming the call and "packed plan", before any HIP call:
+ * tcsc_gpu_sgemm, _sgemm_bf16, _prepare_x, _sgemm_prepared, _sgemm_t,
+ * tcsc_gpu_launch_info, _launch_info_bf16, _launch_geometry and
+ * _launch_combine.  tcsc_gpu_plan_enable_i8 and _enable_w2 return TCSC_OK and
+ * change nothing; tcsc_gpu_plan_has_w2 says 1 and tcsc_gpu_plan_has_i8 0.
+ *
+ * tcsc_gpu_plan_copy_w2: a device-to-device copy of the image of any plan that
+ * has one (packed or after tcsc_gpu_plan_enable_w2) into d_dst, asynchronous
+ * on `stream`; TCSC_E_ARG if the plan has no image or `bytes` is not
+ * tcsc_gpu_w2_image_bytes(K, cols).  The first half of saving a packed model.
+ *
+ * On an ordinary plan that has the 2-bit image, $TCSC_W2GEMM=1 (read per call)
+ * sends the int8 calls that route to TCSC_PATH_MFMA through k_gemm8w2 instead
+ * of k_gemm8: the same route, slices, workspace and bits (the A/B on one plan;
+ * unset or 0 changes nothing, and it is never a default).
+ *
+ * Out of scope: loading a packed plan from a saved image, fp32 or bf16
+ * activations, a backward pass, packed transposed plans, a host-pointer
+ * version, bf16 or int8 Y. */
+int tcsc_gpu_plan_create_packed(const tcsc_t *W, int col_begin, int col_end,
+                                int device, void *stream, tcsc_gpu_plan **out);
+int tcsc_gpu_plan_create_packed_device(int rows, int cols,
+                                       const int *d_col_start_pos,
+                                       const int *d_col_start_neg,
+                                       const int *d_row_index_pos,
+                                       const int *d_row_index_neg,
+                                       int col_begin, int col_end, int device,
+                                       void *stream, tcsc_gpu_plan **out);
+int tcsc_gpu_plan_is_packed(const tcsc_gpu_plan *plan);
+int tcsc_gpu_plan_copy_w2(const tcsc_gpu_plan *plan, void *d_dst, size_t bytes, void *stream);
 
 /* Device-side tcsc_from_dense: dense K x N row-major float matrix on the
  * device -> TCSC arrays on the device, bit-exact with the reference builder

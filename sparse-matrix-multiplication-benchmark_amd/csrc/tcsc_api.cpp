@@ -90,6 +90,11 @@ struct tcsc_gpu_plan {
     // bias tcsc_gpu_sgemm_t hands to the launch; null on every other plan
     float* tbias = nullptr;
     size_t tbias_bytes = 0;
+    // packed plans (tcsc_gpu_plan_create_packed*): w2 above is
+    // all the plan holds of W -- no entry streams, no CSC copy, no bf16 or int8
+    // image, no chains, no combine words -- and only int8 calls run on it:
+    // k_decode8 at M <= 16, k_pack8 + k_gemm8w2 above
+    bool packed = false;
 };
 
 namespace {
@@ -388,11 +393,12 @@ bool mfma_cheaper(const tcsc_gpu_plan* p, int M, int dt) {
 // forced (TCSC_PATH=mfma: mfma_min_M 1): every launch; default: by the cost
 // model.  An int8 call needs the int8 image (tcsc_gpu_plan_enable_i8).
 bool has_mfma(const tcsc_gpu_plan* p, int M, int dt) {  // the plan can run M rows of type dt on the MFMA path
+    if (p->packed) return dt == kI8 && p->w2 && M >= p->mfma_min_M && p->rows > 0;  // k_gemm8w2 on the 2-bit image
     return p->wt && (dt != kI8 || p->w8) && M >= p->mfma_min_M && p->rows > 0;
 }
 bool use_mfma(const tcsc_gpu_plan* p, int M, int dt = kF32) {
     if (!has_mfma(p, M, dt)) return false;
-    if (p->mfma_min_M == 1) return true;
+    if (p->mfma_min_M == 1 || p->packed) return true;  // forced, or the only path the plan has at this M
     return mfma_cheaper(p, M, dt);
 }
 
@@ -534,11 +540,18 @@ int decode_knob() {
     if (!e || !*e) return -1;
     return std::atoi(e) != 0 ? 1 : 0;
 }
+// $TCSC_W2GEMM=1, read per call: int8 calls that route to TCSC_PATH_MFMA on an ordinary plan with the 2-bit
+// image run k_gemm8w2 instead of k_gemm8 (the A/B on one plan); never a default
+bool w2gemm_knob() {
+    const char* e = std::getenv("TCSC_W2GEMM");
+    return e && std::atoi(e) != 0;
+}
 bool has_decode(const tcsc_gpu_plan* p, int M, int dt) {  // the plan can run M rows of type dt on the decode path
     return dt == kI8 && p->w2 && M >= 1 && M <= tcsc::kDecodeMaxM;
 }
 bool use_decode(const tcsc_gpu_plan* p, int M, int dt) {
     if (!has_decode(p, M, dt)) return false;
+    if (p->packed) return true;  // nothing else serves M <= 16 there: neither the rule nor $TCSC_DECODE is asked
     const int knob = decode_knob();
     return knob >= 0 ? knob == 1 : decode_pays(M, p->rows, p->cols, p->n_pos + p->n_neg);
 }
@@ -632,7 +645,7 @@ size_t path_ws_bytes(const tcsc_gpu_plan* p, int M, int path) {
     if (M <= 0 || p->cols == 0) return 0;
     RoutePins pin;
     pin.path = path;
-    return route_call(p, M, kF32, kUnbounded, pin).ws_bytes;
+    return route_call(p, M, p->packed ? kI8 : kF32, kUnbounded, pin).ws_bytes;  // a packed plan runs int8 calls only
 }
 
 // the path of a call of type dt (each type has its own cost model)
@@ -666,6 +679,12 @@ size_t wanted_workspace(const tcsc_gpu_plan* p, int M, int dt = kF32) {
 constexpr long long kNoSplitBase = 40 * 256;
 size_t reserve_bytes(const tcsc_gpu_plan* p, int max_M) {
     if (max_M <= 0 || p->cols == 0) return 0;
+    if (p->packed) {  // the MFMA rule below is all there is: X8 and the i32 slabs of k_gemm8w2 (k_decode8 needs nothing)
+        const int top = std::min(max_M, kMaxLaunchRows);
+        size_t want = path_ws_bytes(p, top, TCSC_PATH_MFMA);
+        for (int M = 64; M < top; M += 64) want = std::max(want, path_ws_bytes(p, M, TCSC_PATH_MFMA));
+        return want;
+    }
     const long long cb = std::max(1, (p->n_groups + tcsc::kWaves - 1) / tcsc::kWaves);
     const int every = (int)std::min<long long>(max_M, (kNoSplitBase + cb - 1) / cb * tcsc::kTM);
     size_t want = 0;
@@ -911,6 +930,16 @@ Route tcsc::route_call(const tcsc_gpu_plan* p, int M, int dt, size_t ws_avail, c
     Route r;
     r.path = pin.path != TCSC_PATH_AUTO ? pin.path : launch_path(p, M, dt);
     r.rows = std::min(M, kMaxLaunchRows);
+    if (p->packed) {
+        // The 2-bit image is the plan's only format: k_decode8 up to 16 rows, k_gemm8w2 above, whatever the
+        // cost models, $TCSC_PATH or $TCSC_DECODE say.  More than kMaxLaunchRows rows run in pieces of that
+        // many on one workspace; every piece computes the same bits on either kernel and any K split.
+        if (pin.path == TCSC_PATH_AUTO) r.path = M <= tcsc::kDecodeMaxM ? TCSC_PATH_DECODE : TCSC_PATH_MFMA;
+        if (r.path != TCSC_PATH_MFMA || !has_mfma(p, r.rows, dt)) return r;  // no workspace, or nothing to run
+        r.slices = d.slices(r.rows, N, K);
+        r.ws_bytes = mfma_ws(dt, r.rows, K, N).bytes;
+        return r;
+    }
     if (r.path == TCSC_PATH_MFMA) {  // [packed X][row flags][the GEMM's split-K slabs]: mfma_ws
         if (!has_mfma(p, M, dt)) return r;
         r.slices = d.slices(M, N, K);
@@ -983,8 +1012,14 @@ int sgemm_mfma(const tcsc_gpu_plan* p, const void* dX, int dt, const float* dSca
             break;
         case kI8:
             HIP_TRY(tcsc::mfma8_pack_x(static_cast<const int8_t*>(dX), M, K, reinterpret_cast<int8_t*>(base), ldx, st));
-            HIP_TRY(tcsc::mfma8_gemm(reinterpret_cast<const int8_t*>(base), p->w8, ldx, K, M, N, dScale, dB, dY, ldy,
-                                     prelu, a, static_cast<int*>(slabs), slab_bytes, st));
+            // B from the 2-bit image (k_gemm8w2): a packed plan has nothing else; an ordinary plan that has
+            // both images takes it under $TCSC_W2GEMM=1 -- the same route, K split, workspace and bits
+            if (p->packed || (p->w2 && w2gemm_knob()))
+                HIP_TRY(tcsc::mfma8_gemm_w2(reinterpret_cast<const int8_t*>(base), p->w2, ldx, K, M, N, dScale, dB, dY,
+                                            ldy, prelu, a, static_cast<int*>(slabs), slab_bytes, st));
+            else
+                HIP_TRY(tcsc::mfma8_gemm(reinterpret_cast<const int8_t*>(base), p->w8, ldx, K, M, N, dScale, dB, dY,
+                                         ldy, prelu, a, static_cast<int*>(slabs), slab_bytes, st));
             break;
     }
     // fast order: bias after the sum for every variant; a
@@ -1013,10 +1048,24 @@ int tcsc::sgemm_ws(const tcsc_gpu_plan* p, const void* dX, const float* dB, floa
         set_error("%s: bad arguments (M=%d ldy=%d variant=%d)", who, M, ldy, variant);
         return TCSC_E_ARG;
     }
+    if (p->packed && dt != kI8) {
+        set_error("%s: a packed plan holds the 2-bit image only and runs tcsc_gpu_sgemm_i8 alone", who);
+        return TCSC_E_ARG;
+    }
     if (M == 0 || p->cols == 0) return TCSC_OK;
     if ((stage != 1 && (!dY || !dB)) || (stage != 2 && !dX && p->rows > 0)) {
         set_error("%s: NULL device pointer", who);
         return TCSC_E_ARG;
+    }
+    if (p->packed && M > kMaxLaunchRows) {  // pieces of at most kMaxLaunchRows rows on one workspace, each routed by its own rows
+        for (int r0 = 0; r0 < M; r0 += kMaxLaunchRows) {
+            const int rc = sgemm_ws(p, static_cast<const char*>(dX) + (size_t)r0 * p->rows * d.elem, dB,
+                                    dY + (size_t)r0 * ldy, std::min(kMaxLaunchRows, M - r0), ldy, variant, a, stream, ws,
+                                    ws_bytes, 0, pin, nullptr, dt, dScale ? dScale + r0 : nullptr);
+            if (rc != TCSC_OK) return rc;
+        }
+        if (ran) *ran = route_call(p, M, dt, ws ? ws_bytes : 0, pin);
+        return TCSC_OK;
     }
     // the gather's arguments the route depends on: Y, B and the split-K slabs behind X^T
     const size_t xtb = tcsc::xt_bytes(std::min(M, kMaxLaunchRows), p->rows);
@@ -1034,7 +1083,8 @@ int tcsc::sgemm_ws(const tcsc_gpu_plan* p, const void* dX, const float* dB, floa
     const Route r = route_call(p, M, dt, ws ? ws_bytes : 0, pins, stage != 1 ? who : nullptr);
     if (ran) *ran = r;
     if ((r.path == TCSC_PATH_MFMA && !has_mfma(p, M, dt)) || (r.path == TCSC_PATH_SMALL && !has_small(p, M)) ||
-        (r.path == TCSC_PATH_DECODE && !has_decode(p, M, dt))) {
+        (r.path == TCSC_PATH_DECODE && !has_decode(p, M, dt)) ||
+        (p->packed && r.path != TCSC_PATH_MFMA && r.path != TCSC_PATH_DECODE)) {
         set_error("%s: the plan cannot run M=%d on the pinned path %d", who, M, r.path);
         return TCSC_E_ARG;
     }
@@ -1210,6 +1260,72 @@ int tcsc::plan_create_impl(const tcsc_t* W, int col_begin, int col_end, int devi
     return rc;
 }
 
+namespace {
+
+// Entry points that need a format a packed plan lacks (fp32 or bf16 activations,
+// the gather's queries, the staged pair, the transposed call): TCSC_E_ARG and a
+// message that names the call, before any HIP call.
+bool refuse_packed(const tcsc_gpu_plan* p, const char* who) {
+    if (!p || !p->packed) return false;
+    set_error("%s: not on a packed plan (it holds the 2-bit image only: tcsc_gpu_sgemm_i8, tcsc_gpu_launch_info_i8)", who);
+    return true;
+}
+
+// What both packed constructors check before they touch the device.
+int packed_args_ok(const char* who, int rows) {
+    if (current_order() == TCSC_ORDER_REFERENCE) {
+        set_error("%s: a packed plan has no reference-order form (TCSC_ORDER / tcsc_gpu_set_order ask for one)", who);
+        return TCSC_E_ARG;
+    }
+    if (rows < 1 || rows >= tcsc::kDecodeMaxK) {
+        set_error("%s: a packed plan needs 1 <= K < %d (K=%d)", who, tcsc::kDecodeMaxK, rows);
+        return TCSC_E_ARG;
+    }
+    return TCSC_OK;
+}
+
+// The packed plan of columns [col_begin, col_begin + ncols) of checked device
+// TCSC arrays (absolute offsets): the 2-bit image by k_w2_from_tcsc and nothing
+// else, so device_bytes is tcsc_gpu_w2_image_bytes(rows, ncols) exactly (the
+// builder's flag word is freed before this returns).
+int build_packed(const char* who, int rows, int col_begin, int ncols, long long n_pos, long long n_neg, const int* csp,
+                 const int* csn, const int* rip, const int* rin, int device, hipStream_t st, tcsc_gpu_plan** out) {
+    std::unique_ptr<tcsc_gpu_plan, PlanDeleter> plan(new tcsc_gpu_plan());
+    plan->device = device;
+    plan->rows = rows;
+    plan->cols = ncols;
+    plan->col_begin = col_begin;
+    plan->n_pos = n_pos;
+    plan->n_neg = n_neg;
+    plan->packed = true;
+    plan->mfma_min_M = tcsc::kDecodeMaxM + 1;
+    HIP_TRY(hipDeviceGetAttribute(&plan->num_cus, hipDeviceAttributeMultiprocessorCount, device));
+    if (ncols > 0) {
+        const size_t bytes = tcsc::w2_image_bytes(rows, ncols);
+        DevBuf bad;
+        if (bad.alloc(sizeof(int)) != hipSuccess || hipMalloc(&plan->w2, bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            plan->w2 = nullptr;
+            set_error("%s: cannot allocate the 2-bit image (%zu bytes)", who, bytes);
+            return TCSC_E_NOMEM;
+        }
+        plan->w2_bytes = bytes;
+        int hbad = 0;
+        HIP_TRY(hipMemsetAsync(bad.p, 0, sizeof(int), st));
+        HIP_TRY(tcsc::w2_from_tcsc(csp, csn, rip, rin, col_begin, ncols, rows, plan->w2, bad.as<int>(), st));
+        HIP_TRY(hipMemcpyAsync(&hbad, bad.p, sizeof(int), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if (hbad) {
+            set_error("%s: W is not ternary: a position's summed weight is outside {-1, 0, +1} (a duplicated index)", who);
+            return TCSC_E_ARG;
+        }
+    }
+    *out = plan.release();
+    return TCSC_OK;
+}
+
+}  // namespace
+
 extern "C" {
 
 int tcsc_gpu_device_count(void) { return device_count_raw(); }
@@ -1281,6 +1397,118 @@ int tcsc_gpu_plan_create_device(int rows, int cols, const int* d_csp, const int*
     return rc;
 }
 
+int tcsc_gpu_plan_create_packed(const tcsc_t* W, int col_begin, int col_end, int device, void* stream,
+                                tcsc_gpu_plan** out) {
+    const char* who = "tcsc_gpu_plan_create_packed";
+    if (!W || !out || col_begin < 0 || col_end > W->cols || col_begin > col_end) {
+        set_error("%s: bad arguments", who);
+        return TCSC_E_ARG;
+    }
+    *out = nullptr;
+    int rc = packed_args_ok(who, W->rows);
+    if (rc != TCSC_OK) return rc;
+    // ranges and rows as tcsc_gpu_plan_create checks them; the order inside a column does not reach the image
+    std::vector<int> unused;
+    rc = check_index_host(W->col_start_pos, W->row_index_pos, col_begin, col_end, W->rows, W->n_elem_pos, "pos", unused);
+    if (rc == TCSC_OK)
+        rc = check_index_host(W->col_start_neg, W->row_index_neg, col_begin, col_end, W->rows, W->n_elem_neg, "neg",
+                              unused);
+    if (rc != TCSC_OK) return rc;
+    DeviceGuard dg(device);
+    if (!dg.ok()) {
+        set_error("%s: cannot select device %d", who, device);
+        return TCSC_E_NODEV;
+    }
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int nc = col_end - col_begin;
+    const int p0 = W->col_start_pos[col_begin], p1 = W->col_start_pos[col_end];
+    const int q0 = W->col_start_neg[col_begin], q1 = W->col_start_neg[col_end];
+    std::vector<int> csp(nc + 1), csn(nc + 1);  // the column slice, rebased to 0
+    for (int j = 0; j <= nc; ++j) {
+        csp[j] = W->col_start_pos[col_begin + j] - p0;
+        csn[j] = W->col_start_neg[col_begin + j] - q0;
+    }
+    DevBuf dcsp, dcsn, drip, drin;  // upload scratch, freed on return
+    HIP_TRY(dcsp.alloc((nc + 1) * sizeof(int)));
+    HIP_TRY(dcsn.alloc((nc + 1) * sizeof(int)));
+    HIP_TRY(drip.alloc((size_t)(p1 - p0) * sizeof(int)));
+    HIP_TRY(drin.alloc((size_t)(q1 - q0) * sizeof(int)));
+    HIP_TRY(hipMemcpyAsync(dcsp.p, csp.data(), (nc + 1) * sizeof(int), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(dcsn.p, csn.data(), (nc + 1) * sizeof(int), hipMemcpyHostToDevice, st));
+    if (p1 > p0)
+        HIP_TRY(hipMemcpyAsync(drip.p, W->row_index_pos + p0, (size_t)(p1 - p0) * sizeof(int), hipMemcpyHostToDevice, st));
+    if (q1 > q0)
+        HIP_TRY(hipMemcpyAsync(drin.p, W->row_index_neg + q0, (size_t)(q1 - q0) * sizeof(int), hipMemcpyHostToDevice, st));
+    rc = build_packed(who, W->rows, 0, nc, p1 - p0, q1 - q0, dcsp.as<int>(), dcsn.as<int>(), drip.as<int>(),
+                      drin.as<int>(), device, st, out);
+    if (rc == TCSC_OK) (*out)->col_begin = col_begin;
+    return rc;
+}
+
+int tcsc_gpu_plan_create_packed_device(int rows, int cols, const int* d_csp, const int* d_csn, const int* d_rip,
+                                       const int* d_rin, int col_begin, int col_end, int device, void* stream,
+                                       tcsc_gpu_plan** out) {
+    const char* who = "tcsc_gpu_plan_create_packed_device";
+    if (!out || !d_csp || !d_csn || col_begin < 0 || col_end > cols || col_begin > col_end) {
+        set_error("%s: bad arguments", who);
+        return TCSC_E_ARG;
+    }
+    *out = nullptr;
+    const int rc = packed_args_ok(who, rows);
+    if (rc != TCSC_OK) return rc;
+    DeviceGuard dg(device);
+    if (!dg.ok()) {
+        set_error("%s: cannot select device %d", who, device);
+        return TCSC_E_NODEV;
+    }
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    int ends[4];
+    HIP_TRY(hipMemcpyAsync(&ends[0], d_csp + col_begin, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&ends[1], d_csp + col_end, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&ends[2], d_csn + col_begin, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&ends[3], d_csn + col_end, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    // tcsc_gpu_plan_create_device's check: a bad range or row is an error; columns out of order are fine here
+    const int nc = col_end - col_begin;
+    DevBuf flag;
+    HIP_TRY(flag.alloc(sizeof(int)));
+    HIP_TRY(hipMemsetAsync(flag.p, 0, sizeof(int), st));
+    HIP_TRY(tcsc::check_index_device(d_csp, d_rip, col_begin, nc, rows, ends[1], flag.as<int>(), st));
+    HIP_TRY(tcsc::check_index_device(d_csn, d_rin, col_begin, nc, rows, ends[3], flag.as<int>(), st));
+    int hflag = 0;
+    HIP_TRY(hipMemcpyAsync(&hflag, flag.p, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (hflag & 1) {
+        set_error("%s: a col_start range or a row index outside [0, %d)", who, rows);
+        return TCSC_E_ARG;
+    }
+    return build_packed(who, rows, col_begin, nc, ends[1] - ends[0], ends[3] - ends[2], d_csp, d_csn, d_rip, d_rin,
+                        device, st, out);
+}
+
+int tcsc_gpu_plan_is_packed(const tcsc_gpu_plan* p) {
+    if (!p) {
+        set_error("tcsc_gpu_plan_is_packed: NULL plan");
+        return 0;
+    }
+    return p->packed ? 1 : 0;
+}
+
+int tcsc_gpu_plan_copy_w2(const tcsc_gpu_plan* p, void* d_dst, size_t bytes, void* stream) {
+    if (!p) {
+        set_error("tcsc_gpu_plan_copy_w2: NULL plan");
+        return TCSC_E_ARG;
+    }
+    if (!p->w2 || bytes != p->w2_bytes || !d_dst) {
+        set_error("tcsc_gpu_plan_copy_w2: %s", !p->w2 ? "the plan has no 2-bit image"
+                                                      : !d_dst ? "NULL destination" : "bytes is not the image's size");
+        return TCSC_E_ARG;
+    }
+    DeviceGuard dg(p->device);
+    HIP_TRY(hipMemcpyAsync(d_dst, p->w2, bytes, hipMemcpyDeviceToDevice, static_cast<hipStream_t>(stream)));
+    return TCSC_OK;
+}
+
 int tcsc_gpu_plan_get_info(const tcsc_gpu_plan* p, tcsc_gpu_plan_info* info) {
     if (!p || !info) {
         set_error("tcsc_gpu_plan_get_info: NULL");
@@ -1298,7 +1526,7 @@ int tcsc_gpu_plan_get_info(const tcsc_gpu_plan* p, tcsc_gpu_plan_info* info) {
     info->device_bytes = p->bytes + p->ws_bytes + p->mfma_bytes + p->i8_bytes + p->w2_bytes + p->csc_bytes + p->tbias_bytes + p->wide_bytes +
                          (p->chain_pos ? p->chain_pos->bytes : 0) + (p->chain_neg ? p->chain_neg->bytes : 0);
     info->order = p->order;
-    info->mfma_min_M = p->wt ? p->mfma_min_M : 0;
+    info->mfma_min_M = (p->wt || p->packed) ? p->mfma_min_M : 0;  // packed: k_gemm8w2 from 17 rows
     return TCSC_OK;
 }
 
@@ -1332,7 +1560,7 @@ int tcsc_gpu_plan_reserve(tcsc_gpu_plan* p, int max_M) {
         return TCSC_E_ARG;
     }
     const size_t want = reserve_bytes(p, max_M);
-    if (!p->csync && p->rows > 0 && p->order == TCSC_ORDER_FAST) {
+    if (!p->csync && p->rows > 0 && p->order == TCSC_ORDER_FAST && !p->packed) {  // the gather's tile words
         DeviceGuard dg(p->device);
         HIP_TRY(hipMalloc(&p->csync, tcsc::kCombineBytes));
         HIP_TRY(hipMemset(p->csync, 0, tcsc::kCombineBytes));
@@ -1381,6 +1609,7 @@ static int launch_info_impl(const char* who, const tcsc_gpu_plan* p, int M, int*
         set_error("%s: bad arguments", who);
         return TCSC_E_ARG;
     }
+    if (dt != kI8 && refuse_packed(p, who)) return TCSC_E_ARG;
     const Route r = plan_route(p, M, dt);
     *path = r.path;
     *slices = r.slices;
@@ -1406,6 +1635,7 @@ int tcsc_gpu_launch_geometry(const tcsc_gpu_plan* p, int M, int* cols_per_wave) 
         set_error("tcsc_gpu_launch_geometry: bad arguments");
         return TCSC_E_ARG;
     }
+    if (refuse_packed(p, "tcsc_gpu_launch_geometry")) return TCSC_E_ARG;
     *cols_per_wave = 0;  // not a gather launch
     const Route r = plan_route(p, M, kF32, "tcsc_gpu_launch_geometry");
     if (r.path != TCSC_PATH_GATHER) return TCSC_OK;
@@ -1419,6 +1649,7 @@ int tcsc_gpu_launch_combine(const tcsc_gpu_plan* p, int M, int* in_launch) {
         set_error("tcsc_gpu_launch_combine: bad arguments");
         return TCSC_E_ARG;
     }
+    if (refuse_packed(p, "tcsc_gpu_launch_combine")) return TCSC_E_ARG;
     *in_launch = plan_route(p, M, kF32).combine;  // 0 off the gather path and where K is not split
     return TCSC_OK;
 }
@@ -1429,6 +1660,7 @@ int tcsc_gpu_launch_combine(const tcsc_gpu_plan* p, int M, int* in_launch) {
 // then run on it.
 static int sgemm_entry(const tcsc_gpu_plan* p, const void* dX, int dt, const float* dScale, const float* dB, float* dY,
                        int M, int ldy, int variant, float a, void* stream) {
+    if (dt != kI8 && refuse_packed(p, kXTypes[dt].sgemm)) return TCSC_E_ARG;
     if (p && M > 0 && p->cols > 0 && p->ws_bytes < wanted_workspace(p, M, dt)) {
         const int rc = tcsc_gpu_plan_reserve(const_cast<tcsc_gpu_plan*>(p), M);
         if (rc != TCSC_OK) return rc;
@@ -1575,6 +1807,7 @@ static int ensure_workspace(const tcsc_gpu_plan* p, int M) {
 }
 
 int tcsc_gpu_prepare_x(const tcsc_gpu_plan* p, const float* dX, int M, void* stream) {
+    if (refuse_packed(p, "tcsc_gpu_prepare_x")) return TCSC_E_ARG;
     int rc = ensure_workspace(p, M);
     if (rc != TCSC_OK) return rc;
     if (p) const_cast<tcsc_gpu_plan*>(p)->staged_M = -1;
@@ -1585,6 +1818,7 @@ int tcsc_gpu_prepare_x(const tcsc_gpu_plan* p, const float* dX, int M, void* str
 
 int tcsc_gpu_sgemm_prepared(const tcsc_gpu_plan* p, const float* dB, float* dY, int M, int ldy, int variant, float a,
                             void* stream) {
+    if (refuse_packed(p, "tcsc_gpu_sgemm_prepared")) return TCSC_E_ARG;
     const int rc = ensure_workspace(p, M);  // a reallocation drops the staged X
     if (rc != TCSC_OK) return rc;
     // the gather reads X^T with the pitch of the M it was staged for
@@ -1928,6 +2162,7 @@ int tcsc_gpu_sgemm_t(const tcsc_gpu_plan* tplan, const float* dG, float* dDX, in
         set_error("tcsc_gpu_sgemm_t: NULL plan");
         return TCSC_E_ARG;
     }
+    if (refuse_packed(tplan, "tcsc_gpu_sgemm_t")) return TCSC_E_ARG;
     if (!tplan->tbias) {
         set_error("tcsc_gpu_sgemm_t: not a transposed plan (tcsc_gpu_plan_create_transposed*)");
         return TCSC_E_ARG;

@@ -67,6 +67,60 @@ __global__ void __launch_bounds__(256) k_w2_from(const int8_t* __restrict__ W8, 
     }
 }
 
+// The 2-bit image straight from the TCSC arrays (packed plans):
+// no bf16 and no int8 image in between.  One workgroup per column tile and
+// group of kW2BuildKb 256-k blocks: it adds the weights of its 16 columns x
+// 1024 k into LDS counters (integer atomics: a +1 and a -1 at one position
+// cancel, a duplicate shows as +-2, and no order of execution reaches the
+// result), 16 threads per column walking that column's two index lists, then
+// packs the counters in k_w2_from's bit layout.  Every workgroup of a column
+// tile walks the whole columns (they need not be sorted), so the index arrays
+// are read ceil(K / 1024) times, mostly from the L2; a build-time kernel.
+constexpr int kW2BuildKb = 4;
+constexpr int kW2BuildK = kW2BuildKb * kW2Blk;
+__global__ void __launch_bounds__(256) k_w2_from_tcsc(const int* __restrict__ csp, const int* __restrict__ csn,
+                                                     const int* __restrict__ rip, const int* __restrict__ rin,
+                                                     int col_begin, int ncols, int K, int nkb, int nkg,
+                                                     uint32_t* __restrict__ W2, int* __restrict__ bad) {
+    __shared__ int w[kW2BuildK * kW2Cols];  // [k - k0][column of the tile]
+    const int t = blockIdx.x / nkg, kg = blockIdx.x % nkg;
+    const int k0 = kg * kW2BuildK;
+    for (int i = threadIdx.x; i < kW2BuildK * kW2Cols; i += 256) w[i] = 0;
+    __syncthreads();
+    const int c = threadIdx.x >> 4, sub = threadIdx.x & 15, col = kW2Cols * t + c;
+    if (col < ncols) {
+#pragma unroll
+        for (int sign = 0; sign < 2; ++sign) {
+            const int* cs = sign ? csn : csp;
+            const int* ri = sign ? rin : rip;
+            const int e1 = cs[col_begin + col + 1];
+            for (int e = cs[col_begin + col] + sub; e < e1; e += 16) {
+                const int k = ri[e];
+                if (k < 0 || k >= K)
+                    *bad = 1;
+                else if (k >= k0 && k < k0 + kW2BuildK)
+                    atomicAdd(&w[(k - k0) * kW2Cols + c], sign ? -1 : 1);
+            }
+        }
+    }
+    __syncthreads();
+    // thread = dword of a tile: lane l = tid >> 2, step i = tid & 3 (k_w2_from's indexing)
+    const int l = threadIdx.x >> 2, i = threadIdx.x & 3;
+    for (int b = 0; b < kW2BuildKb; ++b) {
+        const int kb = kW2BuildKb * kg + b;
+        if (kb >= nkb) break;
+        const int* src = w + (kW2Blk * b + 64 * i + 16 * (l >> 4)) * kW2Cols + (l & 15);
+        uint32_t p = 0;
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+            const int v = src[j * kW2Cols];  // 0 past K and past the last column: code 1
+            if (v < -1 || v > 1) *bad = 1;
+            p |= (uint32_t)((v + 1) & 3) << (8 * (j & 3) + 2 * (j >> 2));
+        }
+        W2[((size_t)t * nkb + kb) * 256 + threadIdx.x] = p;
+    }
+}
+
 // k_decode8.  Grid: ceil(col tiles / T) workgroups of kDecWaves waves.  Wave w
 // takes the 256-k blocks w, w + 8, ...: of each it loads the X fragments once
 // (4 x 16 B per lane: row l & 15, k quarter l >> 4; rows >= M and k >= K are
@@ -191,6 +245,18 @@ hipError_t decode_build_w2(const int8_t* w8, int ncols, int K, int ld8, uint32_t
     const size_t blocks = (dwords + 255) / 256;
     hipLaunchKernelGGL(k_w2_from, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, st, w8, ncols, K, ld8,
                        nkb, dwords, w2, bad);
+    return hipGetLastError();
+}
+
+hipError_t w2_from_tcsc(const int* csp, const int* csn, const int* rip, const int* rin, int col_begin, int ncols, int K,
+                        uint32_t* w2, int* bad, hipStream_t st) {
+    if (ncols <= 0 || K <= 0 || K >= kDecodeMaxK || col_begin < 0 || !csp || !csn || !w2 || !bad)
+        return hipErrorInvalidValue;
+    const int nkb = w2_kblocks(K), nkg = (nkb + kW2BuildKb - 1) / kW2BuildKb;
+    const long long blocks = (long long)w2_col_tiles(ncols) * nkg;
+    if (blocks > 0x7fffffffLL) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_w2_from_tcsc, dim3((unsigned)blocks), dim3(256), 0, st, csp, csn, rip, rin, col_begin, ncols, K,
+                       nkb, nkg, w2, bad);
     return hipGetLastError();
 }
 

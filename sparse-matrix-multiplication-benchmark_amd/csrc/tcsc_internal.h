@@ -446,6 +446,18 @@ inline size_t w2_image_bytes(int K, int N) { return (size_t)w2_col_tiles(N) * w2
 // k_w2_from: the 2-bit image from the int8 one (ncols x ld8); *bad = 1 when a
 // weight is not -1, 0 or +1
 hipError_t decode_build_w2(const int8_t* w8, int ncols, int K, int ld8, uint32_t* w2, int* bad, hipStream_t st);
+// k_w2_from_tcsc: the same image, byte for byte, straight from the TCSC arrays
+// of columns [col_begin, col_begin + ncols) (absolute offsets, any order inside
+// a column; a +1 and a -1 at one position cancel).  *bad = 1 for a row outside
+// [0, K) or a position whose summed weight is not -1, 0 or +1.  Integer adds in
+// the LDS only: no order of execution shows in the image.
+hipError_t w2_from_tcsc(const int* csp, const int* csn, const int* rip, const int* rin, int col_begin, int ncols, int K,
+                        uint32_t* w2, int* bad, hipStream_t st);
+// k_gemm8w2 (tcsc_mfma.hip): mfma8_gemm with B read from the
+// 2-bit image; the same tiles, K split (mfma8_slices), slabs and bits
+hipError_t mfma8_gemm_w2(const int8_t* x8, const uint32_t* w2, int ld8, int K, int M, int N, const float* scale,
+                         const float* B, float* Y, int ldy, bool prelu, float a, int* slabs, size_t slab_bytes,
+                         hipStream_t st);
 // column tiles per workgroup of a k_decode8 launch (1, 2 or 4)
 int decode_tiles_per_wg(int M, int N, int num_cus);
 // k_decode8: Y = act(fl(fl(float(S) * scale[m]) + B[j])) for m < M <= 16, S the

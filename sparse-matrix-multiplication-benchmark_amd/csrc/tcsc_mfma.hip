@@ -1019,6 +1019,184 @@ __global__ void __launch_bounds__(WM * WN * 64) k_gemm8(const int8_t* __restrict
                                                                        out, ldy, a);
 }
 
+// k_gemm8w2: k_gemm8 with the B operand read from the 2-bit
+// image of W (tcsc_internal.h, "int8 decode path") instead of the int8 one.
+// Only shapes of one wave row (WM = 1): every wave owns its FJ column tiles
+// privately, so B never passes through the LDS.  The image is fragment-major:
+// the 8 bytes at 16 lane + 8 (blk & 1) of tile (t, blk >> 1) are this lane's two
+// B fragments of the 128-k block blk (dword kh = half kh), with the lane -> k
+// map of the A fragments.  They are loaded straight into VGPRs two blocks
+// ahead, at the point where k_gemm8 issues its B DMA, and expanded in
+// registers: int8 dword d is (p >> 2d) & 0x03030303, and the codes c = w + 1
+// become signed bytes by one v_perm_b32 that takes each code as the selector
+// into the bytes ff, 00, 01 (codes 0, 1, 2 -> -1, 0, +1: a shift, a mask and
+// a permute per dword, four fewer VALU per fragment than the arithmetic form
+// ((c | 0x80..) - 0x01..) ^ 0x80..), so the MFMAs give S = sum q w itself: no
+// row sums, nothing to correct under split K, and the padding code 1 is a
+// weight 0.  A (X8), its DMA ring, the swizzle, the half-step pipeline and the
+// epilogue are k_gemm8's.  A workgroup's column tiles past the matrix read the
+// last tile again and are not stored; an odd count of 128-k blocks ends the
+// loop inside the last 256-k image block, whose second half is never read.
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+
+__device__ __forceinline__ i32x4 w2_frag(uint32_t p) {
+    i32x4 b;
+#pragma unroll
+    for (int d = 0; d < 4; ++d) {
+        const uint32_t c = (p >> (2 * d)) & 0x03030303u;  // selectors 0 .. 2: bytes 0 .. 2 of the table
+        b[d] = (int)__builtin_amdgcn_perm(0x000100ffu, 0x000100ffu, c);
+    }
+    return b;
+}
+
+template <int WN, int FI, int FJ, bool PRELU, bool PARTIAL, int BS = 2>
+__global__ void __launch_bounds__(WN * 64) k_gemm8w2(const int8_t* __restrict__ A, const uint32_t* __restrict__ W2,
+                                                    int ldk, int M, int N, int nblk, int nkb, int ntiles,
+                                                    const float* __restrict__ scale, const float* __restrict__ bias,
+                                                    float* __restrict__ Y, int ldy, float a, int tiles_m, int tiles_n,
+                                                    int gm, int bps) {
+    static_assert(!(PARTIAL && PRELU), "a partial slab carries raw sums");
+    constexpr int TM = FI * 16, TN = WN * FJ * 16, NW = WN;
+    constexpr int PA = TM / 8, ASLOT = PA * 1024, PAW = PA / NW;
+    static_assert(PA % NW == 0, "whole pieces per wave");
+    // the A ring, or the epilogue's staging (64 rows of TN + 4 ints) where that is larger
+    constexpr int STG = 64 * (TN + 4) * 4, LDSB = 2 * ASLOT > STG ? 2 * ASLOT : STG;
+    __shared__ __attribute__((aligned(1024))) char lds[LDSB];
+
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+
+    int m0, n0;
+    gemm3_tile<TM, TN>(tiles_m, tiles_n, gm, m0, n0);
+
+    const int row_in = lane >> 3, gsel = (lane & 7) ^ row_in;
+    uint32_t offa[PAW];
+#pragma unroll
+    for (int i = 0; i < PAW; ++i)
+        offa[i] = (uint32_t)(min(8 * (wave * PAW + i) + row_in, M - 1 - m0) * ldk + 16 * gsel);
+    const char* abase = reinterpret_cast<const char*>(A + (size_t)m0 * ldk);
+    auto dma_a = [&](int blk, int slot) {
+        const char* g = abase + (size_t)kMfma8Blk * blk;
+#pragma unroll
+        for (int i = 0; i < PAW; ++i)
+            __builtin_amdgcn_global_load_lds(reinterpret_cast<const void*>(g + offa[i]),
+                                             (__attribute__((address_space(3))) void*)(lds + slot * ASLOT +
+                                                                                       (wave * PAW + i) * 1024),
+                                             16, 0, 0);
+    };
+    // this wave's column tiles, clamped into the image: a uniform base and uniform tile offsets (a column tile is
+    // nkb KiB, below 2^24 bytes), so a lane adds only its own 16 lane
+    const int tile0 = min(n0 / kW2Cols + wave * FJ, ntiles - 1);
+    const char* wbase = reinterpret_cast<const char*>(W2) + (size_t)tile0 * nkb * kW2TileBytes;
+    uint32_t toff[FJ];
+#pragma unroll
+    for (int j = 0; j < FJ; ++j) toff[j] = (uint32_t)(min(tile0 + j, ntiles - 1) - tile0) * nkb * kW2TileBytes;
+    auto load_b = [&](int blk, u32x2 (&q)[FJ]) {  // blk < nblk, so blk >> 1 < nkb
+        const uint32_t boff = (uint32_t)(blk >> 1) * kW2TileBytes + 8 * (blk & 1);
+#pragma unroll
+        for (int j = 0; j < FJ; ++j) q[j] = *reinterpret_cast<const u32x2*>(wbase + (toff[j] + boff) + 16 * lane);
+    };
+
+    int foff[2];
+#pragma unroll
+    for (int kh = 0; kh < 2; ++kh)
+        foff[kh] = ((lane & 15) >> 3) * 1024 + 16 * (8 * (lane & 7) + ((4 * kh + (lane >> 4)) ^ (lane & 7)));
+
+    i32x4 acc[FI][FJ];
+#pragma unroll
+    for (int i = 0; i < FI; ++i)
+#pragma unroll
+        for (int j = 0; j < FJ; ++j) acc[i][j] = i32x4{0, 0, 0, 0};
+
+    // BS = 2: the expanded fragments of the two half steps in sets of their own, as the A fragments; BS = 1 (the
+    // 8-wave shape, whose two waves per SIMD leave 256 registers each): one set, expanded between the MFMA groups
+    static_assert(BS == 1 || BS == 2, "one or two sets of B fragments");
+    i32x4 af[2][FI], bfr[BS][FJ];
+    // The image dwords of two consecutive 128-k blocks, ping-pong: a round reads the second dword of its own
+    // block, then loads the block after next into the same registers, so nothing is copied from round to round.
+    // These are ordinary loads that the compiler counts, and it cannot see the explicit waits below: with a
+    // register rotation in the loop it waited for each block's loads right after issuing them, and it sank the
+    // prologue's loads behind the first barrier.  landed() takes the registers just ahead of the first wait,
+    // which keeps the prologue's loads in front of it.
+    u32x2 qa[FJ], qb[FJ];
+    auto landed = [&](u32x2 (&v)[FJ]) {
+#pragma unroll
+        for (int j = 0; j < FJ; ++j) asm volatile("" : "+v"(v[j]));
+    };
+    auto frag_a = [&](int set, int aslot, int kh) {
+        const char* sa = lds + aslot * ASLOT;
+#pragma unroll
+        for (int i = 0; i < FI; ++i) af[set][i] = *reinterpret_cast<const i32x4*>(sa + (i * 2) * 1024 + foff[kh]);
+    };
+    auto frag_b = [&](int set, const u32x2 (&q)[FJ], int kh) {
+#pragma unroll
+        for (int j = 0; j < FJ; ++j) bfr[set % BS][j] = w2_frag(q[j][kh]);
+    };
+    auto mma = [&](int set) {
+#pragma unroll
+        for (int i = 0; i < FI; ++i)
+#pragma unroll
+            for (int j = 0; j < FJ; ++j)
+                acc[i][j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(af[set][i], bfr[set % BS][j], acc[i][j], 0, 0, 0);
+    };
+    // one A read per MFMA pair, as k_gemm8 pins them; the expansion's VALU is left to the scheduler
+    constexpr int NM = FI * FJ, NR = FI;
+    static_assert(2 * NR <= NM, "one read per MFMA pair");
+    auto pin = [&]() {
+#pragma unroll
+        for (int k = 0; k < NR; ++k) {
+            __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);  // MFMA
+            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);  // DS read
+        }
+        if constexpr (NM > 2 * NR) __builtin_amdgcn_sched_group_barrier(0x008, NM - 2 * NR, 0);
+        __builtin_amdgcn_sched_barrier(0);
+    };
+    // this workgroup's 128-k blocks (the host makes every slice non-empty)
+    const int b0 = PARTIAL ? (int)blockIdx.y * bps : 0;
+    const int b1 = PARTIAL ? min(nblk, b0 + bps) : nblk;
+    const int last = b1 - 1;
+    dma_a(b0, 0);
+    load_b(b0, qa);
+    load_b(min(b0 + 1, last), qb);
+    landed(qa);
+    landed(qb);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    dma_a(min(b0 + 1, last), 1);
+    frag_b(0, qa, 0);
+    frag_a(0, 0, 0);
+    // one 128-k block: qc holds its image dwords, qn the next block's; sl is its A slot
+    auto round = [&](int blk, int sl, u32x2 (&qc)[FJ], const u32x2 (&qn)[FJ]) {
+        if constexpr (BS == 2) frag_b(1, qc, 1);
+        frag_a(1, sl, 1);
+        mma(0);
+        pin();
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+        __builtin_amdgcn_sched_barrier(0);
+        const int nxt = min(blk + 2, last);  // uniform; the tail reloads the last block
+        dma_a(nxt, sl);
+        if constexpr (BS == 1) frag_b(1, qc, 1);  // the one set is free once mma(0) is issued
+        load_b(nxt, qc);
+        if constexpr (BS == 2) frag_b(0, qn, 0);  // block blk + 1 (the tail's extra fragments are discarded)
+        frag_a(0, sl ^ 1, 0);
+        mma(1);
+        pin();
+        if constexpr (BS == 1) frag_b(0, qn, 0);
+    };
+    int blk = b0;
+    for (; blk + 1 < b1; blk += 2) {
+        round(blk, 0, qa, qb);
+        round(blk + 1, 1, qb, qa);
+    }
+    if (blk < b1) round(blk, 0, qa, qb);  // an odd count of blocks (uniform)
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+
+    float* out = PARTIAL ? reinterpret_cast<float*>(reinterpret_cast<int*>(Y) + (size_t)blockIdx.y * M * ldy) : Y;
+    gemm8_store<1, WN, FI, FJ, PRELU, PARTIAL, LDSB>(acc, lds, lane, 0, wave, m0, n0, M, N, scale, bias, out, ldy, a);
+}
+
 // tcsc_gpu_quantize_rows_i8: per row, amax = max |x|, scale = amax / 127, inv
 // = 127 / amax, q = clamp(rint(x * inv), -127, 127); amax = 0: q = 0, scale =
 // 0.  Every step is one correctly rounded fp32 operation.  One workgroup per
@@ -1328,6 +1506,22 @@ hipError_t quantize_rows_i8(const float* X, int M, int K, int8_t* Xq, float* sca
     return hipGetLastError();
 }
 
+// k_reduce_i8 on the slabs of a split int8 GEMM (k_gemm8 or k_gemm8w2)
+template <bool PRELU>
+static hipError_t launch_reduce_i8(const int* slabs, int slices, int M, int N, const float* scale, const float* B,
+                                   float* Y, int ldy, float a, hipStream_t st) {
+    const bool vec = N % 4 == 0 && ldy % 4 == 0 &&
+                     ((reinterpret_cast<uintptr_t>(Y) | reinterpret_cast<uintptr_t>(slabs)) & 15) == 0;
+    const long long n = (long long)M * (vec ? N / 4 : N);
+    if (vec)
+        hipLaunchKernelGGL((k_reduce_i8<PRELU, true>), dim3(grid_of(n, 256)), dim3(256), 0, st, slabs, slices, M, N, scale,
+                           B, Y, ldy, a);
+    else
+        hipLaunchKernelGGL((k_reduce_i8<PRELU, false>), dim3(grid_of(n, 256)), dim3(256), 0, st, slabs, slices, M, N, scale,
+                           B, Y, ldy, a);
+    return hipGetLastError();
+}
+
 template <bool PRELU>
 static hipError_t launch_gemm8_t(const int8_t* x8, const int8_t* w8, int ld8, int nblk, int M, int N,
                                  const float* scale, const float* B, float* Y, int ldy, float a, int* slabs,
@@ -1364,16 +1558,50 @@ static hipError_t launch_gemm8_t(const int8_t* x8, const int8_t* w8, int ld8, in
     }
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess || slices <= 1) return e;
-    const bool vec = N % 4 == 0 && ldy % 4 == 0 &&
-                     ((reinterpret_cast<uintptr_t>(Y) | reinterpret_cast<uintptr_t>(slabs)) & 15) == 0;
-    const long long n = (long long)M * (vec ? N / 4 : N);
-    if (vec)
-        hipLaunchKernelGGL((k_reduce_i8<PRELU, true>), dim3(grid_of(n, 256)), dim3(256), 0, st, slabs, slices, M, N, scale,
-                           B, Y, ldy, a);
-    else
-        hipLaunchKernelGGL((k_reduce_i8<PRELU, false>), dim3(grid_of(n, 256)), dim3(256), 0, st, slabs, slices, M, N, scale,
-                           B, Y, ldy, a);
-    return hipGetLastError();
+    return launch_reduce_i8<PRELU>(slabs, slices, M, N, scale, B, Y, ldy, a, st);
+}
+
+// k_gemm8w2 on k_gemm8's three grids, slices and blocks per slice: 128 x 512
+// (8 waves of 128 x 64), 64 x 256 (4 waves of 64 x 64) and 128 x 128 (4 waves
+// of 128 x 32), so mfma_tiles and mfma8_slices count its workgroups as they are.
+template <bool PRELU>
+static hipError_t launch_gemm8w2_t(const int8_t* x8, const uint32_t* w2, int ld8, int nblk, int K, int M, int N,
+                                   const float* scale, const float* B, float* Y, int ldy, float a, int* slabs,
+                                   int slices, hipStream_t st) {
+    constexpr int kGm = 4;
+    float* sl = reinterpret_cast<float*>(slabs);
+    const int bps = (nblk + slices - 1) / std::max(slices, 1);
+    const int nkb = w2_kblocks(K), nt = w2_col_tiles(N);
+    if (mfma_big_tiles(M, N)) {
+        const int tm = (M + 127) / 128, tn = (N + 511) / 512;
+        const int gm = std::min(kGm, tm);
+        if (slices <= 1)
+            hipLaunchKernelGGL((k_gemm8w2<8, 8, 4, PRELU, false, 1>), dim3(tm * tn), dim3(512), 0, st, x8, w2, ld8, M, N, nblk,
+                               nkb, nt, scale, B, Y, ldy, a, tm, tn, gm, nblk);
+        else
+            hipLaunchKernelGGL((k_gemm8w2<8, 8, 4, false, true, 1>), dim3(tm * tn, slices), dim3(512), 0, st, x8, w2, ld8, M,
+                               N, nblk, nkb, nt, nullptr, nullptr, sl, N, 0.0f, tm, tn, gm, bps);
+    } else if (mfma_narrow_tiles(M, N)) {
+        const int tn = (N + 255) / 256;
+        if (slices <= 1)
+            hipLaunchKernelGGL((k_gemm8w2<4, 4, 4, PRELU, false>), dim3(tn), dim3(256), 0, st, x8, w2, ld8, M, N, nblk, nkb,
+                               nt, scale, B, Y, ldy, a, 1, tn, 1, nblk);
+        else
+            hipLaunchKernelGGL((k_gemm8w2<4, 4, 4, false, true>), dim3(tn, slices), dim3(256), 0, st, x8, w2, ld8, M, N,
+                               nblk, nkb, nt, nullptr, nullptr, sl, N, 0.0f, 1, tn, 1, bps);
+    } else {
+        const int tm = (M + 127) / 128, tn = (N + 127) / 128;
+        const int gm = std::min(kGm, tm);
+        if (slices <= 1)
+            hipLaunchKernelGGL((k_gemm8w2<4, 8, 2, PRELU, false>), dim3(tm * tn), dim3(256), 0, st, x8, w2, ld8, M, N, nblk,
+                               nkb, nt, scale, B, Y, ldy, a, tm, tn, gm, nblk);
+        else
+            hipLaunchKernelGGL((k_gemm8w2<4, 8, 2, false, true>), dim3(tm * tn, slices), dim3(256), 0, st, x8, w2, ld8, M,
+                               N, nblk, nkb, nt, nullptr, nullptr, sl, N, 0.0f, tm, tn, gm, bps);
+    }
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess || slices <= 1) return e;
+    return launch_reduce_i8<PRELU>(slabs, slices, M, N, scale, B, Y, ldy, a, st);
 }
 
 hipError_t mfma8_gemm(const int8_t* x8, const int8_t* w8, int ld8, int K, int M, int N, const float* scale,
@@ -1386,6 +1614,18 @@ hipError_t mfma8_gemm(const int8_t* x8, const int8_t* w8, int ld8, int K, int M,
     if (slices > 1 && (!slabs || slab_bytes < mfma8_slab_bytes(M, N, K))) return hipErrorInvalidValue;
     return prelu ? launch_gemm8_t<true>(x8, w8, ld8, nblk, M, N, scale, B, Y, ldy, a, slabs, slices, st)
                  : launch_gemm8_t<false>(x8, w8, ld8, nblk, M, N, scale, B, Y, ldy, a, slabs, slices, st);
+}
+
+hipError_t mfma8_gemm_w2(const int8_t* x8, const uint32_t* w2, int ld8, int K, int M, int N, const float* scale,
+                         const float* B, float* Y, int ldy, bool prelu, float a, int* slabs, size_t slab_bytes,
+                         hipStream_t st) {
+    if (M <= 0 || N <= 0) return hipSuccess;
+    const int nblk = mfma8_nblk(K);
+    if (nblk < 1 || ld8 != mfma8_ldw(K) || K >= kDecodeMaxK || !w2) return hipErrorInvalidValue;
+    const int slices = mfma8_slices(M, N, K);
+    if (slices > 1 && (!slabs || slab_bytes < mfma8_slab_bytes(M, N, K))) return hipErrorInvalidValue;
+    return prelu ? launch_gemm8w2_t<true>(x8, w2, ld8, nblk, K, M, N, scale, B, Y, ldy, a, slabs, slices, st)
+                 : launch_gemm8w2_t<false>(x8, w2, ld8, nblk, K, M, N, scale, B, Y, ldy, a, slabs, slices, st);
 }
 
 }  // namespace tcsc

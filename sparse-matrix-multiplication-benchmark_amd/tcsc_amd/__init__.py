@@ -52,6 +52,8 @@ EXPORTED_SYMBOLS = (
     "tcsc_gpu_quantize_rows_i8", "tcsc_gpu_workspace_bound_i8",
     "tcsc_gpu_plan_enable_w2", "tcsc_gpu_plan_has_w2", "tcsc_gpu_w2_image_bytes", "tcsc_gpu_decode_pays",
     "tcsc_gpu_launch_geometry", "tcsc_gpu_wide_pays",
+    "tcsc_gpu_plan_create_packed", "tcsc_gpu_plan_create_packed_device", "tcsc_gpu_plan_is_packed",
+    "tcsc_gpu_plan_copy_w2",
     # include/sparse/bcsr.h
     "bcsr_from_dense", "bcsr_sgemm_basic", "bcsr_sgemm_prelu_basic", "bcsr_sgemm_avx", "bcsr_sgemm_prelu_avx",
     "bcsr_sgemm_avx2", "bcsr_free",
@@ -163,6 +165,10 @@ def lib():
     L.tcsc_gpu_plan_has_w2.argtypes = [vp]
     L.tcsc_gpu_w2_image_bytes.argtypes = [i, i, C.POINTER(C.c_size_t)]
     L.tcsc_gpu_decode_pays.argtypes = [i, i, i, C.c_longlong]
+    L.tcsc_gpu_plan_create_packed.argtypes = [P, i, i, i, vp, C.POINTER(vp)]
+    L.tcsc_gpu_plan_create_packed_device.argtypes = [i, i, vp, vp, vp, vp, i, i, i, vp, C.POINTER(vp)]
+    L.tcsc_gpu_plan_is_packed.argtypes = [vp]
+    L.tcsc_gpu_plan_copy_w2.argtypes = [vp, vp, C.c_size_t, vp]
     L.tcsc_gpu_prepare_x.argtypes = [vp, vp, i, vp]
     L.tcsc_gpu_sgemm_prepared.argtypes = [vp, vp, vp, i, i, i, f, vp]
     L.tcsc_gpu_from_dense.argtypes = [vp, i, i, vp, vp, vp, vp, C.POINTER(i), C.POINTER(i), vp]
@@ -504,6 +510,50 @@ class Plan:
                "tcsc_gpu_plan_create_transposed_device")
         self.handle = h
         return self
+
+    @classmethod
+    def packed(cls, W: TcscMatrix, col_begin: int = 0, col_end: int | None = None, device: int = 0,
+               stream: int = 0) -> "Plan":
+        """A packed plan of W[:, col_begin:col_end] (tcsc_gpu_plan_create_packed): the 2-bit image and nothing
+        else of W, a quarter byte per weight.  Only :meth:`sgemm_i8` runs on it -- k_decode8 up to 16 rows,
+        k_gemm8w2 above -- with the bits of an ordinary plan's int8 MFMA path; every other call raises.
+        TcscError when W is not ternary (a duplicated index), K >= 2^22, or the reference order is set."""
+        if not getattr(W, "ptr", None):
+            raise TcscError("W is freed or not a TcscMatrix")
+        self = cls.__new__(cls)
+        col_end = W.cols if col_end is None else col_end
+        h = C.c_void_p()
+        _check(lib().tcsc_gpu_plan_create_packed(W.ptr, col_begin, col_end, device, C.c_void_p(stream), C.byref(h)),
+               "tcsc_gpu_plan_create_packed")
+        self.handle = h
+        return self
+
+    @classmethod
+    def packed_from_device(cls, rows, cols, csp, csn, rip, rin, col_begin=0, col_end=None, device=0,
+                           stream=0) -> "Plan":
+        """Same from W's TCSC arrays on the device (tcsc_gpu_plan_create_packed_device)."""
+        self = cls.__new__(cls)
+        col_end = cols if col_end is None else col_end
+        h = C.c_void_p()
+        _check(lib().tcsc_gpu_plan_create_packed_device(rows, cols, C.c_void_p(_ptr(csp)), C.c_void_p(_ptr(csn)),
+                                                        C.c_void_p(_ptr(rip)), C.c_void_p(_ptr(rin)), col_begin,
+                                                        col_end, device, C.c_void_p(stream), C.byref(h)),
+               "tcsc_gpu_plan_create_packed_device")
+        self.handle = h
+        return self
+
+    @property
+    def is_packed(self) -> bool:
+        return bool(lib().tcsc_gpu_plan_is_packed(self.handle))
+
+    def copy_w2(self, dst, nbytes: int | None = None, stream: int = 0) -> None:
+        """Copy the plan's 2-bit image (device to device, asynchronous on the stream) into dst: a contiguous
+        device tensor, whose size is passed as it is, or a pointer with nbytes (tcsc_gpu_plan_copy_w2).
+        TcscError on a plan without the image, or when the size is not w2_image_bytes(K, cols)."""
+        if nbytes is None:
+            nbytes = dst.numel() * dst.element_size() if hasattr(dst, "numel") else 0
+        _check(lib().tcsc_gpu_plan_copy_w2(self.handle, C.c_void_p(_ptr(dst)), int(nbytes), C.c_void_p(stream)),
+               "tcsc_gpu_plan_copy_w2")
 
     def info(self) -> dict:
         inf = plan_info_t()

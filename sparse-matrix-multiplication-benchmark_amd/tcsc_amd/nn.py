@@ -1,5 +1,8 @@
 """torch autograd layer over the TCSC device API.
 
+``PackedTernaryLinear`` is the inference-only layer on a packed plan (DESIGN.md
+§18): the 2-bit image of ``W`` alone, int8 activations quantized per row.
+
 ``TernaryLinear`` computes ``y = act(x . W + b)`` for a frozen ternary ``W``
 (K x N) held as a :class:`tcsc_amd.Plan`, and its backward: ``dZ`` and ``db`` by
 ``tcsc_gpu_prelu_backward``, ``dX = dZ . W^T`` by ``tcsc_gpu_sgemm_t`` on the
@@ -16,7 +19,7 @@ import numpy as np
 
 from . import Plan, TcscError, TcscMatrix, prelu_backward, quantize_rows_i8
 
-__all__ = ["TernaryLinear"]
+__all__ = ["TernaryLinear", "PackedTernaryLinear"]
 
 _classes = None
 
@@ -26,6 +29,28 @@ def _define():
 
     def _stream(device) -> int:
         return torch.cuda.current_stream(device).cuda_stream
+
+    def _ternary_matrix(W, who: str) -> TcscMatrix:
+        """W as the layers take it: a TcscMatrix (kept by reference) or a dense K x N of -1, 0, +1."""
+        if isinstance(W, TcscMatrix):
+            if not W.ptr:
+                raise TcscError(f"{who}: W is a freed TcscMatrix")
+            return W
+        Wd = W.detach().cpu().numpy() if torch.is_tensor(W) else np.asarray(W)
+        if Wd.ndim != 2:
+            raise TcscError(f"{who}: W must be 2-D (K x N), got shape {Wd.shape}")
+        Wd = np.ascontiguousarray(Wd, dtype=np.float32)
+        if not np.isin(Wd, (-1.0, 0.0, 1.0)).all():
+            raise TcscError(f"{who}: W must hold only -1, 0 and +1")
+        return TcscMatrix.from_dense(Wd)
+
+    def _bias_tensor(bias, n: int, dev, who: str):
+        if bias is None:
+            return torch.zeros(n, dtype=torch.float32, device=dev)
+        b = torch.as_tensor(bias).detach().to(device=dev, dtype=torch.float32).reshape(-1).clone()
+        if b.numel() != n:
+            raise TcscError(f"{who}: bias has {b.numel()} elements, W has N={n} columns")
+        return b
 
     class _TernaryLinearFn(torch.autograd.Function):
         """y = act(x . W + b) on an (M x K) contiguous fp32 or bf16 x (y is fp32 either way); W and `a`
@@ -90,29 +115,12 @@ def _define():
 
         def __init__(self, W, bias=None, a: float | None = None, device: int = 0):
             super().__init__()
-            if isinstance(W, TcscMatrix):
-                if not W.ptr:
-                    raise TcscError("TernaryLinear: W is a freed TcscMatrix")
-                self._W = W
-            else:
-                Wd = W.detach().cpu().numpy() if torch.is_tensor(W) else np.asarray(W)
-                if Wd.ndim != 2:
-                    raise TcscError(f"TernaryLinear: W must be 2-D (K x N), got shape {Wd.shape}")
-                Wd = np.ascontiguousarray(Wd, dtype=np.float32)
-                if not np.isin(Wd, (-1.0, 0.0, 1.0)).all():
-                    raise TcscError("TernaryLinear: W must hold only -1, 0 and +1")
-                self._W = TcscMatrix.from_dense(Wd)
+            self._W = _ternary_matrix(W, "TernaryLinear")
             self.in_features, self.out_features = self._W.rows, self._W.cols
             self.a = None if a is None else float(a)
             self.device_index = int(device)
             dev = torch.device("cuda", self.device_index)
-            if bias is None:
-                b = torch.zeros(self.out_features, dtype=torch.float32, device=dev)
-            else:
-                b = torch.as_tensor(bias).detach().to(device=dev, dtype=torch.float32).reshape(-1).clone()
-                if b.numel() != self.out_features:
-                    raise TcscError(f"TernaryLinear: bias has {b.numel()} elements, W has N={self.out_features} columns")
-            self.bias = torch.nn.Parameter(b)
+            self.bias = torch.nn.Parameter(_bias_tensor(bias, self.out_features, dev, "TernaryLinear"))
             self.plan = Plan(self._W, 0, self.out_features, self.device_index, _stream(dev))
             self.transposed_plan = None  # built by the first backward that needs dX, or by reserve()
             self._i8_rows, self._i8_xq, self._i8_scale = 0, None, None  # forward_int8's buffers
@@ -196,7 +204,68 @@ def _define():
         def extra_repr(self) -> str:
             return f"in_features={self.in_features}, out_features={self.out_features}, nnz={self._W.nnz}, a={self.a}"
 
-    return {"TernaryLinear": TernaryLinear}
+    class PackedTernaryLinear(torch.nn.Module):
+        """Inference-only ``y = act(scale * (q . W) + bias)`` on a packed plan (``Plan.packed``): of ``W`` the
+        layer holds the 2-bit image alone, a quarter byte per weight.
+
+        W, bias, a, device: as :class:`TernaryLinear` takes them; the bias is a buffer, not a parameter.
+        ``forward`` takes an fp32 CUDA tensor of shape (..., K), quantizes its rows to int8
+        (``tcsc_amd.quantize_rows_i8``) into buffers the layer keeps and calls ``Plan.sgemm_i8``: k_decode8 up
+        to 16 rows, k_gemm8w2 above -- the bits of ``TernaryLinear.forward_int8`` on the int8 MFMA path.
+        There is no backward and no transposed plan: it raises when grad is enabled and x requires grad.
+        """
+
+        def __init__(self, W, bias=None, a: float | None = None, device: int = 0):
+            super().__init__()
+            Wm = _ternary_matrix(W, "PackedTernaryLinear")  # only read here: the plan keeps no reference to it
+            self.in_features, self.out_features, self.nnz = Wm.rows, Wm.cols, Wm.nnz
+            self.a = None if a is None else float(a)
+            self.device_index = int(device)
+            dev = torch.device("cuda", self.device_index)
+            self.register_buffer("bias", _bias_tensor(bias, self.out_features, dev, "PackedTernaryLinear"))
+            self.plan = Plan.packed(Wm, 0, self.out_features, self.device_index, _stream(dev))
+            self._rows, self._xq, self._scale = 0, None, None
+
+        def _quant_buffers(self, rows: int):
+            if self._rows < rows:
+                dev = torch.device("cuda", self.device_index)
+                self._xq = torch.empty((rows, self.in_features), dtype=torch.int8, device=dev)
+                self._scale = torch.empty(rows, dtype=torch.float32, device=dev)
+                self._rows = rows
+            return self._xq, self._scale
+
+        def reserve(self, max_rows: int) -> None:
+            """The plan's workspace (X8 and the split-K slabs) and the quantization buffers for up to max_rows
+            rows: afterwards a forward allocates nothing but its output."""
+            self.plan.reserve(max_rows)
+            self._quant_buffers(max_rows)
+
+        def forward(self, x):
+            if not torch.is_tensor(x) or x.dtype != torch.float32 or not x.is_cuda:
+                raise TcscError("PackedTernaryLinear: x must be an fp32 CUDA tensor")
+            if torch.is_grad_enabled() and x.requires_grad:
+                raise TcscError("PackedTernaryLinear is inference only: x requires grad")
+            if x.device.index != self.device_index or self.bias.device != x.device:
+                raise TcscError(f"PackedTernaryLinear: x on {x.device}, bias on {self.bias.device}, plan on cuda:"
+                                f"{self.device_index}")
+            if x.dim() < 1 or x.shape[-1] != self.in_features:
+                raise TcscError(f"PackedTernaryLinear: x has shape {tuple(x.shape)}, expected (..., "
+                                f"{self.in_features})")
+            lead = x.shape[:-1]
+            x2 = x.detach().reshape(-1, self.in_features).contiguous()
+            M, K, N = x2.shape[0], self.in_features, self.out_features
+            xq, scale = self._quant_buffers(M)
+            stream = _stream(x.device)
+            y = torch.empty((M, N), dtype=torch.float32, device=x.device)
+            quantize_rows_i8(x2, xq, scale, M, K, stream)
+            variant, a = ("basic", 0.0) if self.a is None else ("prelu_basic", self.a)
+            self.plan.sgemm_i8(xq, scale, self.bias, y, M, N, variant, a, stream)
+            return y.reshape(*lead, N)
+
+        def extra_repr(self) -> str:
+            return f"in_features={self.in_features}, out_features={self.out_features}, nnz={self.nnz}, a={self.a}"
+
+    return {"TernaryLinear": TernaryLinear, "PackedTernaryLinear": PackedTernaryLinear}
 
 
 def __getattr__(name):
