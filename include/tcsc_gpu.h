@@ -461,9 +461,9 @@ int tcsc_gpu_decode_pays(int M, int K, int N, long long nnz);
  * of k_gemm8: the same route, slices, workspace and bits (the A/B on one plan;
  * unset or 0 changes nothing, and it is never a default).
  *
- * Out of scope: loading a packed plan from a saved image, fp32 or bf16
- * activations, a backward pass, packed transposed plans, a host-pointer
- * version, bf16 or int8 Y. */
+ * Out of scope: fp32 or bf16 activations, a backward pass, packed transposed
+ * plans, a host-pointer version, bf16 or int8 Y.  (Loading a packed plan from a
+ * saved image: the block after this one.) */
 int tcsc_gpu_plan_create_packed(const tcsc_t *W, int col_begin, int col_end,
                                 int device, void *stream, tcsc_gpu_plan **out);
 int tcsc_gpu_plan_create_packed_device(int rows, int cols,
@@ -475,6 +475,74 @@ int tcsc_gpu_plan_create_packed_device(int rows, int cols,
                                        void *stream, tcsc_gpu_plan **out);
 int tcsc_gpu_plan_is_packed(const tcsc_gpu_plan *plan);
 int tcsc_gpu_plan_copy_w2(const tcsc_gpu_plan *plan, void *d_dst, size_t bytes, void *stream);
+
+/* ---- saved images: image -> packed plan, image -> TCSC, host packing
+ * tcsc_gpu_plan_copy_w2 writes an image out; these take one back in.  The image
+ * is the layout documented at tcsc_gpu_plan_enable_w2, tcsc_gpu_w2_image_bytes(
+ * rows, cols) bytes, and must be canonical: no code 3, and code 1 at every
+ * padding position (k >= rows, column >= cols).  Every image the library writes
+ * is; copy_w2 round trips and the byte-for-byte invariant above depend on it.
+ *
+ * tcsc_gpu_plan_create_packed_image / _device: a packed plan from an image in
+ * host memory (copied H2D) or on `device` (copied D2D).  `rows` is K, `cols` the
+ * plan's own column count, col_begin >= 0 only labels info.col_begin (how a
+ * column shard's image is reloaded).  The plan owns a copy and never adopts the
+ * caller's pointer; the call synchronises `stream`.  The plan is the one
+ * tcsc_gpu_plan_create_packed builds for the same W: is_packed 1, has_w2 1,
+ * has_i8 0, device_bytes == tcsc_gpu_w2_image_bytes(rows, cols) exactly,
+ * mfma_min_M 17, n_chunks 0, the same routing, reserve, workspace and refusals,
+ * and copy_w2 returns the bytes that went in.  k_w2_check validates the copy and
+ * counts it (one thread per dword, grid-stride; integer adds and one 64-bit
+ * integer atomic per workgroup, so no order of execution shows): info.n_pos /
+ * n_neg / nnz are the +1 / -1 weights of the image.  They equal the counts of
+ * the plan the TCSC
+ * arrays gave whenever W has no cancelling +1/-1 pair at one position (such a
+ * pair is two entries there and weight 0 here).
+ * TCSC_E_ARG with a message naming the call, *out NULL and no HIP call for: a
+ * NULL image or out, rows < 1 or >= 2^22, cols < 1, col_begin < 0, bytes !=
+ * tcsc_gpu_w2_image_bytes(rows, cols), a reference-order request.  TCSC_E_ARG
+ * and no plan (nothing stays allocated) when the image holds a code 3 or
+ * non-canonical padding; the message says which.
+ *
+ * tcsc_gpu_w2_to_tcsc: a device image -> the TCSC arrays of the rows x cols
+ * matrix it encodes, on the current device, by tcsc_gpu_from_dense's two-call
+ * protocol: with d_row_index_* NULL it writes d_col_start_* (cols + 1 offsets
+ * from 0) and *n_pos / *n_neg; with them allocated to those sizes it fills them
+ * too.  Bit for bit what tcsc_from_dense gives for that dense matrix: rows
+ * ascending inside every column.  Integer counters only (k_w2_unpack: per
+ * column and 256-k block counts, an exclusive scan, then every dword writes its
+ * entries behind those of the dwords before it in k order); no atomics in the
+ * fill, so every output position is determined by the image alone.  The image
+ * must not change between the two calls of a pair.  The same validation and
+ * host-side refusals as above, except that the summation order is not asked
+ * (TCSC arrays serve either order); a sign with 2^31 entries or more is
+ * TCSC_E_ARG (tcsc_t offsets are int).  Allocates scratch and synchronises
+ * `stream`, as tcsc_gpu_from_dense does.
+ *
+ * tcsc_gpu_w2_from_tcsc_host / tcsc_gpu_w2_to_tcsc_host: the same two
+ * conversions in host code, with no HIP call: they work where there is no
+ * device.  The first writes the image of W[:, col_begin:col_end) into `image`
+ * with k_w2_from_tcsc's semantics and bytes: a +1 and a -1 at one position
+ * cancel, unsorted columns are accepted; TCSC_E_ARG for a position whose summed
+ * weight is outside {-1, 0, +1}, a row outside [0, K), a col_start that is no
+ * range, K >= 2^22, an empty column range or a wrong `bytes`.  The second
+ * returns a new tcsc_t (free it with tcsc_free) with tcsc_gpu_w2_to_tcsc's
+ * arrays, or NULL with tcsc_gpu_last_error() set on an invalid image or
+ * arguments.
+ *
+ * Out of scope: a multi-layer checkpoint format (one image is one plan), packed
+ * transposed plans, fp32 or bf16 calls on a packed plan, bf16 or int8 Y, and a
+ * host-pointer sgemm on images. */
+int tcsc_gpu_plan_create_packed_image(const void *image, size_t bytes, int rows, int cols,
+                                      int col_begin, int device, void *stream, tcsc_gpu_plan **out);
+int tcsc_gpu_plan_create_packed_image_device(const void *d_image, size_t bytes, int rows, int cols,
+                                             int col_begin, int device, void *stream, tcsc_gpu_plan **out);
+int tcsc_gpu_w2_to_tcsc(const void *d_image, size_t bytes, int rows, int cols,
+                        int *d_col_start_pos, int *d_col_start_neg,
+                        int *d_row_index_pos, int *d_row_index_neg,
+                        int *n_pos, int *n_neg, void *stream);
+int tcsc_gpu_w2_from_tcsc_host(const tcsc_t *W, int col_begin, int col_end, void *image, size_t bytes);
+tcsc_t *tcsc_gpu_w2_to_tcsc_host(const void *image, size_t bytes, int rows, int cols);
 
 /* Device-side tcsc_from_dense: dense K x N row-major float matrix on the
  * device -> TCSC arrays on the device, bit-exact with the reference builder

@@ -1324,6 +1324,101 @@ int build_packed(const char* who, int rows, int col_begin, int ncols, long long 
     return TCSC_OK;
 }
 
+// ---- packed plans and TCSC arrays from a saved image -----------
+// What every entry point that takes an image refuses on the host, before any
+// HIP call.
+int image_args_ok(const char* who, const void* image, size_t bytes, int rows, int cols) {
+    if (!image) {
+        set_error("%s: NULL image", who);
+        return TCSC_E_ARG;
+    }
+    if (rows < 1 || rows >= tcsc::kDecodeMaxK) {
+        set_error("%s: an image needs 1 <= K < %d (rows=%d)", who, tcsc::kDecodeMaxK, rows);
+        return TCSC_E_ARG;
+    }
+    if (cols < 1) {
+        set_error("%s: cols must be at least 1 (cols=%d)", who, cols);
+        return TCSC_E_ARG;
+    }
+    if (bytes != tcsc::w2_image_bytes(rows, cols)) {
+        set_error("%s: bytes=%zu is not tcsc_gpu_w2_image_bytes(%d, %d) = %zu", who, bytes, rows, cols,
+                  tcsc::w2_image_bytes(rows, cols));
+        return TCSC_E_ARG;
+    }
+    return TCSC_OK;
+}
+
+// k_w2_check on a device image: the counts, or TCSC_E_ARG naming the fault.
+// Synchronises st.
+int check_image(const char* who, const uint32_t* w2, int rows, int cols, long long* n_pos, long long* n_neg,
+                hipStream_t st) {
+    struct Acc {
+        unsigned long long n[2];  // +1, -1
+        int bad, pad;
+    } h = {{0, 0}, 0, 0};
+    DevBuf acc;
+    HIP_TRY(acc.alloc(sizeof(Acc)));
+    HIP_TRY(hipMemsetAsync(acc.p, 0, sizeof(Acc), st));
+    Acc* d = acc.as<Acc>();
+    HIP_TRY(tcsc::w2_check(w2, cols, rows, d->n, &d->bad, st));
+    HIP_TRY(hipMemcpyAsync(&h, acc.p, sizeof(Acc), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    const int bad = h.bad;
+    if (bad) {
+        set_error("%s: invalid image: %s%s%s", who, bad & tcsc::kW2BadCode ? "a code 3 (no ternary weight)" : "",
+                  bad == (tcsc::kW2BadCode | tcsc::kW2BadPad) ? "; " : "",
+                  bad & tcsc::kW2BadPad ? "padding (k >= rows or column >= cols) holds a code other than 1" : "");
+        return TCSC_E_ARG;
+    }
+    *n_pos = (long long)h.n[0];
+    *n_neg = (long long)h.n[1];
+    return TCSC_OK;
+}
+
+// tcsc_gpu_plan_create_packed_image / _device: the plan's own copy of the image
+// (`kind` says where `image` lives), validated and counted by k_w2_check.
+int packed_from_image(const char* who, const void* image, hipMemcpyKind kind, size_t bytes, int rows, int cols,
+                      int col_begin, int device, void* stream, tcsc_gpu_plan** out) {
+    if (!out) {
+        set_error("%s: NULL out", who);
+        return TCSC_E_ARG;
+    }
+    *out = nullptr;
+    int rc = image_args_ok(who, image, bytes, rows, cols);
+    if (rc == TCSC_OK) rc = packed_args_ok(who, rows);
+    if (rc != TCSC_OK) return rc;
+    if (col_begin < 0) {
+        set_error("%s: col_begin must not be negative (col_begin=%d)", who, col_begin);
+        return TCSC_E_ARG;
+    }
+    DeviceGuard dg(device);
+    if (!dg.ok()) {
+        set_error("%s: cannot select device %d", who, device);
+        return TCSC_E_NODEV;
+    }
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    std::unique_ptr<tcsc_gpu_plan, PlanDeleter> plan(new tcsc_gpu_plan());  // the fields build_packed sets
+    plan->device = device;
+    plan->rows = rows;
+    plan->cols = cols;
+    plan->col_begin = col_begin;
+    plan->packed = true;
+    plan->mfma_min_M = tcsc::kDecodeMaxM + 1;
+    HIP_TRY(hipDeviceGetAttribute(&plan->num_cus, hipDeviceAttributeMultiprocessorCount, device));
+    if (hipMalloc(&plan->w2, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        plan->w2 = nullptr;
+        set_error("%s: cannot allocate the 2-bit image (%zu bytes)", who, bytes);
+        return TCSC_E_NOMEM;
+    }
+    plan->w2_bytes = bytes;
+    HIP_TRY(hipMemcpyAsync(plan->w2, image, bytes, kind, st));
+    rc = check_image(who, plan->w2, rows, cols, &plan->n_pos, &plan->n_neg, st);
+    if (rc != TCSC_OK) return rc;  // the plan and its copy are freed here
+    *out = plan.release();
+    return TCSC_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1506,6 +1601,63 @@ int tcsc_gpu_plan_copy_w2(const tcsc_gpu_plan* p, void* d_dst, size_t bytes, voi
     }
     DeviceGuard dg(p->device);
     HIP_TRY(hipMemcpyAsync(d_dst, p->w2, bytes, hipMemcpyDeviceToDevice, static_cast<hipStream_t>(stream)));
+    return TCSC_OK;
+}
+
+int tcsc_gpu_plan_create_packed_image(const void* image, size_t bytes, int rows, int cols, int col_begin, int device,
+                                      void* stream, tcsc_gpu_plan** out) {
+    return packed_from_image("tcsc_gpu_plan_create_packed_image", image, hipMemcpyHostToDevice, bytes, rows, cols,
+                             col_begin, device, stream, out);
+}
+
+int tcsc_gpu_plan_create_packed_image_device(const void* d_image, size_t bytes, int rows, int cols, int col_begin,
+                                             int device, void* stream, tcsc_gpu_plan** out) {
+    return packed_from_image("tcsc_gpu_plan_create_packed_image_device", d_image, hipMemcpyDeviceToDevice, bytes, rows,
+                             cols, col_begin, device, stream, out);
+}
+
+int tcsc_gpu_w2_to_tcsc(const void* d_image, size_t bytes, int rows, int cols, int* d_csp, int* d_csn, int* d_rip,
+                        int* d_rin, int* n_pos, int* n_neg, void* stream) {
+    const char* who = "tcsc_gpu_w2_to_tcsc";
+    if (!d_csp || !d_csn || !n_pos || !n_neg) {
+        set_error("%s: NULL col_start or count pointer", who);
+        return TCSC_E_ARG;
+    }
+    int rc = image_args_ok(who, d_image, bytes, rows, cols);
+    if (rc != TCSC_OK) return rc;
+    if (!tcsc::w2_unpack_fits(cols, rows)) {
+        set_error("%s: %d columns x %d k blocks do not fit 32-bit counters", who, cols, tcsc::w2_kblocks(rows));
+        return TCSC_E_ARG;
+    }
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const uint32_t* w2 = static_cast<const uint32_t*>(d_image);
+    long long np = 0, nn = 0;
+    rc = check_image(who, w2, rows, cols, &np, &nn, st);
+    if (rc != TCSC_OK) return rc;
+    if (np > 0x7fffffffLL || nn > 0x7fffffffLL) {
+        set_error("%s: %lld +1 and %lld -1 entries: tcsc_t offsets are int (each sign below 2^31)", who, np, nn);
+        return TCSC_E_ARG;
+    }
+    // per (column, k block) counts, their exclusive scans, col_start out of those
+    const size_t n = (size_t)cols * tcsc::w2_kblocks(rows) + 1;
+    size_t tb = 0;
+    HIP_TRY(tcsc::plan_scan_tmp_bytes((long long)n, &tb));
+    const size_t arr = align256(n * sizeof(int));
+    DevBuf scratch;  // one allocation: [scan scratch][cntp][cntn][offp][offn]
+    HIP_TRY(scratch.alloc(align256(tb) + 4 * arr));
+    char* base = scratch.as<char>() + align256(tb);
+    int *cntp = reinterpret_cast<int*>(base), *cntn = reinterpret_cast<int*>(base + arr);
+    int *offp = reinterpret_cast<int*>(base + 2 * arr), *offn = reinterpret_cast<int*>(base + 3 * arr);
+    HIP_TRY(hipMemsetAsync(cntp + (n - 1), 0, sizeof(int), st));
+    HIP_TRY(hipMemsetAsync(cntn + (n - 1), 0, sizeof(int), st));
+    HIP_TRY(tcsc::w2_unpack_counts(w2, cols, rows, cntp, cntn, st));
+    HIP_TRY(tcsc::exclusive_scan_i32(cntp, offp, (int)n, scratch.p, tb, st));
+    HIP_TRY(tcsc::exclusive_scan_i32(cntn, offn, (int)n, scratch.p, tb, st));
+    HIP_TRY(tcsc::w2_unpack_col_start(offp, offn, cols, rows, d_csp, d_csn, st));
+    if (d_rip && d_rin) HIP_TRY(tcsc::w2_unpack_fill(w2, cols, rows, offp, offn, d_rip, d_rin, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    *n_pos = (int)np;
+    *n_neg = (int)nn;
     return TCSC_OK;
 }
 

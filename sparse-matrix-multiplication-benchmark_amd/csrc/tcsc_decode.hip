@@ -15,6 +15,11 @@
 // against a fragment of ones gives the row sums sum_k q in the accumulator's
 // own layout, and the difference is the exact S = sum_k q w as an integer.
 // The epilogue is i8_out, k_gemm8's own: the same bits as the int8 MFMA path.
+//
+// The build-time kernels around the image live here too: k_w2_from (from the
+// int8 image), k_w2_from_tcsc (packed plans, §18), and the way back in (§19):
+// k_w2_check validates and counts a saved image, k_w2_unpack turns one into
+// TCSC arrays.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -119,6 +124,156 @@ __global__ void __launch_bounds__(256) k_w2_from_tcsc(const int* __restrict__ cs
         }
         W2[((size_t)t * nkb + kb) * 256 + threadIdx.x] = p;
     }
+}
+
+// ---- reading an image back ------------------------------------
+// What one dword p of an image says, given how many of its 16 positions are
+// real (k < K in a column < N; the rest is padding): the +1 positions as the
+// high bits of their codes, the -1 positions as the low bits, and the faults --
+// a code 3 anywhere (kW2BadCode), or padding that does not hold code 1 (kW2BadPad).
+struct W2Word {
+    uint32_t pos, neg;  // bit 8 (j & 3) + 2 (j >> 2) + 1 for a +1 at j, + 0 for a -1
+    int bad;
+};
+__device__ inline W2Word w2_word(uint32_t p, int nreal) {
+    uint32_t m = 0;  // both bits of every real position
+#pragma unroll
+    for (int j = 0; j < 16; ++j)
+        if (j < nreal) m |= 3u << (8 * (j & 3) + 2 * (j >> 2));
+    W2Word r;
+    r.bad = ((p & (p >> 1) & 0x55555555u) ? kW2BadCode : 0) | (((p ^ 0x55555555u) & ~m) ? kW2BadPad : 0);
+    r.pos = p & 0xAAAAAAAAu & m;
+    r.neg = ~(p | (p >> 1)) & 0x55555555u & m;
+    return r;
+}
+// real positions of the dword (lane l, step i) of tile (t, kb)
+__device__ inline int w2_nreal(int t, int kb, int l, int i, int ncols, int K, int* k0) {
+    *k0 = kW2Blk * kb + 64 * i + 16 * (l >> 4);
+    if (kW2Cols * t + (l & 15) >= ncols) return 0;
+    return min(max(K - *k0, 0), 16);
+}
+
+// Validates an image and counts its weights (tcsc_gpu_plan_create_packed_image,
+// tcsc_gpu_w2_to_tcsc).  One thread per dword, grid-stride, as k_w2_from; the
+// +1 and -1 counts are summed per thread, then over the wave, then over the
+// workgroup's four waves in the LDS, then one 64-bit integer atomicAdd per
+// workgroup and sign on a grid of at most kW2CheckBlocks workgroups (the
+// atomics all hit two addresses: one per wave of a thread-per-dword grid took
+// longer than reading the image).  Integer adds only, so no order of execution
+// shows in the counts.  counts[0] = +1, counts[1] = -1; *bad gets
+// kW2BadCode and kW2BadPad OR-ed in.
+constexpr unsigned kW2CheckBlocks = 1024;
+__global__ void __launch_bounds__(256) k_w2_check(const uint32_t* __restrict__ W2, int ncols, int K, int nkb,
+                                                 size_t dwords, unsigned long long* __restrict__ counts,
+                                                 int* __restrict__ bad) {
+    int np = 0, nn = 0, flags = 0;  // a full grid's wave sums are at most dwords / 256: ints hold them for any image below 2 TiB
+    for (size_t g = blockIdx.x * (size_t)blockDim.x + threadIdx.x; g < dwords; g += (size_t)gridDim.x * blockDim.x) {
+        const size_t tile = g >> 8;
+        const int l = (int)(g >> 2) & 63, i = (int)g & 3;
+        int k0;
+        const W2Word w = w2_word(W2[g], w2_nreal((int)(tile / nkb), (int)(tile % nkb), l, i, ncols, K, &k0));
+        np += __popc(w.pos);
+        nn += __popc(w.neg);
+        flags |= w.bad;
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {  // every lane of the wave is here: the loop above has ended for all
+        np += __shfl_xor(np, d, 64);
+        nn += __shfl_xor(nn, d, 64);
+        flags |= __shfl_xor(flags, d, 64);
+    }
+    __shared__ int part[4][3];  // the four waves' sums
+    if ((threadIdx.x & 63) == 0) {
+        part[threadIdx.x >> 6][0] = np;
+        part[threadIdx.x >> 6][1] = nn;
+        part[threadIdx.x >> 6][2] = flags;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned long long p = 0, n = 0;
+        int f = 0;
+        for (int w = 0; w < 4; ++w) {
+            p += (unsigned)part[w][0];
+            n += (unsigned)part[w][1];
+            f |= part[w][2];
+        }
+        if (p) atomicAdd(&counts[0], p);
+        if (n) atomicAdd(&counts[1], n);
+        if (f) atomicOr(bad, f);
+    }
+}
+
+// The image back to TCSC (tcsc_gpu_w2_to_tcsc).  One workgroup per tile, one
+// thread per dword (lane l = tid >> 2, step i = tid & 3).  Inside a 256-k block
+// the ascending k order of one column is step i, then k quarter l >> 4, then j,
+// so the 16 dwords of a column have ranks r = 4 i + (l >> 4).
+//   FILL false: cntp / cntn[col * nkb + kb] = the +1 / -1 entries of the column
+//               in this block.  An exclusive scan of these arrays (column major)
+//               gives every (column, block) its absolute offset, and col_start.
+//   FILL true:  each dword's entries go into an LDS copy of the block's output
+//               -- its column's list, behind the entries of the dwords of lower
+//               rank, in ascending j -- and the lists are then stored to offp /
+//               offn[col * nkb + kb] on, 16 threads per column on consecutive
+//               entries (the stores of a column are contiguous).
+// Integer counters in the LDS, no atomics: every output position is determined
+// by the image alone.
+template <bool FILL>
+__global__ void __launch_bounds__(256) k_w2_unpack(const uint32_t* __restrict__ W2, int ncols, int K, int nkb,
+                                                  int* __restrict__ cntp, int* __restrict__ cntn,
+                                                  const int* __restrict__ offp, const int* __restrict__ offn,
+                                                  int* __restrict__ rip, int* __restrict__ rin) {
+    __shared__ int sp[kW2Cols * 16], sn[kW2Cols * 16];  // [column of the tile][rank]
+    __shared__ int ep[FILL ? kW2Cols * kW2Blk : 1], en[FILL ? kW2Cols * kW2Blk : 1];  // [column][entry]: k
+    const int t = blockIdx.x / nkb, kb = blockIdx.x % nkb;
+    const int l = threadIdx.x >> 2, i = threadIdx.x & 3, c = l & 15, r = 4 * i + (l >> 4);
+    int k0;
+    const int nreal = w2_nreal(t, kb, l, i, ncols, K, &k0);
+    const W2Word w = w2_word(W2[(size_t)blockIdx.x * 256 + threadIdx.x], nreal);
+    sp[c * 16 + r] = __popc(w.pos);
+    sn[c * 16 + r] = __popc(w.neg);
+    __syncthreads();
+    // from here on 16 threads per column: column c2 of the tile, sub = 0 .. 15
+    const int c2 = threadIdx.x >> 4, sub = threadIdx.x & 15, col2 = kW2Cols * t + c2;
+    int totp = 0, totn = 0;
+#pragma unroll
+    for (int q = 0; q < 16; ++q) {
+        totp += sp[c2 * 16 + q];
+        totn += sn[c2 * 16 + q];
+    }
+    const size_t o = (size_t)col2 * nkb + kb;
+    if constexpr (!FILL) {
+        if (sub == 0 && col2 < ncols) {
+            cntp[o] = totp;
+            cntn[o] = totn;
+        }
+    } else {
+        int a = 0, b = 0;  // a column in the padding has no entries: nreal = 0 there
+        for (int q = 0; q < r; ++q) {
+            a += sp[c * 16 + q];
+            b += sn[c * 16 + q];
+        }
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+            const int bit = 8 * (j & 3) + 2 * (j >> 2);
+            if (w.pos >> (bit + 1) & 1) ep[c * kW2Blk + a++] = k0 + j;  // a, b < 256: at most 256 k a block
+            if (w.neg >> bit & 1) en[c * kW2Blk + b++] = k0 + j;
+        }
+        __syncthreads();
+        if (col2 >= ncols) return;
+        int* dp = rip + offp[o];
+        int* dn = rin + offn[o];
+        for (int e = sub; e < totp; e += 16) dp[e] = ep[c2 * kW2Blk + e];
+        for (int e = sub; e < totn; e += 16) dn[e] = en[c2 * kW2Blk + e];
+    }
+}
+
+// csp / csn[j] = the offset of column j's first block, j <= ncols (the scans end in the totals)
+__global__ void __launch_bounds__(256) k_w2_col_start(const int* __restrict__ offp, const int* __restrict__ offn, int ncols,
+                                                     int nkb, int* __restrict__ csp, int* __restrict__ csn) {
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    if (j > ncols) return;
+    csp[j] = offp[(size_t)j * nkb];
+    csn[j] = offn[(size_t)j * nkb];
 }
 
 // k_decode8.  Grid: ceil(col tiles / T) workgroups of kDecWaves waves.  Wave w
@@ -257,6 +412,46 @@ hipError_t w2_from_tcsc(const int* csp, const int* csn, const int* rip, const in
     if (blocks > 0x7fffffffLL) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_w2_from_tcsc, dim3((unsigned)blocks), dim3(256), 0, st, csp, csn, rip, rin, col_begin, ncols, K,
                        nkb, nkg, w2, bad);
+    return hipGetLastError();
+}
+
+hipError_t w2_check(const uint32_t* w2, int ncols, int K, unsigned long long* counts, int* bad, hipStream_t st) {
+    if (ncols <= 0 || K <= 0 || K >= kDecodeMaxK || !w2 || !counts || !bad) return hipErrorInvalidValue;
+    const size_t dwords = w2_image_bytes(K, ncols) / 4;
+    const size_t blocks = (dwords + 255) / 256;
+    hipLaunchKernelGGL(k_w2_check, dim3((unsigned)(blocks < kW2CheckBlocks ? blocks : kW2CheckBlocks)), dim3(256), 0, st, w2, ncols, K,
+                       w2_kblocks(K), dwords, counts, bad);
+    return hipGetLastError();
+}
+
+bool w2_unpack_fits(int ncols, int K) {
+    const long long nkb = w2_kblocks(K);
+    return (long long)w2_col_tiles(ncols) * nkb <= 0x7fffffffLL && (long long)ncols * nkb + 1 <= 0x7fffffffLL;
+}
+
+hipError_t w2_unpack_counts(const uint32_t* w2, int ncols, int K, int* cntp, int* cntn, hipStream_t st) {
+    if (ncols <= 0 || K <= 0 || K >= kDecodeMaxK || !w2_unpack_fits(ncols, K) || !w2 || !cntp || !cntn)
+        return hipErrorInvalidValue;
+    const int nkb = w2_kblocks(K);
+    hipLaunchKernelGGL(k_w2_unpack<false>, dim3((unsigned)(w2_col_tiles(ncols) * nkb)), dim3(256), 0, st, w2, ncols, K,
+                       nkb, cntp, cntn, nullptr, nullptr, nullptr, nullptr);
+    return hipGetLastError();
+}
+
+hipError_t w2_unpack_col_start(const int* offp, const int* offn, int ncols, int K, int* csp, int* csn, hipStream_t st) {
+    if (ncols <= 0 || K <= 0 || !offp || !offn || !csp || !csn) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_w2_col_start, dim3((unsigned)(ncols / 256 + 1)), dim3(256), 0, st, offp, offn, ncols,
+                       w2_kblocks(K), csp, csn);
+    return hipGetLastError();
+}
+
+hipError_t w2_unpack_fill(const uint32_t* w2, int ncols, int K, const int* offp, const int* offn, int* rip, int* rin,
+                          hipStream_t st) {
+    if (ncols <= 0 || K <= 0 || K >= kDecodeMaxK || !w2_unpack_fits(ncols, K) || !w2 || !offp || !offn || !rip || !rin)
+        return hipErrorInvalidValue;
+    const int nkb = w2_kblocks(K);
+    hipLaunchKernelGGL(k_w2_unpack<true>, dim3((unsigned)(w2_col_tiles(ncols) * nkb)), dim3(256), 0, st, w2, ncols, K,
+                       nkb, nullptr, nullptr, offp, offn, rip, rin);
     return hipGetLastError();
 }
 

@@ -27,8 +27,45 @@
 #include "../../include/dense/dense.h"
 #include "../../include/sparse/tcsc.h"
 #include "../../include/tcsc_gpu.h"
+#include "tcsc_internal.h"
 
 namespace {
+
+// ---- the 2-bit image on the host (tcsc_gpu_w2_*_host) ---------
+// The layout of tcsc_internal.h, byte-wise (the image is little-endian dwords):
+// weight (k, col) lives in byte w2_byte(...) at bit 2 (j >> 2), j = k % 16.
+inline size_t w2_byte(int k, int col, int nkb) {
+    const int kk = k % tcsc::kW2Blk, i = kk / 64, q = (kk % 64) / 16, j = kk % 16;
+    const size_t tile = (size_t)(col / tcsc::kW2Cols) * nkb + k / tcsc::kW2Blk;
+    return ((tile * 64 + 16 * q + col % tcsc::kW2Cols) * 4 + i) * 4 + (j & 3);
+}
+inline int w2_shift(int k) { return 2 * ((k % 16) >> 2); }
+
+bool w2_host_fail(const char* who, const char* what) {  // records the message; false, for `return`
+    char buf[256];
+    std::snprintf(buf, sizeof buf, "%s: %s", who, what);
+    tcsc::set_error_msg(buf);
+    return false;
+}
+
+bool w2_host_args_ok(const char* who, const void* image, size_t bytes, int rows, int cols) {
+    if (!image) return w2_host_fail(who, "NULL image");
+    if (rows < 1 || rows >= tcsc::kDecodeMaxK) return w2_host_fail(who, "an image needs 1 <= K < 2^22");
+    if (cols < 1) return w2_host_fail(who, "no columns (cols < 1, or an empty column range)");
+    if (bytes != tcsc::w2_image_bytes(rows, cols))
+        return w2_host_fail(who, "bytes is not tcsc_gpu_w2_image_bytes(rows, cols)");
+    return true;
+}
+
+// one sign's lists of columns [c0, c1): ranges inside [0, n) that do not run backwards, rows inside [0, K)
+bool w2_host_index_ok(const char* who, const int* cs, const int* ri, int c0, int c1, int n, int K) {
+    if (!cs || (n > 0 && !ri)) return w2_host_fail(who, "NULL index array");
+    for (int j = c0; j < c1; ++j)
+        if (cs[j] < 0 || cs[j + 1] < cs[j] || cs[j + 1] > n) return w2_host_fail(who, "a col_start that is no range");
+    for (int e = cs[c0]; e < cs[c1]; ++e)
+        if (ri[e] < 0 || ri[e] >= K) return w2_host_fail(who, "a row index outside [0, K)");
+    return true;
+}
 
 tcsc_t* alloc_tcsc(int rows, int cols, int n_pos, int n_neg) {
     tcsc_t* t = static_cast<tcsc_t*>(std::malloc(sizeof(tcsc_t)));
@@ -177,6 +214,104 @@ tcsc_t* tcsc_from_dense(dense_t dense, int rows, int cols) {
     }
     if (trace) std::fprintf(stderr, "[tcsc_amd] tcsc_from_dense %dx%d: host builder\n", rows, cols);
     return from_dense_host(dense, rows, cols);
+}
+
+// The image of W[:, col_begin:col_end) in host code: k_w2_from_tcsc's semantics
+// and bytes.  Per column the weights are summed into a K-long scratch (a +1 and
+// a -1 at one position cancel, the order inside a column does not matter), the
+// touched positions are written, and the scratch is cleared again.
+int tcsc_gpu_w2_from_tcsc_host(const tcsc_t* W, int col_begin, int col_end, void* image, size_t bytes) {
+    const char* who = "tcsc_gpu_w2_from_tcsc_host";
+    if (!W) return w2_host_fail(who, "NULL W"), TCSC_E_ARG;
+    if (col_begin < 0 || col_end > W->cols || col_begin > col_end)
+        return w2_host_fail(who, "a column range outside W"), TCSC_E_ARG;
+    const int K = W->rows, nc = col_end - col_begin;
+    if (!w2_host_args_ok(who, image, bytes, K, nc)) return TCSC_E_ARG;
+    if (!w2_host_index_ok(who, W->col_start_pos, W->row_index_pos, col_begin, col_end, W->n_elem_pos, K) ||
+        !w2_host_index_ok(who, W->col_start_neg, W->row_index_neg, col_begin, col_end, W->n_elem_neg, K))
+        return TCSC_E_ARG;
+    uint8_t* img = static_cast<uint8_t*>(image);
+    std::memset(img, 0x55, bytes);  // code 1 everywhere: weight 0, and the padding
+    const int nkb = tcsc::w2_kblocks(K);
+    std::vector<int> w((size_t)K, 0);
+    const int* cs[2] = {W->col_start_pos, W->col_start_neg};
+    const int* ri[2] = {W->row_index_pos, W->row_index_neg};
+    for (int c = 0; c < nc; ++c) {
+        const int j = col_begin + c;
+        bool ok = true;
+        for (int s = 0; s < 2; ++s)
+            for (int e = cs[s][j]; e < cs[s][j + 1]; ++e) w[ri[s][e]] += s ? -1 : 1;  // fewer than 2^31 entries a sign
+        for (int s = 0; s < 2; ++s)
+            for (int e = cs[s][j]; e < cs[s][j + 1]; ++e) {
+                const int k = ri[s][e], v = w[k];
+                if (v < -1 || v > 1) ok = false;
+                uint8_t& b = img[w2_byte(k, c, nkb)];
+                b = (uint8_t)((b & ~(3u << w2_shift(k))) | ((unsigned)((v + 1) & 3) << w2_shift(k)));
+            }
+        for (int s = 0; s < 2; ++s)
+            for (int e = cs[s][j]; e < cs[s][j + 1]; ++e) w[ri[s][e]] = 0;
+        if (!ok)
+            return w2_host_fail(who, "W is not ternary: a position's summed weight is outside {-1, 0, +1} "
+                                     "(a duplicated index)"), TCSC_E_ARG;
+    }
+    return TCSC_OK;
+}
+
+// The image back to a tcsc_t: tcsc_gpu_w2_to_tcsc's validation and arrays.  Two
+// walks over the image in tile order; inside a column tile the k blocks, steps,
+// quarters and j ascend, so every column's cursor sees its rows ascending.
+tcsc_t* tcsc_gpu_w2_to_tcsc_host(const void* image, size_t bytes, int rows, int cols) {
+    const char* who = "tcsc_gpu_w2_to_tcsc_host";
+    if (!w2_host_args_ok(who, image, bytes, rows, cols)) return nullptr;
+    const uint8_t* img = static_cast<const uint8_t*>(image);
+    const int nkb = tcsc::w2_kblocks(rows), nt = tcsc::w2_col_tiles(cols);
+    std::vector<long long> cp((size_t)cols + 1, 0), cn((size_t)cols + 1, 0);
+    tcsc_t* t = nullptr;
+    for (int pass = 0; pass < 2; ++pass) {
+        for (int ct = 0; ct < nt; ++ct)
+            for (int kb = 0; kb < nkb; ++kb)
+                for (int i = 0; i < 4; ++i)
+                    for (int q = 0; q < 4; ++q)
+                        for (int c = 0; c < tcsc::kW2Cols; ++c) {
+                            const int col = tcsc::kW2Cols * ct + c, k0 = tcsc::kW2Blk * kb + 64 * i + 16 * q;
+                            const uint8_t* d = img + ((((size_t)ct * nkb + kb) * 64 + 16 * q + c) * 4 + i) * 4;
+                            for (int j = 0; j < 16; ++j) {
+                                const int code = d[j & 3] >> (2 * (j >> 2)) & 3, k = k0 + j;
+                                if (pass) {
+                                    if (code == 2) t->row_index_pos[cp[col]++] = k;
+                                    if (code == 0) t->row_index_neg[cn[col]++] = k;
+                                    continue;
+                                }
+                                if (code == 3) return w2_host_fail(who, "invalid image: a code 3 (no ternary weight)"), nullptr;
+                                if (col >= cols || k >= rows) {
+                                    if (code != 1)
+                                        return w2_host_fail(who, "invalid image: padding (k >= rows or column >= cols) "
+                                                                 "holds a code other than 1"), nullptr;
+                                    continue;
+                                }
+                                cp[col] += code == 2;
+                                cn[col] += code == 0;
+                            }
+                        }
+        if (pass) break;
+        long long p = 0, n = 0;  // counts -> offsets, which the fill pass uses as cursors
+        for (int j = 0; j <= cols; ++j) {
+            const long long a = cp[j], b = cn[j];
+            cp[j] = p;
+            cn[j] = n;
+            p += a;
+            n += b;
+        }
+        if (p > 0x7fffffffLL || n > 0x7fffffffLL)
+            return w2_host_fail(who, "a sign has 2^31 entries or more: tcsc_t offsets are int"), nullptr;
+        t = alloc_tcsc(rows, cols, (int)p, (int)n);
+        if (!t) return w2_host_fail(who, "out of memory"), nullptr;
+        for (int j = 0; j <= cols; ++j) {
+            t->col_start_pos[j] = (int)cp[j];
+            t->col_start_neg[j] = (int)cn[j];
+        }
+    }
+    return t;
 }
 
 // SparseFormat(int* matrix, int K, int N) (SparseGEMM.h:20-39): an int K x N

@@ -453,6 +453,22 @@ hipError_t decode_build_w2(const int8_t* w8, int ncols, int K, int ld8, uint32_t
 // the LDS only: no order of execution shows in the image.
 hipError_t w2_from_tcsc(const int* csp, const int* csn, const int* rip, const int* rin, int col_begin, int ncols, int K,
                         uint32_t* w2, int* bad, hipStream_t st);
+// Reading an image back.  k_w2_check: counts[0] / counts[1] +=
+// the +1 / -1 weights at real positions (64-bit integer atomics; zero them
+// first) and *bad |= kW2BadCode for a code 3, kW2BadPad for padding (k >= K or
+// column >= ncols) that does not hold code 1.
+constexpr int kW2BadCode = 1, kW2BadPad = 2;
+hipError_t w2_check(const uint32_t* w2, int ncols, int K, unsigned long long* counts, int* bad, hipStream_t st);
+// k_w2_unpack: the image of a K x ncols matrix -> TCSC.  cntp / cntn hold
+// ncols * w2_kblocks(K) + 1 ints, [column][k block], the last one the caller's
+// 0; offp / offn are their exclusive scans; col_start j is off[j * nkb].  The
+// fill writes every column's rows ascending.  w2_unpack_fits: the grid and the
+// count arrays stay below 2^31.
+bool w2_unpack_fits(int ncols, int K);
+hipError_t w2_unpack_counts(const uint32_t* w2, int ncols, int K, int* cntp, int* cntn, hipStream_t st);
+hipError_t w2_unpack_col_start(const int* offp, const int* offn, int ncols, int K, int* csp, int* csn, hipStream_t st);
+hipError_t w2_unpack_fill(const uint32_t* w2, int ncols, int K, const int* offp, const int* offn, int* rip, int* rin,
+                          hipStream_t st);
 // k_gemm8w2 (tcsc_mfma.hip): mfma8_gemm with B read from the
 // 2-bit image; the same tiles, K split (mfma8_slices), slabs and bits
 hipError_t mfma8_gemm_w2(const int8_t* x8, const uint32_t* w2, int ld8, int K, int M, int N, const float* scale,

@@ -54,6 +54,8 @@ EXPORTED_SYMBOLS = (
     "tcsc_gpu_launch_geometry", "tcsc_gpu_wide_pays",
     "tcsc_gpu_plan_create_packed", "tcsc_gpu_plan_create_packed_device", "tcsc_gpu_plan_is_packed",
     "tcsc_gpu_plan_copy_w2",
+    "tcsc_gpu_plan_create_packed_image", "tcsc_gpu_plan_create_packed_image_device", "tcsc_gpu_w2_to_tcsc",
+    "tcsc_gpu_w2_from_tcsc_host", "tcsc_gpu_w2_to_tcsc_host",
     # include/sparse/bcsr.h
     "bcsr_from_dense", "bcsr_sgemm_basic", "bcsr_sgemm_prelu_basic", "bcsr_sgemm_avx", "bcsr_sgemm_prelu_avx",
     "bcsr_sgemm_avx2", "bcsr_free",
@@ -169,6 +171,12 @@ def lib():
     L.tcsc_gpu_plan_create_packed_device.argtypes = [i, i, vp, vp, vp, vp, i, i, i, vp, C.POINTER(vp)]
     L.tcsc_gpu_plan_is_packed.argtypes = [vp]
     L.tcsc_gpu_plan_copy_w2.argtypes = [vp, vp, C.c_size_t, vp]
+    L.tcsc_gpu_plan_create_packed_image.argtypes = [vp, C.c_size_t, i, i, i, i, vp, C.POINTER(vp)]
+    L.tcsc_gpu_plan_create_packed_image_device.argtypes = [vp, C.c_size_t, i, i, i, i, vp, C.POINTER(vp)]
+    L.tcsc_gpu_w2_to_tcsc.argtypes = [vp, C.c_size_t, i, i, vp, vp, vp, vp, C.POINTER(i), C.POINTER(i), vp]
+    L.tcsc_gpu_w2_from_tcsc_host.argtypes = [P, i, i, vp, C.c_size_t]
+    L.tcsc_gpu_w2_to_tcsc_host.argtypes = [vp, C.c_size_t, i, i]
+    L.tcsc_gpu_w2_to_tcsc_host.restype = P
     L.tcsc_gpu_prepare_x.argtypes = [vp, vp, i, vp]
     L.tcsc_gpu_sgemm_prepared.argtypes = [vp, vp, vp, i, i, i, f, vp]
     L.tcsc_gpu_from_dense.argtypes = [vp, i, i, vp, vp, vp, vp, C.POINTER(i), C.POINTER(i), vp]
@@ -542,9 +550,45 @@ class Plan:
         self.handle = h
         return self
 
+    @classmethod
+    def packed_from_image(cls, image, rows: int, cols: int, col_begin: int = 0, device: int = 0,
+                          stream: int = 0) -> "Plan":
+        """A packed plan from a saved 2-bit image of a rows x cols W: a numpy uint8 array (host memory,
+        tcsc_gpu_plan_create_packed_image) or a contiguous device tensor / device pointer of
+        w2_image_bytes(rows, cols) bytes (tcsc_gpu_plan_create_packed_image_device).  The plan owns a copy.
+        col_begin only labels info()['col_begin'] (a column shard's image).  TcscError when the size is wrong,
+        K >= 2^22, the reference order is set, or the image holds a code 3 or non-canonical padding."""
+        self = cls.__new__(cls)
+        h = C.c_void_p()
+        if isinstance(image, np.ndarray):
+            if image.dtype != np.uint8:
+                raise TcscError(f"Plan.packed_from_image: a host image must be uint8, got {image.dtype}")
+            host = np.ascontiguousarray(image).reshape(-1)
+            ptr, nbytes, name = host.ctypes.data, host.size, "tcsc_gpu_plan_create_packed_image"
+        else:
+            if hasattr(image, "is_contiguous") and not image.is_contiguous():
+                raise TcscError("Plan.packed_from_image: the device image must be contiguous")
+            nbytes = image.numel() * image.element_size() if hasattr(image, "numel") else w2_image_bytes(rows, cols)
+            ptr, name = _ptr(image), "tcsc_gpu_plan_create_packed_image_device"
+        _check(getattr(lib(), name)(C.c_void_p(ptr), int(nbytes), int(rows), int(cols), int(col_begin), int(device),
+                                    C.c_void_p(stream), C.byref(h)), name)
+        self.handle = h
+        return self
+
     @property
     def is_packed(self) -> bool:
         return bool(lib().tcsc_gpu_plan_is_packed(self.handle))
+
+    def w2_image(self, stream: int = 0):
+        """A new torch.uint8 device tensor holding the plan's 2-bit image (:meth:`copy_w2` into it, asynchronous
+        on the stream): what :meth:`packed_from_image` and :func:`w2_to_tcsc` take."""
+        import torch
+
+        inf = self.info()
+        img = torch.empty(w2_image_bytes(inf["rows"], inf["cols"]), dtype=torch.uint8,
+                          device=torch.device("cuda", inf["device"]))
+        self.copy_w2(img, stream=stream)
+        return img
 
     def copy_w2(self, dst, nbytes: int | None = None, stream: int = 0) -> None:
         """Copy the plan's 2-bit image (device to device, asynchronous on the stream) into dst: a contiguous
@@ -746,6 +790,108 @@ def decode_pays(M: int, K: int, N: int, nnz: int) -> bool:
     """The default rule for the decode path (tcsc_gpu_decode_pays; host arithmetic): 1 <= M <= 16 and (M > 4, or
     the small-M path does not fit (M, K), or 16 * nnz > K * N)."""
     return bool(lib().tcsc_gpu_decode_pays(int(M), int(K), int(N), int(nnz)))
+
+
+def w2_to_tcsc(image, rows: int, cols: int, stream: int = 0):
+    """The TCSC arrays of the rows x cols matrix a 2-bit image on the device encodes (tcsc_gpu_w2_to_tcsc):
+    (col_start_pos, col_start_neg, row_index_pos, row_index_neg) as torch.int32 tensors on the image's device, bit
+    for bit tcsc_from_dense's of that matrix -- what :meth:`Plan.from_device` takes.  image is a contiguous device
+    tensor of w2_image_bytes(rows, cols) bytes.  TcscError on an invalid image.  Synchronises the stream."""
+    import torch
+
+    if not torch.is_tensor(image) or not image.is_cuda or not image.is_contiguous():
+        raise TcscError("w2_to_tcsc: image must be a contiguous CUDA tensor")
+    nbytes = image.numel() * image.element_size()
+    rows, cols = int(rows), int(cols)
+    L, p, q = lib(), C.c_int(), C.c_int()
+    with torch.cuda.device(image.device):
+        csp = torch.empty(max(cols, 0) + 1, dtype=torch.int32, device=image.device)
+        csn = torch.empty_like(csp)
+
+        def call(rip, rin):
+            _check(L.tcsc_gpu_w2_to_tcsc(C.c_void_p(_ptr(image)), nbytes, rows, cols, C.c_void_p(_ptr(csp)),
+                                         C.c_void_p(_ptr(csn)), C.c_void_p(_ptr(rip)), C.c_void_p(_ptr(rin)),
+                                         C.byref(p), C.byref(q), C.c_void_p(stream)), "tcsc_gpu_w2_to_tcsc")
+
+        call(None, None)
+        # at least one element each: an empty tensor's NULL pointer would ask for the counts again
+        rip = torch.empty(max(p.value, 1), dtype=torch.int32, device=image.device)
+        rin = torch.empty(max(q.value, 1), dtype=torch.int32, device=image.device)
+        call(rip, rin)
+    return csp, csn, rip[:p.value], rin[:q.value]
+
+
+def w2_pack_host(W: TcscMatrix, col_begin: int = 0, col_end: int | None = None) -> np.ndarray:
+    """The 2-bit image of W[:, col_begin:col_end] as a numpy uint8 array, made in host code
+    (tcsc_gpu_w2_from_tcsc_host; no device needed): byte for byte the image of ``Plan.packed`` of the same range.
+    TcscError when W is not ternary (a duplicated index), a row is outside [0, K) or K >= 2^22."""
+    if not getattr(W, "ptr", None):
+        raise TcscError("W is freed or not a TcscMatrix")
+    col_end = W.cols if col_end is None else col_end
+    nbytes = _w2_bytes(W.rows, col_end - col_begin)
+    if nbytes is None:
+        raise TcscError(f"w2_pack_host: no image for K={W.rows} and columns [{col_begin}, {col_end})")
+    image = np.empty(nbytes, np.uint8)
+    _check(lib().tcsc_gpu_w2_from_tcsc_host(W.ptr, int(col_begin), int(col_end), C.c_void_p(image.ctypes.data),
+                                            nbytes), "tcsc_gpu_w2_from_tcsc_host")
+    return image
+
+
+def w2_unpack_host(image: np.ndarray, rows: int, cols: int) -> TcscMatrix:
+    """The TcscMatrix a 2-bit image (numpy uint8) encodes, made in host code (tcsc_gpu_w2_to_tcsc_host; no device
+    needed): the arrays tcsc_from_dense gives for that rows x cols matrix.  TcscError on an invalid image."""
+    if not isinstance(image, np.ndarray) or image.dtype != np.uint8:
+        raise TcscError("w2_unpack_host: image must be a numpy uint8 array")
+    host = np.ascontiguousarray(image).reshape(-1)
+    ptr = lib().tcsc_gpu_w2_to_tcsc_host(C.c_void_p(host.ctypes.data), host.size, int(rows), int(cols))
+    if not ptr:
+        raise TcscError(f"tcsc_gpu_w2_to_tcsc_host failed: {last_error()}")
+    return TcscMatrix(ptr)
+
+
+PACKED_FORMAT_VERSION = 1
+
+
+def _w2_bytes(rows: int, cols: int):
+    """w2_image_bytes in Python (no library call), or None where no image exists (K < 1, K >= 2^22, no column)."""
+    if not (1 <= rows < 1 << 22) or cols < 1:
+        return None
+    return ((cols + 15) // 16) * ((rows + 255) // 256) * 1024
+
+
+def save_packed(plan: Plan, path) -> None:
+    """Store one plan's 2-bit image as an .npz (np.savez, no pickle): `image` (uint8), `rows`, `cols`,
+    `col_begin` and `version`.  Any plan that has the image can be saved; :func:`load_packed` gives a packed plan.
+    path is a file name (np.savez appends .npz when it is missing) or a binary file object."""
+    inf = plan.info()
+    img = plan.w2_image()
+    np.savez(path, image=img.cpu().numpy(), rows=np.int64(inf["rows"]), cols=np.int64(inf["cols"]),
+             col_begin=np.int64(inf["col_begin"]), version=np.int64(PACKED_FORMAT_VERSION))
+
+
+def load_packed(path, device: int = 0, stream: int = 0) -> Plan:
+    """The packed plan of a file :func:`save_packed` wrote (np.load with allow_pickle=False).  The version, the
+    image's dtype and its size for (rows, cols) are checked first: a file that fails raises TcscError before the
+    library is called."""
+    with np.load(path, allow_pickle=False) as z:
+        missing = [k for k in ("image", "rows", "cols", "col_begin", "version") if k not in z.files]
+        if missing:
+            raise TcscError(f"load_packed: {path}: missing {', '.join(missing)}")
+        version, image = z["version"], z["image"]
+        if version.shape != () or version.dtype.kind not in "iu" or int(version) != PACKED_FORMAT_VERSION:
+            raise TcscError(f"load_packed: {path}: format version {version!r}, this library reads "
+                            f"{PACKED_FORMAT_VERSION}")
+        dims = [z[k] for k in ("rows", "cols", "col_begin")]
+    if any(d.shape != () or d.dtype.kind not in "iu" for d in dims):
+        raise TcscError(f"load_packed: {path}: rows, cols and col_begin must be integer scalars")
+    rows, cols, col_begin = (int(d) for d in dims)
+    if image.dtype != np.uint8:
+        raise TcscError(f"load_packed: {path}: image has dtype {image.dtype}, expected uint8")
+    want = _w2_bytes(rows, cols)
+    if want is None or col_begin < 0 or image.size != want:
+        raise TcscError(f"load_packed: {path}: image has {image.size} bytes, rows={rows} cols={cols} "
+                        f"col_begin={col_begin} need {want}")
+    return Plan.packed_from_image(image, rows, cols, col_begin, device, stream)
 
 
 def prelu_backward(G, Y, a: float, DZ, DB, M: int, N: int, ldg: int | None = None, ldy: int | None = None,

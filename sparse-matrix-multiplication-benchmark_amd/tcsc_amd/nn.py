@@ -17,7 +17,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from . import Plan, TcscError, TcscMatrix, prelu_backward, quantize_rows_i8
+from . import Plan, TcscError, TcscMatrix, prelu_backward, quantize_rows_i8, w2_image_bytes
 
 __all__ = ["TernaryLinear", "PackedTernaryLinear"]
 
@@ -226,6 +226,63 @@ def _define():
             self.plan = Plan.packed(Wm, 0, self.out_features, self.device_index, _stream(dev))
             self._rows, self._xq, self._scale = 0, None, None
 
+        @classmethod
+        def empty(cls, in_features: int, out_features: int, a: float | None = None, device: int = 0):
+            """A layer of this shape with a zero bias and no plan yet: ``load_state_dict`` fills it from a
+            ``state_dict()`` of a layer of the same shape.  Until then ``forward`` and ``reserve`` raise."""
+            self = cls.__new__(cls)
+            torch.nn.Module.__init__(self)
+            self.in_features, self.out_features, self.nnz = int(in_features), int(out_features), 0
+            self.a = None if a is None else float(a)
+            self.device_index = int(device)
+            dev = torch.device("cuda", self.device_index)
+            self.register_buffer("bias", torch.zeros(self.out_features, dtype=torch.float32, device=dev))
+            self.plan = None
+            self._rows, self._xq, self._scale = 0, None, None
+            return self
+
+        def _loaded_plan(self, what: str) -> Plan:
+            if self.plan is None:
+                raise TcscError(f"PackedTernaryLinear.{what}: the layer is empty (PackedTernaryLinear.empty): load a "
+                                "state_dict first")
+            return self.plan
+
+        def _save_to_state_dict(self, destination, prefix, keep_vars):
+            """``bias`` (the buffer) and ``w2``: the plan's 2-bit image as a uint8 tensor, a fresh copy made at this
+            call -- not a registered buffer, so the layer does not hold the image twice."""
+            super()._save_to_state_dict(destination, prefix, keep_vars)
+            dev = torch.device("cuda", self.device_index)
+            destination[prefix + "w2"] = self._loaded_plan("state_dict").w2_image(_stream(dev))
+
+        def _load_from_state_dict(self, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys,
+                                  error_msgs):
+            """Rebuilds the plan from ``w2`` (``Plan.packed_from_image``, the device path).  Both keys must be
+            there and the image must have the size of this layer's shape, whatever ``strict`` says: TcscError
+            otherwise, with the layer unchanged.  The plan it replaces is destroyed with its workspace, so a
+            ``reserve`` made before the load is gone: reserve again."""
+            for key in ("bias", "w2"):
+                if prefix + key not in state_dict:
+                    raise TcscError(f"PackedTernaryLinear.load_state_dict: missing key {prefix + key!r}")
+            w2, bias = state_dict[prefix + "w2"], state_dict[prefix + "bias"]
+            if not torch.is_tensor(bias) or bias.numel() != self.out_features:
+                raise TcscError(f"PackedTernaryLinear.load_state_dict: {prefix}bias must hold {self.out_features} values")
+            want = w2_image_bytes(self.in_features, self.out_features)
+            if not torch.is_tensor(w2) or w2.dtype != torch.uint8 or w2.numel() != want:
+                got = f"{tuple(w2.shape)} {w2.dtype}" if torch.is_tensor(w2) else type(w2).__name__
+                raise TcscError(f"PackedTernaryLinear.load_state_dict: {prefix}w2 is {got}, a {self.in_features} x "
+                                f"{self.out_features} layer needs {want} uint8 values")
+            dev = torch.device("cuda", self.device_index)
+            image = w2.detach().to(dev).contiguous()
+            plan = Plan.packed_from_image(image, self.in_features, self.out_features, 0, self.device_index, _stream(dev))
+            super()._load_from_state_dict(state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys,
+                                          error_msgs)
+            if prefix + "w2" in unexpected_keys:  # the base class knows parameters and buffers only
+                unexpected_keys.remove(prefix + "w2")
+            old, self.plan = self.plan, plan
+            self.nnz = plan.info()["nnz"]
+            if old is not None:
+                old.destroy()
+
         def _quant_buffers(self, rows: int):
             if self._rows < rows:
                 dev = torch.device("cuda", self.device_index)
@@ -237,10 +294,11 @@ def _define():
         def reserve(self, max_rows: int) -> None:
             """The plan's workspace (X8 and the split-K slabs) and the quantization buffers for up to max_rows
             rows: afterwards a forward allocates nothing but its output."""
-            self.plan.reserve(max_rows)
+            self._loaded_plan("reserve").reserve(max_rows)
             self._quant_buffers(max_rows)
 
         def forward(self, x):
+            plan = self._loaded_plan("forward")
             if not torch.is_tensor(x) or x.dtype != torch.float32 or not x.is_cuda:
                 raise TcscError("PackedTernaryLinear: x must be an fp32 CUDA tensor")
             if torch.is_grad_enabled() and x.requires_grad:
@@ -259,7 +317,7 @@ def _define():
             y = torch.empty((M, N), dtype=torch.float32, device=x.device)
             quantize_rows_i8(x2, xq, scale, M, K, stream)
             variant, a = ("basic", 0.0) if self.a is None else ("prelu_basic", self.a)
-            self.plan.sgemm_i8(xq, scale, self.bias, y, M, N, variant, a, stream)
+            plan.sgemm_i8(xq, scale, self.bias, y, M, N, variant, a, stream)
             return y.reshape(*lead, N)
 
         def extra_repr(self) -> str:
