@@ -544,6 +544,68 @@ int tcsc_gpu_w2_to_tcsc(const void *d_image, size_t bytes, int rows, int cols,
 int tcsc_gpu_w2_from_tcsc_host(const tcsc_t *W, int col_begin, int col_end, void *image, size_t bytes);
 tcsc_t *tcsc_gpu_w2_to_tcsc_host(const void *image, size_t bytes, int rows, int cols);
 
+/* ---- the quantizer fused into the int8 decode call -------------
+ * Token generation through the int8 path is tcsc_gpu_quantize_rows_i8 followed
+ * by tcsc_gpu_sgemm_i8: two launches per layer, an int8 copy of X written and
+ * read back, and fp32 rows only.  tcsc_gpu_sgemm_q8 takes the activations as
+ * they are, fp32 or bf16, and where it pays runs both steps in one launch.
+ *
+ * tcsc_gpu_sgemm_q8:
+ *   dX     : M x K row-major, contiguous; xtype TCSC_X_F32: floats, TCSC_X_BF16:
+ *            bf16 bit patterns (16 bits each); any alignment of the element type
+ *   dXq    : M x K bytes of scratch the caller owns (see below)
+ *   dScale : M floats, always written: the quantizer's scales
+ *   dB, dY, M, ldy, variant, a, stream : exactly as in tcsc_gpu_sgemm_i8
+ * The contract is an equality of bits: dY and dScale hold what
+ * tcsc_gpu_quantize_rows_i8 (xtype TCSC_X_BF16: tcsc_gpu_quantize_rows_i8_bf16)
+ * into (dXq, dScale) followed by tcsc_gpu_sgemm_i8 on the same plan under the
+ * same environment give -- on every plan that takes int8 calls (ordinary,
+ * packed, column shards, transposed), at every M, for every variant and `a`.
+ * Asynchronous on `stream`, capturable, and no workspace beyond the int8
+ * call's: tcsc_gpu_plan_reserve and tcsc_gpu_plan_workspace are unchanged.
+ *
+ * Routing: the int8 route is the one tcsc_gpu_launch_info_i8 reports.  The call
+ * is FUSED when that route is TCSC_PATH_DECODE and tcsc_gpu_quant_fuse_pays says
+ * 1 or $TCSC_QFUSE=1 is set ($TCSC_QFUSE is read per call: 0 never fuses, 1
+ * fuses on every decode route, unset follows the rule).  Fused, one kernel
+ * (k_decode8q) finds the row maxima, writes dScale, quantizes X on the way into
+ * its MFMA fragments with the quantizer's own arithmetic (one shared function)
+ * and runs k_decode8's loop and epilogue; dXq is not touched and may be NULL.
+ * Not fused, the library launches the quantizer into dXq and then the int8
+ * call (two launches, three where k_pack8 runs); dXq must then be non-NULL:
+ * TCSC_E_ARG otherwise, answered like every other argument check (a NULL plan,
+ * X, scale, B or Y, xtype other than 0 or 1, M < 0, ldy < cols, a bad variant)
+ * before any HIP call, with a message naming the call.
+ * tcsc_gpu_launch_info_q8 reports the path, the K slices and whether a call of
+ * M rows of that xtype is fused.
+ *
+ * tcsc_gpu_quant_fuse_pays (host arithmetic: no plan, no device): a fused
+ * workgroup reads all of X twice from the L2 (the row maxima, then the values
+ * it quantizes) and quantizes M K values itself, where k_decode8 reads the M K
+ * bytes of the int8 copy once.  With W the workgroups of the launch
+ * (ceil(ceil(N/16) / T), T the tiles per workgroup of k_decode8's grid rule on
+ * 256 CUs) the rule is
+ *   1 <= M <= 4 and W M K <= 2^23, for either xtype
+ * -- where the fused call was measured no slower than the two launches, in a
+ * replayed graph and eagerly (profiles/q8_bench.json: up to
+ * M = 2 at 8192 x 8192 and M = 4 at 4096 x 4096, 2560 x 6912 and 6912 x 2560;
+ * it loses at every M >= 8 measured).  0 for M < 1, M > 16, K < 1, N < 1 or an
+ * xtype other than 0 or 1.
+ *
+ * tcsc_gpu_quantize_rows_i8_bf16: tcsc_gpu_quantize_rows_i8 on bf16 bit
+ * patterns: each value is widened to fp32 (exact) and then takes the same
+ * formula, so the results are those of the fp32 quantizer on the widened X.
+ * The same guarantees and argument checks.
+ *
+ * Out of scope: bf16 or int8 Y; fusing the quantizer into k_pack8 at M >= 17;
+ * a host-pointer version. */
+enum tcsc_xtype { TCSC_X_F32 = 0, TCSC_X_BF16 = 1 };
+int tcsc_gpu_quantize_rows_i8_bf16(const void *dX_bf16, int M, int K, void *dXq, float *dScale, void *stream);
+int tcsc_gpu_sgemm_q8(const tcsc_gpu_plan *plan, const void *dX, int xtype, void *dXq, float *dScale,
+                      const float *dB, float *dY, int M, int ldy, int variant, float a, void *stream);
+int tcsc_gpu_launch_info_q8(const tcsc_gpu_plan *plan, int M, int xtype, int *path, int *slices, int *fused);
+int tcsc_gpu_quant_fuse_pays(int M, int K, int N, int xtype);
+
 /* Device-side tcsc_from_dense: dense K x N row-major float matrix on the
  * device -> TCSC arrays on the device, bit-exact with the reference builder
  * (tcsc.c:6-66).  Two calls: first with the four output pointers NULL to

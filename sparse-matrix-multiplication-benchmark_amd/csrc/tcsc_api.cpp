@@ -1942,6 +1942,101 @@ int tcsc_gpu_quantize_rows_i8(const float* dX, int M, int K, void* dXq, float* d
     return TCSC_OK;
 }
 
+int tcsc_gpu_quantize_rows_i8_bf16(const void* dX_bf16, int M, int K, void* dXq, float* dScale, void* stream) {
+    if (M < 0 || K < 0) {
+        set_error("tcsc_gpu_quantize_rows_i8_bf16: bad arguments (M=%d K=%d)", M, K);
+        return TCSC_E_ARG;
+    }
+    if (M == 0) return TCSC_OK;
+    if (!dScale || (K > 0 && (!dX_bf16 || !dXq))) {
+        set_error("tcsc_gpu_quantize_rows_i8_bf16: NULL device pointer");
+        return TCSC_E_ARG;
+    }
+    HIP_TRY(tcsc::quantize_rows_i8_bf16(static_cast<const uint16_t*>(dX_bf16), M, K, static_cast<int8_t*>(dXq), dScale,
+                                        static_cast<hipStream_t>(stream)));
+    return TCSC_OK;
+}
+
+// ---- the quantizer fused into the int8 decode call -------------
+// The default rule, host arithmetic.  The fused kernel saves the quantizer's
+// launch and its int8 copy; it pays by every workgroup reading all of X twice
+// (the row maxima, then the values it quantizes) and quantizing the M K values
+// itself.  The byte count put fp32 behind bf16; measured (profiles/q8_bench.json,
+// §20) the type hardly matters and the line runs along the values all
+// workgroups quantize together: fusing wins up to 2^23 of them (M = 2 at 8192^2,
+// M = 4 at 4096^2) and at no M above 4, from where the staging takes a second,
+// unprefetched pass of loads per block.
+static constexpr int kQFuseMaxM = 4;
+static constexpr long long kQFuseValues = 1LL << 23;
+static bool quant_fuse_pays(int M, int K, int N, int xtype) {
+    if (M < 1 || M > kQFuseMaxM || K < 1 || N < 1 || (xtype != TCSC_X_F32 && xtype != TCSC_X_BF16)) return false;
+    const int T = tcsc::decode_tiles_per_wg(M, N, 0);  // the grid on a 256-CU chip
+    const long long wgs = (tcsc::w2_col_tiles(N) + T - 1) / T;
+    return wgs * M * K <= kQFuseValues;
+}
+// $TCSC_QFUSE, read per call: 0 never fuses, 1 fuses on every decode route, unset the rule
+static int qfuse_knob() {
+    const char* e = std::getenv("TCSC_QFUSE");
+    if (!e || !*e) return -1;
+    return std::atoi(e) != 0 ? 1 : 0;
+}
+// the int8 route of M rows on the plan as it stands, and whether a q8 call of this X type fuses on it
+static Route route_q8(const tcsc_gpu_plan* p, int M, int xtype, bool* fused) {
+    const Route r = route_call(p, M, kI8, p->ws_bytes, RoutePins());
+    *fused = false;
+    if (r.path == TCSC_PATH_DECODE && has_decode(p, M, kI8)) {
+        const int knob = qfuse_knob();
+        *fused = knob >= 0 ? knob == 1 : quant_fuse_pays(M, p->rows, p->cols, xtype);
+    }
+    return r;
+}
+
+int tcsc_gpu_quant_fuse_pays(int M, int K, int N, int xtype) { return quant_fuse_pays(M, K, N, xtype) ? 1 : 0; }
+
+int tcsc_gpu_launch_info_q8(const tcsc_gpu_plan* p, int M, int xtype, int* path, int* slices, int* fused) {
+    if (!p || M < 0 || !path || !slices || !fused || (xtype != TCSC_X_F32 && xtype != TCSC_X_BF16)) {
+        set_error("tcsc_gpu_launch_info_q8: bad arguments (M=%d xtype=%d)", M, xtype);
+        return TCSC_E_ARG;
+    }
+    bool f = false;
+    const Route r = route_q8(p, M, xtype, &f);
+    *path = r.path;
+    *slices = r.slices;
+    *fused = f ? 1 : 0;
+    return TCSC_OK;
+}
+
+int tcsc_gpu_sgemm_q8(const tcsc_gpu_plan* p, const void* dX, int xtype, void* dXq, float* dScale, const float* dB,
+                      float* dY, int M, int ldy, int variant, float a, void* stream) {
+    const char* who = "tcsc_gpu_sgemm_q8";
+    if (!p || M < 0 || ldy < p->cols || !valid_variant(variant) || (xtype != TCSC_X_F32 && xtype != TCSC_X_BF16)) {
+        set_error("%s: bad arguments (M=%d ldy=%d variant=%d xtype=%d)", who, M, ldy, variant, xtype);
+        return TCSC_E_ARG;
+    }
+    if (M == 0) return TCSC_OK;
+    if (!dScale || !dB || !dY || (!dX && p->rows > 0)) {
+        set_error("%s: NULL device pointer", who);
+        return TCSC_E_ARG;
+    }
+    bool fused = false;
+    if (p->cols > 0) route_q8(p, M, xtype, &fused);
+    if (!fused) {  // the quantizer into the caller's scratch, then the int8 call as it is: two or three launches
+        if (!dXq && p->rows > 0) {
+            set_error("%s: NULL dXq on a route that is not fused (M=%d)", who, M);
+            return TCSC_E_ARG;
+        }
+        const int rc = xtype == TCSC_X_F32
+                           ? tcsc_gpu_quantize_rows_i8(static_cast<const float*>(dX), M, p->rows, dXq, dScale, stream)
+                           : tcsc_gpu_quantize_rows_i8_bf16(dX, M, p->rows, dXq, dScale, stream);
+        if (rc != TCSC_OK) return rc;
+        return tcsc_gpu_sgemm_i8(p, dXq, dScale, dB, dY, M, ldy, variant, a, stream);
+    }
+    const_cast<tcsc_gpu_plan*>(p)->staged_M = -1;  // as every tcsc_gpu_sgemm* does
+    HIP_TRY(tcsc::decode_gemm_q(dX, xtype == TCSC_X_BF16, p->w2, p->rows, M, p->cols, dScale, dB, dY, ldy,
+                                is_prelu(variant), a, p->num_cus, static_cast<hipStream_t>(stream)));
+    return TCSC_OK;
+}
+
 int tcsc_gpu_workspace_bound_i8(int M, int K, int N, size_t* i8_bytes, size_t* f32_bytes) {
     if (M < 0 || K < 1 || N < 0) {
         set_error("tcsc_gpu_workspace_bound_i8: bad arguments (M=%d K=%d N=%d)", M, K, N);

@@ -26,6 +26,8 @@
 
 #include "tcsc_i8_out.h"
 #include "tcsc_internal.h"
+#include "tcsc_quant.h"
+#include "tcsc_xsrc.h"
 
 namespace tcsc {
 namespace {
@@ -391,6 +393,265 @@ void launch_decode(const int8_t* X, const uint32_t* w2, int K, int M, int N, con
                            ldy, a);
 }
 
+// k_decode8q: k_quant_rows_i8 and k_decode8 in one launch, for
+// fp32 (TX = float) or bf16 (TX = uint16_t) X.  k_decode8's grid, K split over 8
+// waves, image loads, MFMA loop with the row-sum correction, LDS reduce and
+// epilogue; what is new is where the int8 fragments come from.
+//   Phase A: all 512 threads find amax[r] = max_k |x[r, k]| of the rows r < M
+//   over the whole of K -- 512 / Mp threads per row (Mp = M rounded up to a power
+//   of two), shuffles over the 32 lanes of a half-wave, the half-waves' maxima
+//   through the LDS -- then scale and inv by quant_scales; workgroup 0 stores the
+//   scales.  fmaxf is exact in any order: every workgroup gets the quantizer's bits.
+//   Phase B: per 256-k block a wave quantizes the M x 256 values of its block
+//   into its own 4 KiB of the LDS -- lane l takes k = 256 kb + 4 l .. + 3 of
+//   every row (one 16-B or 8-B load, four quant_i8, one 4-B LDS store) -- and its
+//   lanes read their 16-byte fragments from there.  A lane reads the fragment of
+//   row l & 15 directly only at a cost of 64 quant_i8 per block whatever M is
+//   (masked lanes issue too); through the LDS it is 4 M.  Rows >= M and k >= K
+//   are never read: the first stay zero in the fragment, the second are stored
+//   as zeros.  The 16-B slots of a row are swizzled by the row (slot ^ row), so
+//   the 16 rows' fragment reads fall on different banks without padding.
+//   The first four rows of the next block are loaded before this block's MFMAs.
+// ALIGNED: XSrc<TX>::vec_ok -- 16-B loads in phase A, whole loads of a lane's
+// four values in phase B; otherwise guarded scalar loads in both.
+constexpr int kQWaves = 8;           // the product build's K split; the staging of 16 waves would not fit 64 KiB
+constexpr int kQWaveBytes = 16 * kW2Blk;  // a wave's quantized block: 16 rows x 256 k
+template <typename TX, int T, bool ALIGNED, bool PRELU>
+__global__ void __launch_bounds__(kQWaves * 64) k_decode8q(const TX* __restrict__ X, const uint32_t* __restrict__ W2,
+                                                           int K, int M, int N, int nkb, int ntiles,
+                                                           float* __restrict__ scale_out,
+                                                           const float* __restrict__ bias, float* __restrict__ Y,
+                                                           int ldy, float a) {
+    using XS = XSrc<TX>;
+    constexpr int kThreads = kQWaves * 64, kHalves = kThreads / 32;
+    constexpr int kRedBytes = kQWaves * T * 256 * 4, kStageBytes = kQWaves * kQWaveBytes;
+    // the waves' staging blocks during the K loop, the partial sums after it
+    __shared__ __attribute__((aligned(16))) unsigned char smem[kRedBytes > kStageBytes ? kRedBytes : kStageBytes];
+    __shared__ float s_part[kHalves], s_scale[kDecodeMaxM], s_inv[kDecodeMaxM];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int t0 = blockIdx.x * T;
+
+    // ---- phase A: the row maxima, scales and inverses
+    {
+        int sh = 0;  // Mp = 1 << sh
+        while ((1 << sh) < M) ++sh;
+        const int gl = 9 - sh;  // log2 of the threads per row: 512 .. 32
+        static_assert(kThreads == 512 && kDecodeMaxM == 16, "512 threads over at most 16 rows: half-waves do not mix rows");
+        const int arow = tid >> gl, asub = tid & ((1 << gl) - 1), G = 1 << gl;
+        float am = 0.0f;
+        if (arow < M) {
+            const TX* src = X + (size_t)arow * K;
+            if constexpr (ALIGNED) {
+                for (int q = asub; q < K / XS::kVec; q += G) {
+                    float f[XS::kVec];
+                    XS::unpack(*reinterpret_cast<const uint4*>(src + (size_t)q * XS::kVec), 1.0f, f);
+#pragma unroll
+                    for (int e = 0; e < XS::kVec; ++e) am = fmaxf(am, fabsf(f[e]));
+                }
+            } else {
+                for (int k = asub; k < K; k += G) am = fmaxf(am, fabsf(XS::conv(src[k], 1.0f)));
+            }
+        }
+#pragma unroll
+        for (int d = 16; d >= 1; d >>= 1) am = fmaxf(am, __shfl_xor(am, d, 64));  // stays inside the half-wave
+        if ((tid & 31) == 0) s_part[tid >> 5] = am;
+        __syncthreads();
+        if (tid < M) {
+            const int h = G >> 5;  // half-waves per row
+            float m = 0.0f;
+            for (int q = 0; q < h; ++q) m = fmaxf(m, s_part[tid * h + q]);
+            float sc, inv;
+            quant_scales(m, sc, inv);
+            s_scale[tid] = sc;
+            s_inv[tid] = inv;
+            if (blockIdx.x == 0) scale_out[tid] = sc;
+        }
+        __syncthreads();
+    }
+
+    // ---- phase B: k_decode8's loop on fragments quantized through the LDS
+    const int xr = lane & 15, kq = lane >> 4;
+    const bool row_ok = xr < M;
+    const u32x4* wp[T];
+#pragma unroll
+    for (int t = 0; t < T; ++t)
+        wp[t] = reinterpret_cast<const u32x4*>(W2) + (size_t)min(t0 + t, ntiles - 1) * nkb * 64 + lane;
+    unsigned char* qw = smem + wave * kQWaveBytes;
+
+    // the lane's four values of rows j0 .. j0 + 3 of block kb, as raw bits (fp32: one per dword; bf16: two)
+    constexpr int kRaw = (int)sizeof(TX);  // dwords of four values
+    struct Raw {
+        uint32_t w[kRaw];
+    };
+    auto load_rows = [&](int kb, int j0, Raw (&raw)[4]) {
+        const int k = kW2Blk * kb + 4 * lane;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+#pragma unroll
+            for (int d = 0; d < kRaw; ++d) raw[u].w[d] = 0;
+            if (j0 + u >= M || k >= K) continue;  // the first is uniform
+            const TX* src = X + (size_t)(j0 + u) * K + k;
+            if constexpr (ALIGNED) {  // K % 4 == 0: the four values lie wholly below K
+                if constexpr (kRaw == 4) {
+                    const uint4 v = *reinterpret_cast<const uint4*>(src);
+                    raw[u].w[0] = v.x, raw[u].w[1] = v.y, raw[u].w[2] = v.z, raw[u].w[3] = v.w;
+                } else {
+                    const uint2 v = *reinterpret_cast<const uint2*>(src);
+                    raw[u].w[0] = v.x, raw[u].w[1] = v.y;
+                }
+            } else {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    if (k + e >= K) continue;
+                    if constexpr (kRaw == 4)
+                        raw[u].w[e] = __float_as_uint(src[e]);
+                    else
+                        raw[u].w[e >> 1] |= (uint32_t)src[e] << (16 * (e & 1));
+                }
+            }
+        }
+    };
+    // quantized and stored: byte e of the dword is value k + e, zero at k + e >= K
+    auto store_rows = [&](int kb, int j0, const Raw (&raw)[4]) {
+        const int k = kW2Blk * kb + 4 * lane;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int row = j0 + u;
+            if (row >= M) break;  // uniform
+            const float inv = s_inv[row];
+            uint32_t o = 0;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                float x;
+                if constexpr (kRaw == 4)
+                    x = __uint_as_float(raw[u].w[e]);
+                else
+                    x = XS::conv((TX)(raw[u].w[e >> 1] >> (16 * (e & 1))), 1.0f);
+                const uint32_t q = (uint32_t)quant_i8(x, inv) & 0xffu;
+                if (ALIGNED ? k < K : k + e < K) o |= q << (8 * e);
+            }
+            *reinterpret_cast<uint32_t*>(qw + row * kW2Blk + (((lane >> 2) ^ row) << 4) + 4 * (lane & 3)) = o;
+        }
+    };
+    auto stage_rest = [&](int kb, Raw (&raw)[4]) {  // rows 4 .. M - 1, four at a time
+        for (int j0 = 4; j0 < M; j0 += 4) {
+            load_rows(kb, j0, raw);
+            store_rows(kb, j0, raw);
+        }
+    };
+    // the wave's own stores, read by its other lanes: LDS operations of one wave execute in order
+    auto fragments = [&](i32x4 (&xf)[4]) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            xf[i] = i32x4{0, 0, 0, 0};
+            if (row_ok) xf[i] = *reinterpret_cast<const i32x4*>(qw + xr * kW2Blk + (((4 * i + kq) ^ xr) << 4));
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+    };
+    auto load_w = [&](int kb, u32x4 (&p)[T]) {
+#pragma unroll
+        for (int t = 0; t < T; ++t) p[t] = __builtin_nontemporal_load(wp[t] + (size_t)kb * 64);
+    };
+
+    i32x4 acc[T], rs = i32x4{0, 0, 0, 0};
+#pragma unroll
+    for (int t = 0; t < T; ++t) acc[t] = i32x4{0, 0, 0, 0};
+    const i32x4 ones = i32x4{0x01010101, 0x01010101, 0x01010101, 0x01010101};
+
+    i32x4 xf[4];
+    u32x4 p[T], pn[T];
+    Raw raw[4];
+    int kb = wave;
+    if (kb < nkb) {
+        load_w(kb, p);
+        load_rows(kb, 0, raw);
+        store_rows(kb, 0, raw);
+        stage_rest(kb, raw);
+        fragments(xf);
+    }
+    while (kb < nkb) {  // uniform
+        const int nx = kb + kQWaves;
+        if (nx < nkb) {
+            load_w(nx, pn);
+            load_rows(nx, 0, raw);
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            rs = __builtin_amdgcn_mfma_i32_16x16x64_i8(xf[i], ones, rs, 0, 0, 0);
+#pragma unroll
+            for (int t = 0; t < T; ++t) {
+                const uint32_t q = p[t][i];
+                const i32x4 b = i32x4{(int)(q & 0x03030303u), (int)((q >> 2) & 0x03030303u),
+                                      (int)((q >> 4) & 0x03030303u), (int)((q >> 6) & 0x03030303u)};
+                acc[t] = __builtin_amdgcn_mfma_i32_16x16x64_i8(xf[i], b, acc[t], 0, 0, 0);
+            }
+        }
+        if (nx < nkb) {  // this block's fragments are in registers: its staging block is free
+            store_rows(nx, 0, raw);
+            stage_rest(nx, raw);
+            fragments(xf);
+#pragma unroll
+            for (int t = 0; t < T; ++t) p[t] = pn[t];
+        }
+        kb = nx;
+    }
+
+    __syncthreads();  // every wave is done with its staging block: the partial sums take the memory
+    int* red = reinterpret_cast<int*>(smem);
+#pragma unroll
+    for (int t = 0; t < T; ++t)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) red[(wave * T + t) * 256 + r * 64 + lane] = acc[t][r] - rs[r];
+    __syncthreads();
+    for (int o = tid; o < T * 256; o += kThreads) {
+        const int row = o / (16 * T), cg = o % (16 * T), t = cg >> 4, c = cg & 15;
+        const int col = (t0 + t) * kW2Cols + c;
+        if (row >= M || col >= N) continue;
+        int S = 0;
+#pragma unroll
+        for (int w = 0; w < kQWaves; ++w) S += red[(w * T + t) * 256 + (row & 3) * 64 + (row >> 2) * 16 + c];
+        Y[(size_t)row * ldy + col] = i8_out<PRELU>(S, s_scale[row], bias[col], a);
+    }
+}
+
+template <typename TX, int T, bool ALIGNED>
+void launch_decode_q(const TX* X, const uint32_t* w2, int K, int M, int N, float* scale_out, const float* B, float* Y,
+                     int ldy, bool prelu, float a, hipStream_t st) {
+    const int ntiles = w2_col_tiles(N), nkb = w2_kblocks(K);
+    const dim3 grid((ntiles + T - 1) / T), block(kQWaves * 64);
+    if (prelu)
+        hipLaunchKernelGGL((k_decode8q<TX, T, ALIGNED, true>), grid, block, 0, st, X, w2, K, M, N, nkb, ntiles, scale_out,
+                           B, Y, ldy, a);
+    else
+        hipLaunchKernelGGL((k_decode8q<TX, T, ALIGNED, false>), grid, block, 0, st, X, w2, K, M, N, nkb, ntiles,
+                           scale_out, B, Y, ldy, a);
+}
+
+template <typename TX>
+void decode_q_typed(const TX* X, const uint32_t* w2, int K, int M, int N, float* scale_out, const float* B, float* Y,
+                    int ldy, bool prelu, float a, int num_cus, hipStream_t st) {
+    const bool aligned = XSrc<TX>::vec_ok(X, K);
+    const int T = decode_tiles_per_wg(M, N, num_cus);
+#define TCSC_DECODE_Q_LAUNCH(TT)                                                                \
+    if (aligned)                                                                                \
+        launch_decode_q<TX, TT, true>(X, w2, K, M, N, scale_out, B, Y, ldy, prelu, a, st);      \
+    else                                                                                        \
+        launch_decode_q<TX, TT, false>(X, w2, K, M, N, scale_out, B, Y, ldy, prelu, a, st)
+    if (T == 4) {
+        TCSC_DECODE_Q_LAUNCH(4);
+    } else if (T == 2) {
+        TCSC_DECODE_Q_LAUNCH(2);
+    } else {
+        TCSC_DECODE_Q_LAUNCH(1);
+    }
+#undef TCSC_DECODE_Q_LAUNCH
+}
+
 }  // namespace
 
 hipError_t decode_build_w2(const int8_t* w8, int ncols, int K, int ld8, uint32_t* w2, int* bad, hipStream_t st) {
@@ -487,6 +748,17 @@ hipError_t decode_gemm(const int8_t* X, const uint32_t* w2, int K, int M, int N,
         TCSC_DECODE_LAUNCH(1);
     }
 #undef TCSC_DECODE_LAUNCH
+    return hipGetLastError();
+}
+
+hipError_t decode_gemm_q(const void* X, bool bf16, const uint32_t* w2, int K, int M, int N, float* scale_out,
+                         const float* B, float* Y, int ldy, bool prelu, float a, int num_cus, hipStream_t st) {
+    if (M < 1 || M > kDecodeMaxM || K < 1 || K >= kDecodeMaxK || N < 1 || !X || !w2 || !scale_out || !B || !Y || ldy < N)
+        return hipErrorInvalidValue;
+    if (bf16)
+        decode_q_typed(static_cast<const uint16_t*>(X), w2, K, M, N, scale_out, B, Y, ldy, prelu, a, num_cus, st);
+    else
+        decode_q_typed(static_cast<const float*>(X), w2, K, M, N, scale_out, B, Y, ldy, prelu, a, num_cus, st);
     return hipGetLastError();
 }
 

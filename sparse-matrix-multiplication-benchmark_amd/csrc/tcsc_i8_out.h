@@ -1,7 +1,7 @@
 // tcsc_i8_out.h -- the epilogue arithmetic of the int8 call,
 // shared by every kernel that turns an exact i32 sum into Y: k_gemm8 and
-// k_reduce_i8 (tcsc_mfma.hip) and k_decode8 (tcsc_decode.hip).  One definition,
-// so the paths give the same bits.
+// k_reduce_i8 (tcsc_mfma.hip), k_decode8 and k_decode8q (tcsc_decode.hip).  One
+// definition, so the paths give the same bits.
 #pragma once
 #include <hip/hip_runtime.h>
 

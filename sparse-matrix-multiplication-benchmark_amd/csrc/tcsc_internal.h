@@ -425,6 +425,8 @@ hipError_t mfma8_gemm(const int8_t* x8, const int8_t* w8, int ld8, int K, int M,
                       hipStream_t st);
 // k_quant_rows_i8: per-row absmax quantization (tcsc_gpu_quantize_rows_i8)
 hipError_t quantize_rows_i8(const float* X, int M, int K, int8_t* Xq, float* scale, hipStream_t st);
+// the same on bf16 bit patterns, widened first (tcsc_gpu_quantize_rows_i8_bf16)
+hipError_t quantize_rows_i8_bf16(const uint16_t* X, int M, int K, int8_t* Xq, float* scale, hipStream_t st);
 
 // ---- int8 decode path (tcsc_decode.hip) -------------------------
 // The 2-bit image of a ternary W: tiles of kW2Cols columns x kW2Blk k, 1 KiB
@@ -480,6 +482,12 @@ int decode_tiles_per_wg(int M, int N, int num_cus);
 // exact i32 sum; X is M x K int8 of any alignment, read in place
 hipError_t decode_gemm(const int8_t* X, const uint32_t* w2, int K, int M, int N, const float* scale, const float* B,
                        float* Y, int ldy, bool prelu, float a, int num_cus, hipStream_t st);
+// k_decode8q: the quantizer and k_decode8 in one launch.  X is
+// M x K fp32 (bf16 false) or bf16 bit patterns (bf16 true) of any alignment,
+// read in place; scale_out[m] gets the quantizer's scale of row m, and Y the
+// bits of quantize_rows_i8{,_bf16} followed by decode_gemm
+hipError_t decode_gemm_q(const void* X, bool bf16, const uint32_t* w2, int K, int M, int N, float* scale_out,
+                         const float* B, float* Y, int ldy, bool prelu, float a, int num_cus, hipStream_t st);
 
 // Rewrites the flagged rows in k_stream's fast order (no-op when none is).
 hipError_t mfma_fixup(const uint16_t* x3, int M, int K, int ldk, const int* cq, const int* crq, int ncols,

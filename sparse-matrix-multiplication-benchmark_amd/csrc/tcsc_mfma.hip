@@ -37,6 +37,8 @@
 
 #include "tcsc_i8_out.h"
 #include "tcsc_internal.h"
+#include "tcsc_quant.h"
+#include "tcsc_xsrc.h"
 
 namespace tcsc {
 namespace {
@@ -1197,27 +1199,32 @@ __global__ void __launch_bounds__(WN * 64) k_gemm8w2(const int8_t* __restrict__ 
     gemm8_store<1, WN, FI, FJ, PRELU, PARTIAL, LDSB>(acc, lds, lane, 0, wave, m0, n0, M, N, scale, bias, out, ldy, a);
 }
 
-// tcsc_gpu_quantize_rows_i8: per row, amax = max |x|, scale = amax / 127, inv
-// = 127 / amax, q = clamp(rint(x * inv), -127, 127); amax = 0: q = 0, scale =
-// 0.  Every step is one correctly rounded fp32 operation.  One workgroup per
-// row, the row read twice (the second time from the L2).  VEC (K % 4 == 0, X
-// 16-B and Xq 4-B aligned): 16-B loads, 4-B stores of four q.
-template <bool VEC>
-__global__ void __launch_bounds__(256) k_quant_rows_i8(const float* __restrict__ X, int M, int K,
+// tcsc_gpu_quantize_rows_i8{,_bf16}: per row, amax = max |x|, scale = amax /
+// 127, inv = 127 / amax, q = clamp(rint(x * inv), -127, 127); amax = 0: q = 0,
+// scale = 0 (quant_scales and quant_i8, tcsc_quant.h).  Every step is one
+// correctly rounded fp32 operation; TX = uint16_t is bf16 bit patterns, widened
+// first (XSrc, exact).  One workgroup per row, the row read twice (the second
+// time from the L2).  VEC (K a multiple of the kVec elements of a 16-B load, X
+// 16-B and Xq kVec-B aligned): 16-B loads, stores of kVec q.
+template <typename TX, bool VEC>
+__global__ void __launch_bounds__(256) k_quant_rows_i8(const TX* __restrict__ X, int M, int K,
                                                       int8_t* __restrict__ Xq, float* __restrict__ scale) {
+    using XS = XSrc<TX>;
+    constexpr int kVec = XS::kVec;
     __shared__ float red[256];
     const int row = blockIdx.x;
-    const float* src = X + (size_t)row * K;
+    const TX* src = X + (size_t)row * K;
     int8_t* dst = Xq + (size_t)row * K;
     float amax = 0.0f;
     if (VEC) {
-        for (int q = threadIdx.x; q < K / 4; q += blockDim.x) {
-            const f32x4 w = *reinterpret_cast<const f32x4*>(src + 4 * q);
+        for (int q = threadIdx.x; q < K / kVec; q += blockDim.x) {
+            float w[kVec];
+            XS::unpack(*reinterpret_cast<const uint4*>(src + kVec * q), 1.0f, w);
 #pragma unroll
-            for (int u = 0; u < 4; ++u) amax = fmaxf(amax, fabsf(w[u]));
+            for (int u = 0; u < kVec; ++u) amax = fmaxf(amax, fabsf(w[u]));
         }
     } else {
-        for (int k = threadIdx.x; k < K; k += blockDim.x) amax = fmaxf(amax, fabsf(src[k]));
+        for (int k = threadIdx.x; k < K; k += blockDim.x) amax = fmaxf(amax, fabsf(XS::conv(src[k], 1.0f)));
     }
     red[threadIdx.x] = amax;
     __syncthreads();
@@ -1225,24 +1232,27 @@ __global__ void __launch_bounds__(256) k_quant_rows_i8(const float* __restrict__
         if ((int)threadIdx.x < s) red[threadIdx.x] = fmaxf(red[threadIdx.x], red[threadIdx.x + s]);
         __syncthreads();
     }
-    amax = red[0];
-    const bool zero = !(amax > 0.0f);
-    const float inv = zero ? 0.0f : __fdiv_rn(127.0f, amax);
-    if (threadIdx.x == 0) scale[row] = zero ? 0.0f : __fdiv_rn(amax, 127.0f);
-    auto quant = [&](float x) {
-        const float r = fminf(fmaxf(rintf(__fmul_rn(x, inv)), -127.0f), 127.0f);
-        return (int)r;
-    };
+    float sc, inv;
+    quant_scales(red[0], sc, inv);
+    if (threadIdx.x == 0) scale[row] = sc;
     if (VEC) {
-        for (int q = threadIdx.x; q < K / 4; q += blockDim.x) {
-            const f32x4 w = *reinterpret_cast<const f32x4*>(src + 4 * q);
-            uint32_t o = 0;
+        for (int q = threadIdx.x; q < K / kVec; q += blockDim.x) {
+            float w[kVec];
+            XS::unpack(*reinterpret_cast<const uint4*>(src + kVec * q), 1.0f, w);
+            uint32_t o[kVec / 4];
 #pragma unroll
-            for (int u = 0; u < 4; ++u) o |= ((uint32_t)quant(w[u]) & 0xffu) << (8 * u);
-            *reinterpret_cast<uint32_t*>(dst + 4 * q) = o;
+            for (int d = 0; d < kVec / 4; ++d) {
+                o[d] = 0;
+#pragma unroll
+                for (int u = 0; u < 4; ++u) o[d] |= ((uint32_t)quant_i8(w[4 * d + u], inv) & 0xffu) << (8 * u);
+            }
+            if constexpr (kVec == 4)
+                *reinterpret_cast<uint32_t*>(dst + kVec * q) = o[0];
+            else
+                *reinterpret_cast<uint2*>(dst + kVec * q) = make_uint2(o[0], o[1]);
         }
     } else {
-        for (int k = threadIdx.x; k < K; k += blockDim.x) dst[k] = (int8_t)quant(src[k]);
+        for (int k = threadIdx.x; k < K; k += blockDim.x) dst[k] = (int8_t)quant_i8(XS::conv(src[k], 1.0f), inv);
     }
 }
 
@@ -1496,14 +1506,23 @@ hipError_t mfma8_build_w8(const uint16_t* wt, int ncols, int K, int ldw, int8_t*
     return hipGetLastError();
 }
 
-hipError_t quantize_rows_i8(const float* X, int M, int K, int8_t* Xq, float* scale, hipStream_t st) {
+template <typename TX>
+static hipError_t launch_quant_rows(const TX* X, int M, int K, int8_t* Xq, float* scale, hipStream_t st) {
     if (M <= 0) return hipSuccess;
-    const bool vec = K % 4 == 0 && (reinterpret_cast<uintptr_t>(X) & 15) == 0 && (reinterpret_cast<uintptr_t>(Xq) & 3) == 0;
+    const bool vec = XSrc<TX>::vec_ok(X, K) && (reinterpret_cast<uintptr_t>(Xq) & (XSrc<TX>::kVec - 1)) == 0;
     if (vec)
-        hipLaunchKernelGGL(k_quant_rows_i8<true>, dim3(M), dim3(256), 0, st, X, M, K, Xq, scale);
+        hipLaunchKernelGGL((k_quant_rows_i8<TX, true>), dim3(M), dim3(256), 0, st, X, M, K, Xq, scale);
     else
-        hipLaunchKernelGGL(k_quant_rows_i8<false>, dim3(M), dim3(256), 0, st, X, M, K, Xq, scale);
+        hipLaunchKernelGGL((k_quant_rows_i8<TX, false>), dim3(M), dim3(256), 0, st, X, M, K, Xq, scale);
     return hipGetLastError();
+}
+
+hipError_t quantize_rows_i8(const float* X, int M, int K, int8_t* Xq, float* scale, hipStream_t st) {
+    return launch_quant_rows(X, M, K, Xq, scale, st);
+}
+
+hipError_t quantize_rows_i8_bf16(const uint16_t* X, int M, int K, int8_t* Xq, float* scale, hipStream_t st) {
+    return launch_quant_rows(X, M, K, Xq, scale, st);
 }
 
 // k_reduce_i8 on the slabs of a split int8 GEMM (k_gemm8 or k_gemm8w2)

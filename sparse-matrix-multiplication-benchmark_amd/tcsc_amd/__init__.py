@@ -56,6 +56,7 @@ EXPORTED_SYMBOLS = (
     "tcsc_gpu_plan_copy_w2",
     "tcsc_gpu_plan_create_packed_image", "tcsc_gpu_plan_create_packed_image_device", "tcsc_gpu_w2_to_tcsc",
     "tcsc_gpu_w2_from_tcsc_host", "tcsc_gpu_w2_to_tcsc_host",
+    "tcsc_gpu_quantize_rows_i8_bf16", "tcsc_gpu_sgemm_q8", "tcsc_gpu_launch_info_q8", "tcsc_gpu_quant_fuse_pays",
     # include/sparse/bcsr.h
     "bcsr_from_dense", "bcsr_sgemm_basic", "bcsr_sgemm_prelu_basic", "bcsr_sgemm_avx", "bcsr_sgemm_prelu_avx",
     "bcsr_sgemm_avx2", "bcsr_free",
@@ -177,6 +178,10 @@ def lib():
     L.tcsc_gpu_w2_from_tcsc_host.argtypes = [P, i, i, vp, C.c_size_t]
     L.tcsc_gpu_w2_to_tcsc_host.argtypes = [vp, C.c_size_t, i, i]
     L.tcsc_gpu_w2_to_tcsc_host.restype = P
+    L.tcsc_gpu_quantize_rows_i8_bf16.argtypes = [vp, i, i, vp, vp, vp]
+    L.tcsc_gpu_sgemm_q8.argtypes = [vp, vp, i, vp, vp, vp, vp, i, i, i, f, vp]
+    L.tcsc_gpu_launch_info_q8.argtypes = [vp, i, i, C.POINTER(i), C.POINTER(i), C.POINTER(i)]
+    L.tcsc_gpu_quant_fuse_pays.argtypes = [i, i, i, i]
     L.tcsc_gpu_prepare_x.argtypes = [vp, vp, i, vp]
     L.tcsc_gpu_sgemm_prepared.argtypes = [vp, vp, vp, i, i, i, f, vp]
     L.tcsc_gpu_from_dense.argtypes = [vp, i, i, vp, vp, vp, vp, C.POINTER(i), C.POINTER(i), vp]
@@ -709,6 +714,27 @@ class Plan:
                                        C.c_void_p(_ptr(B)), C.c_void_p(_ptr(Y)), int(M), int(ldy),
                                        VARIANT_ID[variant], float(a), C.c_void_p(stream)), "tcsc_gpu_sgemm_i8")
 
+    def sgemm_q8(self, X, Xq, scale, B, Y, M: int, ldy: int, variant: str = "prelu_basic", a: float = 0.2,
+                 stream: int = 0, xtype=None) -> None:
+        """The quantizer and :meth:`sgemm_i8` in one call (tcsc_gpu_sgemm_q8): X is M x K contiguous fp32 or bf16
+        (a torch tensor, whose dtype says which, or a pointer with xtype 'f32' / 'bf16'), scale (M floats) is
+        written, Xq (M x K int8) is scratch -- untouched, and allowed to be None, where the call is fused
+        (:meth:`launch_info_q8`).  Y and scale get the bits of :func:`quantize_rows_i8` + :meth:`sgemm_i8`."""
+        xt = _xtype_of(X) if xtype is None else _xtype(xtype)
+        _check(lib().tcsc_gpu_sgemm_q8(self.handle, C.c_void_p(_ptr(X)), xt, C.c_void_p(_ptr(Xq)),
+                                       C.c_void_p(_ptr(scale)), C.c_void_p(_ptr(B)), C.c_void_p(_ptr(Y)), int(M),
+                                       int(ldy), VARIANT_ID[variant], float(a), C.c_void_p(stream)),
+               "tcsc_gpu_sgemm_q8")
+
+    def launch_info_q8(self, M: int, dtype="f32") -> tuple[str, int, bool]:
+        """(path, K slices, fused) of an :meth:`sgemm_q8` launch of M rows of that dtype ('f32', 'bf16' or a
+        torch dtype): the int8 route, and whether the quantizer runs inside the decode kernel
+        (tcsc_gpu_launch_info_q8)."""
+        path, slices, fused = C.c_int(), C.c_int(), C.c_int()
+        _check(lib().tcsc_gpu_launch_info_q8(self.handle, int(M), _xtype(dtype), C.byref(path), C.byref(slices),
+                                             C.byref(fused)), "tcsc_gpu_launch_info_q8")
+        return ("gather", "fused", "mfma", "small", "decode")[path.value], slices.value, bool(fused.value)
+
     def sgemm_t(self, G, DX, M: int, ldx: int, stream: int = 0) -> None:
         """dX (M x K, pitch ldx) = G (M x plan rows, contiguous) . W[:, range]^T on a transposed
         plan (tcsc_gpu_sgemm_t); TcscError on a plan that :meth:`transposed` did not make."""
@@ -769,13 +795,41 @@ def gpu_transpose_index(rows: int, cols: int, d_csp, d_csn, d_rip, d_rin, col_be
            "tcsc_gpu_transpose_index")
 
 
+XTYPE_ID = {"f32": 0, "bf16": 1}
+
+
+def _xtype(spec) -> int:
+    """enum tcsc_xtype of 'f32' / 'bf16', a torch dtype, or the enum's own integer (passed on as it is)."""
+    if isinstance(spec, int):
+        return spec
+    if isinstance(spec, str) and spec in XTYPE_ID:
+        return XTYPE_ID[spec]
+    name = str(spec)
+    if name in ("torch.float32", "torch.bfloat16"):
+        return int(name == "torch.bfloat16")
+    raise TcscError(f"activations must be fp32 or bf16 ('f32', 'bf16' or the torch dtype), got {spec!r}")
+
+
+def _xtype_of(X) -> int:
+    """enum tcsc_xtype of a buffer: a tensor's dtype says; a raw pointer or None counts as fp32."""
+    dt = getattr(X, "dtype", None)
+    return 0 if dt is None else _xtype(dt)
+
+
 def quantize_rows_i8(X, Xq, scale, M: int, K: int, stream: int = 0) -> None:
-    """Per-row absmax quantization on the device (tcsc_gpu_quantize_rows_i8): X is M x K contiguous fp32;
-    Xq (M x K int8) and scale (M floats) are written: scale = amax / 127, q = clamp(rint(x * (127 / amax)),
-    -127, 127), a row of zeros gives q = 0 and scale = 0."""
-    _check(lib().tcsc_gpu_quantize_rows_i8(C.c_void_p(_ptr(X)), int(M), int(K), C.c_void_p(_ptr(Xq)),
-                                           C.c_void_p(_ptr(scale)), C.c_void_p(stream)),
-           "tcsc_gpu_quantize_rows_i8")
+    """Per-row absmax quantization on the device (tcsc_gpu_quantize_rows_i8, or _bf16 for a torch.bfloat16 X):
+    X is M x K contiguous fp32 or bf16; Xq (M x K int8) and scale (M floats) are written: scale = amax / 127,
+    q = clamp(rint(x * (127 / amax)), -127, 127), a row of zeros gives q = 0 and scale = 0.  bf16 values are
+    widened to fp32 first (exact)."""
+    name = "tcsc_gpu_quantize_rows_i8_bf16" if _xtype_of(X) else "tcsc_gpu_quantize_rows_i8"
+    _check(getattr(lib(), name)(C.c_void_p(_ptr(X)), int(M), int(K), C.c_void_p(_ptr(Xq)),
+                                C.c_void_p(_ptr(scale)), C.c_void_p(stream)), name)
+
+
+def quant_fuse_pays(M: int, K: int, N: int, dtype="f32") -> bool:
+    """The default rule for fusing the quantizer into the decode call (tcsc_gpu_quant_fuse_pays; host
+    arithmetic): whether :meth:`Plan.sgemm_q8` of M rows of that dtype on a K x N decode route runs one kernel."""
+    return bool(lib().tcsc_gpu_quant_fuse_pays(int(M), int(K), int(N), _xtype(dtype)))
 
 
 def w2_image_bytes(K: int, N: int) -> int:

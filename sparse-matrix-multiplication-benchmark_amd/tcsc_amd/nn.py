@@ -17,7 +17,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from . import Plan, TcscError, TcscMatrix, prelu_backward, quantize_rows_i8, w2_image_bytes
+from . import Plan, TcscError, TcscMatrix, prelu_backward, w2_image_bytes
 
 __all__ = ["TernaryLinear", "PackedTernaryLinear"]
 
@@ -160,13 +160,15 @@ def _define():
             return self._i8_xq, self._i8_scale
 
         def forward_int8(self, x):
-            """Inference with int8 activations: the rows of the fp32 x are quantized per row
-            (``tcsc_amd.quantize_rows_i8``) into buffers the layer keeps, then ``Plan.sgemm_i8`` computes
-            ``act(scale * (q . W) + bias)`` on the current stream.  On the int8 MFMA path after
+            """Inference with int8 activations: ``Plan.sgemm_q8`` quantizes the rows of the fp32 or bf16 x per
+            row (the arithmetic of ``tcsc_amd.quantize_rows_i8``; the scales, and off the fused route the int8
+            copy, go into buffers the layer keeps) and computes ``act(scale * (q . W) + bias)`` on the current
+            stream -- in one launch where the call decodes and fusing pays, as the quantizer followed by
+            ``Plan.sgemm_i8`` elsewhere, with the same bits either way.  On the int8 MFMA path after
             ``reserve(rows, int8=True)``; without the image the gather serves the call.  No backward:
             raises when grad is enabled and x requires grad."""
-            if not torch.is_tensor(x) or x.dtype != torch.float32 or not x.is_cuda:
-                raise TcscError("TernaryLinear.forward_int8: x must be an fp32 CUDA tensor")
+            if not torch.is_tensor(x) or x.dtype not in (torch.float32, torch.bfloat16) or not x.is_cuda:
+                raise TcscError("TernaryLinear.forward_int8: x must be an fp32 or bf16 CUDA tensor")
             if torch.is_grad_enabled() and x.requires_grad:
                 raise TcscError("TernaryLinear.forward_int8 is inference only: x requires grad")
             if x.device.index != self.device_index or self.bias.device != x.device:
@@ -180,11 +182,10 @@ def _define():
             xq, scale = self._i8_buffers(M)
             stream = _stream(x.device)
             y = torch.empty((M, N), dtype=torch.float32, device=x.device)
-            quantize_rows_i8(x2, xq, scale, M, K, stream)
             if self.a is None:
-                self.plan.sgemm_i8(xq, scale, self.bias.detach(), y, M, N, "basic", 0.0, stream)
+                self.plan.sgemm_q8(x2, xq, scale, self.bias.detach(), y, M, N, "basic", 0.0, stream)
             else:
-                self.plan.sgemm_i8(xq, scale, self.bias.detach(), y, M, N, "prelu_basic", self.a, stream)
+                self.plan.sgemm_q8(x2, xq, scale, self.bias.detach(), y, M, N, "prelu_basic", self.a, stream)
             return y.reshape(*lead, N)
 
         def forward(self, x):
@@ -209,9 +210,10 @@ def _define():
         layer holds the 2-bit image alone, a quarter byte per weight.
 
         W, bias, a, device: as :class:`TernaryLinear` takes them; the bias is a buffer, not a parameter.
-        ``forward`` takes an fp32 CUDA tensor of shape (..., K), quantizes its rows to int8
-        (``tcsc_amd.quantize_rows_i8``) into buffers the layer keeps and calls ``Plan.sgemm_i8``: k_decode8 up
-        to 16 rows, k_gemm8w2 above -- the bits of ``TernaryLinear.forward_int8`` on the int8 MFMA path.
+        ``forward`` takes an fp32 or bf16 CUDA tensor of shape (..., K) and calls ``Plan.sgemm_q8``, which
+        quantizes its rows to int8 (the arithmetic of ``tcsc_amd.quantize_rows_i8``) and multiplies: up to 16
+        rows k_decode8q in one launch where fusing pays, the quantizer and k_decode8 elsewhere, k_gemm8w2
+        above -- the bits of ``TernaryLinear.forward_int8`` on the int8 MFMA path.
         There is no backward and no transposed plan: it raises when grad is enabled and x requires grad.
         """
 
@@ -299,8 +301,8 @@ def _define():
 
         def forward(self, x):
             plan = self._loaded_plan("forward")
-            if not torch.is_tensor(x) or x.dtype != torch.float32 or not x.is_cuda:
-                raise TcscError("PackedTernaryLinear: x must be an fp32 CUDA tensor")
+            if not torch.is_tensor(x) or x.dtype not in (torch.float32, torch.bfloat16) or not x.is_cuda:
+                raise TcscError("PackedTernaryLinear: x must be an fp32 or bf16 CUDA tensor")
             if torch.is_grad_enabled() and x.requires_grad:
                 raise TcscError("PackedTernaryLinear is inference only: x requires grad")
             if x.device.index != self.device_index or self.bias.device != x.device:
@@ -315,9 +317,8 @@ def _define():
             xq, scale = self._quant_buffers(M)
             stream = _stream(x.device)
             y = torch.empty((M, N), dtype=torch.float32, device=x.device)
-            quantize_rows_i8(x2, xq, scale, M, K, stream)
             variant, a = ("basic", 0.0) if self.a is None else ("prelu_basic", self.a)
-            plan.sgemm_i8(xq, scale, self.bias, y, M, N, variant, a, stream)
+            plan.sgemm_q8(x2, xq, scale, self.bias, y, M, N, variant, a, stream)
             return y.reshape(*lead, N)
 
         def extra_repr(self) -> str:
