@@ -162,6 +162,24 @@ int tcsc_gpu_launch_geometry(const tcsc_gpu_plan *plan, int M, int *cols_per_wav
  * columns on num_cus CUs take fewer column-rounds with 352-column workgroups
  * than with 256-column ones, weighted by the measured cost per column. */
 int tcsc_gpu_wide_pays(int M, int ncols, int num_cus);
+/* The slot map of a plan's 22-column streams and what it buys (read-only; an
+ * error on a plan without them).  A workgroup of k_stream_w covers a block of
+ * 352 columns with 16 waves of 22 slots; slot j of wave w of block b owns the
+ * block's column map[b * 352 + w * 22 + j].  tcsc_gpu_plan_reserve deals every
+ * full block's columns to its waves so that the busiest wave of each 48-row
+ * chunk of K, for which the other 15 wait, has fewer entries; the last, partial
+ * block, and every block of a plan reserved under TCSC_WIDE_BALANCE=0, keep
+ * the identity (wave w owns columns 22 w .. 22 w + 21).  Outputs are the same
+ * bits under any map.  With L[w][c] = the nonzeros of wave w's columns in
+ * chunk c:
+ *   stats[0], stats[1]  sum over blocks and chunks of max_w L[w][c], for the
+ *                       identity and for the map in use
+ *   stats[2], stats[3]  the (wave, chunk) streams with L[w][c] > 30, the
+ *                       kernel's scalar entry buffer, for either
+ * map (may be NULL, like stats) receives the map: map_entries must be
+ * 352 * ceil(cols / 352).  Copies from the device and synchronises. */
+int tcsc_gpu_plan_wide_stats(const tcsc_gpu_plan *plan, long long stats[4], unsigned short *map,
+                             size_t map_entries);
 
 /* Allocate the plan's workspace for launches of up to `max_M` rows: X^T
  * (K x max_M rounded up to 256 floats; the kernel streams X^T rows into LDS)

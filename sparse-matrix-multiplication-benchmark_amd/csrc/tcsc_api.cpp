@@ -85,6 +85,11 @@ struct tcsc_gpu_plan {
     int* sptr_w = nullptr;
     long long n_entries_w = 0;
     int n_groups_w = 0;
+    // the wide streams' slot map (which columns of a column block each wave
+    // owns: tcsc::wide_blocks_for(cols) x 352 entries, k_wide_balance) and its
+    // statistics as tcsc_gpu_plan_wide_stats reports them
+    unsigned short* wperm = nullptr;
+    long long wide_stats[4] = {0, 0, 0, 0};
     size_t wide_bytes = 0;
     // transposed plans (tcsc_gpu_plan_create_transposed*): `cols` zeros, the
     // bias tcsc_gpu_sgemm_t hands to the launch; null on every other plan
@@ -854,31 +859,49 @@ int build_wide(tcsc_gpu_plan* p) {
     const int nch = p->n_chunks, G = p->n_groups, ncols = p->cols, Gw = tcsc::wide_groups_for(ncols);
     const long long nc = (long long)nch * ncols, ng = (long long)nch * Gw;
     if (nch <= 0 || ng + 1 > 0x7fffffffLL) return TCSC_OK;
-    DevBuf cnt, cptr, gcnt, tmp;
+    // $TCSC_WIDE_BALANCE=0 keeps every wave on its contiguous 22 columns (the
+    // identity slot map: the A/B of the balanced assignment); read here only
+    const char* bal_s = std::getenv("TCSC_WIDE_BALANCE");
+    const int balance = bal_s && std::atoi(bal_s) == 0 ? 0 : 1;
+    const size_t nmap = (size_t)tcsc::wide_blocks_for(ncols) * tcsc::kWideWgCols;
+    DevBuf cnt, cptr, gcnt, tmp, loads, winv, wstats;
     size_t tb1 = 0, tb2 = 0;
     HIP_TRY(tcsc::plan_scan_tmp_bytes(nc + 1, &tb1));
     HIP_TRY(tcsc::plan_scan_tmp_bytes(ng + 1, &tb2));
     const size_t tb = std::max(tb1, tb2);
     int* sptr_w = nullptr;
+    unsigned short* wperm = nullptr;
     if (cnt.alloc((size_t)(nc + 1) * sizeof(int)) != hipSuccess || cptr.alloc((size_t)(nc + 1) * sizeof(int)) != hipSuccess ||
         gcnt.alloc((size_t)(ng + 1) * sizeof(int)) != hipSuccess || tmp.alloc(tb) != hipSuccess ||
+        loads.alloc(nmap / tcsc::kWideCW * nch * sizeof(int)) != hipSuccess ||
+        winv.alloc((size_t)ncols * sizeof(unsigned short)) != hipSuccess ||
+        wstats.alloc(4 * sizeof(unsigned long long)) != hipSuccess ||
         hipMalloc(&sptr_w, (size_t)(ng + 1) * sizeof(int)) != hipSuccess) {
         (void)hipGetLastError();
         return TCSC_OK;
     }
     std::unique_ptr<int, void (*)(int*)> sptr_guard(sptr_w, [](int* q) { (void)hipFree(q); });
+    if (hipMalloc(&wperm, nmap * sizeof(unsigned short)) != hipSuccess) {
+        (void)hipGetLastError();
+        return TCSC_OK;
+    }
+    std::unique_ptr<unsigned short, void (*)(unsigned short*)> wperm_guard(wperm, [](unsigned short* q) { (void)hipFree(q); });
     HIP_TRY(hipDeviceSynchronize());  // the plan's streams are complete (built on the creator's stream)
-    HIP_TRY(tcsc::wide_counts(p->ent, p->sptr, G, nch, ncols, Gw, cnt.as<int>(), cptr.as<int>(), gcnt.as<int>(), sptr_w,
+    HIP_TRY(tcsc::wide_counts(p->ent, p->sptr, G, nch, ncols, Gw, balance, cnt.as<int>(), cptr.as<int>(), gcnt.as<int>(),
+                              sptr_w, loads.as<int>(), wperm, winv.as<unsigned short>(), wstats.as<unsigned long long>(),
                               tmp.p, tb, st));
     int total = 0;
+    unsigned long long stats[4] = {0, 0, 0, 0};
     HIP_TRY(hipMemcpyAsync(&total, sptr_w + ng, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(stats, wstats.p, sizeof stats, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     int2* ent_w = nullptr;
     if (hipMalloc(&ent_w, (size_t)(total + tcsc::kEntGuard) * sizeof(int2)) != hipSuccess) {
         (void)hipGetLastError();
         return TCSC_OK;
     }
-    hipError_t e = tcsc::wide_fill(p->ent, p->sptr, G, nch, ncols, Gw, cptr.as<int>(), sptr_w, ent_w, total, st);
+    hipError_t e = tcsc::wide_fill(p->ent, p->sptr, G, nch, ncols, Gw, cptr.as<int>(), winv.as<unsigned short>(), sptr_w,
+                                   ent_w, total, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);  // the scratch is freed on return
     if (e != hipSuccess) {
         (void)hipFree(ent_w);
@@ -886,9 +909,12 @@ int build_wide(tcsc_gpu_plan* p) {
     }
     p->ent_w = ent_w;
     p->sptr_w = sptr_guard.release();
+    p->wperm = wperm_guard.release();
+    for (int i = 0; i < 4; ++i) p->wide_stats[i] = (long long)stats[i];
     p->n_entries_w = total;
     p->n_groups_w = Gw;
-    p->wide_bytes = (size_t)(ng + 1) * sizeof(int) + (size_t)(total + tcsc::kEntGuard) * sizeof(int2);
+    p->wide_bytes = (size_t)(ng + 1) * sizeof(int) + (size_t)(total + tcsc::kEntGuard) * sizeof(int2) +
+                    nmap * sizeof(unsigned short);
     return TCSC_OK;
 }
 
@@ -1176,6 +1202,7 @@ int tcsc::sgemm_ws(const tcsc_gpu_plan* p, const void* dX, const float* dB, floa
             g.geo = r.geo;
             g.ent = p->ent_w;
             g.sptr = p->sptr_w;
+            g.wperm = p->wperm;
             g.n_entries = p->n_entries_w;
             g.n_groups = p->n_groups_w;
             g.slices = 1;
@@ -1699,6 +1726,7 @@ void tcsc_gpu_plan_destroy(tcsc_gpu_plan* p) {
     if (p->tbias) (void)hipFree(p->tbias);
     if (p->ent_w) (void)hipFree(p->ent_w);
     if (p->sptr_w) (void)hipFree(p->sptr_w);
+    if (p->wperm) (void)hipFree(p->wperm);
     free_mfma(p);
     free_csc(p);
     tcsc_gpu_plan_destroy(p->chain_pos);
@@ -1781,6 +1809,29 @@ int tcsc_gpu_launch_info_i8(const tcsc_gpu_plan* p, int M, int* path, int* slice
 }
 
 int tcsc_gpu_wide_pays(int M, int ncols, int num_cus) { return wide_pays(M, ncols, num_cus) ? 1 : 0; }
+
+int tcsc_gpu_plan_wide_stats(const tcsc_gpu_plan* p, long long stats[4], unsigned short* map, size_t map_entries) {
+    if (!p || (!stats && !map)) {
+        set_error("tcsc_gpu_plan_wide_stats: bad arguments");
+        return TCSC_E_ARG;
+    }
+    if (!p->ent_w || !p->wperm) {
+        set_error("tcsc_gpu_plan_wide_stats: the plan has no wide streams (tcsc_gpu_plan_reserve builds them)");
+        return TCSC_E_ARG;
+    }
+    if (stats)
+        for (int i = 0; i < 4; ++i) stats[i] = p->wide_stats[i];
+    if (map) {
+        const size_t nmap = (size_t)tcsc::wide_blocks_for(p->cols) * tcsc::kWideWgCols;
+        if (map_entries != nmap) {
+            set_error("tcsc_gpu_plan_wide_stats: the map has %zu entries, not %zu", nmap, map_entries);
+            return TCSC_E_ARG;
+        }
+        DeviceGuard dg(p->device);
+        HIP_TRY(hipMemcpy(map, p->wperm, nmap * sizeof(unsigned short), hipMemcpyDeviceToHost));
+    }
+    return TCSC_OK;
+}
 
 int tcsc_gpu_launch_geometry(const tcsc_gpu_plan* p, int M, int* cols_per_wave) {
     if (!p || M < 0 || !cols_per_wave) {

@@ -146,6 +146,9 @@ __host__ __device__ constexpr int wide_group_col0(int g) { return (g / kWaves) *
 __host__ __device__ constexpr int wide_groups_for(int ncols) {
     return (ncols / kWideWgCols) * kWaves + (ncols % kWideWgCols + kWideCW - 1) / kWideCW;
 }
+// column blocks (workgroup columns) of ncols columns; the slot map has kWideWgCols 16-bit entries for each:
+// slot j of wave w of block b owns the block's column wperm[b * kWideWgCols + w * kWideCW + j]
+__host__ __device__ constexpr int wide_blocks_for(int ncols) { return (ncols + kWideWgCols - 1) / kWideWgCols; }
 
 // Input TCSC arrays (device pointers, absolute offsets as in tcsc_t) and the
 // column range a plan covers.
@@ -209,8 +212,9 @@ struct GemmArgs {
     long long n_entries2 = 0;
     int n_groups = 0;
     // columns per wave: kCW (k_stream) or kWideCW (k_stream_w: ent, sptr, n_entries and n_groups
-    // are the wide streams; unsplit K, order 0)
+    // are the wide streams and wperm their slot map; unsplit K, order 0)
     int geo = kCW;
+    const unsigned short* wperm = nullptr;
     int ncols = 0;
     const float* B = nullptr;
     float* Y = nullptr;
@@ -259,15 +263,20 @@ size_t xt_bytes(int M, int K);
 hipError_t launch_gemm(const GemmArgs& g, hipStream_t st);
 // The wide geometry (tcsc_wide.hip).  wide_counts / wide_fill re-group a
 // plan's 16-column streams (ent, sptr: G groups x nch chunks) into Gw =
-// wide_groups_for(ncols) 22-column ones: cnt, cptr (nch*ncols + 1 ints each)
-// and gcnt (Gw*nch + 1) are scratch, tmp serves plan_scan_tmp_bytes of either
-// length; sptr_w (Gw*nch + 1) ends in the entry count, and ent_w holds that
-// many entries + kEntGuard.  launch_stream_wide is launch_gemm's gather
-// launch for GemmArgs::geo == kWideCW.
-hipError_t wide_counts(const int2* ent, const int* sptr, int G, int nch, int ncols, int Gw, int* cnt, int* cptr,
-                       int* gcnt, int* sptr_w, void* tmp, size_t tmp_bytes, hipStream_t st);
+// wide_groups_for(ncols) 22-column ones: cnt, cptr (nch*ncols + 1 ints each),
+// gcnt (Gw*nch + 1), loads (wide_blocks_for(ncols) * kWaves * nch ints) and
+// winv (ncols 16-bit entries, the slot map's inverse) are scratch, tmp serves
+// plan_scan_tmp_bytes of either length; wperm (wide_blocks_for(ncols) *
+// kWideWgCols 16-bit entries) is the slot map, balanced where `balance` is
+// set and the identity otherwise, and wstats[4] its statistics
+// (tcsc_gpu_plan_wide_stats); sptr_w (Gw*nch + 1) ends in the entry count, and
+// ent_w holds that many entries + kEntGuard.  launch_stream_wide is
+// launch_gemm's gather launch for GemmArgs::geo == kWideCW.
+hipError_t wide_counts(const int2* ent, const int* sptr, int G, int nch, int ncols, int Gw, int balance, int* cnt,
+                       int* cptr, int* gcnt, int* sptr_w, int* loads, unsigned short* wperm, unsigned short* winv,
+                       unsigned long long* wstats, void* tmp, size_t tmp_bytes, hipStream_t st);
 hipError_t wide_fill(const int2* ent, const int* sptr, int G, int nch, int ncols, int Gw, const int* cptr,
-                     const int* sptr_w, int2* ent_w, long long n_entries, hipStream_t st);
+                     const unsigned short* winv, const int* sptr_w, int2* ent_w, long long n_entries, hipStream_t st);
 hipError_t launch_stream_wide(const GemmArgs& g, hipStream_t st);
 // tcsc_from_dense on the device
 // tile counts cp/cn ([row tile][col], dense_tile_rows(rows) rows per tile)

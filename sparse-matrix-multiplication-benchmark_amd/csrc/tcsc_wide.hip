@@ -26,8 +26,14 @@
 //    DMA waves) instead of twelve per-lane offsets;
 //  * the chunk loop has only s0..s35 beside the gather's pinned SGPRs, so the
 //    epilogue reads its arguments and recomputes its tile after the loop;
-//  * the epilogue parks 88-byte row pieces with 8-byte LDS stores into rows of
-//    1408 + 16 bytes and stores each tile row as 88 quads;
+//  * which 22 of a column block's 352 columns a wave owns is a plan-time
+//    choice, the slot map wperm[block][16 * 22] (k_wide_balance: the busiest
+//    wave ends every chunk, so the columns are dealt to level the waves'
+//    entries per chunk).  The chunk loop does not know: only the streams
+//    (wide_counts / wide_fill) and the epilogue's parking read the map;
+//  * the epilogue parks each slot's column with 4-byte LDS stores at the
+//    map's position in rows of 1408 + 16 bytes and stores each tile row as
+//    88 quads;
 //  * the streams are re-grouped from the plan's 16-column streams on the
 //    device (wide_counts / wide_fill), so a plan needs nothing but its own
 //    arrays to grow the second copy.
@@ -162,7 +168,7 @@ constexpr int kStrideW = kWideWgCols * 4 + 16;        // bytes per parked tile r
 constexpr int kLdsBytesW = kRingBytes + kPfScratch;
 static_assert(kEpiRowsW * kStrideW <= kRingBytes, "the epilogue staging fits below the ring's end");
 static_assert(kLdsBytesW <= 160 * 1024, "LDS");
-static_assert((kWideCW * 4) % 8 == 0 && kWideCW % 2 == 0, "a wave's parked row piece is whole 8-byte pairs");
+static_assert(kWideCW <= 64 && kWideWgCols <= 65535, "one lane per slot reads its 16-bit column position");
 static_assert(kWideWgCols % 4 == 0 && kWideWgCols / 4 > 64 && kWideWgCols / 4 <= 128,
               "a tile row is 64 quads plus a second, partial set");
 
@@ -171,14 +177,15 @@ static_assert(kWideWgCols % 4 == 0 && kWideWgCols / 4 > 64 && kWideWgCols / 4 <=
 // The kernel's arguments as the kernarg segment lays them out (each at its
 // natural alignment, in order).  The chunk loop has 36 SGPRs beside the 66 the
 // gather pins (a 30-entry scalar buffer, header and chain pointer), so what
-// only the epilogue needs (Bias, Y, ldy, a, M, ncols) is read from the kernarg
-// segment after the loop instead of living in SGPRs across it.
+// only the epilogue needs (Bias, Y, wperm, ldy, a, M, ncols) is read from the
+// kernarg segment after the loop instead of living in SGPRs across it.
 struct WideArgs {
     const float* XT;
     const int2* ent;
     const int* sptr;
     const float* Bias;
     float* Y;
+    const unsigned short* wperm;
     long long n_entries;
     int ldxt, M, G, ncols, nch, ldy;
     float a;
@@ -188,8 +195,9 @@ struct WideArgs {
 template <bool BIAS_FIRST, bool PRELU>
 __global__ void __launch_bounds__(kWaves * 64, kWavesPerSimd)
 k_stream_w(const float* __restrict__ XT, const int2* __restrict__ ent, const int* __restrict__ sptr,
-           const float* __restrict__ Bias0, float* __restrict__ Y0, long long n_entries, int ldxt, int M0, int G,
-           int ncols0, int nch, int ldy0, float a0, int pf_dist, int pf_lines) {
+           const float* __restrict__ Bias0, float* __restrict__ Y0, const unsigned short* __restrict__ wperm0,
+           long long n_entries, int ldxt, int M0, int G, int ncols0, int nch, int ldy0, float a0, int pf_dist,
+           int pf_lines) {
     __shared__ __attribute__((aligned(16))) char lds[kLdsBytesW];
     const int lane = threadIdx.x & 63;
     const unsigned lane16 = 16u * lane;
@@ -203,8 +211,9 @@ k_stream_w(const float* __restrict__ XT, const int2* __restrict__ ent, const int
     AccW acc;
     acc_zero(acc);
     if (BIAS_FIRST && active) {
-        const int cb = wide_group_col0(g) + lane;
-        const float bv = (lane < kWideCW && cb < ncols0) ? Bias0[cb] : 0.f;
+        // slot j's column through the slot map (the identity on a partial block: cb < ncols there)
+        const int cb = lane < kWideCW ? tcb * kWideWgCols + wperm0[tcb * kWideWgCols + wave * kWideCW + lane] : ncols0;
+        const float bv = cb < ncols0 ? Bias0[cb] : 0.f;
 #pragma unroll
         for (int j = 0; j < kWideCW; ++j) {
             const float b = __shfl(bv, j);
@@ -264,10 +273,11 @@ k_stream_w(const float* __restrict__ XT, const int2* __restrict__ ent, const int
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     }
 
-    // Epilogue (k_stream's, OUT 0 / HOW 0): per pass of 64 tile rows every wave
-    // parks its 64 x 22 block -- 88-byte row pieces, 8-byte stores -- then each
-    // wave reads back whole tile rows (wave, wave + 16, ...) as 88 quads: lane l
-    // stores quad l, lanes 0..23 also quad 64 + l.
+    // Epilogue (k_stream's, OUT 0 / HOW 0): per pass of 64 tile rows (every
+    // fourth: lane l holds tile rows 4 l .. 4 l + 3) every wave parks its 64 x 22
+    // block -- slot j at the column the slot map gives it, 4-byte stores -- then
+    // each wave reads back whole parked rows (wave, wave + 16, ...) as 88 quads:
+    // lane l stores quad l, lanes 0..23 also quad 64 + l.
     __syncthreads();  // every wave is done with the tile ring
     // the epilogue's arguments, read now (see WideArgs): the empty asm keeps the loads below it
     typedef __attribute__((address_space(4))) const WideArgs const_args;
@@ -286,9 +296,14 @@ k_stream_w(const float* __restrict__ XT, const int2* __restrict__ ent, const int
     xcd_tile_w(bx, by, gx, gy, tcb_e, trt_e);
     const bool active_e = tcb_e * kWaves + wave_e < E->G;
     const int m0_e = trt_e * kTM;
-    constexpr int kLanesPerPass = kEpiRowsW / 4;
+    static_assert(kEpiRowsW == 64 && kTM == 4 * kEpiRowsW, "a pass parks one of each lane's four rows");
     constexpr int kQuads = kWideWgCols / 4;
-    const int pcol = kWideCW * wave_e;  // this wave's first column in a parked row
+    // this wave's 22 column positions in a parked row (the slot map): one 16-bit load per lane, uniform per slot
+    const unsigned short* __restrict__ wperm = E->wperm;
+    const int posv = lane < kWideCW ? wperm[tcb_e * kWideWgCols + wave_e * kWideCW + lane] : 0;
+    int pos[kWideCW];
+#pragma unroll
+    for (int j = 0; j < kWideCW; ++j) pos[j] = __builtin_amdgcn_readlane(posv, j);
     const bool vec_ok = (ldy & 3) == 0 && ((reinterpret_cast<uintptr_t>(Y) & 15) == 0);
     float4 bq[2];
 #pragma unroll
@@ -302,22 +317,18 @@ k_stream_w(const float* __restrict__ XT, const int2* __restrict__ ent, const int
     }
 #pragma unroll
     for (int h = 0; h < kTM / kEpiRowsW; ++h) {
-        if (active_e && lane / kLanesPerPass == h) {
-            const int lh = lane % kLanesPerPass;
+        // pass h: row h of every lane's four (tile row 4 * lane + h) into parked row `lane`, all 64 lanes
+        // storing: 22 LDS stores per wave and pass
+        if (active_e) {
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int R = 4 * lh + r;
-#pragma unroll
-                for (int j = 0; j < kWideCW; j += 2)
-                    *reinterpret_cast<float2*>(lds + R * kStrideW + (pcol + j) * 4) =
-                        make_float2(acc_get(acc, 4 * j + r), acc_get(acc, 4 * (j + 1) + r));
-            }
+            for (int j = 0; j < kWideCW; ++j)
+                *reinterpret_cast<float*>(lds + lane * kStrideW + pos[j] * 4) = acc_get(acc, 4 * j + h);
         }
         __syncthreads();
 #pragma unroll
         for (int i = 0; i < kEpiRowsW / kWaves; ++i) {
             const int R = wave_e + kWaves * i;
-            const int row = m0_e + kEpiRowsW * h + R;
+            const int row = m0_e + 4 * R + h;
 #pragma unroll
             for (int s = 0; s < 2; ++s) {
                 const int q = lane + 64 * s;
@@ -357,11 +368,12 @@ k_stream_w(const float* __restrict__ XT, const int2* __restrict__ ent, const int
 // ---------------------------------------------------------------------------
 // The wide streams from the plan's own 16-column streams
 // ---------------------------------------------------------------------------
-// A (group, chunk) stream lists its columns one after the other, each
-// column's entries in ascending k, so a 22-column stream is the matching
-// column ranges of two or three 16-column streams of the same chunk, in
-// order.  One thread walks one 16-column stream; only it touches the
-// (chunk, column) cells of its group, so nothing is atomic.
+// A (group, chunk) stream lists its slots' columns one after the other, each
+// column's entries in ascending k, so a 22-column stream is runs of entries
+// of the 16-column streams of the same chunk that hold its columns (the slot
+// map below says which), each run as it stands.  One thread walks one
+// 16-column stream; only it touches the (chunk, column) cells of its group,
+// so nothing is atomic.
 
 namespace {
 
@@ -400,7 +412,173 @@ __global__ void k_wide_col_counts(const int2* __restrict__ ent, const int* __res
     }
 }
 
-// gcnt[gw*nch + c] = header + entries of wide group gw in chunk c (group-major)
+// ---- the slot map ----------------------------------------------------------
+// wperm[b * 352 + w * 22 + j] = the column (0..351, inside block b) that slot j
+// of wave w owns; winv[col] = w * 22 + j, its inverse over the plan's columns.
+// Every wave waits at the chunk barrier for the wave with the most entries in
+// that chunk, so a block's cost is about sum_c max_w L[w][c], L[w][c] = the
+// entries of wave w's columns in chunk c.  One workgroup per column block
+// deals the block's columns to its 16 waves, heaviest column first (ties: the
+// lower column), each to the wave with a free slot whose chunk profile it
+// overlaps least: the smallest sum_c L[w][c] * cnt[c][col], in 64-bit integers,
+// ties to the lowest wave.  Slots fill in that order.  The result is kept only
+// where sum_c max_w L[w][c] is strictly below the contiguous assignment's; the
+// last, partial block and every block under balance == 0 keep the identity.
+// Integer arithmetic in a fixed order: the same W gives the same map.  L is
+// 16 * nch ints per block in global memory (any number of chunks).
+template <typename T>
+__device__ __forceinline__ T wave_sum(T v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+
+__global__ void __launch_bounds__(kWaves * 64)
+k_wide_balance(const int* __restrict__ cnt, int ncols, int nch, int balance, int* L0, unsigned short* __restrict__ wperm,
+               unsigned short* __restrict__ winv) {
+    __shared__ int tot[kWideWgCols];
+    __shared__ unsigned short order[kWideWgCols], cand[kWideWgCols];
+    __shared__ int nslot[kWaves];
+    __shared__ unsigned long long score[kWaves], red[2][kWaves];
+    __shared__ int best_s, keep_s;
+    const int tid = threadIdx.x, nt = blockDim.x, lane = tid & 63, wave = tid >> 6;
+    const int c0 = blockIdx.x * kWideWgCols;
+    unsigned short* perm = wperm + (size_t)blockIdx.x * kWideWgCols;
+    if (!balance || c0 + kWideWgCols > ncols) {  // uniform: the identity
+        for (int i = tid; i < kWideWgCols; i += nt) {
+            perm[i] = (unsigned short)i;
+            if (c0 + i < ncols) winv[c0 + i] = (unsigned short)i;
+        }
+        return;
+    }
+    const int* blk = cnt + c0;  // blk[c * ncols + col]
+    int* L = L0 + (size_t)blockIdx.x * kWaves * nch;
+    for (int col = tid; col < kWideWgCols; col += nt) {
+        int s = 0;
+        for (int c = 0; c < nch; ++c) s += blk[(size_t)c * ncols + col];
+        tot[col] = s;
+    }
+    for (int i = tid; i < kWaves * nch; i += nt) L[i] = 0;
+    if (tid < kWaves) nslot[tid] = 0;
+    __syncthreads();
+    for (int i = tid; i < kWideWgCols; i += nt) {
+        int r = 0;
+        for (int j = 0; j < kWideWgCols; ++j) r += (tot[j] > tot[i] || (tot[j] == tot[i] && j < i)) ? 1 : 0;
+        order[r] = (unsigned short)i;
+    }
+    __syncthreads();
+    for (int step = 0; step < kWideWgCols; ++step) {
+        const int col = order[step];
+        const int* cc = blk + col;
+        unsigned long long s = 0;  // wave w scores wave-column w
+        if (nslot[wave] < kWideCW)
+            for (int c = lane; c < nch; c += 64)
+                s += (unsigned long long)L[(size_t)wave * nch + c] * (unsigned long long)cc[(size_t)c * ncols];
+        s = wave_sum(s);
+        if (lane == 0) score[wave] = s;
+        __syncthreads();
+        if (tid == 0) {
+            int best = -1;
+            for (int w = 0; w < kWaves; ++w)
+                if (nslot[w] < kWideCW && (best < 0 || score[w] < score[best])) best = w;
+            cand[best * kWideCW + nslot[best]++] = (unsigned short)col;
+            best_s = best;
+        }
+        __syncthreads();
+        const int bw = best_s;
+        for (int c = tid; c < nch; c += nt) L[(size_t)bw * nch + c] += cc[(size_t)c * ncols];
+        __syncthreads();
+    }
+    // keep the deal only where it lowers sum_c max_w L[w][c]
+    unsigned long long sg = 0, si = 0;
+    for (int c = tid; c < nch; c += nt) {
+        int mg = 0, mi = 0;
+        for (int w = 0; w < kWaves; ++w) {
+            mg = max(mg, L[(size_t)w * nch + c]);
+            int s = 0;
+            for (int j = 0; j < kWideCW; ++j) s += blk[(size_t)c * ncols + w * kWideCW + j];
+            mi = max(mi, s);
+        }
+        sg += (unsigned long long)mg;
+        si += (unsigned long long)mi;
+    }
+    sg = wave_sum(sg);
+    si = wave_sum(si);
+    if (lane == 0) {
+        red[0][wave] = sg;
+        red[1][wave] = si;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        unsigned long long g = 0, i = 0;
+        for (int w = 0; w < kWaves; ++w) {
+            g += red[0][w];
+            i += red[1][w];
+        }
+        keep_s = g < i ? 1 : 0;
+    }
+    __syncthreads();
+    const bool keep = keep_s != 0;
+    for (int i = tid; i < kWideWgCols; i += nt) {
+        const int v = keep ? cand[i] : i;
+        perm[i] = (unsigned short)v;
+        winv[c0 + v] = (unsigned short)i;
+    }
+}
+
+// The counts in slot order: cntp[c*ncols + b*352 + p] = cnt[c*ncols + b*352 +
+// wperm[b*352 + p]] (p = 22 * wave + slot), so that a wave's columns are again
+// one range of every chunk row and the prefix sums below serve as before.
+__global__ void k_wide_permute_counts(const int* __restrict__ cnt, const unsigned short* __restrict__ wperm, int ncols,
+                                      int nch, int* __restrict__ cntp) {
+    const long long total = (long long)nch * ncols;
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i <= total;
+         i += (long long)gridDim.x * blockDim.x) {
+        if (i == total) {
+            cntp[i] = 0;
+            continue;
+        }
+        const int q = (int)(i % ncols), b0 = q / kWideWgCols * kWideWgCols;
+        cntp[i] = cnt[i - q + b0 + wperm[q]];
+    }
+}
+
+// Per column block: sum_c max_w (entries of wave w in chunk c) and the number
+// of (wave, chunk) streams longer than the generated loop's scalar buffer, for
+// the contiguous assignment (st[0], st[2]) and the map in use (st[1], st[3]).
+__global__ void k_wide_stats(const int* __restrict__ cnt, const unsigned short* __restrict__ wperm, int ncols, int nch,
+                             unsigned long long* __restrict__ st) {
+    const int c0 = blockIdx.x * kWideWgCols;
+    const unsigned short* perm = wperm + (size_t)blockIdx.x * kWideWgCols;
+    unsigned long long v[4] = {0, 0, 0, 0};
+    for (int c = threadIdx.x; c < nch; c += blockDim.x) {
+        const int* row = cnt + (size_t)c * ncols + c0;
+        int mi = 0, mp = 0;
+        for (int w = 0; w < kWaves; ++w) {
+            int si = 0, sp = 0;
+            for (int j = 0; j < kWideCW; ++j) {
+                const int ci = w * kWideCW + j, cp = perm[ci];
+                si += c0 + ci < ncols ? row[ci] : 0;
+                sp += c0 + cp < ncols ? row[cp] : 0;
+            }
+            mi = max(mi, si);
+            mp = max(mp, sp);
+            v[2] += si > TCSCW_GEN_CAP ? 1 : 0;
+            v[3] += sp > TCSCW_GEN_CAP ? 1 : 0;
+        }
+        v[0] += (unsigned long long)mi;
+        v[1] += (unsigned long long)mp;
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const unsigned long long s = wave_sum(v[k]);
+        if ((threadIdx.x & 63) == 0 && s) atomicAdd(st + k, s);
+    }
+}
+
+// gcnt[gw*nch + c] = header + entries of wide group gw in chunk c (group-major);
+// cptr is the prefix sum of the counts in slot order, where group gw is the
+// range [wide_group_col0(gw), + 22) cut at ncols (a partial block keeps the identity)
 __global__ void k_wide_group_counts(const int* __restrict__ cptr, int ncols, int nch, int Gw, int* __restrict__ gcnt) {
     const long long total = (long long)nch * Gw;
     for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total;
@@ -412,7 +590,8 @@ __global__ void k_wide_group_counts(const int* __restrict__ cptr, int ncols, int
 }
 
 __global__ void k_wide_scatter(const int2* __restrict__ ent, const int* __restrict__ sptr, int G, int nch, int ncols,
-                               const int* __restrict__ cptr, const int* __restrict__ sptr_w, int2* __restrict__ ent_w) {
+                               const int* __restrict__ cptr, const unsigned short* __restrict__ winv,
+                               const int* __restrict__ sptr_w, int2* __restrict__ ent_w) {
     const long long total = (long long)G * nch;
     for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total;
          i += (long long)gridDim.x * blockDim.x) {
@@ -425,14 +604,15 @@ __global__ void k_wide_scatter(const int2* __restrict__ ent, const int* __restri
             const int2 v = ent[first + e];
             if (is_pad(v.y)) continue;
             const int s = (v.y & 0x3ff) >> 2;
-            if (s != slot) {  // the next column: its wide group, slot there and first position
-                slot = s;
+            if (s != slot) {  // the next column: its wide group and slot there (the slot map), its first
+                slot = s;     // position = the entries of the group's lower slots in this chunk
                 rank = 0;
                 const int col = n0 + s;
-                const int gw = (col / kWideWgCols) * kWaves + (col % kWideWgCols) / kWideCW;
-                jw = col - wide_group_col0(gw);
+                const int p = col / kWideWgCols * kWideWgCols + winv[col];  // the column in slot order
+                const int gw = (p / kWideWgCols) * kWaves + (p % kWideWgCols) / kWideCW;
+                jw = p - wide_group_col0(gw);
                 base = sptr_w[(long long)gw * nch + c] + kHdr +
-                       (cptr[(long long)c * ncols + col] - cptr[(long long)c * ncols + wide_group_col0(gw)]);
+                       (cptr[(long long)c * ncols + p] - cptr[(long long)c * ncols + wide_group_col0(gw)]);
             }
             ent_w[base + rank++] = make_int2(v.x, (v.y & ~0x3ff) | (4 * jw));
         }
@@ -466,19 +646,32 @@ inline int grid_for(long long n, int block) {
 
 }  // namespace
 
-// Phase 1: cnt (zeroed here) -> cptr (nch*ncols + 1), gcnt (Gw*nch + 1, the
-// last 0) -> sptr_w.  tmp serves exclusive scans of either length.
-hipError_t wide_counts(const int2* ent, const int* sptr, int G, int nch, int ncols, int Gw, int* cnt, int* cptr,
-                       int* gcnt, int* sptr_w, void* tmp, size_t tmp_bytes, hipStream_t st) {
+// Phase 1: cnt (zeroed here, per column) -> the slot map (wperm, its inverse
+// winv, the statistics wstats[4] of k_wide_stats) -> cptr (nch*ncols + 1: the
+// counts in slot order, summed in place), gcnt (Gw*nch + 1, the last 0) ->
+// sptr_w.  tmp serves exclusive scans of either length.
+hipError_t wide_counts(const int2* ent, const int* sptr, int G, int nch, int ncols, int Gw, int balance, int* cnt,
+                       int* cptr, int* gcnt, int* sptr_w, int* loads, unsigned short* wperm, unsigned short* winv,
+                       unsigned long long* wstats, void* tmp, size_t tmp_bytes, hipStream_t st) {
     hipError_t e;
     const long long nc = (long long)nch * ncols, ng = (long long)nch * Gw;
+    const int nblk = wide_blocks_for(ncols);
     if ((e = hipMemsetAsync(cnt, 0, (size_t)(nc + 1) * sizeof(int), st)) != hipSuccess) return e;
     if ((e = hipMemsetAsync(gcnt + ng, 0, sizeof(int), st)) != hipSuccess) return e;
+    if ((e = hipMemsetAsync(wstats, 0, 4 * sizeof(unsigned long long), st)) != hipSuccess) return e;
     hipLaunchKernelGGL(k_wide_col_counts, dim3(grid_for((long long)G * nch, 128)), dim3(128), 0, st, ent, sptr, G, nch,
                        ncols, cnt);
     if ((e = hipGetLastError()) != hipSuccess) return e;
+    hipLaunchKernelGGL(k_wide_balance, dim3(nblk), dim3(kWaves * 64), 0, st, cnt, ncols, nch, balance, loads, wperm,
+                       winv);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    hipLaunchKernelGGL(k_wide_stats, dim3(nblk), dim3(256), 0, st, cnt, wperm, ncols, nch, wstats);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    hipLaunchKernelGGL(k_wide_permute_counts, dim3(grid_for(nc + 1, 256)), dim3(256), 0, st, cnt, wperm, ncols, nch,
+                       cptr);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
     size_t tb = tmp_bytes;
-    if ((e = hipcub::DeviceScan::ExclusiveSum(tmp, tb, cnt, cptr, (int)(nc + 1), st)) != hipSuccess) return e;
+    if ((e = hipcub::DeviceScan::ExclusiveSum(tmp, tb, cptr, cptr, (int)(nc + 1), st)) != hipSuccess) return e;
     hipLaunchKernelGGL(k_wide_group_counts, dim3(grid_for(ng, 256)), dim3(256), 0, st, cptr, ncols, nch, Gw, gcnt);
     if ((e = hipGetLastError()) != hipSuccess) return e;
     tb = tmp_bytes;
@@ -487,9 +680,9 @@ hipError_t wide_counts(const int2* ent, const int* sptr, int G, int nch, int nco
 
 // Phase 2: ent_w (n_entries + kEntGuard entries) from the 16-column streams.
 hipError_t wide_fill(const int2* ent, const int* sptr, int G, int nch, int ncols, int Gw, const int* cptr,
-                     const int* sptr_w, int2* ent_w, long long n_entries, hipStream_t st) {
+                     const unsigned short* winv, const int* sptr_w, int2* ent_w, long long n_entries, hipStream_t st) {
     hipLaunchKernelGGL(k_wide_scatter, dim3(grid_for((long long)G * nch, 128)), dim3(128), 0, st, ent, sptr, G, nch,
-                       ncols, cptr, sptr_w, ent_w);
+                       ncols, cptr, winv, sptr_w, ent_w);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_wide_headers, dim3(grid_for((long long)nch * Gw, 256)), dim3(256), 0, st, sptr_w, nch, Gw,
@@ -500,16 +693,16 @@ hipError_t wide_fill(const int2* ent, const int* sptr, int G, int nch, int ncols
 // The gather launch of launch_gemm for GemmArgs::geo == kWideCW: g.ent, g.sptr,
 // g.n_entries and g.n_groups are the wide streams; X^T is staged already.
 hipError_t launch_stream_wide(const GemmArgs& g, hipStream_t st) {
-    if (g.order != 0 || g.ent == nullptr) return hipErrorInvalidValue;
+    if (g.order != 0 || g.ent == nullptr || g.wperm == nullptr) return hipErrorInvalidValue;
     const int nch = (g.K + kTK - 1) / kTK;
     const int ldxt = ldxt_for(g.M);
     dim3 grid((g.n_groups + kWaves - 1) / kWaves, (g.M + kTM - 1) / kTM, 1);
     dim3 block(kWaves * 64);
     int pfd = 0, pfl = 1;
     pf_stream_params(g.n_entries, g.n_groups, nch, &pfd, &pfl);
-#define TCSC_LAUNCH_W(BF, PR)                                                                                         \
-    hipLaunchKernelGGL((k_stream_w<BF, PR>), grid, block, 0, st, g.XT, g.ent, g.sptr, g.B, g.Y, g.n_entries, ldxt, g.M, \
-                       g.n_groups, g.ncols, nch, g.ldy, g.a, pfd, pfl)
+#define TCSC_LAUNCH_W(BF, PR)                                                                                \
+    hipLaunchKernelGGL((k_stream_w<BF, PR>), grid, block, 0, st, g.XT, g.ent, g.sptr, g.B, g.Y, g.wperm, g.n_entries, \
+                       ldxt, g.M, g.n_groups, g.ncols, nch, g.ldy, g.a, pfd, pfl)
     if (g.bias_first) {
         if (g.prelu) TCSC_LAUNCH_W(true, true);
         else TCSC_LAUNCH_W(true, false);

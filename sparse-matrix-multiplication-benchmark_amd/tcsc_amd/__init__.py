@@ -51,7 +51,7 @@ EXPORTED_SYMBOLS = (
     "tcsc_gpu_plan_enable_i8", "tcsc_gpu_plan_has_i8", "tcsc_gpu_sgemm_i8", "tcsc_gpu_launch_info_i8",
     "tcsc_gpu_quantize_rows_i8", "tcsc_gpu_workspace_bound_i8",
     "tcsc_gpu_plan_enable_w2", "tcsc_gpu_plan_has_w2", "tcsc_gpu_w2_image_bytes", "tcsc_gpu_decode_pays",
-    "tcsc_gpu_launch_geometry", "tcsc_gpu_wide_pays",
+    "tcsc_gpu_launch_geometry", "tcsc_gpu_wide_pays", "tcsc_gpu_plan_wide_stats",
     "tcsc_gpu_plan_create_packed", "tcsc_gpu_plan_create_packed_device", "tcsc_gpu_plan_is_packed",
     "tcsc_gpu_plan_copy_w2",
     "tcsc_gpu_plan_create_packed_image", "tcsc_gpu_plan_create_packed_image_device", "tcsc_gpu_w2_to_tcsc",
@@ -151,6 +151,7 @@ def lib():
     L.tcsc_gpu_launch_combine.argtypes = [vp, i, C.POINTER(i)]
     L.tcsc_gpu_launch_geometry.argtypes = [vp, i, C.POINTER(i)]
     L.tcsc_gpu_wide_pays.argtypes = [i, i, i]
+    L.tcsc_gpu_plan_wide_stats.argtypes = [vp, C.POINTER(C.c_longlong), vp, C.c_size_t]
     L.tcsc_gpu_plan_reserve.argtypes = [vp, i]
     L.tcsc_gpu_plan_workspace.argtypes = [vp, i, i, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
     L.tcsc_gpu_plan_destroy.argtypes = [vp]
@@ -645,6 +646,20 @@ class Plan:
         v = C.c_int()
         _check(lib().tcsc_gpu_launch_geometry(self.handle, int(M), C.byref(v)), "tcsc_gpu_launch_geometry")
         return v.value
+
+    def wide_stats(self) -> dict:
+        """The slot map of the plan's 22-column streams and its statistics (tcsc_gpu_plan_wide_stats):
+        ``map`` is a (column blocks, 16 waves, 22 slots) uint16 array of block-local columns;
+        ``max_identity`` / ``max_balanced`` are the sums over blocks and chunks of the busiest wave's
+        entries under contiguous columns and under the map in use; ``long_identity`` / ``long_balanced``
+        count the (wave, chunk) streams longer than the kernel's 30-entry scalar buffer.  TcscError on a
+        plan whose reserve built no wide streams."""
+        st = (C.c_longlong * 4)()
+        nblk = (self.info()["cols"] + 351) // 352
+        m = np.empty((nblk, 16, 22), np.uint16)
+        _check(lib().tcsc_gpu_plan_wide_stats(self.handle, st, C.c_void_p(m.ctypes.data), m.size),
+               "tcsc_gpu_plan_wide_stats")
+        return dict(max_identity=st[0], max_balanced=st[1], long_identity=st[2], long_balanced=st[3], map=m)
 
     def reserve(self, max_M: int) -> None:
         """Allocate the workspace (X^T + split-K slabs) for launches of up to max_M rows."""
