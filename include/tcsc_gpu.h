@@ -286,7 +286,8 @@ int tcsc_gpu_sgemm_prepared(const tcsc_gpu_plan *plan, const float *dB, float *d
  * divided by 3; $TCSC_PATH, $TCSC_SLICES, $TCSC_MFMA_WGS and
  * $TCSC_SMALL_M act as on the fp32 call.  tcsc_gpu_launch_info_bf16 reports
  * what a bf16 call of M rows runs (as tcsc_gpu_launch_info does for fp32).
- * Out of scope: a host-pointer version, bf16 Y, bf16 B, and a
+ * Out of scope: a host-pointer version, bf16 Y (the int8 call has one on its
+ * decode and MFMA routes: tcsc_gpu_sgemm_i8_out), bf16 B, and a
  * prepare_x / sgemm_prepared pair for bf16. */
 int tcsc_gpu_sgemm_bf16(const tcsc_gpu_plan *plan, const void *dX_bf16, const float *dB,
                         float *dY, int M, int ldy, int variant, float a, void *stream);
@@ -349,9 +350,10 @@ int tcsc_gpu_launch_info_bf16(const tcsc_gpu_plan *plan, int M, int *path, int *
  * workspace of an int8 and of an fp32 launch of an M x K x N problem; the
  * first never exceeds the second.
  *
- * Out of scope: int8 or bf16 Y, per-column weight scales, a host-pointer
- * version, a backward pass for the int8 call, and keeping X^T narrow inside
- * the gather's LDS ring. */
+ * Out of scope: int8 Y, a host-pointer version, a backward pass for the int8
+ * call, and keeping X^T narrow inside the gather's LDS ring.  (A bf16 Y and
+ * per-column weight scales: tcsc_gpu_sgemm_i8_out, below -- on the decode and
+ * MFMA routes; on the gather and small-M routes they stay out of scope.) */
 int tcsc_gpu_plan_enable_i8(tcsc_gpu_plan *plan, void *stream);
 int tcsc_gpu_plan_has_i8(const tcsc_gpu_plan *plan);
 int tcsc_gpu_sgemm_i8(const tcsc_gpu_plan *plan, const void *dXq, const float *dScale,
@@ -414,7 +416,7 @@ int tcsc_gpu_workspace_bound_i8(int M, int K, int N, size_t *i8_bytes, size_t *f
  * tcsc_gpu_launch_info_i8 names the path; tcsc_gpu_launch_info and _bf16 never
  * do.
  *
- * Out of scope: bf16 or int8 Y; a host-pointer version.  (M > 16 on the image,
+ * Out of scope: int8 Y; a host-pointer version.  (M > 16 on the image,
  * plans that hold nothing else, and the image without the int8 one: packed
  * plans, below.) */
 int tcsc_gpu_plan_enable_w2(tcsc_gpu_plan *plan, void *stream);
@@ -480,7 +482,7 @@ int tcsc_gpu_decode_pays(int M, int K, int N, long long nnz);
  * unset or 0 changes nothing, and it is never a default).
  *
  * Out of scope: fp32 or bf16 activations, a backward pass, packed transposed
- * plans, a host-pointer version, bf16 or int8 Y.  (Loading a packed plan from a
+ * plans, a host-pointer version, int8 Y.  (Loading a packed plan from a
  * saved image: the block after this one.) */
 int tcsc_gpu_plan_create_packed(const tcsc_t *W, int col_begin, int col_end,
                                 int device, void *stream, tcsc_gpu_plan **out);
@@ -549,7 +551,7 @@ int tcsc_gpu_plan_copy_w2(const tcsc_gpu_plan *plan, void *d_dst, size_t bytes, 
  * arguments.
  *
  * Out of scope: a multi-layer checkpoint format (one image is one plan), packed
- * transposed plans, fp32 or bf16 calls on a packed plan, bf16 or int8 Y, and a
+ * transposed plans, fp32 or bf16 calls on a packed plan, int8 Y, and a
  * host-pointer sgemm on images. */
 int tcsc_gpu_plan_create_packed_image(const void *image, size_t bytes, int rows, int cols,
                                       int col_begin, int device, void *stream, tcsc_gpu_plan **out);
@@ -615,14 +617,72 @@ tcsc_t *tcsc_gpu_w2_to_tcsc_host(const void *image, size_t bytes, int rows, int 
  * formula, so the results are those of the fp32 quantizer on the widened X.
  * The same guarantees and argument checks.
  *
- * Out of scope: bf16 or int8 Y; fusing the quantizer into k_pack8 at M >= 17;
- * a host-pointer version. */
+ * Out of scope: int8 Y; fusing the quantizer into k_pack8 at M >= 17; a
+ * host-pointer version. */
 enum tcsc_xtype { TCSC_X_F32 = 0, TCSC_X_BF16 = 1 };
 int tcsc_gpu_quantize_rows_i8_bf16(const void *dX_bf16, int M, int K, void *dXq, float *dScale, void *stream);
 int tcsc_gpu_sgemm_q8(const tcsc_gpu_plan *plan, const void *dX, int xtype, void *dXq, float *dScale,
                       const float *dB, float *dY, int M, int ldy, int variant, float a, void *stream);
 int tcsc_gpu_launch_info_q8(const tcsc_gpu_plan *plan, int M, int xtype, int *path, int *slices, int *fused);
 int tcsc_gpu_quant_fuse_pays(int M, int K, int N, int xtype);
+
+/* ---- int8 calls: per-column weight scales and a bf16 Y ---------
+ * A ternarized weight is beta T with T in {-1, 0, +1}, beta one number per
+ * tensor or one per output column, and the layer that follows reads bf16.  With
+ * the calls above that is a zero bias, then mul_(beta), add_(bias), the
+ * activation and a conversion: three or four launches and as many passes over an
+ * fp32 Y beside a kernel of a few microseconds.  These two calls finish the
+ * layer in the launches the int8 call already has.
+ *
+ * tcsc_gpu_sgemm_i8_out: tcsc_gpu_sgemm_i8, and tcsc_gpu_sgemm_q8_out:
+ * tcsc_gpu_sgemm_q8, with
+ *   dColScale : cols floats c[j] (the plan's slice, as dB), or NULL for all ones
+ *   dY, ytype : TCSC_Y_F32: floats; TCSC_Y_BF16: bf16 bit patterns (16 bits
+ *               each), which need 2-byte alignment only
+ *   ldy       : the pitch of Y in elements of its type, >= cols
+ * and every other argument exactly as in the call it extends.  With S the exact
+ * i32 sum, s[m] the row scale (NULL: one), c[j] and b[j]:
+ *   v = fl(fl(float(S) * s[m]) * c[j])      two multiplies, in this order
+ *   v = fl(v + b[j])                        never contracted with a multiply
+ *   v = v < 0 ? a * v : v                   the PReLU variants
+ *   Y[m, j] = v                             TCSC_Y_F32
+ *   Y[m, j] = bf16(v)                       TCSC_Y_BF16: round to nearest even
+ *                                           on the fp32 bits -- for every finite
+ *                                           v and +-inf what a conversion of
+ *                                           the fp32 Y gives; a NaN stays a NaN
+ * x * 1.0f == x, so (NULL, TCSC_Y_F32) gives the bits of tcsc_gpu_sgemm_i8 /
+ * _q8, which are these calls with those two arguments.  The arithmetic is one
+ * function shared by k_gemm8, k_gemm8w2, k_reduce_i8, k_decode8 and k_decode8q:
+ * the same bits on every route, tile shape and K split, packed or ordinary
+ * plan, fused quantizer or not.  Only rows < M and columns < cols are written:
+ * a bf16 store never touches a 2-byte element outside them (column `cols` of an
+ * odd cols, the element before an odd-aligned Y); four columns go out as one
+ * 8-byte store only where Y is 8-byte aligned and ldy % 4 == 0.
+ *
+ * Routes: a call whose int8 route (tcsc_gpu_launch_info_i8 / _q8) is
+ * TCSC_PATH_DECODE or TCSC_PATH_MFMA -- every call on a packed plan, and calls
+ * on ordinary plans wherever the router picks those paths.  Where the route is
+ * the gather or the small-M path, (NULL, TCSC_Y_F32) is the call as it was and
+ * anything else returns TCSC_E_ARG before any HIP call, with a message naming
+ * the call and the path: those paths finish in fp32 kernels shared with
+ * tcsc_gpu_sgemm.  Routing, $TCSC_DECODE, $TCSC_QFUSE, $TCSC_W2GEMM,
+ * $TCSC_MFMA_WGS, the fusing rule, the workspace, tcsc_gpu_plan_reserve and the
+ * launch_info queries are unchanged: the calls allocate nothing once the
+ * workspace covers M and can be captured.  The 2^22-row pieces of a packed plan
+ * advance Y by the element size of its type.
+ * On top of the checks of the calls they extend, TCSC_E_ARG with a message
+ * naming the call and no HIP call for: ytype other than 0 or 1, a NULL plan, a
+ * NULL dY, a NULL dB (these four whatever M is).
+ *
+ * Out of scope: int8 Y; column scales and a bf16 Y on the gather and small-M
+ * routes and on the fp32 and bf16 calls; a host-pointer version. */
+enum tcsc_ytype { TCSC_Y_F32 = 0, TCSC_Y_BF16 = 1 };
+int tcsc_gpu_sgemm_i8_out(const tcsc_gpu_plan *plan, const void *dXq, const float *dScale,
+                          const float *dColScale, const float *dB, void *dY, int ytype,
+                          int M, int ldy, int variant, float a, void *stream);
+int tcsc_gpu_sgemm_q8_out(const tcsc_gpu_plan *plan, const void *dX, int xtype, void *dXq,
+                          float *dScale, const float *dColScale, const float *dB, void *dY,
+                          int ytype, int M, int ldy, int variant, float a, void *stream);
 
 /* Device-side tcsc_from_dense: dense K x N row-major float matrix on the
  * device -> TCSC arrays on the device, bit-exact with the reference builder

@@ -304,6 +304,9 @@ size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 using tcsc::kBf16;
 using tcsc::kF32;
 using tcsc::kI8;
+using tcsc::kYBf16;
+using tcsc::kYF32;
+using tcsc::YOut;
 struct XType {
     const char* sgemm;  // the entry point, as error messages name it
     size_t elem;        // bytes of one element of X
@@ -1007,10 +1010,12 @@ namespace {
 //         only, stage 2 the GEMM + fixup on the staged X3 (fp32 alone has stages)
 //   bf16: k_pack1 (X -> X1 + flags, k_split3's rule), the one-part k_gemm3 and k_fixup
 //   int8: k_pack8 (X -> X8), k_gemm8 against the int8 image (+ k_reduce_i8 when
-//         K is split) with the row scales; no flags, no fixup
-int sgemm_mfma(const tcsc_gpu_plan* p, const void* dX, int dt, const float* dScale, const float* dB, float* dY, int M,
-               int ldy, int variant, float a, void* stream, float* ws, size_t ws_bytes, int stage) {
+//         K is split) with the row scales, the output descriptor's column
+//         scales and Y type (§21); no flags, no fixup
+int sgemm_mfma(const tcsc_gpu_plan* p, const void* dX, int dt, const float* dScale, const float* dB, const YOut& y,
+               int M, int ldy, int variant, float a, void* stream, float* ws, size_t ws_bytes, int stage) {
     const XType& d = kXTypes[dt];
+    float* dY = static_cast<float*>(y.Y);  // the fp32 and bf16 calls write floats (y.plain())
     const int K = p->rows, N = p->cols, ldx = d.ldx(K), ldw = d.ldw(K);
     const MfmaWs w = mfma_ws(dt, M, K, N);
     if (!ws || ws_bytes < w.bytes) {
@@ -1041,10 +1046,10 @@ int sgemm_mfma(const tcsc_gpu_plan* p, const void* dX, int dt, const float* dSca
             // B from the 2-bit image (k_gemm8w2): a packed plan has nothing else; an ordinary plan that has
             // both images takes it under $TCSC_W2GEMM=1 -- the same route, K split, workspace and bits
             if (p->packed || (p->w2 && w2gemm_knob()))
-                HIP_TRY(tcsc::mfma8_gemm_w2(reinterpret_cast<const int8_t*>(base), p->w2, ldx, K, M, N, dScale, dB, dY,
+                HIP_TRY(tcsc::mfma8_gemm_w2(reinterpret_cast<const int8_t*>(base), p->w2, ldx, K, M, N, dScale, dB, y,
                                             ldy, prelu, a, static_cast<int*>(slabs), slab_bytes, st));
             else
-                HIP_TRY(tcsc::mfma8_gemm(reinterpret_cast<const int8_t*>(base), p->w8, ldx, K, M, N, dScale, dB, dY,
+                HIP_TRY(tcsc::mfma8_gemm(reinterpret_cast<const int8_t*>(base), p->w8, ldx, K, M, N, dScale, dB, y,
                                          ldy, prelu, a, static_cast<int*>(slabs), slab_bytes, st));
             break;
     }
@@ -1059,13 +1064,40 @@ int sgemm_mfma(const tcsc_gpu_plan* p, const void* dX, int dt, const float* dSca
 
 }  // namespace
 
+// What the decode and MFMA routes of the int8 call can write and the others
+// cannot: a bf16 Y, a column scale.  The gather and the small-M
+// path finish in fp32 kernels shared with the fp32 call.
+static const char* path_name(int path) {
+    switch (path) {
+        case TCSC_PATH_GATHER: return "gather";
+        case TCSC_PATH_MFMA: return "MFMA";
+        case TCSC_PATH_SMALL: return "small-M";
+        case TCSC_PATH_DECODE: return "decode";
+        default: return "unknown";
+    }
+}
+static bool refuse_out(const char* who, int path, const YOut& y, int M) {
+    if (y.plain() || path == TCSC_PATH_DECODE || path == TCSC_PATH_MFMA) return false;
+    set_error("%s: %s%s%s needs the decode or the MFMA path, and M=%d routes to the %s path (%d), which writes an fp32 Y "
+              "without column scales", who, y.ytype == kYBf16 ? "a bf16 Y" : "", y.ytype == kYBf16 && y.cscale ? " with " : "",
+              y.cscale ? "a column scale" : "", M, path_name(path), path);
+    return true;
+}
+
 // One call on the workspace ws: routed once (route_call, with what `pin`
-// fixes and what the pointers allow), then launched as routed.
+// fixes and what the pointers allow), then launched as routed.  `out`, if
+// given, replaces dY: the int8 call's Y with its type and column scales.
 int tcsc::sgemm_ws(const tcsc_gpu_plan* p, const void* dX, const float* dB, float* dY, int M, int ldy, int variant,
                    float a, void* stream, float* ws, size_t ws_bytes, int stage, const RoutePins& pin, Route* ran,
-                   int dt, const float* dScale) {
+                   int dt, const float* dScale, const YOut* out, const char* as) {
     const XType& d = kXTypes[dt];
-    const char* who = d.sgemm;
+    const char* who = as ? as : d.sgemm;
+    const YOut y = out ? *out : YOut{dY, kYF32, nullptr};
+    if (out) dY = y.plain() ? static_cast<float*>(y.Y) : nullptr;  // the fp32 routes never see another Y
+    if (dt != kI8 && !y.plain()) {
+        set_error("%s: only the int8 call has a typed Y and column scales", who);
+        return TCSC_E_ARG;
+    }
     if (dt != kF32 && stage != 0) {
         set_error("%s: no staged form", who);
         return TCSC_E_ARG;
@@ -1079,15 +1111,16 @@ int tcsc::sgemm_ws(const tcsc_gpu_plan* p, const void* dX, const float* dB, floa
         return TCSC_E_ARG;
     }
     if (M == 0 || p->cols == 0) return TCSC_OK;
-    if ((stage != 1 && (!dY || !dB)) || (stage != 2 && !dX && p->rows > 0)) {
+    if ((stage != 1 && (!y.Y || !dB)) || (stage != 2 && !dX && p->rows > 0)) {
         set_error("%s: NULL device pointer", who);
         return TCSC_E_ARG;
     }
     if (p->packed && M > kMaxLaunchRows) {  // pieces of at most kMaxLaunchRows rows on one workspace, each routed by its own rows
         for (int r0 = 0; r0 < M; r0 += kMaxLaunchRows) {
-            const int rc = sgemm_ws(p, static_cast<const char*>(dX) + (size_t)r0 * p->rows * d.elem, dB,
-                                    dY + (size_t)r0 * ldy, std::min(kMaxLaunchRows, M - r0), ldy, variant, a, stream, ws,
-                                    ws_bytes, 0, pin, nullptr, dt, dScale ? dScale + r0 : nullptr);
+            const YOut piece = y.rows_on((size_t)r0, ldy);  // Y advances by the element size of its type
+            const int rc = sgemm_ws(p, static_cast<const char*>(dX) + (size_t)r0 * p->rows * d.elem, dB, nullptr,
+                                    std::min(kMaxLaunchRows, M - r0), ldy, variant, a, stream, ws, ws_bytes, 0, pin,
+                                    nullptr, dt, dScale ? dScale + r0 : nullptr, &piece, as);
             if (rc != TCSC_OK) return rc;
         }
         if (ran) *ran = route_call(p, M, dt, ws ? ws_bytes : 0, pin);
@@ -1114,13 +1147,14 @@ int tcsc::sgemm_ws(const tcsc_gpu_plan* p, const void* dX, const float* dB, floa
         set_error("%s: the plan cannot run M=%d on the pinned path %d", who, M, r.path);
         return TCSC_E_ARG;
     }
+    if (refuse_out(who, r.path, y, M)) return TCSC_E_ARG;
     if (r.path == TCSC_PATH_DECODE) {
-        HIP_TRY(tcsc::decode_gemm(static_cast<const int8_t*>(dX), p->w2, p->rows, M, p->cols, dScale, dB, dY, ldy,
+        HIP_TRY(tcsc::decode_gemm(static_cast<const int8_t*>(dX), p->w2, p->rows, M, p->cols, dScale, dB, y, ldy,
                                   is_prelu(variant), a, p->num_cus, static_cast<hipStream_t>(stream)));
         return TCSC_OK;
     }
     if (r.path == TCSC_PATH_MFMA)
-        return sgemm_mfma(p, dX, dt, dScale, dB, dY, M, ldy, variant, a, stream, ws, ws_bytes, stage);
+        return sgemm_mfma(p, dX, dt, dScale, dB, y, M, ldy, variant, a, stream, ws, ws_bytes, stage);
     if (r.path == TCSC_PATH_SMALL) {
         // stage 1 stages X as is (the kernel reads X rows directly), stage 2 reads the staged copy
         hipStream_t st = static_cast<hipStream_t>(stream);
@@ -1158,7 +1192,7 @@ int tcsc::sgemm_ws(const tcsc_gpu_plan* p, const void* dX, const float* dB, floa
             const int rows = std::min(kMaxLaunchRows, M - r0);
             const void* xr = static_cast<const char*>(dX) + (size_t)r0 * p->rows * d.elem;
             const int rc = sgemm_ws(p, xr, dB, dY + (size_t)r0 * ldy, rows, ldy, variant, a, stream, ws, ws_bytes, 0,
-                                    piece, nullptr, dt, dScale ? dScale + r0 : nullptr);
+                                    piece, nullptr, dt, dScale ? dScale + r0 : nullptr, nullptr, as);
             if (rc != TCSC_OK) return rc;
         }
         return TCSC_OK;
@@ -1861,16 +1895,23 @@ int tcsc_gpu_launch_combine(const tcsc_gpu_plan* p, int M, int* in_launch) {
 // (tcsc_gpu_plan_reserve up front keeps the call allocation-free and
 // graph-capturable: its size covers every launch of every type, mfma_ws),
 // then run on it.
+// `out` and `as`: the typed Y with its column scales and the name of the call in
+// messages, for the int8 call's _out form (sgemm_ws); a route that cannot write
+// what `out` asks for is refused here, ahead of the workspace and of any launch
 static int sgemm_entry(const tcsc_gpu_plan* p, const void* dX, int dt, const float* dScale, const float* dB, float* dY,
-                       int M, int ldy, int variant, float a, void* stream) {
+                       int M, int ldy, int variant, float a, void* stream, const YOut* out = nullptr,
+                       const char* as = nullptr) {
     if (dt != kI8 && refuse_packed(p, kXTypes[dt].sgemm)) return TCSC_E_ARG;
+    if (out && !out->plain() && p && M > 0 && p->cols > 0 &&
+        refuse_out(as ? as : kXTypes[dt].sgemm, route_call(p, M, dt, p->ws_bytes, RoutePins()).path, *out, M))
+        return TCSC_E_ARG;
     if (p && M > 0 && p->cols > 0 && p->ws_bytes < wanted_workspace(p, M, dt)) {
         const int rc = tcsc_gpu_plan_reserve(const_cast<tcsc_gpu_plan*>(p), M);
         if (rc != TCSC_OK) return rc;
     }
     if (p) const_cast<tcsc_gpu_plan*>(p)->staged_M = -1;  // this call's X^T or packed X replaces any staged one
     return sgemm_ws(p, dX, dB, dY, M, ldy, variant, a, stream, p ? p->ws : nullptr, p ? p->ws_bytes : 0, 0, RoutePins(),
-                    nullptr, dt, dScale);
+                    nullptr, dt, dScale, out, as);
 }
 
 int tcsc_gpu_sgemm(const tcsc_gpu_plan* p, const float* dX, const float* dB, float* dY, int M, int ldy,
@@ -1974,9 +2015,38 @@ int tcsc_gpu_w2_image_bytes(int K, int N, size_t* bytes) {
 
 int tcsc_gpu_decode_pays(int M, int K, int N, long long nnz) { return decode_pays(M, K, N, nnz) ? 1 : 0; }
 
+// tcsc_gpu_sgemm_i8_out with (NULL, TCSC_Y_F32)
 int tcsc_gpu_sgemm_i8(const tcsc_gpu_plan* p, const void* dXq, const float* dScale, const float* dB, float* dY, int M,
                       int ldy, int variant, float a, void* stream) {
-    return sgemm_entry(p, dXq, kI8, dScale, dB, dY, M, ldy, variant, a, stream);
+    const YOut y{dY, kYF32, nullptr};
+    return sgemm_entry(p, dXq, kI8, dScale, dB, nullptr, M, ldy, variant, a, stream, &y);
+}
+
+// ---- the typed Y and the column scales of the int8 calls -------
+// what the _out calls check on top of the calls they extend, ahead of any HIP call
+static int out_args(const char* who, const tcsc_gpu_plan* p, const float* dB, const void* dY, int ytype) {
+    if (ytype != TCSC_Y_F32 && ytype != TCSC_Y_BF16) {
+        set_error("%s: ytype=%d is neither TCSC_Y_F32 (0) nor TCSC_Y_BF16 (1)", who, ytype);
+        return TCSC_E_ARG;
+    }
+    if (!p) {
+        set_error("%s: NULL plan", who);
+        return TCSC_E_ARG;
+    }
+    if (!dY || !dB) {
+        set_error("%s: NULL %s", who, !dY ? "dY" : "dB");
+        return TCSC_E_ARG;
+    }
+    return TCSC_OK;
+}
+
+int tcsc_gpu_sgemm_i8_out(const tcsc_gpu_plan* p, const void* dXq, const float* dScale, const float* dColScale,
+                          const float* dB, void* dY, int ytype, int M, int ldy, int variant, float a, void* stream) {
+    const char* who = "tcsc_gpu_sgemm_i8_out";
+    const int rc = out_args(who, p, dB, dY, ytype);
+    if (rc != TCSC_OK) return rc;
+    const YOut y{dY, ytype == TCSC_Y_BF16 ? kYBf16 : kYF32, dColScale};
+    return sgemm_entry(p, dXq, kI8, dScale, dB, nullptr, M, ldy, variant, a, stream, &y, who);
 }
 
 int tcsc_gpu_quantize_rows_i8(const float* dX, int M, int K, void* dXq, float* dScale, void* stream) {
@@ -2057,9 +2127,11 @@ int tcsc_gpu_launch_info_q8(const tcsc_gpu_plan* p, int M, int xtype, int* path,
     return TCSC_OK;
 }
 
-int tcsc_gpu_sgemm_q8(const tcsc_gpu_plan* p, const void* dX, int xtype, void* dXq, float* dScale, const float* dB,
-                      float* dY, int M, int ldy, int variant, float a, void* stream) {
-    const char* who = "tcsc_gpu_sgemm_q8";
+// `inner`: the name the int8 call behind an unfused route gives itself (null: tcsc_gpu_sgemm_i8)
+static int sgemm_q8_impl(const char* who, const char* inner, const tcsc_gpu_plan* p, const void* dX, int xtype, void* dXq,
+                         float* dScale, const float* dB, const YOut& y, int M, int ldy, int variant, float a,
+                         void* stream) {
+    void* dY = y.Y;
     if (!p || M < 0 || ldy < p->cols || !valid_variant(variant) || (xtype != TCSC_X_F32 && xtype != TCSC_X_BF16)) {
         set_error("%s: bad arguments (M=%d ldy=%d variant=%d xtype=%d)", who, M, ldy, variant, xtype);
         return TCSC_E_ARG;
@@ -2070,7 +2142,7 @@ int tcsc_gpu_sgemm_q8(const tcsc_gpu_plan* p, const void* dX, int xtype, void* d
         return TCSC_E_ARG;
     }
     bool fused = false;
-    if (p->cols > 0) route_q8(p, M, xtype, &fused);
+    if (p->cols > 0 && refuse_out(who, route_q8(p, M, xtype, &fused).path, y, M)) return TCSC_E_ARG;
     if (!fused) {  // the quantizer into the caller's scratch, then the int8 call as it is: two or three launches
         if (!dXq && p->rows > 0) {
             set_error("%s: NULL dXq on a route that is not fused (M=%d)", who, M);
@@ -2080,12 +2152,29 @@ int tcsc_gpu_sgemm_q8(const tcsc_gpu_plan* p, const void* dX, int xtype, void* d
                            ? tcsc_gpu_quantize_rows_i8(static_cast<const float*>(dX), M, p->rows, dXq, dScale, stream)
                            : tcsc_gpu_quantize_rows_i8_bf16(dX, M, p->rows, dXq, dScale, stream);
         if (rc != TCSC_OK) return rc;
-        return tcsc_gpu_sgemm_i8(p, dXq, dScale, dB, dY, M, ldy, variant, a, stream);
+        return sgemm_entry(p, dXq, kI8, dScale, dB, nullptr, M, ldy, variant, a, stream, &y, inner);
     }
     const_cast<tcsc_gpu_plan*>(p)->staged_M = -1;  // as every tcsc_gpu_sgemm* does
-    HIP_TRY(tcsc::decode_gemm_q(dX, xtype == TCSC_X_BF16, p->w2, p->rows, M, p->cols, dScale, dB, dY, ldy,
+    HIP_TRY(tcsc::decode_gemm_q(dX, xtype == TCSC_X_BF16, p->w2, p->rows, M, p->cols, dScale, dB, y, ldy,
                                 is_prelu(variant), a, p->num_cus, static_cast<hipStream_t>(stream)));
     return TCSC_OK;
+}
+
+// tcsc_gpu_sgemm_q8_out with (NULL, TCSC_Y_F32)
+int tcsc_gpu_sgemm_q8(const tcsc_gpu_plan* p, const void* dX, int xtype, void* dXq, float* dScale, const float* dB,
+                      float* dY, int M, int ldy, int variant, float a, void* stream) {
+    return sgemm_q8_impl("tcsc_gpu_sgemm_q8", nullptr, p, dX, xtype, dXq, dScale, dB, YOut{dY, kYF32, nullptr}, M, ldy,
+                         variant, a, stream);
+}
+
+int tcsc_gpu_sgemm_q8_out(const tcsc_gpu_plan* p, const void* dX, int xtype, void* dXq, float* dScale,
+                          const float* dColScale, const float* dB, void* dY, int ytype, int M, int ldy, int variant,
+                          float a, void* stream) {
+    const char* who = "tcsc_gpu_sgemm_q8_out";
+    const int rc = out_args(who, p, dB, dY, ytype);
+    if (rc != TCSC_OK) return rc;
+    return sgemm_q8_impl(who, who, p, dX, xtype, dXq, dScale, dB, YOut{dY, ytype == TCSC_Y_BF16 ? kYBf16 : kYF32, dColScale},
+                         M, ldy, variant, a, stream);
 }
 
 int tcsc_gpu_workspace_bound_i8(int M, int K, int N, size_t* i8_bytes, size_t* f32_bytes) {

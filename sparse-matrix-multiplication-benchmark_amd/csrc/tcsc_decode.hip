@@ -288,11 +288,12 @@ __global__ void __launch_bounds__(256) k_w2_col_start(const int* __restrict__ of
 // K tails and column tails need nothing in the tile loop: the image's padding
 // is weight 0 (code 1, cancelled by the row sums: X is zero there anyway) and
 // columns >= N are computed and not stored.
-template <int T, bool ALIGNED, bool PRELU>
+template <int T, bool ALIGNED, bool PRELU, typename TY>
 __global__ void __launch_bounds__(kDecWaves * 64) k_decode8(const int8_t* __restrict__ X,
                                                              const uint32_t* __restrict__ W2, int K, int M, int N,
                                                              int nkb, int ntiles, const float* __restrict__ scale,
-                                                             const float* __restrict__ bias, float* __restrict__ Y,
+                                                             const float* __restrict__ cscale,
+                                                             const float* __restrict__ bias, TY* __restrict__ Y,
                                                              int ldy, float a) {
     __shared__ int red[kDecWaves * T * 256];
     const int lane = threadIdx.x & 63;
@@ -376,21 +377,21 @@ __global__ void __launch_bounds__(kDecWaves * 64) k_decode8(const int8_t* __rest
 #pragma unroll
         for (int w = 0; w < kDecWaves; ++w) S += red[(w * T + t) * 256 + (row & 3) * 64 + (row >> 2) * 16 + c];
         const float sc = scale ? scale[row] : 1.0f;
-        Y[(size_t)row * ldy + col] = i8_out<PRELU>(S, sc, bias[col], a);
+        I8Y<TY>::put(Y + (size_t)row * ldy + col, i8_out<PRELU>(S, sc, i8_cscale(cscale, col), bias[col], a));
     }
 }
 
-template <int T, bool ALIGNED>
-void launch_decode(const int8_t* X, const uint32_t* w2, int K, int M, int N, const float* scale, const float* B,
-                   float* Y, int ldy, bool prelu, float a, hipStream_t st) {
+template <int T, bool ALIGNED, typename TY>
+void launch_decode(const int8_t* X, const uint32_t* w2, int K, int M, int N, const float* scale, const float* cscale,
+                   const float* B, TY* Y, int ldy, bool prelu, float a, hipStream_t st) {
     const int ntiles = w2_col_tiles(N), nkb = w2_kblocks(K);
     const dim3 grid((ntiles + T - 1) / T), block(kDecWaves * 64);
     if (prelu)
-        hipLaunchKernelGGL((k_decode8<T, ALIGNED, true>), grid, block, 0, st, X, w2, K, M, N, nkb, ntiles, scale, B, Y,
-                           ldy, a);
+        hipLaunchKernelGGL((k_decode8<T, ALIGNED, true, TY>), grid, block, 0, st, X, w2, K, M, N, nkb, ntiles, scale,
+                           cscale, B, Y, ldy, a);
     else
-        hipLaunchKernelGGL((k_decode8<T, ALIGNED, false>), grid, block, 0, st, X, w2, K, M, N, nkb, ntiles, scale, B, Y,
-                           ldy, a);
+        hipLaunchKernelGGL((k_decode8<T, ALIGNED, false, TY>), grid, block, 0, st, X, w2, K, M, N, nkb, ntiles, scale,
+                           cscale, B, Y, ldy, a);
 }
 
 // k_decode8q: k_quant_rows_i8 and k_decode8 in one launch, for
@@ -416,11 +417,12 @@ void launch_decode(const int8_t* X, const uint32_t* w2, int K, int M, int N, con
 // four values in phase B; otherwise guarded scalar loads in both.
 constexpr int kQWaves = 8;           // the product build's K split; the staging of 16 waves would not fit 64 KiB
 constexpr int kQWaveBytes = 16 * kW2Blk;  // a wave's quantized block: 16 rows x 256 k
-template <typename TX, int T, bool ALIGNED, bool PRELU>
+template <typename TX, int T, bool ALIGNED, bool PRELU, typename TY>
 __global__ void __launch_bounds__(kQWaves * 64) k_decode8q(const TX* __restrict__ X, const uint32_t* __restrict__ W2,
                                                            int K, int M, int N, int nkb, int ntiles,
                                                            float* __restrict__ scale_out,
-                                                           const float* __restrict__ bias, float* __restrict__ Y,
+                                                           const float* __restrict__ cscale,
+                                                           const float* __restrict__ bias, TY* __restrict__ Y,
                                                            int ldy, float a) {
     using XS = XSrc<TX>;
     constexpr int kThreads = kQWaves * 64, kHalves = kThreads / 32;
@@ -615,33 +617,34 @@ __global__ void __launch_bounds__(kQWaves * 64) k_decode8q(const TX* __restrict_
         int S = 0;
 #pragma unroll
         for (int w = 0; w < kQWaves; ++w) S += red[(w * T + t) * 256 + (row & 3) * 64 + (row >> 2) * 16 + c];
-        Y[(size_t)row * ldy + col] = i8_out<PRELU>(S, s_scale[row], bias[col], a);
+        I8Y<TY>::put(Y + (size_t)row * ldy + col,
+                     i8_out<PRELU>(S, s_scale[row], i8_cscale(cscale, col), bias[col], a));
     }
 }
 
-template <typename TX, int T, bool ALIGNED>
-void launch_decode_q(const TX* X, const uint32_t* w2, int K, int M, int N, float* scale_out, const float* B, float* Y,
-                     int ldy, bool prelu, float a, hipStream_t st) {
+template <typename TX, int T, bool ALIGNED, typename TY>
+void launch_decode_q(const TX* X, const uint32_t* w2, int K, int M, int N, float* scale_out, const float* cscale,
+                     const float* B, TY* Y, int ldy, bool prelu, float a, hipStream_t st) {
     const int ntiles = w2_col_tiles(N), nkb = w2_kblocks(K);
     const dim3 grid((ntiles + T - 1) / T), block(kQWaves * 64);
     if (prelu)
-        hipLaunchKernelGGL((k_decode8q<TX, T, ALIGNED, true>), grid, block, 0, st, X, w2, K, M, N, nkb, ntiles, scale_out,
-                           B, Y, ldy, a);
+        hipLaunchKernelGGL((k_decode8q<TX, T, ALIGNED, true, TY>), grid, block, 0, st, X, w2, K, M, N, nkb, ntiles,
+                           scale_out, cscale, B, Y, ldy, a);
     else
-        hipLaunchKernelGGL((k_decode8q<TX, T, ALIGNED, false>), grid, block, 0, st, X, w2, K, M, N, nkb, ntiles,
-                           scale_out, B, Y, ldy, a);
+        hipLaunchKernelGGL((k_decode8q<TX, T, ALIGNED, false, TY>), grid, block, 0, st, X, w2, K, M, N, nkb, ntiles,
+                           scale_out, cscale, B, Y, ldy, a);
 }
 
-template <typename TX>
-void decode_q_typed(const TX* X, const uint32_t* w2, int K, int M, int N, float* scale_out, const float* B, float* Y,
-                    int ldy, bool prelu, float a, int num_cus, hipStream_t st) {
+template <typename TX, typename TY>
+void decode_q_typed(const TX* X, const uint32_t* w2, int K, int M, int N, float* scale_out, const float* cscale,
+                    const float* B, TY* Y, int ldy, bool prelu, float a, int num_cus, hipStream_t st) {
     const bool aligned = XSrc<TX>::vec_ok(X, K);
     const int T = decode_tiles_per_wg(M, N, num_cus);
-#define TCSC_DECODE_Q_LAUNCH(TT)                                                                \
-    if (aligned)                                                                                \
-        launch_decode_q<TX, TT, true>(X, w2, K, M, N, scale_out, B, Y, ldy, prelu, a, st);      \
-    else                                                                                        \
-        launch_decode_q<TX, TT, false>(X, w2, K, M, N, scale_out, B, Y, ldy, prelu, a, st)
+#define TCSC_DECODE_Q_LAUNCH(TT)                                                                        \
+    if (aligned)                                                                                        \
+        launch_decode_q<TX, TT, true>(X, w2, K, M, N, scale_out, cscale, B, Y, ldy, prelu, a, st);      \
+    else                                                                                                \
+        launch_decode_q<TX, TT, false>(X, w2, K, M, N, scale_out, cscale, B, Y, ldy, prelu, a, st)
     if (T == 4) {
         TCSC_DECODE_Q_LAUNCH(4);
     } else if (T == 2) {
@@ -729,17 +732,17 @@ int decode_tiles_per_wg(int M, int N, int num_cus) {
     return T;
 }
 
-hipError_t decode_gemm(const int8_t* X, const uint32_t* w2, int K, int M, int N, const float* scale, const float* B,
-                       float* Y, int ldy, bool prelu, float a, int num_cus, hipStream_t st) {
-    if (M < 1 || M > kDecodeMaxM || K < 1 || K >= kDecodeMaxK || N < 1 || !X || !w2 || !B || !Y || ldy < N)
-        return hipErrorInvalidValue;
+template <typename TY>
+static void decode_typed(const int8_t* X, const uint32_t* w2, int K, int M, int N, const float* scale,
+                         const float* cscale, const float* B, TY* Y, int ldy, bool prelu, float a, int num_cus,
+                         hipStream_t st) {
     const bool aligned = K % 16 == 0 && (reinterpret_cast<uintptr_t>(X) & 15) == 0;
     const int T = decode_tiles_per_wg(M, N, num_cus);
-#define TCSC_DECODE_LAUNCH(TT)                                                        \
-    if (aligned)                                                                      \
-        launch_decode<TT, true>(X, w2, K, M, N, scale, B, Y, ldy, prelu, a, st);      \
-    else                                                                              \
-        launch_decode<TT, false>(X, w2, K, M, N, scale, B, Y, ldy, prelu, a, st)
+#define TCSC_DECODE_LAUNCH(TT)                                                                \
+    if (aligned)                                                                              \
+        launch_decode<TT, true>(X, w2, K, M, N, scale, cscale, B, Y, ldy, prelu, a, st);      \
+    else                                                                                      \
+        launch_decode<TT, false>(X, w2, K, M, N, scale, cscale, B, Y, ldy, prelu, a, st)
     if (T == 4) {
         TCSC_DECODE_LAUNCH(4);
     } else if (T == 2) {
@@ -748,17 +751,39 @@ hipError_t decode_gemm(const int8_t* X, const uint32_t* w2, int K, int M, int N,
         TCSC_DECODE_LAUNCH(1);
     }
 #undef TCSC_DECODE_LAUNCH
+}
+
+hipError_t decode_gemm(const int8_t* X, const uint32_t* w2, int K, int M, int N, const float* scale, const float* B,
+                       const YOut& y, int ldy, bool prelu, float a, int num_cus, hipStream_t st) {
+    if (M < 1 || M > kDecodeMaxM || K < 1 || K >= kDecodeMaxK || N < 1 || !X || !w2 || !B || !y.Y || ldy < N)
+        return hipErrorInvalidValue;
+    if (y.ytype == kYBf16)
+        decode_typed(X, w2, K, M, N, scale, y.cscale, B, static_cast<uint16_t*>(y.Y), ldy, prelu, a, num_cus, st);
+    else
+        decode_typed(X, w2, K, M, N, scale, y.cscale, B, static_cast<float*>(y.Y), ldy, prelu, a, num_cus, st);
     return hipGetLastError();
 }
 
 hipError_t decode_gemm_q(const void* X, bool bf16, const uint32_t* w2, int K, int M, int N, float* scale_out,
-                         const float* B, float* Y, int ldy, bool prelu, float a, int num_cus, hipStream_t st) {
-    if (M < 1 || M > kDecodeMaxM || K < 1 || K >= kDecodeMaxK || N < 1 || !X || !w2 || !scale_out || !B || !Y || ldy < N)
+                         const float* B, const YOut& y, int ldy, bool prelu, float a, int num_cus, hipStream_t st) {
+    if (M < 1 || M > kDecodeMaxM || K < 1 || K >= kDecodeMaxK || N < 1 || !X || !w2 || !scale_out || !B || !y.Y ||
+        ldy < N)
         return hipErrorInvalidValue;
-    if (bf16)
-        decode_q_typed(static_cast<const uint16_t*>(X), w2, K, M, N, scale_out, B, Y, ldy, prelu, a, num_cus, st);
-    else
-        decode_q_typed(static_cast<const float*>(X), w2, K, M, N, scale_out, B, Y, ldy, prelu, a, num_cus, st);
+#define TCSC_DECODE_Q_TYPED(TX, TY)                                                                                  \
+    decode_q_typed(static_cast<const TX*>(X), w2, K, M, N, scale_out, y.cscale, B, static_cast<TY*>(y.Y), ldy, prelu, \
+                   a, num_cus, st)
+    if (bf16) {
+        if (y.ytype == kYBf16)
+            TCSC_DECODE_Q_TYPED(uint16_t, uint16_t);
+        else
+            TCSC_DECODE_Q_TYPED(uint16_t, float);
+    } else {
+        if (y.ytype == kYBf16)
+            TCSC_DECODE_Q_TYPED(float, uint16_t);
+        else
+            TCSC_DECODE_Q_TYPED(float, float);
+    }
+#undef TCSC_DECODE_Q_TYPED
     return hipGetLastError();
 }
 

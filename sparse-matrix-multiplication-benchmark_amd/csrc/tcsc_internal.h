@@ -195,6 +195,22 @@ constexpr size_t kCombineBytes = (size_t)kCombineTiles * kCombineWords * 4;
 // (tcsc_api.cpp), the kernels' is XSrc (tcsc_xsrc.h).
 enum { kF32 = 0, kBf16 = 1, kI8 = 2 };
 
+// The output of an int8 call (tcsc_gpu_sgemm_i8_out / _q8_out),
+// beside the activation type: Y is M x ldy floats (kYF32, TCSC_Y_F32) or bf16
+// bit patterns (kYBf16, TCSC_Y_BF16), ldy in elements; cscale[j] multiplies
+// column j after the row scale and before the bias (null: by one).  The fp32
+// and bf16 calls, and the gather and small-M routes of the int8 one, write
+// floats without a column scale: {Y, kYF32, nullptr}.
+enum { kYF32 = 0, kYBf16 = 1 };
+struct YOut {
+    void* Y = nullptr;
+    int ytype = kYF32;
+    const float* cscale = nullptr;
+    size_t elem() const { return ytype == kYBf16 ? 2 : 4; }
+    bool plain() const { return ytype == kYF32 && !cscale; }  // what every route can write
+    YOut rows_on(size_t r0, int ldy) const { return YOut{static_cast<char*>(Y) + r0 * ldy * elem(), ytype, cscale}; }
+};
+
 struct GemmArgs {
     const void* X = nullptr;        // M x K of xtype; the transpose converts it into the fp32 X^T and
     int xtype = kF32;
@@ -427,10 +443,10 @@ hipError_t mfma8_pack_x(const int8_t* X, int M, int K, int8_t* x8, int ld8, hipS
 // column's sum of |w| >= 2^24
 hipError_t mfma8_build_w8(const uint16_t* wt, int ncols, int K, int ldw, int8_t* w8, int ld8, int* bad,
                           hipStream_t st);
-// k_gemm8 (+ k_reduce_i8 when K is split): Y = act(fl(fl(float(S) * scale[m]) +
-// B[j])), S the exact i32 sum; scale null = all ones
+// k_gemm8 (+ k_reduce_i8 when K is split): Y = act(fl(fl(fl(float(S) * scale[m])
+// * cscale[j]) + B[j])) in y's type, S the exact i32 sum; a null scale = all ones
 hipError_t mfma8_gemm(const int8_t* x8, const int8_t* w8, int ld8, int K, int M, int N, const float* scale,
-                      const float* B, float* Y, int ldy, bool prelu, float a, int* slabs, size_t slab_bytes,
+                      const float* B, const YOut& y, int ldy, bool prelu, float a, int* slabs, size_t slab_bytes,
                       hipStream_t st);
 // k_quant_rows_i8: per-row absmax quantization (tcsc_gpu_quantize_rows_i8)
 hipError_t quantize_rows_i8(const float* X, int M, int K, int8_t* Xq, float* scale, hipStream_t st);
@@ -483,20 +499,20 @@ hipError_t w2_unpack_fill(const uint32_t* w2, int ncols, int K, const int* offp,
 // k_gemm8w2 (tcsc_mfma.hip): mfma8_gemm with B read from the
 // 2-bit image; the same tiles, K split (mfma8_slices), slabs and bits
 hipError_t mfma8_gemm_w2(const int8_t* x8, const uint32_t* w2, int ld8, int K, int M, int N, const float* scale,
-                         const float* B, float* Y, int ldy, bool prelu, float a, int* slabs, size_t slab_bytes,
+                         const float* B, const YOut& y, int ldy, bool prelu, float a, int* slabs, size_t slab_bytes,
                          hipStream_t st);
 // column tiles per workgroup of a k_decode8 launch (1, 2 or 4)
 int decode_tiles_per_wg(int M, int N, int num_cus);
-// k_decode8: Y = act(fl(fl(float(S) * scale[m]) + B[j])) for m < M <= 16, S the
-// exact i32 sum; X is M x K int8 of any alignment, read in place
+// k_decode8: mfma8_gemm's Y for m < M <= 16; X is M x K int8 of any alignment,
+// read in place
 hipError_t decode_gemm(const int8_t* X, const uint32_t* w2, int K, int M, int N, const float* scale, const float* B,
-                       float* Y, int ldy, bool prelu, float a, int num_cus, hipStream_t st);
+                       const YOut& y, int ldy, bool prelu, float a, int num_cus, hipStream_t st);
 // k_decode8q: the quantizer and k_decode8 in one launch.  X is
 // M x K fp32 (bf16 false) or bf16 bit patterns (bf16 true) of any alignment,
 // read in place; scale_out[m] gets the quantizer's scale of row m, and Y the
 // bits of quantize_rows_i8{,_bf16} followed by decode_gemm
 hipError_t decode_gemm_q(const void* X, bool bf16, const uint32_t* w2, int K, int M, int N, float* scale_out,
-                         const float* B, float* Y, int ldy, bool prelu, float a, int num_cus, hipStream_t st);
+                         const float* B, const YOut& y, int ldy, bool prelu, float a, int num_cus, hipStream_t st);
 
 // Rewrites the flagged rows in k_stream's fast order (no-op when none is).
 hipError_t mfma_fixup(const uint16_t* x3, int M, int K, int ldk, const int* cq, const int* crq, int ncols,

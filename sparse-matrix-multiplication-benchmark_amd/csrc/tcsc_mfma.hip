@@ -702,9 +702,11 @@ __global__ void __launch_bounds__(WM * WN * 64) k_gemm3(const uint16_t* __restri
 // flags, no fixup; the i32 sums are exact, so every K split gives one result.
 // ---------------------------------------------------------------------------
 typedef int i32x4 __attribute__((ext_vector_type(4)));
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 
-// The epilogue arithmetic, act(fl(fl(float(S) * s) + b)), is i8_out of
-// tcsc_i8_out.h: k_decode8 (tcsc_decode.hip) runs the same definition.
+// The epilogue arithmetic, act(fl(fl(fl(float(S) * s) * c) + b)) as floats or
+// rounded to bf16, is i8_out and i8_bf16 of tcsc_i8_out.h:
+// k_decode8 and k_decode8q (tcsc_decode.hip) run the same definitions.
 
 // int8 X (M x K, pitch K) -> X8 (M x ld8 bytes): the row as it is, zeros past
 // K, one workgroup per row.  VEC (K % 16 == 0, X 16-B aligned): kSplitU 16-B
@@ -769,11 +771,13 @@ __global__ void __launch_bounds__(256) k_w8_from(const uint16_t* __restrict__ WT
 
 // Split K: the i32 slabs added as integers (any order gives the same sum),
 // then the unsplit epilogue's arithmetic.  VEC: 4 columns per thread (N % 4 ==
-// 0, ldy % 4 == 0, 16-B aligned slabs and Y), all slices' loads in flight.
-template <bool PRELU, bool VEC>
+// 0, ldy % 4 == 0, 16-B aligned slabs, Y aligned to 4 of its elements), all
+// slices' loads in flight.  TY: float, or uint16_t for a bf16 Y (§21).
+template <bool PRELU, bool VEC, typename TY>
 __global__ void __launch_bounds__(256) k_reduce_i8(const int* __restrict__ ws, int slices, int M, int N,
-                                                   const float* __restrict__ scale, const float* __restrict__ Bias,
-                                                   float* __restrict__ Y, int ldy, float a) {
+                                                   const float* __restrict__ scale,
+                                                   const float* __restrict__ cscale, const float* __restrict__ Bias,
+                                                   TY* __restrict__ Y, int ldy, float a) {
     constexpr int W = VEC ? 4 : 1;
     const int nq = N / W;
     const long long total = (long long)M * nq;
@@ -801,36 +805,49 @@ __global__ void __launch_bounds__(256) k_reduce_i8(const int* __restrict__ ws, i
 #pragma unroll
             for (int s = 0; s < 16; ++s)
                 if (s < slices) t += p[s][u];
-            v[u] = i8_out<PRELU>(t, sc, Bias[col + u], a);
+            v[u] = i8_out<PRELU>(t, sc, i8_cscale(cscale, col + u), Bias[col + u], a);
         }
-        float* dst = Y + (size_t)row * ldy + col;
-        if constexpr (VEC) {
+        TY* dst = Y + (size_t)row * ldy + col;
+        if constexpr (!VEC) {
+            I8Y<TY>::put(dst, v[0]);
+        } else if constexpr (std::is_same<TY, float>::value) {
             const f32x4 o = {v[0], v[1], v[2], v[3]};
             __builtin_nontemporal_store(o, reinterpret_cast<f32x4*>(dst));
-        } else {
-            dst[0] = v[0];
+        } else {  // four bf16 of this lane's own: one 8-B store
+            const u32x2 o = {(uint32_t)i8_bf16(v[0]) | (uint32_t)i8_bf16(v[1]) << 16,
+                             (uint32_t)i8_bf16(v[2]) | (uint32_t)i8_bf16(v[3]) << 16};
+            __builtin_nontemporal_store(o, reinterpret_cast<u32x2*>(dst));
         }
     }
 }
 
 // The k_gemm8 epilogue: gemm3_store's staging (the raw i32 sums parked in the
 // LDS, read back as whole rows, 16-B stores).  PARTIAL: the raw sums go into
-// the i32 slab (Yi, pitch ldy); otherwise Y = i8_out(S, scale[row], bias[col]).
-template <int WM, int WN, int FI, int FJ, bool PRELU, bool PARTIAL, int LDSB>
+// the i32 slab (Yi, pitch ldy); otherwise Y = i8_out(S, scale[row], cscale[col],
+// bias[col]), as floats or (TY = uint16_t) bf16 bits.  A lane's four columns go
+// out as one store -- 16 B of floats, 8 B of bf16 -- where Y is aligned to four
+// of its elements and ldy % 4 == 0, else element by element, each guarded.
+template <int WM, int WN, int FI, int FJ, bool PRELU, bool PARTIAL, int LDSB, typename TY>
 __device__ __forceinline__ void gemm8_store(const i32x4 (&acc)[FI][FJ], char* lds, int lane, int wr, int wc, int m0,
                                             int n0, int M, int N, const float* __restrict__ scale,
-                                            const float* __restrict__ bias, float* __restrict__ Y, int ldy, float a) {
+                                            const float* __restrict__ cscale, const float* __restrict__ bias,
+                                            TY* __restrict__ Y, int ldy, float a) {
+    static_assert(!PARTIAL || std::is_same<TY, float>::value, "the i32 slabs travel as the float instantiation");
     constexpr int TM = WM * FI * 16, TN = WN * FJ * 16, NW = WM * WN;
     constexpr int PR = 64, SROW = TN + 4, LPR = TN / 4;  // rows per pass, staged row, lanes per row
     static_assert(PR * SROW * 4 <= LDSB && TM % PR == 0 && (64 % LPR == 0 || LPR % 64 == 0), "epilogue staging");
     static_assert((NW * 64) % LPR == 0, "a lane keeps its columns across the read-back");
     int* stg = reinterpret_cast<int*>(lds);
-    const bool vec = (ldy & 3) == 0 && (reinterpret_cast<uintptr_t>(Y) & 15) == 0;
+    const bool vec = (ldy & 3) == 0 && (reinterpret_cast<uintptr_t>(Y) & (4 * sizeof(TY) - 1)) == 0;
     const int c4 = 4 * (threadIdx.x % LPR), col = n0 + c4;
-    f32x4 bq = f32x4{0.f, 0.f, 0.f, 0.f};
-    if (!PARTIAL)
+    f32x4 bq = f32x4{0.f, 0.f, 0.f, 0.f}, cq = f32x4{1.f, 1.f, 1.f, 1.f};
+    if (!PARTIAL) {
 #pragma unroll
         for (int u = 0; u < 4; ++u) bq[u] = col + u < N ? bias[col + u] : 0.0f;
+        if (cscale)
+#pragma unroll
+            for (int u = 0; u < 4; ++u) cq[u] = col + u < N ? cscale[col + u] : 1.0f;
+    }
 #pragma unroll
     for (int p = 0; p < TM / PR; ++p) {
 #pragma unroll
@@ -863,14 +880,20 @@ __device__ __forceinline__ void gemm8_store(const i32x4 (&acc)[FI][FJ], char* ld
                 const float sc = scale ? scale[row] : 1.0f;
                 f32x4 v;
 #pragma unroll
-                for (int u = 0; u < 4; ++u) v[u] = i8_out<PRELU>(s[u], sc, bq[u], a);
-                float* dst = Y + (size_t)row * ldy + col;
+                for (int u = 0; u < 4; ++u) v[u] = i8_out<PRELU>(s[u], sc, cq[u], bq[u], a);
+                TY* dst = Y + (size_t)row * ldy + col;
                 if (vec && col + 3 < N) {
-                    __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(dst));
+                    if constexpr (std::is_same<TY, float>::value) {
+                        __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(dst));
+                    } else {
+                        const u32x2 o = {(uint32_t)i8_bf16(v[0]) | (uint32_t)i8_bf16(v[1]) << 16,
+                                         (uint32_t)i8_bf16(v[2]) | (uint32_t)i8_bf16(v[3]) << 16};
+                        __builtin_nontemporal_store(o, reinterpret_cast<u32x2*>(dst));
+                    }
                 } else {
 #pragma unroll
                     for (int u = 0; u < 4; ++u)
-                        if (col + u < N) __builtin_nontemporal_store(v[u], dst + u);
+                        if (col + u < N) I8Y<TY>::put_nt(dst + u, v[u]);
                 }
             }
         }
@@ -887,11 +910,12 @@ __device__ __forceinline__ void gemm8_store(const i32x4 (&acc)[FI][FJ], char* ld
 // k values whichever they are, and an integer dot product does not depend on
 // their order.  ldk = ldw = mfma8_ldw(K) bytes.  PARTIAL: raw i32 sums into
 // slab blockIdx.y of Y (M x ldy ints), added by k_reduce_i8.
-template <int WM, int WN, int FI, int FJ, bool PRELU, bool PARTIAL>
+template <int WM, int WN, int FI, int FJ, bool PRELU, bool PARTIAL, typename TY = float>
 __global__ void __launch_bounds__(WM * WN * 64) k_gemm8(const int8_t* __restrict__ A, const int8_t* __restrict__ Bt,
                                                       int ldk, int ldw, int M, int N, int nblk,
                                                       const float* __restrict__ scale,
-                                                      const float* __restrict__ bias, float* __restrict__ Y, int ldy,
+                                                      const float* __restrict__ cscale,
+                                                      const float* __restrict__ bias, TY* __restrict__ Y, int ldy,
                                                       float a, int tiles_m, int tiles_n, int gm, int bps) {
     static_assert(!(PARTIAL && PRELU), "a partial slab carries raw sums");
     constexpr int TM = WM * FI * 16, TN = WN * FJ * 16, NW = WM * WN;
@@ -1016,8 +1040,8 @@ __global__ void __launch_bounds__(WM * WN * 64) k_gemm8(const int8_t* __restrict
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
 
-    float* out = PARTIAL ? reinterpret_cast<float*>(reinterpret_cast<int*>(Y) + (size_t)blockIdx.y * M * ldy) : Y;
-    gemm8_store<WM, WN, FI, FJ, PRELU, PARTIAL, 2 * ASLOT + 2 * BSLOT>(acc, lds, lane, wr, wc, m0, n0, M, N, scale, bias,
+    TY* out = PARTIAL ? reinterpret_cast<TY*>(reinterpret_cast<int*>(Y) + (size_t)blockIdx.y * M * ldy) : Y;
+    gemm8_store<WM, WN, FI, FJ, PRELU, PARTIAL, 2 * ASLOT + 2 * BSLOT>(acc, lds, lane, wr, wc, m0, n0, M, N, scale, cscale, bias,
                                                                        out, ldy, a);
 }
 
@@ -1039,8 +1063,6 @@ __global__ void __launch_bounds__(WM * WN * 64) k_gemm8(const int8_t* __restrict
 // epilogue are k_gemm8's.  A workgroup's column tiles past the matrix read the
 // last tile again and are not stored; an odd count of 128-k blocks ends the
 // loop inside the last 256-k image block, whose second half is never read.
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-
 __device__ __forceinline__ i32x4 w2_frag(uint32_t p) {
     i32x4 b;
 #pragma unroll
@@ -1051,12 +1073,12 @@ __device__ __forceinline__ i32x4 w2_frag(uint32_t p) {
     return b;
 }
 
-template <int WN, int FI, int FJ, bool PRELU, bool PARTIAL, int BS = 2>
+template <int WN, int FI, int FJ, bool PRELU, bool PARTIAL, int BS = 2, typename TY = float>
 __global__ void __launch_bounds__(WN * 64) k_gemm8w2(const int8_t* __restrict__ A, const uint32_t* __restrict__ W2,
                                                     int ldk, int M, int N, int nblk, int nkb, int ntiles,
-                                                    const float* __restrict__ scale, const float* __restrict__ bias,
-                                                    float* __restrict__ Y, int ldy, float a, int tiles_m, int tiles_n,
-                                                    int gm, int bps) {
+                                                    const float* __restrict__ scale, const float* __restrict__ cscale,
+                                                    const float* __restrict__ bias, TY* __restrict__ Y, int ldy,
+                                                    float a, int tiles_m, int tiles_n, int gm, int bps) {
     static_assert(!(PARTIAL && PRELU), "a partial slab carries raw sums");
     constexpr int TM = FI * 16, TN = WN * FJ * 16, NW = WN;
     constexpr int PA = TM / 8, ASLOT = PA * 1024, PAW = PA / NW;
@@ -1195,8 +1217,9 @@ __global__ void __launch_bounds__(WN * 64) k_gemm8w2(const int8_t* __restrict__ 
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
 
-    float* out = PARTIAL ? reinterpret_cast<float*>(reinterpret_cast<int*>(Y) + (size_t)blockIdx.y * M * ldy) : Y;
-    gemm8_store<1, WN, FI, FJ, PRELU, PARTIAL, LDSB>(acc, lds, lane, 0, wave, m0, n0, M, N, scale, bias, out, ldy, a);
+    TY* out = PARTIAL ? reinterpret_cast<TY*>(reinterpret_cast<int*>(Y) + (size_t)blockIdx.y * M * ldy) : Y;
+    gemm8_store<1, WN, FI, FJ, PRELU, PARTIAL, LDSB>(acc, lds, lane, 0, wave, m0, n0, M, N, scale, cscale, bias, out, ldy,
+                                                     a);
 }
 
 // tcsc_gpu_quantize_rows_i8{,_bf16}: per row, amax = max |x|, scale = amax /
@@ -1526,25 +1549,25 @@ hipError_t quantize_rows_i8_bf16(const uint16_t* X, int M, int K, int8_t* Xq, fl
 }
 
 // k_reduce_i8 on the slabs of a split int8 GEMM (k_gemm8 or k_gemm8w2)
-template <bool PRELU>
-static hipError_t launch_reduce_i8(const int* slabs, int slices, int M, int N, const float* scale, const float* B,
-                                   float* Y, int ldy, float a, hipStream_t st) {
-    const bool vec = N % 4 == 0 && ldy % 4 == 0 &&
-                     ((reinterpret_cast<uintptr_t>(Y) | reinterpret_cast<uintptr_t>(slabs)) & 15) == 0;
+template <bool PRELU, typename TY>
+static hipError_t launch_reduce_i8(const int* slabs, int slices, int M, int N, const float* scale, const float* cscale,
+                                   const float* B, TY* Y, int ldy, float a, hipStream_t st) {
+    const bool vec = N % 4 == 0 && ldy % 4 == 0 && (reinterpret_cast<uintptr_t>(Y) & (4 * sizeof(TY) - 1)) == 0 &&
+                     (reinterpret_cast<uintptr_t>(slabs) & 15) == 0;
     const long long n = (long long)M * (vec ? N / 4 : N);
     if (vec)
-        hipLaunchKernelGGL((k_reduce_i8<PRELU, true>), dim3(grid_of(n, 256)), dim3(256), 0, st, slabs, slices, M, N, scale,
-                           B, Y, ldy, a);
+        hipLaunchKernelGGL((k_reduce_i8<PRELU, true, TY>), dim3(grid_of(n, 256)), dim3(256), 0, st, slabs, slices, M, N, scale,
+                           cscale, B, Y, ldy, a);
     else
-        hipLaunchKernelGGL((k_reduce_i8<PRELU, false>), dim3(grid_of(n, 256)), dim3(256), 0, st, slabs, slices, M, N, scale,
-                           B, Y, ldy, a);
+        hipLaunchKernelGGL((k_reduce_i8<PRELU, false, TY>), dim3(grid_of(n, 256)), dim3(256), 0, st, slabs, slices, M, N, scale,
+                           cscale, B, Y, ldy, a);
     return hipGetLastError();
 }
 
-template <bool PRELU>
+template <bool PRELU, typename TY>
 static hipError_t launch_gemm8_t(const int8_t* x8, const int8_t* w8, int ld8, int nblk, int M, int N,
-                                 const float* scale, const float* B, float* Y, int ldy, float a, int* slabs,
-                                 int slices, hipStream_t st) {
+                                 const float* scale, const float* cscale, const float* B, TY* Y, int ldy, float a,
+                                 int* slabs, int slices, hipStream_t st) {
     constexpr int kGm = 4;  // bands of 4 row tiles, as launch_gemm3_t
     float* sl = reinterpret_cast<float*>(slabs);
     const int bps = (nblk + slices - 1) / std::max(slices, 1);
@@ -1552,41 +1575,41 @@ static hipError_t launch_gemm8_t(const int8_t* x8, const int8_t* w8, int ld8, in
         const int tm = (M + 127) / 128, tn = (N + 511) / 512;
         const int gm = std::min(kGm, tm);
         if (slices <= 1)
-            hipLaunchKernelGGL((k_gemm8<1, 8, 8, 4, PRELU, false>), dim3(tm * tn), dim3(512), 0, st, x8, w8, ld8, ld8, M, N,
-                               nblk, scale, B, Y, ldy, a, tm, tn, gm, nblk);
+            hipLaunchKernelGGL((k_gemm8<1, 8, 8, 4, PRELU, false, TY>), dim3(tm * tn), dim3(512), 0, st, x8, w8, ld8, ld8, M, N,
+                               nblk, scale, cscale, B, Y, ldy, a, tm, tn, gm, nblk);
         else
             hipLaunchKernelGGL((k_gemm8<1, 8, 8, 4, false, true>), dim3(tm * tn, slices), dim3(512), 0, st, x8, w8, ld8,
-                               ld8, M, N, nblk, nullptr, nullptr, sl, N, 0.0f, tm, tn, gm, bps);
+                               ld8, M, N, nblk, nullptr, nullptr, nullptr, sl, N, 0.0f, tm, tn, gm, bps);
     } else if (mfma_narrow_tiles(M, N)) {
         const int tn = (N + 255) / 256;
         if (slices <= 1)
-            hipLaunchKernelGGL((k_gemm8<1, 4, 4, 4, PRELU, false>), dim3(tn), dim3(256), 0, st, x8, w8, ld8, ld8, M, N, nblk,
-                               scale, B, Y, ldy, a, 1, tn, 1, nblk);
+            hipLaunchKernelGGL((k_gemm8<1, 4, 4, 4, PRELU, false, TY>), dim3(tn), dim3(256), 0, st, x8, w8, ld8, ld8, M, N, nblk,
+                               scale, cscale, B, Y, ldy, a, 1, tn, 1, nblk);
         else
             hipLaunchKernelGGL((k_gemm8<1, 4, 4, 4, false, true>), dim3(tn, slices), dim3(256), 0, st, x8, w8, ld8, ld8, M,
-                               N, nblk, nullptr, nullptr, sl, N, 0.0f, 1, tn, 1, bps);
+                               N, nblk, nullptr, nullptr, nullptr, sl, N, 0.0f, 1, tn, 1, bps);
     } else {
         const int tm = (M + 127) / 128, tn = (N + 127) / 128;
         const int gm = std::min(kGm, tm);
         if (slices <= 1)
-            hipLaunchKernelGGL((k_gemm8<2, 2, 4, 4, PRELU, false>), dim3(tm * tn), dim3(256), 0, st, x8, w8, ld8, ld8, M, N,
-                               nblk, scale, B, Y, ldy, a, tm, tn, gm, nblk);
+            hipLaunchKernelGGL((k_gemm8<2, 2, 4, 4, PRELU, false, TY>), dim3(tm * tn), dim3(256), 0, st, x8, w8, ld8, ld8, M, N,
+                               nblk, scale, cscale, B, Y, ldy, a, tm, tn, gm, nblk);
         else
             hipLaunchKernelGGL((k_gemm8<2, 2, 4, 4, false, true>), dim3(tm * tn, slices), dim3(256), 0, st, x8, w8, ld8,
-                               ld8, M, N, nblk, nullptr, nullptr, sl, N, 0.0f, tm, tn, gm, bps);
+                               ld8, M, N, nblk, nullptr, nullptr, nullptr, sl, N, 0.0f, tm, tn, gm, bps);
     }
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess || slices <= 1) return e;
-    return launch_reduce_i8<PRELU>(slabs, slices, M, N, scale, B, Y, ldy, a, st);
+    return launch_reduce_i8<PRELU>(slabs, slices, M, N, scale, cscale, B, Y, ldy, a, st);
 }
 
 // k_gemm8w2 on k_gemm8's three grids, slices and blocks per slice: 128 x 512
 // (8 waves of 128 x 64), 64 x 256 (4 waves of 64 x 64) and 128 x 128 (4 waves
 // of 128 x 32), so mfma_tiles and mfma8_slices count its workgroups as they are.
-template <bool PRELU>
+template <bool PRELU, typename TY>
 static hipError_t launch_gemm8w2_t(const int8_t* x8, const uint32_t* w2, int ld8, int nblk, int K, int M, int N,
-                                   const float* scale, const float* B, float* Y, int ldy, float a, int* slabs,
-                                   int slices, hipStream_t st) {
+                                   const float* scale, const float* cscale, const float* B, TY* Y, int ldy, float a,
+                                   int* slabs, int slices, hipStream_t st) {
     constexpr int kGm = 4;
     float* sl = reinterpret_cast<float*>(slabs);
     const int bps = (nblk + slices - 1) / std::max(slices, 1);
@@ -1595,56 +1618,63 @@ static hipError_t launch_gemm8w2_t(const int8_t* x8, const uint32_t* w2, int ld8
         const int tm = (M + 127) / 128, tn = (N + 511) / 512;
         const int gm = std::min(kGm, tm);
         if (slices <= 1)
-            hipLaunchKernelGGL((k_gemm8w2<8, 8, 4, PRELU, false, 1>), dim3(tm * tn), dim3(512), 0, st, x8, w2, ld8, M, N, nblk,
-                               nkb, nt, scale, B, Y, ldy, a, tm, tn, gm, nblk);
+            hipLaunchKernelGGL((k_gemm8w2<8, 8, 4, PRELU, false, 1, TY>), dim3(tm * tn), dim3(512), 0, st, x8, w2, ld8, M, N, nblk,
+                               nkb, nt, scale, cscale, B, Y, ldy, a, tm, tn, gm, nblk);
         else
             hipLaunchKernelGGL((k_gemm8w2<8, 8, 4, false, true, 1>), dim3(tm * tn, slices), dim3(512), 0, st, x8, w2, ld8, M,
-                               N, nblk, nkb, nt, nullptr, nullptr, sl, N, 0.0f, tm, tn, gm, bps);
+                               N, nblk, nkb, nt, nullptr, nullptr, nullptr, sl, N, 0.0f, tm, tn, gm, bps);
     } else if (mfma_narrow_tiles(M, N)) {
         const int tn = (N + 255) / 256;
         if (slices <= 1)
-            hipLaunchKernelGGL((k_gemm8w2<4, 4, 4, PRELU, false>), dim3(tn), dim3(256), 0, st, x8, w2, ld8, M, N, nblk, nkb,
-                               nt, scale, B, Y, ldy, a, 1, tn, 1, nblk);
+            hipLaunchKernelGGL((k_gemm8w2<4, 4, 4, PRELU, false, 2, TY>), dim3(tn), dim3(256), 0, st, x8, w2, ld8, M, N, nblk, nkb,
+                               nt, scale, cscale, B, Y, ldy, a, 1, tn, 1, nblk);
         else
             hipLaunchKernelGGL((k_gemm8w2<4, 4, 4, false, true>), dim3(tn, slices), dim3(256), 0, st, x8, w2, ld8, M, N,
-                               nblk, nkb, nt, nullptr, nullptr, sl, N, 0.0f, 1, tn, 1, bps);
+                               nblk, nkb, nt, nullptr, nullptr, nullptr, sl, N, 0.0f, 1, tn, 1, bps);
     } else {
         const int tm = (M + 127) / 128, tn = (N + 127) / 128;
         const int gm = std::min(kGm, tm);
         if (slices <= 1)
-            hipLaunchKernelGGL((k_gemm8w2<4, 8, 2, PRELU, false>), dim3(tm * tn), dim3(256), 0, st, x8, w2, ld8, M, N, nblk,
-                               nkb, nt, scale, B, Y, ldy, a, tm, tn, gm, nblk);
+            hipLaunchKernelGGL((k_gemm8w2<4, 8, 2, PRELU, false, 2, TY>), dim3(tm * tn), dim3(256), 0, st, x8, w2, ld8, M, N, nblk,
+                               nkb, nt, scale, cscale, B, Y, ldy, a, tm, tn, gm, nblk);
         else
             hipLaunchKernelGGL((k_gemm8w2<4, 8, 2, false, true>), dim3(tm * tn, slices), dim3(256), 0, st, x8, w2, ld8, M,
-                               N, nblk, nkb, nt, nullptr, nullptr, sl, N, 0.0f, tm, tn, gm, bps);
+                               N, nblk, nkb, nt, nullptr, nullptr, nullptr, sl, N, 0.0f, tm, tn, gm, bps);
     }
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess || slices <= 1) return e;
-    return launch_reduce_i8<PRELU>(slabs, slices, M, N, scale, B, Y, ldy, a, st);
+    return launch_reduce_i8<PRELU>(slabs, slices, M, N, scale, cscale, B, Y, ldy, a, st);
 }
 
+// the Y type and the PReLU into template arguments
+#define TCSC_I8_DISPATCH(FN, ...)                                                                            \
+    (y.ytype == kYBf16                                                                                       \
+         ? (prelu ? FN<true>(__VA_ARGS__, static_cast<uint16_t*>(y.Y), ldy, a, slabs, slices, st)            \
+                  : FN<false>(__VA_ARGS__, static_cast<uint16_t*>(y.Y), ldy, a, slabs, slices, st))          \
+         : (prelu ? FN<true>(__VA_ARGS__, static_cast<float*>(y.Y), ldy, a, slabs, slices, st)               \
+                  : FN<false>(__VA_ARGS__, static_cast<float*>(y.Y), ldy, a, slabs, slices, st)))
+
 hipError_t mfma8_gemm(const int8_t* x8, const int8_t* w8, int ld8, int K, int M, int N, const float* scale,
-                      const float* B, float* Y, int ldy, bool prelu, float a, int* slabs, size_t slab_bytes,
+                      const float* B, const YOut& y, int ldy, bool prelu, float a, int* slabs, size_t slab_bytes,
                       hipStream_t st) {
     if (M <= 0 || N <= 0) return hipSuccess;
     const int nblk = mfma8_nblk(K);
-    if (nblk < 1 || ld8 != mfma8_ldw(K)) return hipErrorInvalidValue;
+    if (nblk < 1 || ld8 != mfma8_ldw(K) || !y.Y) return hipErrorInvalidValue;
     const int slices = mfma8_slices(M, N, K);
     if (slices > 1 && (!slabs || slab_bytes < mfma8_slab_bytes(M, N, K))) return hipErrorInvalidValue;
-    return prelu ? launch_gemm8_t<true>(x8, w8, ld8, nblk, M, N, scale, B, Y, ldy, a, slabs, slices, st)
-                 : launch_gemm8_t<false>(x8, w8, ld8, nblk, M, N, scale, B, Y, ldy, a, slabs, slices, st);
+    return TCSC_I8_DISPATCH(launch_gemm8_t, x8, w8, ld8, nblk, M, N, scale, y.cscale, B);
 }
 
 hipError_t mfma8_gemm_w2(const int8_t* x8, const uint32_t* w2, int ld8, int K, int M, int N, const float* scale,
-                         const float* B, float* Y, int ldy, bool prelu, float a, int* slabs, size_t slab_bytes,
+                         const float* B, const YOut& y, int ldy, bool prelu, float a, int* slabs, size_t slab_bytes,
                          hipStream_t st) {
     if (M <= 0 || N <= 0) return hipSuccess;
     const int nblk = mfma8_nblk(K);
-    if (nblk < 1 || ld8 != mfma8_ldw(K) || K >= kDecodeMaxK || !w2) return hipErrorInvalidValue;
+    if (nblk < 1 || ld8 != mfma8_ldw(K) || K >= kDecodeMaxK || !w2 || !y.Y) return hipErrorInvalidValue;
     const int slices = mfma8_slices(M, N, K);
     if (slices > 1 && (!slabs || slab_bytes < mfma8_slab_bytes(M, N, K))) return hipErrorInvalidValue;
-    return prelu ? launch_gemm8w2_t<true>(x8, w2, ld8, nblk, K, M, N, scale, B, Y, ldy, a, slabs, slices, st)
-                 : launch_gemm8w2_t<false>(x8, w2, ld8, nblk, K, M, N, scale, B, Y, ldy, a, slabs, slices, st);
+    return TCSC_I8_DISPATCH(launch_gemm8w2_t, x8, w2, ld8, nblk, K, M, N, scale, y.cscale, B);
 }
+#undef TCSC_I8_DISPATCH
 
 }  // namespace tcsc

@@ -93,10 +93,15 @@ Route route_call(const tcsc_gpu_plan* p, int M, int dt, size_t ws_avail, const R
 
 // One call on a caller's workspace.  dX is M x K of type dt (with the int8
 // type the row scales dScale, null for ones); the narrow types have stage 0
-// only.  *ran, if given, receives the route that ran.
+// only.  *ran, if given, receives the route that ran.  Beside the activation
+// type, the output descriptor: `out`, if given, replaces dY with a Y of its own
+// type (fp32 or bf16, ldy in its elements) and the column scales (YOut,
+// tcsc_internal.h) -- the int8 call's decode and MFMA routes alone write
+// anything but {fp32, no column scale}; `as` is the call's name in messages.
 int sgemm_ws(const tcsc_gpu_plan* p, const void* dX, const float* dB, float* dY, int M, int ldy, int variant, float a,
              void* stream, float* ws, size_t ws_bytes, int stage = 0, const RoutePins& pin = RoutePins(),
-             Route* ran = nullptr, int dt = kF32, const float* dScale = nullptr);
+             Route* ran = nullptr, int dt = kF32, const float* dScale = nullptr, const YOut* out = nullptr,
+             const char* as = nullptr);
 
 }  // namespace tcsc
 #pragma GCC visibility pop

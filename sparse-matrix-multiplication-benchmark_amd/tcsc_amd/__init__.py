@@ -57,6 +57,7 @@ EXPORTED_SYMBOLS = (
     "tcsc_gpu_plan_create_packed_image", "tcsc_gpu_plan_create_packed_image_device", "tcsc_gpu_w2_to_tcsc",
     "tcsc_gpu_w2_from_tcsc_host", "tcsc_gpu_w2_to_tcsc_host",
     "tcsc_gpu_quantize_rows_i8_bf16", "tcsc_gpu_sgemm_q8", "tcsc_gpu_launch_info_q8", "tcsc_gpu_quant_fuse_pays",
+    "tcsc_gpu_sgemm_i8_out", "tcsc_gpu_sgemm_q8_out",
     # include/sparse/bcsr.h
     "bcsr_from_dense", "bcsr_sgemm_basic", "bcsr_sgemm_prelu_basic", "bcsr_sgemm_avx", "bcsr_sgemm_prelu_avx",
     "bcsr_sgemm_avx2", "bcsr_free",
@@ -183,6 +184,8 @@ def lib():
     L.tcsc_gpu_sgemm_q8.argtypes = [vp, vp, i, vp, vp, vp, vp, i, i, i, f, vp]
     L.tcsc_gpu_launch_info_q8.argtypes = [vp, i, i, C.POINTER(i), C.POINTER(i), C.POINTER(i)]
     L.tcsc_gpu_quant_fuse_pays.argtypes = [i, i, i, i]
+    L.tcsc_gpu_sgemm_i8_out.argtypes = [vp, vp, vp, vp, vp, vp, i, i, i, i, f, vp]
+    L.tcsc_gpu_sgemm_q8_out.argtypes = [vp, vp, i, vp, vp, vp, vp, vp, i, i, i, i, f, vp]
     L.tcsc_gpu_prepare_x.argtypes = [vp, vp, i, vp]
     L.tcsc_gpu_sgemm_prepared.argtypes = [vp, vp, vp, i, i, i, f, vp]
     L.tcsc_gpu_from_dense.argtypes = [vp, i, i, vp, vp, vp, vp, C.POINTER(i), C.POINTER(i), vp]
@@ -722,24 +725,31 @@ class Plan:
         return bool(lib().tcsc_gpu_plan_has_w2(self.handle))
 
     def sgemm_i8(self, Xq, scale, B, Y, M: int, ldy: int, variant: str = "prelu_basic", a: float = 0.2,
-                 stream: int = 0) -> None:
-        """Y = act(scale[m] * (Xq . W) + B) for int8 activations (tcsc_gpu_sgemm_i8): Xq is M x K contiguous
-        int8 (a torch.int8 tensor or a pointer), scale M floats or None for all ones; B and Y are fp32."""
-        _check(lib().tcsc_gpu_sgemm_i8(self.handle, C.c_void_p(_ptr(Xq)), C.c_void_p(_ptr(scale)),
-                                       C.c_void_p(_ptr(B)), C.c_void_p(_ptr(Y)), int(M), int(ldy),
-                                       VARIANT_ID[variant], float(a), C.c_void_p(stream)), "tcsc_gpu_sgemm_i8")
+                 stream: int = 0, col_scale=None, ytype=None) -> None:
+        """Y = act(scale[m] * col_scale[j] * (Xq . W) + B) for int8 activations (tcsc_gpu_sgemm_i8_out): Xq is
+        M x K contiguous int8 (a torch.int8 tensor or a pointer), scale M floats or None for all ones, col_scale
+        the plan's cols floats or None for all ones; B is fp32.  Y is fp32 or bf16, ldy in its elements: a
+        tensor's dtype says which, a raw pointer is fp32 unless ytype ('f32' / 'bf16') says otherwise.  A
+        col_scale or a bf16 Y needs the decode or the MFMA route (:meth:`launch_info_i8`): TcscError elsewhere."""
+        yt = _ytype_of(Y) if ytype is None else _ytype(ytype)
+        _check(lib().tcsc_gpu_sgemm_i8_out(self.handle, C.c_void_p(_ptr(Xq)), C.c_void_p(_ptr(scale)),
+                                           C.c_void_p(_ptr(col_scale)), C.c_void_p(_ptr(B)), C.c_void_p(_ptr(Y)), yt,
+                                           int(M), int(ldy), VARIANT_ID[variant], float(a), C.c_void_p(stream)),
+               "tcsc_gpu_sgemm_i8_out")
 
     def sgemm_q8(self, X, Xq, scale, B, Y, M: int, ldy: int, variant: str = "prelu_basic", a: float = 0.2,
-                 stream: int = 0, xtype=None) -> None:
-        """The quantizer and :meth:`sgemm_i8` in one call (tcsc_gpu_sgemm_q8): X is M x K contiguous fp32 or bf16
-        (a torch tensor, whose dtype says which, or a pointer with xtype 'f32' / 'bf16'), scale (M floats) is
+                 stream: int = 0, xtype=None, col_scale=None, ytype=None) -> None:
+        """The quantizer and :meth:`sgemm_i8` in one call (tcsc_gpu_sgemm_q8_out): X is M x K contiguous fp32 or
+        bf16 (a torch tensor, whose dtype says which, or a pointer with xtype 'f32' / 'bf16'), scale (M floats) is
         written, Xq (M x K int8) is scratch -- untouched, and allowed to be None, where the call is fused
-        (:meth:`launch_info_q8`).  Y and scale get the bits of :func:`quantize_rows_i8` + :meth:`sgemm_i8`."""
+        (:meth:`launch_info_q8`).  Y and scale get the bits of :func:`quantize_rows_i8` + :meth:`sgemm_i8`;
+        col_scale, the type of Y and ytype as there."""
         xt = _xtype_of(X) if xtype is None else _xtype(xtype)
-        _check(lib().tcsc_gpu_sgemm_q8(self.handle, C.c_void_p(_ptr(X)), xt, C.c_void_p(_ptr(Xq)),
-                                       C.c_void_p(_ptr(scale)), C.c_void_p(_ptr(B)), C.c_void_p(_ptr(Y)), int(M),
-                                       int(ldy), VARIANT_ID[variant], float(a), C.c_void_p(stream)),
-               "tcsc_gpu_sgemm_q8")
+        yt = _ytype_of(Y) if ytype is None else _ytype(ytype)
+        _check(lib().tcsc_gpu_sgemm_q8_out(self.handle, C.c_void_p(_ptr(X)), xt, C.c_void_p(_ptr(Xq)),
+                                           C.c_void_p(_ptr(scale)), C.c_void_p(_ptr(col_scale)), C.c_void_p(_ptr(B)),
+                                           C.c_void_p(_ptr(Y)), yt, int(M), int(ldy), VARIANT_ID[variant], float(a),
+                                           C.c_void_p(stream)), "tcsc_gpu_sgemm_q8_out")
 
     def launch_info_q8(self, M: int, dtype="f32") -> tuple[str, int, bool]:
         """(path, K slices, fused) of an :meth:`sgemm_q8` launch of M rows of that dtype ('f32', 'bf16' or a
@@ -829,6 +839,40 @@ def _xtype_of(X) -> int:
     """enum tcsc_xtype of a buffer: a tensor's dtype says; a raw pointer or None counts as fp32."""
     dt = getattr(X, "dtype", None)
     return 0 if dt is None else _xtype(dt)
+
+
+YTYPE_ID = {"f32": 0, "bf16": 1}
+
+
+def _ytype(spec) -> int:
+    """enum tcsc_ytype of 'f32' / 'bf16', a torch dtype, or the enum's own integer (passed on as it is)."""
+    if isinstance(spec, int):
+        return spec
+    if isinstance(spec, str) and spec in YTYPE_ID:
+        return YTYPE_ID[spec]
+    name = str(spec)
+    if name in ("torch.float32", "torch.bfloat16"):
+        return int(name == "torch.bfloat16")
+    raise TcscError(f"Y must be fp32 or bf16 ('f32', 'bf16' or the torch dtype), got {spec!r}")
+
+
+def _ytype_of(Y) -> int:
+    """enum tcsc_ytype of an output buffer: a tensor's dtype says; a raw pointer or None counts as fp32."""
+    dt = getattr(Y, "dtype", None)
+    return 0 if dt is None else _ytype(dt)
+
+
+def ternarize_absmean(Wf):
+    """The absmean rule of ternary-weight models, on the host (numpy only, no device): for a float matrix Wf,
+    beta = mean |W| in fp32 and T = clip(rint(W / beta), -1, 1) as int8, so that W ~ beta * T.  rint rounds ties
+    to even: |w| = 0.5 beta gives 0, |w| = 1.5 beta gives +-1 by the clip.  An all-zero (or empty) W gives
+    beta 0 and T zeros.  Returns (T, beta) with beta a numpy float32; T is what :class:`TcscMatrix.from_dense`
+    and ``PackedTernaryLinear`` take, beta the layer's per-tensor ``weight_scale``."""
+    W = np.ascontiguousarray(Wf, dtype=np.float32)
+    beta = np.float32(np.mean(np.abs(W), dtype=np.float32)) if W.size else np.float32(0.0)
+    if not beta > 0:
+        return np.zeros(W.shape, dtype=np.int8), np.float32(0.0)
+    return np.clip(np.rint(W / beta), -1, 1).astype(np.int8), beta
 
 
 def quantize_rows_i8(X, Xq, scale, M: int, K: int, stream: int = 0) -> None:

@@ -17,7 +17,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from . import Plan, TcscError, TcscMatrix, prelu_backward, w2_image_bytes
+from . import Plan, TcscError, TcscMatrix, prelu_backward, ternarize_absmean, w2_image_bytes
 
 __all__ = ["TernaryLinear", "PackedTernaryLinear"]
 
@@ -51,6 +51,23 @@ def _define():
         if b.numel() != n:
             raise TcscError(f"{who}: bias has {b.numel()} elements, W has N={n} columns")
         return b
+
+    def _weight_scale_tensor(ws, n: int, dev):
+        """None, one float (broadcast) or n values -> None or n contiguous floats on dev."""
+        if ws is None:
+            return None
+        t = torch.as_tensor(ws).detach().to(device=dev, dtype=torch.float32).reshape(-1)
+        if t.numel() == 1:
+            return t.expand(n).contiguous()
+        if t.numel() != n:
+            raise TcscError(f"PackedTernaryLinear: weight_scale has {t.numel()} elements, W has N={n} columns "
+                            "(one value or one per column)")
+        return t.clone()
+
+    def _out_dtype(dt):
+        if dt not in (torch.float32, torch.bfloat16):
+            raise TcscError(f"PackedTernaryLinear: out_dtype must be torch.float32 or torch.bfloat16, got {dt!r}")
+        return dt
 
     class _TernaryLinearFn(torch.autograd.Function):
         """y = act(x . W + b) on an (M x K) contiguous fp32 or bf16 x (y is fp32 either way); W and `a`
@@ -206,10 +223,15 @@ def _define():
             return f"in_features={self.in_features}, out_features={self.out_features}, nnz={self._W.nnz}, a={self.a}"
 
     class PackedTernaryLinear(torch.nn.Module):
-        """Inference-only ``y = act(scale * (q . W) + bias)`` on a packed plan (``Plan.packed``): of ``W`` the
-        layer holds the 2-bit image alone, a quarter byte per weight.
+        """Inference-only ``y = act(scale * weight_scale * (q . W) + bias)`` on a packed plan (``Plan.packed``):
+        of ``W`` the layer holds the 2-bit image alone, a quarter byte per weight.
 
         W, bias, a, device: as :class:`TernaryLinear` takes them; the bias is a buffer, not a parameter.
+        weight_scale: None, one float (the beta of a per-tensor ternarization, ``tcsc_amd.ternarize_absmean``)
+        or N values (one per output column); kept as a buffer of N floats and applied in the kernel's epilogue
+        after the row scale and before the bias.  out_dtype: torch.float32 or torch.bfloat16, what ``forward``
+        returns -- written by the kernel, rounded to nearest even from the fp32 value (``Plan.sgemm_q8``).
+        ``state_dict()`` carries ``weight_scale`` only when the layer has one.
         ``forward`` takes an fp32 or bf16 CUDA tensor of shape (..., K) and calls ``Plan.sgemm_q8``, which
         quantizes its rows to int8 (the arithmetic of ``tcsc_amd.quantize_rows_i8``) and multiplies: up to 16
         rows k_decode8q in one launch where fusing pays, the quantizer and k_decode8 elsewhere, k_gemm8w2
@@ -217,28 +239,45 @@ def _define():
         There is no backward and no transposed plan: it raises when grad is enabled and x requires grad.
         """
 
-        def __init__(self, W, bias=None, a: float | None = None, device: int = 0):
+        def __init__(self, W, bias=None, a: float | None = None, device: int = 0, weight_scale=None,
+                     out_dtype=torch.float32):
             super().__init__()
             Wm = _ternary_matrix(W, "PackedTernaryLinear")  # only read here: the plan keeps no reference to it
             self.in_features, self.out_features, self.nnz = Wm.rows, Wm.cols, Wm.nnz
             self.a = None if a is None else float(a)
             self.device_index = int(device)
+            self.out_dtype = _out_dtype(out_dtype)
             dev = torch.device("cuda", self.device_index)
             self.register_buffer("bias", _bias_tensor(bias, self.out_features, dev, "PackedTernaryLinear"))
+            self.register_buffer("weight_scale", _weight_scale_tensor(weight_scale, self.out_features, dev))
             self.plan = Plan.packed(Wm, 0, self.out_features, self.device_index, _stream(dev))
             self._rows, self._xq, self._scale = 0, None, None
 
         @classmethod
-        def empty(cls, in_features: int, out_features: int, a: float | None = None, device: int = 0):
-            """A layer of this shape with a zero bias and no plan yet: ``load_state_dict`` fills it from a
-            ``state_dict()`` of a layer of the same shape.  Until then ``forward`` and ``reserve`` raise."""
+        def from_float(cls, Wf, bias=None, a: float | None = None, device: int = 0, out_dtype=torch.float32):
+            """The layer of a float weight matrix Wf (K x N): ``T, beta = tcsc_amd.ternarize_absmean(Wf)``, then
+            the packed plan of T with the per-tensor ``weight_scale = beta``, so that the layer computes
+            ``act(x . (beta T) + bias)`` on the quantized x."""
+            if torch.is_tensor(Wf):
+                Wf = Wf.detach().cpu().numpy()
+            T, beta = ternarize_absmean(Wf)
+            return cls(T, bias, a, device, weight_scale=float(beta), out_dtype=out_dtype)
+
+        @classmethod
+        def empty(cls, in_features: int, out_features: int, a: float | None = None, device: int = 0,
+                  out_dtype=torch.float32):
+            """A layer of this shape with a zero bias, no weight scale and no plan yet: ``load_state_dict`` fills it
+            from a ``state_dict()`` of a layer of the same shape (its ``weight_scale`` included, when it has one).
+            Until then ``forward`` and ``reserve`` raise."""
             self = cls.__new__(cls)
             torch.nn.Module.__init__(self)
             self.in_features, self.out_features, self.nnz = int(in_features), int(out_features), 0
             self.a = None if a is None else float(a)
             self.device_index = int(device)
+            self.out_dtype = _out_dtype(out_dtype)
             dev = torch.device("cuda", self.device_index)
             self.register_buffer("bias", torch.zeros(self.out_features, dtype=torch.float32, device=dev))
+            self.register_buffer("weight_scale", None)
             self.plan = None
             self._rows, self._xq, self._scale = 0, None, None
             return self
@@ -250,7 +289,8 @@ def _define():
             return self.plan
 
         def _save_to_state_dict(self, destination, prefix, keep_vars):
-            """``bias`` (the buffer) and ``w2``: the plan's 2-bit image as a uint8 tensor, a fresh copy made at this
+            """``bias`` (the buffer), ``weight_scale`` (a buffer too, so only when the layer has one: a buffer that
+            is None is not saved) and ``w2``: the plan's 2-bit image as a uint8 tensor, a fresh copy made at this
             call -- not a registered buffer, so the layer does not hold the image twice."""
             super()._save_to_state_dict(destination, prefix, keep_vars)
             dev = torch.device("cuda", self.device_index)
@@ -258,10 +298,11 @@ def _define():
 
         def _load_from_state_dict(self, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys,
                                   error_msgs):
-            """Rebuilds the plan from ``w2`` (``Plan.packed_from_image``, the device path).  Both keys must be
-            there and the image must have the size of this layer's shape, whatever ``strict`` says: TcscError
-            otherwise, with the layer unchanged.  The plan it replaces is destroyed with its workspace, so a
-            ``reserve`` made before the load is gone: reserve again."""
+            """Rebuilds the plan from ``w2`` (``Plan.packed_from_image``, the device path).  ``bias`` and ``w2``
+            must be there and the image must have the size of this layer's shape, whatever ``strict`` says:
+            TcscError otherwise, with the layer unchanged.  ``weight_scale`` is taken when present (N values) and
+            the layer has none afterwards when it is absent.  The plan it replaces is destroyed with its
+            workspace, so a ``reserve`` made before the load is gone: reserve again."""
             for key in ("bias", "w2"):
                 if prefix + key not in state_dict:
                     raise TcscError(f"PackedTernaryLinear.load_state_dict: missing key {prefix + key!r}")
@@ -274,8 +315,14 @@ def _define():
                 raise TcscError(f"PackedTernaryLinear.load_state_dict: {prefix}w2 is {got}, a {self.in_features} x "
                                 f"{self.out_features} layer needs {want} uint8 values")
             dev = torch.device("cuda", self.device_index)
+            ws = state_dict.get(prefix + "weight_scale")
+            if ws is not None and (not torch.is_tensor(ws) or ws.numel() != self.out_features):
+                raise TcscError(f"PackedTernaryLinear.load_state_dict: {prefix}weight_scale must hold "
+                                f"{self.out_features} values")
             image = w2.detach().to(dev).contiguous()
             plan = Plan.packed_from_image(image, self.in_features, self.out_features, 0, self.device_index, _stream(dev))
+            # the base class copies into the buffers the layer has: give it one of the state's kind
+            self.weight_scale = None if ws is None else torch.empty(self.out_features, dtype=torch.float32, device=dev)
             super()._load_from_state_dict(state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys,
                                           error_msgs)
             if prefix + "w2" in unexpected_keys:  # the base class knows parameters and buffers only
@@ -316,13 +363,14 @@ def _define():
             M, K, N = x2.shape[0], self.in_features, self.out_features
             xq, scale = self._quant_buffers(M)
             stream = _stream(x.device)
-            y = torch.empty((M, N), dtype=torch.float32, device=x.device)
+            y = torch.empty((M, N), dtype=self.out_dtype, device=x.device)
             variant, a = ("basic", 0.0) if self.a is None else ("prelu_basic", self.a)
-            plan.sgemm_q8(x2, xq, scale, self.bias, y, M, N, variant, a, stream)
+            plan.sgemm_q8(x2, xq, scale, self.bias, y, M, N, variant, a, stream, col_scale=self.weight_scale)
             return y.reshape(*lead, N)
 
         def extra_repr(self) -> str:
-            return f"in_features={self.in_features}, out_features={self.out_features}, nnz={self.nnz}, a={self.a}"
+            return (f"in_features={self.in_features}, out_features={self.out_features}, nnz={self.nnz}, a={self.a}, "
+                    f"weight_scale={self.weight_scale is not None}, out_dtype={self.out_dtype}")
 
     return {"TernaryLinear": TernaryLinear, "PackedTernaryLinear": PackedTernaryLinear}
 
