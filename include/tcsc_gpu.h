@@ -684,6 +684,82 @@ int tcsc_gpu_sgemm_q8_out(const tcsc_gpu_plan *plan, const void *dX, int xtype, 
                           float *dScale, const float *dColScale, const float *dB, void *dY,
                           int ytype, int M, int ldy, int variant, float a, void *stream);
 
+/* ---- RMSNorm in the int8 call ----------------------------------
+ * Every ternary linear of a BitNet-style model reads quant(RMSNorm(x) gamma).
+ * These calls move the norm into the launches the int8 call already has.
+ *
+ * The arithmetic is pinned (csrc/tcsc_norm.h), every step one correctly rounded
+ * fp32 operation, never contracted.  For a row x[0 .. K), bf16 widened exactly:
+ *   ss     the sum of fl(x[k] x[k]) in an order that depends on K alone: 512
+ *          partials, element k in partial (k >> 3) & 511, each partial summed
+ *          in ascending k from +0, then the tree p[c] = fl(p[c] + p[c + s]) for
+ *          s = 256, 128, .., 1
+ *   r      mean = fl(ss / float(K)); r = fl(1 / fl(sqrt(fl(mean + eps))))
+ *   xn[k]  fl(fl(x[k] r) gamma[k]); dGamma NULL = all ones, the same bits
+ * and then the quantizer of tcsc_gpu_quantize_rows_i8 on xn.  Inputs must be
+ * finite with squares that do not overflow; otherwise the values are
+ * unspecified.  Rows >= M and elements >= K are never read.
+ *
+ * tcsc_gpu_rmsnorm_rows: dXn (M x K floats) = xn, and dRinv[m] = r where dRinv
+ *   is not NULL.  dX: M x K, xtype as in tcsc_gpu_sgemm_q8; dGamma: K floats or
+ *   NULL.  Every pointer needs the alignment of its element type only.
+ * tcsc_gpu_quantize_rows_i8_norm: the bits of tcsc_gpu_rmsnorm_rows into an fp32
+ *   Xn followed by tcsc_gpu_quantize_rows_i8 of Xn, in one launch at every M.
+ * tcsc_gpu_sgemm_q8_norm: tcsc_gpu_sgemm_q8_out with the norm in front.  dY and
+ *   dScale hold the bits of tcsc_gpu_rmsnorm_rows, tcsc_gpu_quantize_rows_i8 and
+ *   tcsc_gpu_sgemm_i8_out on the same plan and environment: at every M, variant,
+ *   a, ytype and column scale, on packed, ordinary, column-shard and transposed
+ *   plans.
+ *
+ * Routing: the int8 route is what tcsc_gpu_launch_info_i8 reports.  The call is
+ * FUSED -- one launch of the norm form of k_decode8q -- when that route is
+ * TCSC_PATH_DECODE and tcsc_gpu_norm_fuse_pays says 1 or $TCSC_QFUSE=1 is set
+ * ($TCSC_QFUSE as in tcsc_gpu_sgemm_q8: 0 never fuses, unset follows the rule);
+ * dXq is then not touched and may be NULL.  Otherwise the call is
+ * tcsc_gpu_quantize_rows_i8_norm into dXq (non-NULL) and the int8 call: two
+ * launches, three where k_pack8 runs.  dColScale and ytype as in
+ * tcsc_gpu_sgemm_q8_out, the refusal on the gather and small-M routes included.
+ * Workspace, tcsc_gpu_plan_reserve and capture are unchanged; no call allocates
+ * or synchronises.  tcsc_gpu_launch_info_q8_norm reports the path, the K slices
+ * and whether a call of M rows of that xtype is fused.
+ *
+ * On top of the checks of tcsc_gpu_sgemm_q8_out, TCSC_E_ARG with a message
+ * naming the call and no HIP call for: an eps that is not finite or not > 0,
+ * K < 1, an xtype other than 0 or 1, a NULL dXn in tcsc_gpu_rmsnorm_rows.
+ *
+ * tcsc_gpu_norm_fuse_pays (host arithmetic: no plan, no device): 0 for every
+ * argument, as measured.  Every fused workgroup sweeps all of X three times
+ * (the squares, the maxima of xn, the values it quantizes) where
+ * tcsc_gpu_sgemm_q8's sweeps it twice, and the launch it saves is the norm form of
+ * the quantizer, which reads a row of up to 8192 elements once.  The rule keeps
+ * tcsc_gpu_quant_fuse_pays's form, 1 <= M <= M0 and W M K <= V0 with W the
+ * workgroups of the launch, and its fit is M0 = 0: in replayed graphs
+ * (profiles/norm_bench.json; packed plans at 4096 x 4096,
+ * 8192 x 8192, 2560 x 6912 and 6912 x 2560, M = 1, 2, 4, 8, 16, fp32 and bf16 x)
+ * the fused call beat the library's own two launches beyond the run's spread
+ * only at a few points of M <= 2 with bf16 x, by 6 % at the most, and was
+ * level or slower everywhere else, down to a quarter of the speed at M = 16 --
+ * also at M = 1 with bf16 x on shapes whose W M K lie between those of the
+ * wins, so no bound on W M K separates the two.  So without
+ * $TCSC_QFUSE=1 the call is always the norm form of the quantizer followed by
+ * the int8 call, and the fused form is there for a caller who has measured a
+ * point of their own.
+ *
+ * Out of scope: a bf16 gamma; LayerNorm with a mean; writing xn out of the
+ * fused call; the norm on the fp32, bf16 and plain int8 calls; int8 Y; a
+ * host-pointer version. */
+int tcsc_gpu_rmsnorm_rows(const void *dX, int xtype, const float *dGamma, float eps,
+                          int M, int K, float *dXn, float *dRinv /* may be NULL */, void *stream);
+int tcsc_gpu_quantize_rows_i8_norm(const void *dX, int xtype, const float *dGamma, float eps,
+                                   int M, int K, void *dXq, float *dScale, void *stream);
+int tcsc_gpu_sgemm_q8_norm(const tcsc_gpu_plan *plan, const void *dX, int xtype,
+                           const float *dGamma, float eps, void *dXq, float *dScale,
+                           const float *dColScale, const float *dB, void *dY, int ytype,
+                           int M, int ldy, int variant, float a, void *stream);
+int tcsc_gpu_launch_info_q8_norm(const tcsc_gpu_plan *plan, int M, int xtype,
+                                 int *path, int *slices, int *fused);
+int tcsc_gpu_norm_fuse_pays(int M, int K, int N, int xtype);   /* host arithmetic */
+
 /* Device-side tcsc_from_dense: dense K x N row-major float matrix on the
  * device -> TCSC arrays on the device, bit-exact with the reference builder
  * (tcsc.c:6-66).  Two calls: first with the four output pointers NULL to

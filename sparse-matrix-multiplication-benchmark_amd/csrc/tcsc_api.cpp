@@ -11,6 +11,7 @@
 #include <rocblas/rocblas.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
@@ -2101,13 +2102,41 @@ static int qfuse_knob() {
     if (!e || !*e) return -1;
     return std::atoi(e) != 0 ? 1 : 0;
 }
-// the int8 route of M rows on the plan as it stands, and whether a q8 call of this X type fuses on it
-static Route route_q8(const tcsc_gpu_plan* p, int M, int xtype, bool* fused) {
+// The RMSNorm in front of the quantizer: gamma (null = ones) and
+// eps of a tcsc_gpu_sgemm_q8_norm call, and the rule for fusing all three steps.
+// Every fused workgroup sweeps all of X three times (the squares, the maxima of
+// xn, the values it quantizes) where §20's sweeps it twice, and the launch it
+// saves is the norm form of the quantizer, which reads a row once and costs
+// little more than the plain one.  The rule has quant_fuse_pays's form, W M K <=
+// kNFuseValues for 1 <= M <= kNFuseMaxM with W the launch's workgroups, and the
+// fit to profiles/norm_bench.json is the empty set: of the 40 decode points the
+// fused call was faster than the two launches beyond the run's spread only at a
+// few of M <= 2 with bf16 x (4096^2, 6912 x 2560: 6 % at the most) and slower
+// or level at all others, with losses at M = 1, bf16 (8192^2, 2560 x 6912) at a
+// W M K between those of the wins: no bound on W M K separates them, and the
+// rule must be 0 wherever the fused call lost.  So kNFuseMaxM = 0: the answer
+// is 0 everywhere, and $TCSC_QFUSE=1 is how the fused form runs.
+struct NormArgs {
+    const float* gamma;
+    float eps;
+};
+static constexpr int kNFuseMaxM = 0;
+static constexpr long long kNFuseValues = 0;
+static bool norm_fuse_pays(int M, int K, int N, int xtype) {
+    if (M < 1 || M > kNFuseMaxM || K < 1 || N < 1 || (xtype != TCSC_X_F32 && xtype != TCSC_X_BF16)) return false;
+    const int T = tcsc::decode_tiles_per_wg(M, N, 0);  // the grid on a 256-CU chip
+    const long long wgs = (tcsc::w2_col_tiles(N) + T - 1) / T;
+    return wgs * M * K <= kNFuseValues;
+}
+// the int8 route of M rows on the plan as it stands, and whether a q8 call of this X type (norm: a
+// q8_norm call) fuses on it
+static Route route_q8(const tcsc_gpu_plan* p, int M, int xtype, bool* fused, bool norm = false) {
     const Route r = route_call(p, M, kI8, p->ws_bytes, RoutePins());
     *fused = false;
     if (r.path == TCSC_PATH_DECODE && has_decode(p, M, kI8)) {
         const int knob = qfuse_knob();
-        *fused = knob >= 0 ? knob == 1 : quant_fuse_pays(M, p->rows, p->cols, xtype);
+        *fused = knob >= 0 ? knob == 1
+                           : norm ? norm_fuse_pays(M, p->rows, p->cols, xtype) : quant_fuse_pays(M, p->rows, p->cols, xtype);
     }
     return r;
 }
@@ -2128,9 +2157,10 @@ int tcsc_gpu_launch_info_q8(const tcsc_gpu_plan* p, int M, int xtype, int* path,
 }
 
 // `inner`: the name the int8 call behind an unfused route gives itself (null: tcsc_gpu_sgemm_i8)
+// `norm`: the RMSNorm of a tcsc_gpu_sgemm_q8_norm call in front of the quantizer (null: none)
 static int sgemm_q8_impl(const char* who, const char* inner, const tcsc_gpu_plan* p, const void* dX, int xtype, void* dXq,
                          float* dScale, const float* dB, const YOut& y, int M, int ldy, int variant, float a,
-                         void* stream) {
+                         void* stream, const NormArgs* norm = nullptr) {
     void* dY = y.Y;
     if (!p || M < 0 || ldy < p->cols || !valid_variant(variant) || (xtype != TCSC_X_F32 && xtype != TCSC_X_BF16)) {
         set_error("%s: bad arguments (M=%d ldy=%d variant=%d xtype=%d)", who, M, ldy, variant, xtype);
@@ -2142,19 +2172,25 @@ static int sgemm_q8_impl(const char* who, const char* inner, const tcsc_gpu_plan
         return TCSC_E_ARG;
     }
     bool fused = false;
-    if (p->cols > 0 && refuse_out(who, route_q8(p, M, xtype, &fused).path, y, M)) return TCSC_E_ARG;
+    if (p->cols > 0 && refuse_out(who, route_q8(p, M, xtype, &fused, norm != nullptr).path, y, M)) return TCSC_E_ARG;
     if (!fused) {  // the quantizer into the caller's scratch, then the int8 call as it is: two or three launches
         if (!dXq && p->rows > 0) {
             set_error("%s: NULL dXq on a route that is not fused (M=%d)", who, M);
             return TCSC_E_ARG;
         }
-        const int rc = xtype == TCSC_X_F32
+        const int rc = norm ? tcsc_gpu_quantize_rows_i8_norm(dX, xtype, norm->gamma, norm->eps, M, p->rows, dXq, dScale, stream)
+                       : xtype == TCSC_X_F32
                            ? tcsc_gpu_quantize_rows_i8(static_cast<const float*>(dX), M, p->rows, dXq, dScale, stream)
                            : tcsc_gpu_quantize_rows_i8_bf16(dX, M, p->rows, dXq, dScale, stream);
         if (rc != TCSC_OK) return rc;
         return sgemm_entry(p, dXq, kI8, dScale, dB, nullptr, M, ldy, variant, a, stream, &y, inner);
     }
     const_cast<tcsc_gpu_plan*>(p)->staged_M = -1;  // as every tcsc_gpu_sgemm* does
+    if (norm) {
+        HIP_TRY(tcsc::decode_gemm_qn(dX, xtype == TCSC_X_BF16, norm->gamma, norm->eps, p->w2, p->rows, M, p->cols, dScale,
+                                     dB, y, ldy, is_prelu(variant), a, p->num_cus, static_cast<hipStream_t>(stream)));
+        return TCSC_OK;
+    }
     HIP_TRY(tcsc::decode_gemm_q(dX, xtype == TCSC_X_BF16, p->w2, p->rows, M, p->cols, dScale, dB, y, ldy,
                                 is_prelu(variant), a, p->num_cus, static_cast<hipStream_t>(stream)));
     return TCSC_OK;
@@ -2175,6 +2211,86 @@ int tcsc_gpu_sgemm_q8_out(const tcsc_gpu_plan* p, const void* dX, int xtype, voi
     if (rc != TCSC_OK) return rc;
     return sgemm_q8_impl(who, who, p, dX, xtype, dXq, dScale, dB, YOut{dY, ytype == TCSC_Y_BF16 ? kYBf16 : kYF32, dColScale},
                          M, ldy, variant, a, stream);
+}
+
+// ---- RMSNorm in the int8 call ----------------------------------
+// what the norm calls check on top of the calls they extend, ahead of any HIP call
+static int norm_args(const char* who, int xtype, float eps, int K) {
+    if (xtype != TCSC_X_F32 && xtype != TCSC_X_BF16) {
+        set_error("%s: xtype=%d is neither TCSC_X_F32 (0) nor TCSC_X_BF16 (1)", who, xtype);
+        return TCSC_E_ARG;
+    }
+    if (!std::isfinite(eps) || !(eps > 0.0f)) {
+        set_error("%s: eps=%g is not a finite number > 0", who, (double)eps);
+        return TCSC_E_ARG;
+    }
+    if (K < 1) {
+        set_error("%s: K=%d < 1", who, K);
+        return TCSC_E_ARG;
+    }
+    return TCSC_OK;
+}
+
+int tcsc_gpu_rmsnorm_rows(const void* dX, int xtype, const float* dGamma, float eps, int M, int K, float* dXn,
+                          float* dRinv, void* stream) {
+    const char* who = "tcsc_gpu_rmsnorm_rows";
+    const int rc = norm_args(who, xtype, eps, K);
+    if (rc != TCSC_OK) return rc;
+    if (M < 0 || !dXn || (M > 0 && !dX)) {
+        set_error("%s: %s", who, M < 0 ? "M < 0" : !dXn ? "NULL dXn" : "NULL dX");
+        return TCSC_E_ARG;
+    }
+    if (M == 0) return TCSC_OK;
+    HIP_TRY(tcsc::rmsnorm_rows(dX, xtype == TCSC_X_BF16, dGamma, eps, M, K, dXn, dRinv,
+                               static_cast<hipStream_t>(stream)));
+    return TCSC_OK;
+}
+
+int tcsc_gpu_quantize_rows_i8_norm(const void* dX, int xtype, const float* dGamma, float eps, int M, int K, void* dXq,
+                                   float* dScale, void* stream) {
+    const char* who = "tcsc_gpu_quantize_rows_i8_norm";
+    const int rc = norm_args(who, xtype, eps, K);
+    if (rc != TCSC_OK) return rc;
+    if (M < 0) {
+        set_error("%s: M < 0", who);
+        return TCSC_E_ARG;
+    }
+    if (M == 0) return TCSC_OK;
+    if (!dX || !dXq || !dScale) {
+        set_error("%s: NULL device pointer", who);
+        return TCSC_E_ARG;
+    }
+    HIP_TRY(tcsc::quantize_rows_i8_norm(dX, xtype == TCSC_X_BF16, dGamma, eps, M, K, static_cast<int8_t*>(dXq), dScale,
+                                        static_cast<hipStream_t>(stream)));
+    return TCSC_OK;
+}
+
+int tcsc_gpu_norm_fuse_pays(int M, int K, int N, int xtype) { return norm_fuse_pays(M, K, N, xtype) ? 1 : 0; }
+
+int tcsc_gpu_launch_info_q8_norm(const tcsc_gpu_plan* p, int M, int xtype, int* path, int* slices, int* fused) {
+    if (!p || M < 0 || !path || !slices || !fused || (xtype != TCSC_X_F32 && xtype != TCSC_X_BF16)) {
+        set_error("tcsc_gpu_launch_info_q8_norm: bad arguments (M=%d xtype=%d)", M, xtype);
+        return TCSC_E_ARG;
+    }
+    bool f = false;
+    const Route r = route_q8(p, M, xtype, &f, true);
+    *path = r.path;
+    *slices = r.slices;
+    *fused = f ? 1 : 0;
+    return TCSC_OK;
+}
+
+int tcsc_gpu_sgemm_q8_norm(const tcsc_gpu_plan* p, const void* dX, int xtype, const float* dGamma, float eps, void* dXq,
+                           float* dScale, const float* dColScale, const float* dB, void* dY, int ytype, int M, int ldy,
+                           int variant, float a, void* stream) {
+    const char* who = "tcsc_gpu_sgemm_q8_norm";
+    int rc = norm_args(who, xtype, eps, p ? p->rows : 1);  // K is the plan's: a NULL plan is out_args'
+    if (rc != TCSC_OK) return rc;
+    rc = out_args(who, p, dB, dY, ytype);
+    if (rc != TCSC_OK) return rc;
+    const NormArgs norm{dGamma, eps};
+    return sgemm_q8_impl(who, who, p, dX, xtype, dXq, dScale, dB, YOut{dY, ytype == TCSC_Y_BF16 ? kYBf16 : kYF32, dColScale},
+                         M, ldy, variant, a, stream, &norm);
 }
 
 int tcsc_gpu_workspace_bound_i8(int M, int K, int N, size_t* i8_bytes, size_t* f32_bytes) {

@@ -26,6 +26,7 @@
 
 #include "tcsc_i8_out.h"
 #include "tcsc_internal.h"
+#include "tcsc_norm.h"
 #include "tcsc_quant.h"
 #include "tcsc_xsrc.h"
 
@@ -415,21 +416,73 @@ void launch_decode(const int8_t* X, const uint32_t* w2, int K, int M, int N, con
 //   The first four rows of the next block are loaded before this block's MFMAs.
 // ALIGNED: XSrc<TX>::vec_ok -- 16-B loads in phase A, whole loads of a lane's
 // four values in phase B; otherwise guarded scalar loads in both.
+//
+// NORM: the RMSNorm in front of the quantizer as well.  Phase A
+// sweeps the row twice (decode_norm_sweeps): the sum of squares in tcsc_norm.h's
+// order -- the 512 / Mp threads of a row are a team that owns Mp partials each
+// -- then r and the maximum of |xn|; r[row] joins the scales in the LDS.  Phase
+// B's store_rows applies r and gamma in front of quant_i8; a lane's four gamma
+// of a block are loaded once, with the block's first rows, and serve every row.
+// Everything after the fragments is the same code.  The instantiations without
+// NORM read neither gamma nor eps.
 constexpr int kQWaves = 8;           // the product build's K split; the staging of 16 waves would not fit 64 KiB
 constexpr int kQWaveBytes = 16 * kW2Blk;  // a wave's quantized block: 16 rows x 256 k
-template <typename TX, int T, bool ALIGNED, bool PRELU, typename TY>
+
+// The two sweeps of the norm form's phase A for Mp = MP: thread tid is thread
+// tid % NT of row tid / NT's team, NT = 512 / MP.  r of the thread's row and the
+// thread's share of max |xn| come back (a row >= M is never read: r is of an
+// empty row then and am = 0).  part: 512 floats of the LDS.  Every thread of
+// the workgroup calls this.
+template <typename TX, bool ALIGNED, int MP>
+__device__ __forceinline__ void decode_norm_sweeps(const TX* __restrict__ X, const float* __restrict__ gamma, float eps,
+                                                   int K, int M, int tid, float* part, float& r, float& am) {
+    using XS = XSrc<TX>;
+    constexpr int NT = kNormPartials / MP;
+    const int arow = tid / NT, asub = tid % NT;
+    const bool live = arow < M;
+    const TX* src = X + (size_t)(live ? arow : 0) * K;
+    const float node = live ? norm_ss_thread<TX, NT, ALIGNED>(src, K, asub) : 0.0f;
+    r = norm_rinv(norm_ss_team<NT>(node, part, tid), K, eps);
+    am = 0.0f;
+    if (!live) return;
+    if constexpr (ALIGNED) {  // K % 4 == 0: a piece's gamma is whole 16-B loads where gamma is aligned
+        const bool gvec = (reinterpret_cast<uintptr_t>(gamma) & 15) == 0;
+        for (int q = asub; q < K / XS::kVec; q += NT) {
+            float f[XS::kVec];
+            XS::unpack(*reinterpret_cast<const uint4*>(src + (size_t)q * XS::kVec), 1.0f, f);
+            if (gvec) {
+                norm_piece<XS::kVec>(f, r, gamma, q * XS::kVec);
+            } else {
+#pragma unroll
+                for (int e = 0; e < XS::kVec; ++e) f[e] = norm_apply(f[e], r, gamma[q * XS::kVec + e]);
+            }
+#pragma unroll
+            for (int e = 0; e < XS::kVec; ++e) am = fmaxf(am, fabsf(f[e]));
+        }
+    } else {
+        for (int k = asub; k < K; k += NT) {
+            const float x = XS::conv(src[k], 1.0f);
+            am = fmaxf(am, fabsf(gamma ? norm_apply(x, r, gamma[k]) : norm_apply(x, r)));
+        }
+    }
+}
+
+template <typename TX, int T, bool ALIGNED, bool PRELU, typename TY, bool NORM = false>
 __global__ void __launch_bounds__(kQWaves * 64) k_decode8q(const TX* __restrict__ X, const uint32_t* __restrict__ W2,
                                                            int K, int M, int N, int nkb, int ntiles,
                                                            float* __restrict__ scale_out,
                                                            const float* __restrict__ cscale,
                                                            const float* __restrict__ bias, TY* __restrict__ Y,
-                                                           int ldy, float a) {
+                                                           int ldy, float a, const float* __restrict__ gamma = nullptr,
+                                                           float eps = 0.0f) {
     using XS = XSrc<TX>;
     constexpr int kThreads = kQWaves * 64, kHalves = kThreads / 32;
     constexpr int kRedBytes = kQWaves * T * 256 * 4, kStageBytes = kQWaves * kQWaveBytes;
-    // the waves' staging blocks during the K loop, the partial sums after it
+    // the waves' staging blocks during the K loop, the partial sums after it (and, in the norm form's
+    // phase A, the teams' 512 tree nodes)
     __shared__ __attribute__((aligned(16))) unsigned char smem[kRedBytes > kStageBytes ? kRedBytes : kStageBytes];
     __shared__ float s_part[kHalves], s_scale[kDecodeMaxM], s_inv[kDecodeMaxM];
+    __shared__ float s_r[NORM ? kDecodeMaxM : 1];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int t0 = blockIdx.x * T;
@@ -442,7 +495,19 @@ __global__ void __launch_bounds__(kQWaves * 64) k_decode8q(const TX* __restrict_
         static_assert(kThreads == 512 && kDecodeMaxM == 16, "512 threads over at most 16 rows: half-waves do not mix rows");
         const int arow = tid >> gl, asub = tid & ((1 << gl) - 1), G = 1 << gl;
         float am = 0.0f;
-        if (arow < M) {
+        if constexpr (NORM) {
+            static_assert(kThreads == kNormPartials && kStageBytes >= kNormPartials * 4, "one thread per partial at M = 1");
+            float* part = reinterpret_cast<float*>(smem);
+            float r;
+            switch (sh) {  // uniform
+                case 0: decode_norm_sweeps<TX, ALIGNED, 1>(X, gamma, eps, K, M, tid, part, r, am); break;
+                case 1: decode_norm_sweeps<TX, ALIGNED, 2>(X, gamma, eps, K, M, tid, part, r, am); break;
+                case 2: decode_norm_sweeps<TX, ALIGNED, 4>(X, gamma, eps, K, M, tid, part, r, am); break;
+                case 3: decode_norm_sweeps<TX, ALIGNED, 8>(X, gamma, eps, K, M, tid, part, r, am); break;
+                default: decode_norm_sweeps<TX, ALIGNED, 16>(X, gamma, eps, K, M, tid, part, r, am); break;
+            }
+            if (arow < M && asub == 0) s_r[arow] = r;
+        } else if (arow < M) {
             const TX* src = X + (size_t)arow * K;
             if constexpr (ALIGNED) {
                 for (int q = asub; q < K / XS::kVec; q += G) {
@@ -514,6 +579,25 @@ __global__ void __launch_bounds__(kQWaves * 64) k_decode8q(const TX* __restrict_
             }
         }
     };
+    // the norm form: gamma of the lane's four k of block kb, shared by all rows (ones past K, unused)
+    [[maybe_unused]] float gm[4] = {1.0f, 1.0f, 1.0f, 1.0f};
+    [[maybe_unused]] const bool gvec = NORM && K % 4 == 0 && (reinterpret_cast<uintptr_t>(gamma) & 15) == 0;
+    auto load_gamma = [&](int kb) {
+        if constexpr (NORM) {
+            const int k = kW2Blk * kb + 4 * lane;
+            if (!gamma) return;  // uniform
+            if (gvec) {          // uniform; the four lie wholly below K or wholly past it
+                if (k < K) {
+                    const float4 g = *reinterpret_cast<const float4*>(gamma + k);
+                    gm[0] = g.x, gm[1] = g.y, gm[2] = g.z, gm[3] = g.w;
+                }
+            } else {
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                    if (k + e < K) gm[e] = gamma[k + e];
+            }
+        }
+    };
     // quantized and stored: byte e of the dword is value k + e, zero at k + e >= K
     auto store_rows = [&](int kb, int j0, const Raw (&raw)[4]) {
         const int k = kW2Blk * kb + 4 * lane;
@@ -522,6 +606,7 @@ __global__ void __launch_bounds__(kQWaves * 64) k_decode8q(const TX* __restrict_
             const int row = j0 + u;
             if (row >= M) break;  // uniform
             const float inv = s_inv[row];
+            [[maybe_unused]] const float r = NORM ? s_r[row] : 1.0f;
             uint32_t o = 0;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
@@ -530,6 +615,7 @@ __global__ void __launch_bounds__(kQWaves * 64) k_decode8q(const TX* __restrict_
                     x = __uint_as_float(raw[u].w[e]);
                 else
                     x = XS::conv((TX)(raw[u].w[e >> 1] >> (16 * (e & 1))), 1.0f);
+                if constexpr (NORM) x = gamma ? norm_apply(x, r, gm[e]) : norm_apply(x, r);
                 const uint32_t q = (uint32_t)quant_i8(x, inv) & 0xffu;
                 if (ALIGNED ? k < K : k + e < K) o |= q << (8 * e);
             }
@@ -571,6 +657,7 @@ __global__ void __launch_bounds__(kQWaves * 64) k_decode8q(const TX* __restrict_
     int kb = wave;
     if (kb < nkb) {
         load_w(kb, p);
+        load_gamma(kb);
         load_rows(kb, 0, raw);
         store_rows(kb, 0, raw);
         stage_rest(kb, raw);
@@ -580,6 +667,7 @@ __global__ void __launch_bounds__(kQWaves * 64) k_decode8q(const TX* __restrict_
         const int nx = kb + kQWaves;
         if (nx < nkb) {
             load_w(nx, pn);
+            load_gamma(nx);  // this block's staging is done: its gamma is free
             load_rows(nx, 0, raw);
         }
 #pragma unroll
@@ -633,6 +721,42 @@ void launch_decode_q(const TX* X, const uint32_t* w2, int K, int M, int N, float
     else
         hipLaunchKernelGGL((k_decode8q<TX, T, ALIGNED, false, TY>), grid, block, 0, st, X, w2, K, M, N, nkb, ntiles,
                            scale_out, cscale, B, Y, ldy, a);
+}
+
+// the norm form of k_decode8q: the same grid and tiles per workgroup
+template <typename TX, int T, bool ALIGNED, typename TY>
+void launch_decode_qn(const TX* X, const float* gamma, float eps, const uint32_t* w2, int K, int M, int N,
+                      float* scale_out, const float* cscale, const float* B, TY* Y, int ldy, bool prelu, float a,
+                      hipStream_t st) {
+    const int ntiles = w2_col_tiles(N), nkb = w2_kblocks(K);
+    const dim3 grid((ntiles + T - 1) / T), block(kQWaves * 64);
+    if (prelu)
+        hipLaunchKernelGGL((k_decode8q<TX, T, ALIGNED, true, TY, true>), grid, block, 0, st, X, w2, K, M, N, nkb, ntiles,
+                           scale_out, cscale, B, Y, ldy, a, gamma, eps);
+    else
+        hipLaunchKernelGGL((k_decode8q<TX, T, ALIGNED, false, TY, true>), grid, block, 0, st, X, w2, K, M, N, nkb, ntiles,
+                           scale_out, cscale, B, Y, ldy, a, gamma, eps);
+}
+
+template <typename TX, typename TY>
+void decode_qn_typed(const TX* X, const float* gamma, float eps, const uint32_t* w2, int K, int M, int N,
+                     float* scale_out, const float* cscale, const float* B, TY* Y, int ldy, bool prelu, float a,
+                     int num_cus, hipStream_t st) {
+    const bool aligned = XSrc<TX>::vec_ok(X, K);
+    const int T = decode_tiles_per_wg(M, N, num_cus);
+#define TCSC_DECODE_QN_LAUNCH(TT)                                                                                  \
+    if (aligned)                                                                                                   \
+        launch_decode_qn<TX, TT, true>(X, gamma, eps, w2, K, M, N, scale_out, cscale, B, Y, ldy, prelu, a, st);    \
+    else                                                                                                           \
+        launch_decode_qn<TX, TT, false>(X, gamma, eps, w2, K, M, N, scale_out, cscale, B, Y, ldy, prelu, a, st)
+    if (T == 4) {
+        TCSC_DECODE_QN_LAUNCH(4);
+    } else if (T == 2) {
+        TCSC_DECODE_QN_LAUNCH(2);
+    } else {
+        TCSC_DECODE_QN_LAUNCH(1);
+    }
+#undef TCSC_DECODE_QN_LAUNCH
 }
 
 template <typename TX, typename TY>
@@ -784,6 +908,30 @@ hipError_t decode_gemm_q(const void* X, bool bf16, const uint32_t* w2, int K, in
             TCSC_DECODE_Q_TYPED(float, float);
     }
 #undef TCSC_DECODE_Q_TYPED
+    return hipGetLastError();
+}
+
+hipError_t decode_gemm_qn(const void* X, bool bf16, const float* gamma, float eps, const uint32_t* w2, int K, int M,
+                          int N, float* scale_out, const float* B, const YOut& y, int ldy, bool prelu, float a,
+                          int num_cus, hipStream_t st) {
+    if (M < 1 || M > kDecodeMaxM || K < 1 || K >= kDecodeMaxK || N < 1 || !X || !w2 || !scale_out || !B || !y.Y ||
+        ldy < N)
+        return hipErrorInvalidValue;
+#define TCSC_DECODE_QN_TYPED(TX, TY)                                                                                 \
+    decode_qn_typed(static_cast<const TX*>(X), gamma, eps, w2, K, M, N, scale_out, y.cscale, B, static_cast<TY*>(y.Y), \
+                    ldy, prelu, a, num_cus, st)
+    if (bf16) {
+        if (y.ytype == kYBf16)
+            TCSC_DECODE_QN_TYPED(uint16_t, uint16_t);
+        else
+            TCSC_DECODE_QN_TYPED(uint16_t, float);
+    } else {
+        if (y.ytype == kYBf16)
+            TCSC_DECODE_QN_TYPED(float, uint16_t);
+        else
+            TCSC_DECODE_QN_TYPED(float, float);
+    }
+#undef TCSC_DECODE_QN_TYPED
     return hipGetLastError();
 }
 

@@ -452,6 +452,14 @@ hipError_t mfma8_gemm(const int8_t* x8, const int8_t* w8, int ld8, int K, int M,
 hipError_t quantize_rows_i8(const float* X, int M, int K, int8_t* Xq, float* scale, hipStream_t st);
 // the same on bf16 bit patterns, widened first (tcsc_gpu_quantize_rows_i8_bf16)
 hipError_t quantize_rows_i8_bf16(const uint16_t* X, int M, int K, int8_t* Xq, float* scale, hipStream_t st);
+// k_rmsnorm_rows (the arithmetic of tcsc_norm.h): Xn = fl(fl(x r)
+// gamma) in fp32, r per row into rinv where it is given; X is fp32 or bf16 bit
+// patterns, gamma fp32 or null (all ones), any alignment
+hipError_t rmsnorm_rows(const void* X, bool bf16, const float* gamma, float eps, int M, int K, float* Xn, float* rinv,
+                        hipStream_t st);
+// k_quant_rows_i8<.., NORM>: the bits of rmsnorm_rows followed by quantize_rows_i8, in one launch
+hipError_t quantize_rows_i8_norm(const void* X, bool bf16, const float* gamma, float eps, int M, int K, int8_t* Xq,
+                                 float* scale, hipStream_t st);
 
 // ---- int8 decode path (tcsc_decode.hip) -------------------------
 // The 2-bit image of a ternary W: tiles of kW2Cols columns x kW2Blk k, 1 KiB
@@ -513,6 +521,12 @@ hipError_t decode_gemm(const int8_t* X, const uint32_t* w2, int K, int M, int N,
 // bits of quantize_rows_i8{,_bf16} followed by decode_gemm
 hipError_t decode_gemm_q(const void* X, bool bf16, const uint32_t* w2, int K, int M, int N, float* scale_out,
                          const float* B, const YOut& y, int ldy, bool prelu, float a, int num_cus, hipStream_t st);
+// k_decode8q<.., NORM>: the RMSNorm in front of the quantizer as
+// well, in the same launch: the bits of rmsnorm_rows, quantize_rows_i8 and
+// decode_gemm.  gamma null = all ones
+hipError_t decode_gemm_qn(const void* X, bool bf16, const float* gamma, float eps, const uint32_t* w2, int K, int M,
+                          int N, float* scale_out, const float* B, const YOut& y, int ldy, bool prelu, float a,
+                          int num_cus, hipStream_t st);
 
 // Rewrites the flagged rows in k_stream's fast order (no-op when none is).
 hipError_t mfma_fixup(const uint16_t* x3, int M, int K, int ldk, const int* cq, const int* crq, int ncols,

@@ -37,6 +37,7 @@
 
 #include "tcsc_i8_out.h"
 #include "tcsc_internal.h"
+#include "tcsc_norm.h"
 #include "tcsc_quant.h"
 #include "tcsc_xsrc.h"
 
@@ -1229,53 +1230,174 @@ __global__ void __launch_bounds__(WN * 64) k_gemm8w2(const int8_t* __restrict__ 
 // first (XSrc, exact).  One workgroup per row, the row read twice (the second
 // time from the L2).  VEC (K a multiple of the kVec elements of a 16-B load, X
 // 16-B and Xq kVec-B aligned): 16-B loads, stores of kVec q.
-template <typename TX, bool VEC>
+//
+// NORM (tcsc_gpu_quantize_rows_i8_norm): the quantizer of
+// xn = RMSNorm(x) gamma.  Three passes -- the sum of squares in tcsc_norm.h's
+// order (thread t owns the partials t and t + 256: the groups t + 256 j), the
+// maximum of |xn|, the quantized values -- of which only the first reads the
+// row where it is short: a thread keeps its first kNormCached groups in
+// registers (rows of up to 8192 elements whole), turns them into xn in place
+// and quantizes them from there; the groups of a longer row beyond those are
+// streamed again in each pass.  VEC then also asks gamma (if any) to be 16-B
+// aligned; the q of a half group go out as one 4-B store.  The instantiations
+// without NORM are the kernel as it was and read neither gamma nor eps.
+constexpr int kNormCached = 4;
+template <typename TX, bool VEC, bool NORM = false>
 __global__ void __launch_bounds__(256) k_quant_rows_i8(const TX* __restrict__ X, int M, int K,
-                                                      int8_t* __restrict__ Xq, float* __restrict__ scale) {
+                                                      int8_t* __restrict__ Xq, float* __restrict__ scale,
+                                                      const float* __restrict__ gamma = nullptr, float eps = 0.0f) {
     using XS = XSrc<TX>;
     constexpr int kVec = XS::kVec;
     __shared__ float red[256];
     const int row = blockIdx.x;
     const TX* src = X + (size_t)row * K;
     int8_t* dst = Xq + (size_t)row * K;
-    float amax = 0.0f;
-    if (VEC) {
-        for (int q = threadIdx.x; q < K / kVec; q += blockDim.x) {
-            float w[kVec];
-            XS::unpack(*reinterpret_cast<const uint4*>(src + kVec * q), 1.0f, w);
+    if constexpr (NORM) {
+        const int t = threadIdx.x, ngroups = (K + kNormGroup - 1) / kNormGroup;
+        constexpr int kStream = 256 * kNormCached;  // the first streamed group of thread 0
+        float xc[kNormCached][kNormGroup];
+        float p[2] = {0.0f, 0.0f};  // the partials t and t + 256
 #pragma unroll
-            for (int u = 0; u < kVec; ++u) amax = fmaxf(amax, fabsf(w[u]));
+        for (int j = 0; j < kNormCached; ++j) {
+            norm_load_group<TX, VEC>(src, K, min(t + 256 * j, ngroups), xc[j]);  // group `ngroups` is past K: zeros, no load
+#pragma unroll
+            for (int e = 0; e < kNormGroup; ++e) p[j & 1] = norm_sq_add(p[j & 1], xc[j][e]);
         }
-    } else {
-        for (int k = threadIdx.x; k < K; k += blockDim.x) amax = fmaxf(amax, fabsf(XS::conv(src[k], 1.0f)));
-    }
-    red[threadIdx.x] = amax;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) red[threadIdx.x] = fmaxf(red[threadIdx.x], red[threadIdx.x + s]);
-        __syncthreads();
-    }
-    float sc, inv;
-    quant_scales(red[0], sc, inv);
-    if (threadIdx.x == 0) scale[row] = sc;
-    if (VEC) {
-        for (int q = threadIdx.x; q < K / kVec; q += blockDim.x) {
-            float w[kVec];
-            XS::unpack(*reinterpret_cast<const uint4*>(src + kVec * q), 1.0f, w);
-            uint32_t o[kVec / 4];
+        for (int g = kStream + t; g < ngroups; g += 512) {  // two groups a round: partial t, then t + 256
 #pragma unroll
-            for (int d = 0; d < kVec / 4; ++d) {
-                o[d] = 0;
+            for (int h = 0; h < 2; ++h) {
+                float x[kNormGroup];
+                norm_load_group<TX, VEC>(src, K, min(g + 256 * h, ngroups), x);
 #pragma unroll
-                for (int u = 0; u < 4; ++u) o[d] |= ((uint32_t)quant_i8(w[4 * d + u], inv) & 0xffu) << (8 * u);
+                for (int e = 0; e < kNormGroup; ++e) p[h] = norm_sq_add(p[h], x[e]);
             }
-            if constexpr (kVec == 4)
-                *reinterpret_cast<uint32_t*>(dst + kVec * q) = o[0];
-            else
-                *reinterpret_cast<uint2*>(dst + kVec * q) = make_uint2(o[0], o[1]);
+        }
+        const float r = norm_rinv(norm_ss_team<256>(norm_add(p[0], p[1]), red, t), K, eps);
+        __syncthreads();  // red is written again below
+        float amax = 0.0f;
+#pragma unroll
+        for (int j = 0; j < kNormCached; ++j) {
+            norm_group_xn<VEC>(xc[j], r, gamma, K, min(t + 256 * j, ngroups));
+#pragma unroll
+            for (int e = 0; e < kNormGroup; ++e) amax = fmaxf(amax, fabsf(xc[j][e]));
+        }
+        for (int g = kStream + t; g < ngroups; g += 256) {
+            float x[kNormGroup];
+            norm_load_group<TX, VEC>(src, K, g, x);
+            norm_group_xn<VEC>(x, r, gamma, K, g);
+#pragma unroll
+            for (int e = 0; e < kNormGroup; ++e) amax = fmaxf(amax, fabsf(x[e]));
+        }
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) amax = fmaxf(amax, __shfl_xor(amax, d, 64));  // fmaxf is exact in any order
+        if ((t & 63) == 0) red[t >> 6] = amax;
+        __syncthreads();
+        float sc, inv;
+        quant_scales(fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3])), sc, inv);
+        if (t == 0) scale[row] = sc;
+        // the q of group g: bytes in memory order, stored where k < K
+        auto store_group = [&](int g, const float (&x)[kNormGroup]) {
+            const int k0 = kNormGroup * g;
+            if constexpr (VEC) {  // K % 4 == 0 and Xq 4-B aligned: a half group is one store or lies past K
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {
+                    if (k0 + 4 * h >= K) break;
+                    uint32_t o = 0;
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) o |= ((uint32_t)quant_i8(x[4 * h + u], inv) & 0xffu) << (8 * u);
+                    *reinterpret_cast<uint32_t*>(dst + k0 + 4 * h) = o;
+                }
+            } else {
+#pragma unroll
+                for (int e = 0; e < kNormGroup; ++e)
+                    if (k0 + e < K) dst[k0 + e] = (int8_t)quant_i8(x[e], inv);
+            }
+        };
+#pragma unroll
+        for (int j = 0; j < kNormCached; ++j)
+            if (t + 256 * j < ngroups) store_group(t + 256 * j, xc[j]);
+        for (int g = kStream + t; g < ngroups; g += 256) {
+            float x[kNormGroup];
+            norm_load_group<TX, VEC>(src, K, g, x);
+            norm_group_xn<VEC>(x, r, gamma, K, g);
+            store_group(g, x);
         }
     } else {
-        for (int k = threadIdx.x; k < K; k += blockDim.x) dst[k] = (int8_t)quant_i8(XS::conv(src[k], 1.0f), inv);
+        float amax = 0.0f;
+        if (VEC) {
+            for (int q = threadIdx.x; q < K / kVec; q += blockDim.x) {
+                float w[kVec];
+                XS::unpack(*reinterpret_cast<const uint4*>(src + kVec * q), 1.0f, w);
+#pragma unroll
+                for (int u = 0; u < kVec; ++u) amax = fmaxf(amax, fabsf(w[u]));
+            }
+        } else {
+            for (int k = threadIdx.x; k < K; k += blockDim.x) amax = fmaxf(amax, fabsf(XS::conv(src[k], 1.0f)));
+        }
+        red[threadIdx.x] = amax;
+        __syncthreads();
+        for (int s = 128; s > 0; s >>= 1) {
+            if ((int)threadIdx.x < s) red[threadIdx.x] = fmaxf(red[threadIdx.x], red[threadIdx.x + s]);
+            __syncthreads();
+        }
+        float sc, inv;
+        quant_scales(red[0], sc, inv);
+        if (threadIdx.x == 0) scale[row] = sc;
+        if (VEC) {
+            for (int q = threadIdx.x; q < K / kVec; q += blockDim.x) {
+                float w[kVec];
+                XS::unpack(*reinterpret_cast<const uint4*>(src + kVec * q), 1.0f, w);
+                uint32_t o[kVec / 4];
+#pragma unroll
+                for (int d = 0; d < kVec / 4; ++d) {
+                    o[d] = 0;
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) o[d] |= ((uint32_t)quant_i8(w[4 * d + u], inv) & 0xffu) << (8 * u);
+                }
+                if constexpr (kVec == 4)
+                    *reinterpret_cast<uint32_t*>(dst + kVec * q) = o[0];
+                else
+                    *reinterpret_cast<uint2*>(dst + kVec * q) = make_uint2(o[0], o[1]);
+            }
+        } else {
+            for (int k = threadIdx.x; k < K; k += blockDim.x) dst[k] = (int8_t)quant_i8(XS::conv(src[k], 1.0f), inv);
+        }
+    }
+}
+
+// tcsc_gpu_rmsnorm_rows: Xn = fl(fl(x r) gamma) in fp32 and,
+// where rinv is given, r per row -- the arithmetic of tcsc_norm.h, one
+// workgroup per row, the row read twice.  It is the definition the fused forms
+// (k_quant_rows_i8<.., NORM>, k_decode8q<.., NORM>) are compared against.  VEC:
+// X as in k_quant_rows_i8, and Xn and gamma (if any) 16-B aligned.
+template <typename TX, bool VEC>
+__global__ void __launch_bounds__(256) k_rmsnorm_rows(const TX* __restrict__ X, const float* __restrict__ gamma,
+                                                     float eps, int M, int K, float* __restrict__ Xn,
+                                                     float* __restrict__ rinv) {
+    using XS = XSrc<TX>;
+    constexpr int kVec = XS::kVec;
+    __shared__ float part[256];
+    const int row = blockIdx.x;
+    const TX* src = X + (size_t)row * K;
+    float* dst = Xn + (size_t)row * K;
+    const float r =
+        norm_rinv(norm_ss_team<256>(norm_ss_thread<TX, 256, VEC>(src, K, threadIdx.x), part, threadIdx.x), K, eps);
+    if (threadIdx.x == 0 && rinv) rinv[row] = r;
+    if (VEC) {
+        for (int q = threadIdx.x; q < K / kVec; q += blockDim.x) {
+            float w[kVec];
+            XS::unpack(*reinterpret_cast<const uint4*>(src + kVec * q), 1.0f, w);
+            norm_piece<kVec>(w, r, gamma, kVec * q);
+#pragma unroll
+            for (int d = 0; d < kVec / 4; ++d)
+                *reinterpret_cast<float4*>(dst + kVec * q + 4 * d) =
+                    make_float4(w[4 * d], w[4 * d + 1], w[4 * d + 2], w[4 * d + 3]);
+        }
+    } else {
+        for (int k = threadIdx.x; k < K; k += blockDim.x) {
+            const float x = XS::conv(src[k], 1.0f);
+            dst[k] = gamma ? norm_apply(x, r, gamma[k]) : norm_apply(x, r);
+        }
     }
 }
 
@@ -1542,6 +1664,46 @@ static hipError_t launch_quant_rows(const TX* X, int M, int K, int8_t* Xq, float
 
 hipError_t quantize_rows_i8(const float* X, int M, int K, int8_t* Xq, float* scale, hipStream_t st) {
     return launch_quant_rows(X, M, K, Xq, scale, st);
+}
+
+static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+template <typename TX>
+static hipError_t launch_quant_rows_norm(const TX* X, const float* gamma, float eps, int M, int K, int8_t* Xq,
+                                         float* scale, hipStream_t st) {
+    if (M <= 0) return hipSuccess;
+    const bool vec = XSrc<TX>::vec_ok(X, K) && (reinterpret_cast<uintptr_t>(Xq) & (XSrc<TX>::kVec - 1)) == 0 &&
+                     aligned16(gamma);
+    if (vec)
+        hipLaunchKernelGGL((k_quant_rows_i8<TX, true, true>), dim3(M), dim3(256), 0, st, X, M, K, Xq, scale, gamma, eps);
+    else
+        hipLaunchKernelGGL((k_quant_rows_i8<TX, false, true>), dim3(M), dim3(256), 0, st, X, M, K, Xq, scale, gamma, eps);
+    return hipGetLastError();
+}
+
+hipError_t quantize_rows_i8_norm(const void* X, bool bf16, const float* gamma, float eps, int M, int K, int8_t* Xq,
+                                 float* scale, hipStream_t st) {
+    if (K < 1 || !X || !Xq || !scale) return M <= 0 ? hipSuccess : hipErrorInvalidValue;
+    return bf16 ? launch_quant_rows_norm(static_cast<const uint16_t*>(X), gamma, eps, M, K, Xq, scale, st)
+                : launch_quant_rows_norm(static_cast<const float*>(X), gamma, eps, M, K, Xq, scale, st);
+}
+
+template <typename TX>
+static hipError_t launch_rmsnorm_rows(const TX* X, const float* gamma, float eps, int M, int K, float* Xn, float* rinv,
+                                      hipStream_t st) {
+    if (M <= 0) return hipSuccess;
+    if (XSrc<TX>::vec_ok(X, K) && aligned16(Xn) && aligned16(gamma))
+        hipLaunchKernelGGL((k_rmsnorm_rows<TX, true>), dim3(M), dim3(256), 0, st, X, gamma, eps, M, K, Xn, rinv);
+    else
+        hipLaunchKernelGGL((k_rmsnorm_rows<TX, false>), dim3(M), dim3(256), 0, st, X, gamma, eps, M, K, Xn, rinv);
+    return hipGetLastError();
+}
+
+hipError_t rmsnorm_rows(const void* X, bool bf16, const float* gamma, float eps, int M, int K, float* Xn, float* rinv,
+                        hipStream_t st) {
+    if (K < 1 || !X || !Xn) return M <= 0 ? hipSuccess : hipErrorInvalidValue;
+    return bf16 ? launch_rmsnorm_rows(static_cast<const uint16_t*>(X), gamma, eps, M, K, Xn, rinv, st)
+                : launch_rmsnorm_rows(static_cast<const float*>(X), gamma, eps, M, K, Xn, rinv, st);
 }
 
 hipError_t quantize_rows_i8_bf16(const uint16_t* X, int M, int K, int8_t* Xq, float* scale, hipStream_t st) {

@@ -58,6 +58,8 @@ EXPORTED_SYMBOLS = (
     "tcsc_gpu_w2_from_tcsc_host", "tcsc_gpu_w2_to_tcsc_host",
     "tcsc_gpu_quantize_rows_i8_bf16", "tcsc_gpu_sgemm_q8", "tcsc_gpu_launch_info_q8", "tcsc_gpu_quant_fuse_pays",
     "tcsc_gpu_sgemm_i8_out", "tcsc_gpu_sgemm_q8_out",
+    "tcsc_gpu_rmsnorm_rows", "tcsc_gpu_quantize_rows_i8_norm", "tcsc_gpu_sgemm_q8_norm",
+    "tcsc_gpu_launch_info_q8_norm", "tcsc_gpu_norm_fuse_pays",
     # include/sparse/bcsr.h
     "bcsr_from_dense", "bcsr_sgemm_basic", "bcsr_sgemm_prelu_basic", "bcsr_sgemm_avx", "bcsr_sgemm_prelu_avx",
     "bcsr_sgemm_avx2", "bcsr_free",
@@ -186,6 +188,11 @@ def lib():
     L.tcsc_gpu_quant_fuse_pays.argtypes = [i, i, i, i]
     L.tcsc_gpu_sgemm_i8_out.argtypes = [vp, vp, vp, vp, vp, vp, i, i, i, i, f, vp]
     L.tcsc_gpu_sgemm_q8_out.argtypes = [vp, vp, i, vp, vp, vp, vp, vp, i, i, i, i, f, vp]
+    L.tcsc_gpu_rmsnorm_rows.argtypes = [vp, i, vp, f, i, i, vp, vp, vp]
+    L.tcsc_gpu_quantize_rows_i8_norm.argtypes = [vp, i, vp, f, i, i, vp, vp, vp]
+    L.tcsc_gpu_sgemm_q8_norm.argtypes = [vp, vp, i, vp, f, vp, vp, vp, vp, vp, i, i, i, i, f, vp]
+    L.tcsc_gpu_launch_info_q8_norm.argtypes = [vp, i, i, C.POINTER(i), C.POINTER(i), C.POINTER(i)]
+    L.tcsc_gpu_norm_fuse_pays.argtypes = [i, i, i, i]
     L.tcsc_gpu_prepare_x.argtypes = [vp, vp, i, vp]
     L.tcsc_gpu_sgemm_prepared.argtypes = [vp, vp, vp, i, i, i, f, vp]
     L.tcsc_gpu_from_dense.argtypes = [vp, i, i, vp, vp, vp, vp, C.POINTER(i), C.POINTER(i), vp]
@@ -760,6 +767,29 @@ class Plan:
                                              C.byref(fused)), "tcsc_gpu_launch_info_q8")
         return ("gather", "fused", "mfma", "small", "decode")[path.value], slices.value, bool(fused.value)
 
+    def sgemm_q8_norm(self, X, Xq, scale, B, Y, M: int, ldy: int, norm_weight=None, eps: float = 1e-6,
+                      variant: str = "prelu_basic", a: float = 0.2, stream: int = 0, xtype=None, col_scale=None,
+                      ytype=None) -> None:
+        """:meth:`sgemm_q8` on RMSNorm(X) * norm_weight (tcsc_gpu_sgemm_q8_norm): norm_weight is K floats or None
+        for all ones.  Y and scale get the bits of :func:`rmsnorm_rows` + :func:`quantize_rows_i8` +
+        :meth:`sgemm_i8`; one launch where the call is fused (:meth:`launch_info_q8_norm`: Xq is then untouched and
+        may be None), :func:`quantize_rows_i8_norm` into Xq and the int8 call elsewhere."""
+        xt = _xtype_of(X) if xtype is None else _xtype(xtype)
+        yt = _ytype_of(Y) if ytype is None else _ytype(ytype)
+        _check(lib().tcsc_gpu_sgemm_q8_norm(self.handle, C.c_void_p(_ptr(X)), xt, C.c_void_p(_ptr(norm_weight)),
+                                            float(eps), C.c_void_p(_ptr(Xq)), C.c_void_p(_ptr(scale)),
+                                            C.c_void_p(_ptr(col_scale)), C.c_void_p(_ptr(B)), C.c_void_p(_ptr(Y)), yt,
+                                            int(M), int(ldy), VARIANT_ID[variant], float(a), C.c_void_p(stream)),
+               "tcsc_gpu_sgemm_q8_norm")
+
+    def launch_info_q8_norm(self, M: int, dtype="f32") -> tuple[str, int, bool]:
+        """(path, K slices, fused) of an :meth:`sgemm_q8_norm` launch of M rows of that dtype
+        (tcsc_gpu_launch_info_q8_norm): the int8 route, and whether norm, quantizer and GEMM are one kernel."""
+        path, slices, fused = C.c_int(), C.c_int(), C.c_int()
+        _check(lib().tcsc_gpu_launch_info_q8_norm(self.handle, int(M), _xtype(dtype), C.byref(path), C.byref(slices),
+                                                  C.byref(fused)), "tcsc_gpu_launch_info_q8_norm")
+        return ("gather", "fused", "mfma", "small", "decode")[path.value], slices.value, bool(fused.value)
+
     def sgemm_t(self, G, DX, M: int, ldx: int, stream: int = 0) -> None:
         """dX (M x K, pitch ldx) = G (M x plan rows, contiguous) . W[:, range]^T on a transposed
         plan (tcsc_gpu_sgemm_t); TcscError on a plan that :meth:`transposed` did not make."""
@@ -889,6 +919,33 @@ def quant_fuse_pays(M: int, K: int, N: int, dtype="f32") -> bool:
     """The default rule for fusing the quantizer into the decode call (tcsc_gpu_quant_fuse_pays; host
     arithmetic): whether :meth:`Plan.sgemm_q8` of M rows of that dtype on a K x N decode route runs one kernel."""
     return bool(lib().tcsc_gpu_quant_fuse_pays(int(M), int(K), int(N), _xtype(dtype)))
+
+
+def rmsnorm_rows(X, Xn, M: int, K: int, weight=None, eps: float = 1e-6, rinv=None, stream: int = 0, xtype=None) -> None:
+    """RMSNorm of the rows of X in the library's pinned arithmetic (tcsc_gpu_rmsnorm_rows): X is M x K contiguous
+    fp32 or bf16, weight K floats or None for all ones; Xn (M x K floats) = fl(fl(x * r) * weight) with
+    r = 1 / sqrt(mean(x^2) + eps), the sum of squares in a fixed order; rinv (M floats), where given, gets r."""
+    xt = _xtype_of(X) if xtype is None else _xtype(xtype)
+    _check(lib().tcsc_gpu_rmsnorm_rows(C.c_void_p(_ptr(X)), xt, C.c_void_p(_ptr(weight)), float(eps), int(M), int(K),
+                                       C.c_void_p(_ptr(Xn)), C.c_void_p(_ptr(rinv)), C.c_void_p(stream)),
+           "tcsc_gpu_rmsnorm_rows")
+
+
+def quantize_rows_i8_norm(X, Xq, scale, M: int, K: int, weight=None, eps: float = 1e-6, stream: int = 0,
+                          xtype=None) -> None:
+    """:func:`rmsnorm_rows` and :func:`quantize_rows_i8` in one launch, the same bits
+    (tcsc_gpu_quantize_rows_i8_norm): Xq (M x K int8) and scale (M floats) are written."""
+    xt = _xtype_of(X) if xtype is None else _xtype(xtype)
+    _check(lib().tcsc_gpu_quantize_rows_i8_norm(C.c_void_p(_ptr(X)), xt, C.c_void_p(_ptr(weight)), float(eps), int(M),
+                                                int(K), C.c_void_p(_ptr(Xq)), C.c_void_p(_ptr(scale)),
+                                                C.c_void_p(stream)), "tcsc_gpu_quantize_rows_i8_norm")
+
+
+def norm_fuse_pays(M: int, K: int, N: int, dtype="f32") -> bool:
+    """The default rule for fusing norm and quantizer into the decode call (tcsc_gpu_norm_fuse_pays; host
+    arithmetic): whether :meth:`Plan.sgemm_q8_norm` of M rows of that dtype on a K x N decode route runs one
+    kernel."""
+    return bool(lib().tcsc_gpu_norm_fuse_pays(int(M), int(K), int(N), _xtype(dtype)))
 
 
 def w2_image_bytes(K: int, N: int) -> int:

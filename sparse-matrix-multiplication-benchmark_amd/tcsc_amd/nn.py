@@ -64,6 +64,22 @@ def _define():
                             "(one value or one per column)")
         return t.clone()
 
+    def _norm_args(norm_weight, norm_eps, k: int, dev):
+        """(norm_weight as None or k contiguous floats on dev, norm_eps as None or a float > 0)."""
+        if norm_eps is None:
+            if norm_weight is not None:
+                raise TcscError("PackedTernaryLinear: norm_weight needs norm_eps (the layer has no norm without it)")
+            return None, None
+        eps = float(norm_eps)
+        if not (eps > 0.0 and eps < float("inf")):
+            raise TcscError(f"PackedTernaryLinear: norm_eps must be a finite number > 0, got {norm_eps!r}")
+        if norm_weight is None:
+            return None, eps
+        t = torch.as_tensor(norm_weight).detach().to(device=dev, dtype=torch.float32).reshape(-1).clone()
+        if t.numel() != k:
+            raise TcscError(f"PackedTernaryLinear: norm_weight has {t.numel()} elements, W has K={k} rows")
+        return t, eps
+
     def _out_dtype(dt):
         if dt not in (torch.float32, torch.bfloat16):
             raise TcscError(f"PackedTernaryLinear: out_dtype must be torch.float32 or torch.bfloat16, got {dt!r}")
@@ -236,11 +252,16 @@ def _define():
         quantizes its rows to int8 (the arithmetic of ``tcsc_amd.quantize_rows_i8``) and multiplies: up to 16
         rows k_decode8q in one launch where fusing pays, the quantizer and k_decode8 elsewhere, k_gemm8w2
         above -- the bits of ``TernaryLinear.forward_int8`` on the int8 MFMA path.
+        norm_weight, norm_eps: with norm_eps given the layer reads ``RMSNorm(x) * norm_weight`` in place of x
+        (norm_weight: K values, or None for all ones): ``forward`` calls ``Plan.sgemm_q8_norm``, the norm in the
+        library's pinned arithmetic (``tcsc_amd.rmsnorm_rows``) inside the quantizer's launch, or inside the one
+        decode launch where fusing pays.  norm_weight is a buffer: ``state_dict()`` carries it when the layer has
+        one; norm_eps is a constructor argument, as ``a`` is.  Without norm_eps the layer is what it was.
         There is no backward and no transposed plan: it raises when grad is enabled and x requires grad.
         """
 
         def __init__(self, W, bias=None, a: float | None = None, device: int = 0, weight_scale=None,
-                     out_dtype=torch.float32):
+                     out_dtype=torch.float32, norm_weight=None, norm_eps: float | None = None):
             super().__init__()
             Wm = _ternary_matrix(W, "PackedTernaryLinear")  # only read here: the plan keeps no reference to it
             self.in_features, self.out_features, self.nnz = Wm.rows, Wm.cols, Wm.nnz
@@ -250,24 +271,29 @@ def _define():
             dev = torch.device("cuda", self.device_index)
             self.register_buffer("bias", _bias_tensor(bias, self.out_features, dev, "PackedTernaryLinear"))
             self.register_buffer("weight_scale", _weight_scale_tensor(weight_scale, self.out_features, dev))
+            nw, self.norm_eps = _norm_args(norm_weight, norm_eps, self.in_features, dev)
+            self.register_buffer("norm_weight", nw)
             self.plan = Plan.packed(Wm, 0, self.out_features, self.device_index, _stream(dev))
             self._rows, self._xq, self._scale = 0, None, None
 
         @classmethod
-        def from_float(cls, Wf, bias=None, a: float | None = None, device: int = 0, out_dtype=torch.float32):
+        def from_float(cls, Wf, bias=None, a: float | None = None, device: int = 0, out_dtype=torch.float32,
+                       norm_weight=None, norm_eps: float | None = None):
             """The layer of a float weight matrix Wf (K x N): ``T, beta = tcsc_amd.ternarize_absmean(Wf)``, then
             the packed plan of T with the per-tensor ``weight_scale = beta``, so that the layer computes
             ``act(x . (beta T) + bias)`` on the quantized x."""
             if torch.is_tensor(Wf):
                 Wf = Wf.detach().cpu().numpy()
             T, beta = ternarize_absmean(Wf)
-            return cls(T, bias, a, device, weight_scale=float(beta), out_dtype=out_dtype)
+            return cls(T, bias, a, device, weight_scale=float(beta), out_dtype=out_dtype, norm_weight=norm_weight,
+                       norm_eps=norm_eps)
 
         @classmethod
         def empty(cls, in_features: int, out_features: int, a: float | None = None, device: int = 0,
-                  out_dtype=torch.float32):
+                  out_dtype=torch.float32, norm_eps: float | None = None):
             """A layer of this shape with a zero bias, no weight scale and no plan yet: ``load_state_dict`` fills it
-            from a ``state_dict()`` of a layer of the same shape (its ``weight_scale`` included, when it has one).
+            from a ``state_dict()`` of a layer of the same shape (its ``weight_scale`` and ``norm_weight`` included,
+            when it has them; a state with a ``norm_weight`` needs a layer made with norm_eps).
             Until then ``forward`` and ``reserve`` raise."""
             self = cls.__new__(cls)
             torch.nn.Module.__init__(self)
@@ -278,6 +304,8 @@ def _define():
             dev = torch.device("cuda", self.device_index)
             self.register_buffer("bias", torch.zeros(self.out_features, dtype=torch.float32, device=dev))
             self.register_buffer("weight_scale", None)
+            _, self.norm_eps = _norm_args(None, norm_eps, self.in_features, dev)
+            self.register_buffer("norm_weight", None)
             self.plan = None
             self._rows, self._xq, self._scale = 0, None, None
             return self
@@ -319,10 +347,18 @@ def _define():
             if ws is not None and (not torch.is_tensor(ws) or ws.numel() != self.out_features):
                 raise TcscError(f"PackedTernaryLinear.load_state_dict: {prefix}weight_scale must hold "
                                 f"{self.out_features} values")
+            nw = state_dict.get(prefix + "norm_weight")
+            if nw is not None and (not torch.is_tensor(nw) or nw.numel() != self.in_features):
+                raise TcscError(f"PackedTernaryLinear.load_state_dict: {prefix}norm_weight must hold "
+                                f"{self.in_features} values")
+            if nw is not None and self.norm_eps is None:
+                raise TcscError(f"PackedTernaryLinear.load_state_dict: {prefix}norm_weight for a layer made without "
+                                "norm_eps")
             image = w2.detach().to(dev).contiguous()
             plan = Plan.packed_from_image(image, self.in_features, self.out_features, 0, self.device_index, _stream(dev))
             # the base class copies into the buffers the layer has: give it one of the state's kind
             self.weight_scale = None if ws is None else torch.empty(self.out_features, dtype=torch.float32, device=dev)
+            self.norm_weight = None if nw is None else torch.empty(self.in_features, dtype=torch.float32, device=dev)
             super()._load_from_state_dict(state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys,
                                           error_msgs)
             if prefix + "w2" in unexpected_keys:  # the base class knows parameters and buffers only
@@ -365,12 +401,18 @@ def _define():
             stream = _stream(x.device)
             y = torch.empty((M, N), dtype=self.out_dtype, device=x.device)
             variant, a = ("basic", 0.0) if self.a is None else ("prelu_basic", self.a)
-            plan.sgemm_q8(x2, xq, scale, self.bias, y, M, N, variant, a, stream, col_scale=self.weight_scale)
+            if self.norm_eps is None:
+                plan.sgemm_q8(x2, xq, scale, self.bias, y, M, N, variant, a, stream, col_scale=self.weight_scale)
+            else:
+                plan.sgemm_q8_norm(x2, xq, scale, self.bias, y, M, N, self.norm_weight, self.norm_eps, variant, a,
+                                   stream, col_scale=self.weight_scale)
             return y.reshape(*lead, N)
 
         def extra_repr(self) -> str:
             return (f"in_features={self.in_features}, out_features={self.out_features}, nnz={self.nnz}, a={self.a}, "
-                    f"weight_scale={self.weight_scale is not None}, out_dtype={self.out_dtype}")
+                    f"weight_scale={self.weight_scale is not None}, out_dtype={self.out_dtype}"
+                    + ("" if self.norm_eps is None else f", norm_eps={self.norm_eps}, "
+                       f"norm_weight={self.norm_weight is not None}"))
 
     return {"TernaryLinear": TernaryLinear, "PackedTernaryLinear": PackedTernaryLinear}
 
