@@ -307,6 +307,10 @@ using tcsc::kF32;
 using tcsc::kI8;
 using tcsc::kYBf16;
 using tcsc::kYF32;
+using tcsc::Call;
+using tcsc::I8Epi;
+using tcsc::make_call;
+using tcsc::RmsNorm;
 using tcsc::YOut;
 struct XType {
     const char* sgemm;  // the entry point, as error messages name it
@@ -1004,6 +1008,18 @@ Route tcsc::route_call(const tcsc_gpu_plan* p, int M, int dt, size_t ws_avail, c
 }
 
 namespace {
+// the epilogue of an int8 call, for the kernels' launchers
+I8Epi i8_epi(const Call& c) {
+    I8Epi e;
+    e.rscale = c.xscale;
+    e.B = c.B;
+    e.y = c.y;
+    e.ldy = c.ldy;
+    e.prelu = is_prelu(c.variant);
+    e.a = c.a;
+    return e;
+}
+
 // The MFMA path: pack X into the type's GEMM operand in the workspace, run
 // the GEMM against W's image (the bias and PReLU in its store), and where the
 // type keeps row flags rewrite the flagged rows exactly.
@@ -1013,23 +1029,26 @@ namespace {
 //   int8: k_pack8 (X -> X8), k_gemm8 against the int8 image (+ k_reduce_i8 when
 //         K is split) with the row scales, the output descriptor's column
 //         scales and Y type (§21); no flags, no fixup
-int sgemm_mfma(const tcsc_gpu_plan* p, const void* dX, int dt, const float* dScale, const float* dB, const YOut& y,
-               int M, int ldy, int variant, float a, void* stream, float* ws, size_t ws_bytes, int stage) {
+int sgemm_mfma(const tcsc_gpu_plan* p, const Call& c, float* ws, size_t ws_bytes, int stage) {
+    const int dt = c.xtype, M = c.M, ldy = c.ldy;
     const XType& d = kXTypes[dt];
-    float* dY = static_cast<float*>(y.Y);  // the fp32 and bf16 calls write floats (y.plain())
+    const void* dX = c.X;
+    const float* dB = c.B;
+    float* dY = static_cast<float*>(c.y.Y);  // the fp32 and bf16 calls write floats (y.plain())
+    const float a = c.a;
     const int K = p->rows, N = p->cols, ldx = d.ldx(K), ldw = d.ldw(K);
     const MfmaWs w = mfma_ws(dt, M, K, N);
     if (!ws || ws_bytes < w.bytes) {
         set_error("%s: workspace of %zu bytes < %zu needed for M=%d", d.sgemm, ws ? ws_bytes : (size_t)0, w.bytes, M);
         return TCSC_E_ARG;
     }
-    hipStream_t st = static_cast<hipStream_t>(stream);
+    hipStream_t st = static_cast<hipStream_t>(c.stream);
     char* base = reinterpret_cast<char*>(ws);
     uint16_t* xp = reinterpret_cast<uint16_t*>(base);
     int* flags = reinterpret_cast<int*>(base + w.flags_off);
     void* slabs = base + w.slabs_off;
     const size_t slab_bytes = ws_bytes - w.slabs_off;
-    const bool prelu = is_prelu(variant);
+    const bool prelu = is_prelu(c.variant);
     switch (dt) {
         case kF32:
             if (stage != 2) HIP_TRY(tcsc::mfma_split_x(static_cast<const float*>(dX), M, K, xp, ldx, flags, st));
@@ -1042,17 +1061,19 @@ int sgemm_mfma(const tcsc_gpu_plan* p, const void* dX, int dt, const float* dSca
             HIP_TRY(tcsc::mfma_gemm1(xp, ldx, p->wt, ldw, K, M, N, dB, dY, ldy, prelu, a, static_cast<float*>(slabs),
                                      slab_bytes, flags, p->ccq, p->crq, st));
             break;
-        case kI8:
+        case kI8: {
             HIP_TRY(tcsc::mfma8_pack_x(static_cast<const int8_t*>(dX), M, K, reinterpret_cast<int8_t*>(base), ldx, st));
+            const I8Epi e = i8_epi(c);
             // B from the 2-bit image (k_gemm8w2): a packed plan has nothing else; an ordinary plan that has
             // both images takes it under $TCSC_W2GEMM=1 -- the same route, K split, workspace and bits
             if (p->packed || (p->w2 && w2gemm_knob()))
-                HIP_TRY(tcsc::mfma8_gemm_w2(reinterpret_cast<const int8_t*>(base), p->w2, ldx, K, M, N, dScale, dB, y,
-                                            ldy, prelu, a, static_cast<int*>(slabs), slab_bytes, st));
+                HIP_TRY(tcsc::mfma8_gemm_w2(reinterpret_cast<const int8_t*>(base), p->w2, ldx, K, M, N, e,
+                                            static_cast<int*>(slabs), slab_bytes, st));
             else
-                HIP_TRY(tcsc::mfma8_gemm(reinterpret_cast<const int8_t*>(base), p->w8, ldx, K, M, N, dScale, dB, y,
-                                         ldy, prelu, a, static_cast<int*>(slabs), slab_bytes, st));
+                HIP_TRY(tcsc::mfma8_gemm(reinterpret_cast<const int8_t*>(base), p->w8, ldx, K, M, N, e,
+                                         static_cast<int*>(slabs), slab_bytes, st));
             break;
+        }
     }
     // fast order: bias after the sum for every variant; a
     // split K rewrote the flagged rows in its reduce already
@@ -1086,15 +1107,18 @@ static bool refuse_out(const char* who, int path, const YOut& y, int M) {
 }
 
 // One call on the workspace ws: routed once (route_call, with what `pin`
-// fixes and what the pointers allow), then launched as routed.  `out`, if
-// given, replaces dY: the int8 call's Y with its type and column scales.
-int tcsc::sgemm_ws(const tcsc_gpu_plan* p, const void* dX, const float* dB, float* dY, int M, int ldy, int variant,
-                   float a, void* stream, float* ws, size_t ws_bytes, int stage, const RoutePins& pin, Route* ran,
-                   int dt, const float* dScale, const YOut* out, const char* as) {
+// fixes and what the pointers allow), then launched as routed.
+int tcsc::sgemm_ws(const tcsc_gpu_plan* p, const Call& c, float* ws, size_t ws_bytes, int stage, const RoutePins& pin,
+                   Route* ran) {
+    const int dt = c.xtype, M = c.M, ldy = c.ldy, variant = c.variant;
     const XType& d = kXTypes[dt];
-    const char* who = as ? as : d.sgemm;
-    const YOut y = out ? *out : YOut{dY, kYF32, nullptr};
-    if (out) dY = y.plain() ? static_cast<float*>(y.Y) : nullptr;  // the fp32 routes never see another Y
+    const char* who = c.who ? c.who : d.sgemm;
+    const void* dX = c.X;
+    const float *dScale = c.xscale, *dB = c.B;
+    const YOut& y = c.y;
+    float* dY = y.plain() ? static_cast<float*>(y.Y) : nullptr;  // the fp32 routes never see another Y
+    const float a = c.a;
+    void* stream = c.stream;
     if (dt != kI8 && !y.plain()) {
         set_error("%s: only the int8 call has a typed Y and column scales", who);
         return TCSC_E_ARG;
@@ -1118,10 +1142,8 @@ int tcsc::sgemm_ws(const tcsc_gpu_plan* p, const void* dX, const float* dB, floa
     }
     if (p->packed && M > kMaxLaunchRows) {  // pieces of at most kMaxLaunchRows rows on one workspace, each routed by its own rows
         for (int r0 = 0; r0 < M; r0 += kMaxLaunchRows) {
-            const YOut piece = y.rows_on((size_t)r0, ldy);  // Y advances by the element size of its type
-            const int rc = sgemm_ws(p, static_cast<const char*>(dX) + (size_t)r0 * p->rows * d.elem, dB, nullptr,
-                                    std::min(kMaxLaunchRows, M - r0), ldy, variant, a, stream, ws, ws_bytes, 0, pin,
-                                    nullptr, dt, dScale ? dScale + r0 : nullptr, &piece, as);
+            const int rc = sgemm_ws(p, c.rows(r0, std::min(kMaxLaunchRows, M - r0), p->rows, d.elem), ws, ws_bytes, 0, pin,
+                                    nullptr);
             if (rc != TCSC_OK) return rc;
         }
         if (ran) *ran = route_call(p, M, dt, ws ? ws_bytes : 0, pin);
@@ -1150,12 +1172,11 @@ int tcsc::sgemm_ws(const tcsc_gpu_plan* p, const void* dX, const float* dB, floa
     }
     if (refuse_out(who, r.path, y, M)) return TCSC_E_ARG;
     if (r.path == TCSC_PATH_DECODE) {
-        HIP_TRY(tcsc::decode_gemm(static_cast<const int8_t*>(dX), p->w2, p->rows, M, p->cols, dScale, dB, y, ldy,
-                                  is_prelu(variant), a, p->num_cus, static_cast<hipStream_t>(stream)));
+        HIP_TRY(tcsc::decode_gemm(tcsc::DecodeX{dX, kI8, nullptr, nullptr}, p->w2, p->rows, M, p->cols, i8_epi(c),
+                                  p->num_cus, static_cast<hipStream_t>(stream)));
         return TCSC_OK;
     }
-    if (r.path == TCSC_PATH_MFMA)
-        return sgemm_mfma(p, dX, dt, dScale, dB, y, M, ldy, variant, a, stream, ws, ws_bytes, stage);
+    if (r.path == TCSC_PATH_MFMA) return sgemm_mfma(p, c, ws, ws_bytes, stage);
     if (r.path == TCSC_PATH_SMALL) {
         // stage 1 stages X as is (the kernel reads X rows directly), stage 2 reads the staged copy
         hipStream_t st = static_cast<hipStream_t>(stream);
@@ -1190,10 +1211,8 @@ int tcsc::sgemm_ws(const tcsc_gpu_plan* p, const void* dX, const float* dB, floa
         piece.path = TCSC_PATH_GATHER;  // a short tail stays on the gather too
         piece.slices = r.slices;
         for (int r0 = 0; r0 < M; r0 += kMaxLaunchRows) {
-            const int rows = std::min(kMaxLaunchRows, M - r0);
-            const void* xr = static_cast<const char*>(dX) + (size_t)r0 * p->rows * d.elem;
-            const int rc = sgemm_ws(p, xr, dB, dY + (size_t)r0 * ldy, rows, ldy, variant, a, stream, ws, ws_bytes, 0,
-                                    piece, nullptr, dt, dScale ? dScale + r0 : nullptr, nullptr, as);
+            const int rc = sgemm_ws(p, c.rows(r0, std::min(kMaxLaunchRows, M - r0), p->rows, d.elem), ws, ws_bytes, 0,
+                                    piece, nullptr);
             if (rc != TCSC_OK) return rc;
         }
         return TCSC_OK;
@@ -1896,33 +1915,35 @@ int tcsc_gpu_launch_combine(const tcsc_gpu_plan* p, int M, int* in_launch) {
 // (tcsc_gpu_plan_reserve up front keeps the call allocation-free and
 // graph-capturable: its size covers every launch of every type, mfma_ws),
 // then run on it.
-// `out` and `as`: the typed Y with its column scales and the name of the call in
-// messages, for the int8 call's _out form (sgemm_ws); a route that cannot write
-// what `out` asks for is refused here, ahead of the workspace and of any launch
-static int sgemm_entry(const tcsc_gpu_plan* p, const void* dX, int dt, const float* dScale, const float* dB, float* dY,
-                       int M, int ldy, int variant, float a, void* stream, const YOut* out = nullptr,
-                       const char* as = nullptr) {
+// A route that cannot write the typed Y or the column scales the call asks for
+// (the int8 call's _out form) is refused here, ahead of the workspace and of
+// any launch.
+static int sgemm_entry(const tcsc_gpu_plan* p, const Call& c) {
+    const int dt = c.xtype, M = c.M;
     if (dt != kI8 && refuse_packed(p, kXTypes[dt].sgemm)) return TCSC_E_ARG;
-    if (out && !out->plain() && p && M > 0 && p->cols > 0 &&
-        refuse_out(as ? as : kXTypes[dt].sgemm, route_call(p, M, dt, p->ws_bytes, RoutePins()).path, *out, M))
+    if (!c.y.plain() && p && M > 0 && p->cols > 0 &&
+        refuse_out(c.who ? c.who : kXTypes[dt].sgemm, route_call(p, M, dt, p->ws_bytes, RoutePins()).path, c.y, M))
         return TCSC_E_ARG;
     if (p && M > 0 && p->cols > 0 && p->ws_bytes < wanted_workspace(p, M, dt)) {
         const int rc = tcsc_gpu_plan_reserve(const_cast<tcsc_gpu_plan*>(p), M);
         if (rc != TCSC_OK) return rc;
     }
     if (p) const_cast<tcsc_gpu_plan*>(p)->staged_M = -1;  // this call's X^T or packed X replaces any staged one
-    return sgemm_ws(p, dX, dB, dY, M, ldy, variant, a, stream, p ? p->ws : nullptr, p ? p->ws_bytes : 0, 0, RoutePins(),
-                    nullptr, dt, dScale, out, as);
+    return sgemm_ws(p, c, p ? p->ws : nullptr, p ? p->ws_bytes : 0, 0, RoutePins(), nullptr);
+}
+
+static YOut y_out(void* dY, int ytype, const float* dColScale) {
+    return YOut{dY, ytype == TCSC_Y_BF16 ? kYBf16 : kYF32, dColScale};
 }
 
 int tcsc_gpu_sgemm(const tcsc_gpu_plan* p, const float* dX, const float* dB, float* dY, int M, int ldy,
                    int variant, float a, void* stream) {
-    return sgemm_entry(p, dX, kF32, nullptr, dB, dY, M, ldy, variant, a, stream);
+    return sgemm_entry(p, make_call(dX, kF32, nullptr, dB, YOut{dY, kYF32, nullptr}, M, ldy, variant, a, stream));
 }
 
 int tcsc_gpu_sgemm_bf16(const tcsc_gpu_plan* p, const void* dX_bf16, const float* dB, float* dY, int M, int ldy,
                         int variant, float a, void* stream) {
-    return sgemm_entry(p, dX_bf16, kBf16, nullptr, dB, dY, M, ldy, variant, a, stream);
+    return sgemm_entry(p, make_call(dX_bf16, kBf16, nullptr, dB, YOut{dY, kYF32, nullptr}, M, ldy, variant, a, stream));
 }
 
 int tcsc_gpu_plan_enable_i8(tcsc_gpu_plan* p, void* stream) {
@@ -2019,8 +2040,7 @@ int tcsc_gpu_decode_pays(int M, int K, int N, long long nnz) { return decode_pay
 // tcsc_gpu_sgemm_i8_out with (NULL, TCSC_Y_F32)
 int tcsc_gpu_sgemm_i8(const tcsc_gpu_plan* p, const void* dXq, const float* dScale, const float* dB, float* dY, int M,
                       int ldy, int variant, float a, void* stream) {
-    const YOut y{dY, kYF32, nullptr};
-    return sgemm_entry(p, dXq, kI8, dScale, dB, nullptr, M, ldy, variant, a, stream, &y);
+    return sgemm_entry(p, make_call(dXq, kI8, dScale, dB, YOut{dY, kYF32, nullptr}, M, ldy, variant, a, stream));
 }
 
 // ---- the typed Y and the column scales of the int8 calls -------
@@ -2046,37 +2066,33 @@ int tcsc_gpu_sgemm_i8_out(const tcsc_gpu_plan* p, const void* dXq, const float* 
     const char* who = "tcsc_gpu_sgemm_i8_out";
     const int rc = out_args(who, p, dB, dY, ytype);
     if (rc != TCSC_OK) return rc;
-    const YOut y{dY, ytype == TCSC_Y_BF16 ? kYBf16 : kYF32, dColScale};
-    return sgemm_entry(p, dXq, kI8, dScale, dB, nullptr, M, ldy, variant, a, stream, &y, who);
+    return sgemm_entry(p, make_call(dXq, kI8, dScale, dB, y_out(dY, ytype, dColScale), M, ldy, variant, a, stream, who));
 }
 
-int tcsc_gpu_quantize_rows_i8(const float* dX, int M, int K, void* dXq, float* dScale, void* stream) {
+// the plain quantizer of an fp32 or bf16 X (TCSC_X_F32 / TCSC_X_BF16), under the name of its entry point
+static_assert(TCSC_X_F32 == kF32 && TCSC_X_BF16 == kBf16, "the public X types are the internal ones");
+static int quantize_rows(int xtype, const void* dX, int M, int K, void* dXq, float* dScale, void* stream) {
+    const char* who = xtype == TCSC_X_BF16 ? "tcsc_gpu_quantize_rows_i8_bf16" : "tcsc_gpu_quantize_rows_i8";
     if (M < 0 || K < 0) {
-        set_error("tcsc_gpu_quantize_rows_i8: bad arguments (M=%d K=%d)", M, K);
+        set_error("%s: bad arguments (M=%d K=%d)", who, M, K);
         return TCSC_E_ARG;
     }
     if (M == 0) return TCSC_OK;
     if (!dScale || (K > 0 && (!dX || !dXq))) {
-        set_error("tcsc_gpu_quantize_rows_i8: NULL device pointer");
+        set_error("%s: NULL device pointer", who);
         return TCSC_E_ARG;
     }
-    HIP_TRY(tcsc::quantize_rows_i8(dX, M, K, static_cast<int8_t*>(dXq), dScale, static_cast<hipStream_t>(stream)));
+    HIP_TRY(tcsc::quantize_rows_i8(dX, xtype, nullptr, M, K, static_cast<int8_t*>(dXq), dScale,
+                                   static_cast<hipStream_t>(stream)));
     return TCSC_OK;
 }
 
+int tcsc_gpu_quantize_rows_i8(const float* dX, int M, int K, void* dXq, float* dScale, void* stream) {
+    return quantize_rows(TCSC_X_F32, dX, M, K, dXq, dScale, stream);
+}
+
 int tcsc_gpu_quantize_rows_i8_bf16(const void* dX_bf16, int M, int K, void* dXq, float* dScale, void* stream) {
-    if (M < 0 || K < 0) {
-        set_error("tcsc_gpu_quantize_rows_i8_bf16: bad arguments (M=%d K=%d)", M, K);
-        return TCSC_E_ARG;
-    }
-    if (M == 0) return TCSC_OK;
-    if (!dScale || (K > 0 && (!dX_bf16 || !dXq))) {
-        set_error("tcsc_gpu_quantize_rows_i8_bf16: NULL device pointer");
-        return TCSC_E_ARG;
-    }
-    HIP_TRY(tcsc::quantize_rows_i8_bf16(static_cast<const uint16_t*>(dX_bf16), M, K, static_cast<int8_t*>(dXq), dScale,
-                                        static_cast<hipStream_t>(stream)));
-    return TCSC_OK;
+    return quantize_rows(TCSC_X_BF16, dX_bf16, M, K, dXq, dScale, stream);
 }
 
 // ---- the quantizer fused into the int8 decode call -------------
@@ -2090,11 +2106,12 @@ int tcsc_gpu_quantize_rows_i8_bf16(const void* dX_bf16, int M, int K, void* dXq,
 // unprefetched pass of loads per block.
 static constexpr int kQFuseMaxM = 4;
 static constexpr long long kQFuseValues = 1LL << 23;
-static bool quant_fuse_pays(int M, int K, int N, int xtype) {
-    if (M < 1 || M > kQFuseMaxM || K < 1 || N < 1 || (xtype != TCSC_X_F32 && xtype != TCSC_X_BF16)) return false;
+// the form of the rule, here and for the norm (below): W M K <= values for 1 <= M <= max_M, W the launch's workgroups
+static bool fuse_pays(int M, int K, int N, int xtype, int max_M, long long values) {
+    if (M < 1 || M > max_M || K < 1 || N < 1 || (xtype != TCSC_X_F32 && xtype != TCSC_X_BF16)) return false;
     const int T = tcsc::decode_tiles_per_wg(M, N, 0);  // the grid on a 256-CU chip
     const long long wgs = (tcsc::w2_col_tiles(N) + T - 1) / T;
-    return wgs * M * K <= kQFuseValues;
+    return wgs * M * K <= values;
 }
 // $TCSC_QFUSE, read per call: 0 never fuses, 1 fuses on every decode route, unset the rule
 static int qfuse_knob() {
@@ -2107,7 +2124,7 @@ static int qfuse_knob() {
 // Every fused workgroup sweeps all of X three times (the squares, the maxima of
 // xn, the values it quantizes) where §20's sweeps it twice, and the launch it
 // saves is the norm form of the quantizer, which reads a row once and costs
-// little more than the plain one.  The rule has quant_fuse_pays's form, W M K <=
+// little more than the plain one.  The rule has the plain one's form (fuse_pays), W M K <=
 // kNFuseValues for 1 <= M <= kNFuseMaxM with W the launch's workgroups, and the
 // fit to profiles/norm_bench.json is the empty set: of the 40 decode points the
 // fused call was faster than the two launches beyond the run's spread only at a
@@ -2116,91 +2133,90 @@ static int qfuse_knob() {
 // W M K between those of the wins: no bound on W M K separates them, and the
 // rule must be 0 wherever the fused call lost.  So kNFuseMaxM = 0: the answer
 // is 0 everywhere, and $TCSC_QFUSE=1 is how the fused form runs.
-struct NormArgs {
-    const float* gamma;
-    float eps;
-};
 static constexpr int kNFuseMaxM = 0;
 static constexpr long long kNFuseValues = 0;
-static bool norm_fuse_pays(int M, int K, int N, int xtype) {
-    if (M < 1 || M > kNFuseMaxM || K < 1 || N < 1 || (xtype != TCSC_X_F32 && xtype != TCSC_X_BF16)) return false;
-    const int T = tcsc::decode_tiles_per_wg(M, N, 0);  // the grid on a 256-CU chip
-    const long long wgs = (tcsc::w2_col_tiles(N) + T - 1) / T;
-    return wgs * M * K <= kNFuseValues;
+static bool q8_fuse_pays(int M, int K, int N, int xtype, bool norm) {
+    return norm ? fuse_pays(M, K, N, xtype, kNFuseMaxM, kNFuseValues) : fuse_pays(M, K, N, xtype, kQFuseMaxM, kQFuseValues);
 }
 // the int8 route of M rows on the plan as it stands, and whether a q8 call of this X type (norm: a
 // q8_norm call) fuses on it
-static Route route_q8(const tcsc_gpu_plan* p, int M, int xtype, bool* fused, bool norm = false) {
+static Route route_q8(const tcsc_gpu_plan* p, int M, int xtype, bool* fused, bool norm) {
     const Route r = route_call(p, M, kI8, p->ws_bytes, RoutePins());
     *fused = false;
     if (r.path == TCSC_PATH_DECODE && has_decode(p, M, kI8)) {
         const int knob = qfuse_knob();
-        *fused = knob >= 0 ? knob == 1
-                           : norm ? norm_fuse_pays(M, p->rows, p->cols, xtype) : quant_fuse_pays(M, p->rows, p->cols, xtype);
+        *fused = knob >= 0 ? knob == 1 : q8_fuse_pays(M, p->rows, p->cols, xtype, norm);
     }
     return r;
 }
 
-int tcsc_gpu_quant_fuse_pays(int M, int K, int N, int xtype) { return quant_fuse_pays(M, K, N, xtype) ? 1 : 0; }
+int tcsc_gpu_quant_fuse_pays(int M, int K, int N, int xtype) { return q8_fuse_pays(M, K, N, xtype, false) ? 1 : 0; }
 
-int tcsc_gpu_launch_info_q8(const tcsc_gpu_plan* p, int M, int xtype, int* path, int* slices, int* fused) {
+static int launch_info_q8(const char* who, const tcsc_gpu_plan* p, int M, int xtype, bool norm, int* path, int* slices,
+                          int* fused) {
     if (!p || M < 0 || !path || !slices || !fused || (xtype != TCSC_X_F32 && xtype != TCSC_X_BF16)) {
-        set_error("tcsc_gpu_launch_info_q8: bad arguments (M=%d xtype=%d)", M, xtype);
+        set_error("%s: bad arguments (M=%d xtype=%d)", who, M, xtype);
         return TCSC_E_ARG;
     }
     bool f = false;
-    const Route r = route_q8(p, M, xtype, &f);
+    const Route r = route_q8(p, M, xtype, &f, norm);
     *path = r.path;
     *slices = r.slices;
     *fused = f ? 1 : 0;
     return TCSC_OK;
 }
 
-// `inner`: the name the int8 call behind an unfused route gives itself (null: tcsc_gpu_sgemm_i8)
-// `norm`: the RMSNorm of a tcsc_gpu_sgemm_q8_norm call in front of the quantizer (null: none)
-static int sgemm_q8_impl(const char* who, const char* inner, const tcsc_gpu_plan* p, const void* dX, int xtype, void* dXq,
-                         float* dScale, const float* dB, const YOut& y, int M, int ldy, int variant, float a,
-                         void* stream, const NormArgs* norm = nullptr) {
-    void* dY = y.Y;
-    if (!p || M < 0 || ldy < p->cols || !valid_variant(variant) || (xtype != TCSC_X_F32 && xtype != TCSC_X_BF16)) {
-        set_error("%s: bad arguments (M=%d ldy=%d variant=%d xtype=%d)", who, M, ldy, variant, xtype);
+int tcsc_gpu_launch_info_q8(const tcsc_gpu_plan* p, int M, int xtype, int* path, int* slices, int* fused) {
+    return launch_info_q8("tcsc_gpu_launch_info_q8", p, M, xtype, false, path, slices, fused);
+}
+
+// The q8 calls: c is the call as received (X of TCSC_X_F32 / TCSC_X_BF16; c.who names it), dXq the
+// caller's scratch for the quantized X and dScale where the row scales go.  `inner`: the name the
+// int8 call behind an unfused route gives itself (null: tcsc_gpu_sgemm_i8).  `norm`: the RMSNorm of a
+// tcsc_gpu_sgemm_q8_norm call in front of the quantizer (null: none).
+static int sgemm_q8_impl(const tcsc_gpu_plan* p, const Call& c, const char* inner, void* dXq, float* dScale,
+                         const RmsNorm* norm = nullptr) {
+    const char* who = c.who;
+    const int M = c.M, xtype = c.xtype;
+    if (!p || M < 0 || c.ldy < p->cols || !valid_variant(c.variant) || (xtype != TCSC_X_F32 && xtype != TCSC_X_BF16)) {
+        set_error("%s: bad arguments (M=%d ldy=%d variant=%d xtype=%d)", who, M, c.ldy, c.variant, xtype);
         return TCSC_E_ARG;
     }
     if (M == 0) return TCSC_OK;
-    if (!dScale || !dB || !dY || (!dX && p->rows > 0)) {
+    if (!dScale || !c.B || !c.y.Y || (!c.X && p->rows > 0)) {
         set_error("%s: NULL device pointer", who);
         return TCSC_E_ARG;
     }
     bool fused = false;
-    if (p->cols > 0 && refuse_out(who, route_q8(p, M, xtype, &fused, norm != nullptr).path, y, M)) return TCSC_E_ARG;
+    if (p->cols > 0 && refuse_out(who, route_q8(p, M, xtype, &fused, norm != nullptr).path, c.y, M)) return TCSC_E_ARG;
     if (!fused) {  // the quantizer into the caller's scratch, then the int8 call as it is: two or three launches
         if (!dXq && p->rows > 0) {
             set_error("%s: NULL dXq on a route that is not fused (M=%d)", who, M);
             return TCSC_E_ARG;
         }
-        const int rc = norm ? tcsc_gpu_quantize_rows_i8_norm(dX, xtype, norm->gamma, norm->eps, M, p->rows, dXq, dScale, stream)
-                       : xtype == TCSC_X_F32
-                           ? tcsc_gpu_quantize_rows_i8(static_cast<const float*>(dX), M, p->rows, dXq, dScale, stream)
-                           : tcsc_gpu_quantize_rows_i8_bf16(dX, M, p->rows, dXq, dScale, stream);
+        const int rc = norm ? tcsc_gpu_quantize_rows_i8_norm(c.X, xtype, norm->gamma, norm->eps, M, p->rows, dXq, dScale,
+                                                             c.stream)
+                            : quantize_rows(xtype, c.X, M, p->rows, dXq, dScale, c.stream);
         if (rc != TCSC_OK) return rc;
-        return sgemm_entry(p, dXq, kI8, dScale, dB, nullptr, M, ldy, variant, a, stream, &y, inner);
+        Call q = c;  // the same call on the quantized X
+        q.X = dXq;
+        q.xtype = kI8;
+        q.xscale = dScale;
+        q.who = inner;
+        return sgemm_entry(p, q);
     }
     const_cast<tcsc_gpu_plan*>(p)->staged_M = -1;  // as every tcsc_gpu_sgemm* does
-    if (norm) {
-        HIP_TRY(tcsc::decode_gemm_qn(dX, xtype == TCSC_X_BF16, norm->gamma, norm->eps, p->w2, p->rows, M, p->cols, dScale,
-                                     dB, y, ldy, is_prelu(variant), a, p->num_cus, static_cast<hipStream_t>(stream)));
-        return TCSC_OK;
-    }
-    HIP_TRY(tcsc::decode_gemm_q(dX, xtype == TCSC_X_BF16, p->w2, p->rows, M, p->cols, dScale, dB, y, ldy,
-                                is_prelu(variant), a, p->num_cus, static_cast<hipStream_t>(stream)));
+    HIP_TRY(tcsc::decode_gemm(tcsc::DecodeX{c.X, xtype, dScale, norm}, p->w2, p->rows, M, p->cols, i8_epi(c), p->num_cus,
+                              static_cast<hipStream_t>(c.stream)));
     return TCSC_OK;
 }
 
 // tcsc_gpu_sgemm_q8_out with (NULL, TCSC_Y_F32)
 int tcsc_gpu_sgemm_q8(const tcsc_gpu_plan* p, const void* dX, int xtype, void* dXq, float* dScale, const float* dB,
                       float* dY, int M, int ldy, int variant, float a, void* stream) {
-    return sgemm_q8_impl("tcsc_gpu_sgemm_q8", nullptr, p, dX, xtype, dXq, dScale, dB, YOut{dY, kYF32, nullptr}, M, ldy,
-                         variant, a, stream);
+    return sgemm_q8_impl(p, make_call(dX, xtype, nullptr, dB, YOut{dY, kYF32, nullptr}, M, ldy, variant, a, stream,
+                                      "tcsc_gpu_sgemm_q8"),
+                         nullptr, dXq, dScale);
 }
 
 int tcsc_gpu_sgemm_q8_out(const tcsc_gpu_plan* p, const void* dX, int xtype, void* dXq, float* dScale,
@@ -2209,8 +2225,8 @@ int tcsc_gpu_sgemm_q8_out(const tcsc_gpu_plan* p, const void* dX, int xtype, voi
     const char* who = "tcsc_gpu_sgemm_q8_out";
     const int rc = out_args(who, p, dB, dY, ytype);
     if (rc != TCSC_OK) return rc;
-    return sgemm_q8_impl(who, who, p, dX, xtype, dXq, dScale, dB, YOut{dY, ytype == TCSC_Y_BF16 ? kYBf16 : kYF32, dColScale},
-                         M, ldy, variant, a, stream);
+    return sgemm_q8_impl(p, make_call(dX, xtype, nullptr, dB, y_out(dY, ytype, dColScale), M, ldy, variant, a, stream, who),
+                         who, dXq, dScale);
 }
 
 // ---- RMSNorm in the int8 call ----------------------------------
@@ -2260,24 +2276,16 @@ int tcsc_gpu_quantize_rows_i8_norm(const void* dX, int xtype, const float* dGamm
         set_error("%s: NULL device pointer", who);
         return TCSC_E_ARG;
     }
-    HIP_TRY(tcsc::quantize_rows_i8_norm(dX, xtype == TCSC_X_BF16, dGamma, eps, M, K, static_cast<int8_t*>(dXq), dScale,
-                                        static_cast<hipStream_t>(stream)));
+    const RmsNorm norm{dGamma, eps};
+    HIP_TRY(tcsc::quantize_rows_i8(dX, xtype, &norm, M, K, static_cast<int8_t*>(dXq), dScale,
+                                   static_cast<hipStream_t>(stream)));
     return TCSC_OK;
 }
 
-int tcsc_gpu_norm_fuse_pays(int M, int K, int N, int xtype) { return norm_fuse_pays(M, K, N, xtype) ? 1 : 0; }
+int tcsc_gpu_norm_fuse_pays(int M, int K, int N, int xtype) { return q8_fuse_pays(M, K, N, xtype, true) ? 1 : 0; }
 
 int tcsc_gpu_launch_info_q8_norm(const tcsc_gpu_plan* p, int M, int xtype, int* path, int* slices, int* fused) {
-    if (!p || M < 0 || !path || !slices || !fused || (xtype != TCSC_X_F32 && xtype != TCSC_X_BF16)) {
-        set_error("tcsc_gpu_launch_info_q8_norm: bad arguments (M=%d xtype=%d)", M, xtype);
-        return TCSC_E_ARG;
-    }
-    bool f = false;
-    const Route r = route_q8(p, M, xtype, &f, true);
-    *path = r.path;
-    *slices = r.slices;
-    *fused = f ? 1 : 0;
-    return TCSC_OK;
+    return launch_info_q8("tcsc_gpu_launch_info_q8_norm", p, M, xtype, true, path, slices, fused);
 }
 
 int tcsc_gpu_sgemm_q8_norm(const tcsc_gpu_plan* p, const void* dX, int xtype, const float* dGamma, float eps, void* dXq,
@@ -2288,9 +2296,9 @@ int tcsc_gpu_sgemm_q8_norm(const tcsc_gpu_plan* p, const void* dX, int xtype, co
     if (rc != TCSC_OK) return rc;
     rc = out_args(who, p, dB, dY, ytype);
     if (rc != TCSC_OK) return rc;
-    const NormArgs norm{dGamma, eps};
-    return sgemm_q8_impl(who, who, p, dX, xtype, dXq, dScale, dB, YOut{dY, ytype == TCSC_Y_BF16 ? kYBf16 : kYF32, dColScale},
-                         M, ldy, variant, a, stream, &norm);
+    const RmsNorm norm{dGamma, eps};
+    return sgemm_q8_impl(p, make_call(dX, xtype, nullptr, dB, y_out(dY, ytype, dColScale), M, ldy, variant, a, stream, who),
+                         who, dXq, dScale, &norm);
 }
 
 int tcsc_gpu_workspace_bound_i8(int M, int K, int N, size_t* i8_bytes, size_t* f32_bytes) {
@@ -2314,7 +2322,8 @@ int tcsc_gpu_prepare_x(const tcsc_gpu_plan* p, const float* dX, int M, void* str
     int rc = ensure_workspace(p, M);
     if (rc != TCSC_OK) return rc;
     if (p) const_cast<tcsc_gpu_plan*>(p)->staged_M = -1;
-    rc = sgemm_ws(p, dX, nullptr, nullptr, M, 0, 0, 0.f, stream, p ? p->ws : nullptr, p ? p->ws_bytes : 0, 1);
+    rc = sgemm_ws(p, make_call(dX, kF32, nullptr, nullptr, YOut{}, M, 0, 0, 0.f, stream), p ? p->ws : nullptr,
+                  p ? p->ws_bytes : 0, 1, RoutePins(), nullptr);
     if (rc == TCSC_OK && p) const_cast<tcsc_gpu_plan*>(p)->staged_M = M;
     return rc;
 }
@@ -2330,7 +2339,8 @@ int tcsc_gpu_sgemm_prepared(const tcsc_gpu_plan* p, const float* dB, float* dY, 
                   p->staged_M < 0 ? "no X is staged" : "the staged X has another M");
         return TCSC_E_ARG;
     }
-    return sgemm_ws(p, nullptr, dB, dY, M, ldy, variant, a, stream, p ? p->ws : nullptr, p ? p->ws_bytes : 0, 2);
+    return sgemm_ws(p, make_call(nullptr, kF32, nullptr, dB, YOut{dY, kYF32, nullptr}, M, ldy, variant, a, stream),
+                    p ? p->ws : nullptr, p ? p->ws_bytes : 0, 2, RoutePins(), nullptr);
 }
 
 // The two calls (counts, then fill) share the tile offsets: the first call

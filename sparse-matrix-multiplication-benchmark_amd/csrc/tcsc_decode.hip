@@ -28,12 +28,12 @@
 #include "tcsc_internal.h"
 #include "tcsc_norm.h"
 #include "tcsc_quant.h"
+#include "tcsc_w2.h"
 #include "tcsc_xsrc.h"
 
 namespace tcsc {
 namespace {
 
-typedef int i32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 // Waves per workgroup (the K split) and, for A/B builds, a fixed number of
@@ -289,6 +289,65 @@ __global__ void __launch_bounds__(256) k_w2_col_start(const int* __restrict__ of
 // K tails and column tails need nothing in the tile loop: the image's padding
 // is weight 0 (code 1, cancelled by the row sums: X is zero there anyway) and
 // columns >= N are computed and not stored.
+//
+// What k_decode8 and k_decode8q (below) share, each written once:
+
+// The image pointers of a workgroup's T tiles: this wave's 16 bytes of tile
+// (t, kb) are at wp[t] + 64 * kb (16-B units).  A workgroup's last tiles past
+// the matrix read the last tile again (uniform) and are not stored.
+template <int T>
+__device__ __forceinline__ void decode_tile_ptrs(const uint32_t* __restrict__ W2, int t0, int ntiles, int nkb, int lane,
+                                                 const u32x4* (&wp)[T]) {
+#pragma unroll
+    for (int t = 0; t < T; ++t)
+        wp[t] = reinterpret_cast<const u32x4*>(W2) + (size_t)min(t0 + t, ntiles - 1) * nkb * 64 + lane;
+}
+template <int T>
+__device__ __forceinline__ void decode_load_w(const u32x4* const (&wp)[T], int kb, u32x4 (&p)[T]) {
+#pragma unroll
+    for (int t = 0; t < T; ++t) p[t] = __builtin_nontemporal_load(wp[t] + (size_t)kb * 64);
+}
+
+// One 256-k block: per 64-k step one MFMA against a fragment of ones (the row
+// sums) and one per tile against the tile's codes (w2_codes, tcsc_w2.h).
+template <int T>
+__device__ __forceinline__ void decode_block(const i32x4 (&xf)[4], const u32x4 (&p)[T], i32x4 (&acc)[T], i32x4& rs) {
+    const i32x4 ones = i32x4{0x01010101, 0x01010101, 0x01010101, 0x01010101};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        rs = __builtin_amdgcn_mfma_i32_16x16x64_i8(xf[i], ones, rs, 0, 0, 0);
+#pragma unroll
+        for (int t = 0; t < T; ++t) acc[t] = __builtin_amdgcn_mfma_i32_16x16x64_i8(xf[i], w2_codes(p[t][i]), acc[t], 0, 0, 0);
+    }
+}
+
+// The tail.  S of this wave's K share is parked in `red` in the accumulator
+// layout (register r of lane l: row 4 (l >> 4) + r, column l & 15; a wave
+// without blocks adds zeros), then one thread per output -- a row's 16 T
+// columns on consecutive threads -- adds the WAVES shares and stores
+// i8_out(S, row_scale(row), ...).  The kernels differ in WAVES and in where
+// the row scale comes from.  Every thread of the workgroup calls this.
+template <int WAVES, int T, bool PRELU, typename TY, typename RowScale>
+__device__ __forceinline__ void decode_reduce_store(int* red, const i32x4 (&acc)[T], const i32x4& rs, int wave, int lane,
+                                                    int t0, int M, int N, RowScale row_scale,
+                                                    const float* __restrict__ cscale, const float* __restrict__ bias,
+                                                    TY* __restrict__ Y, int ldy, float a) {
+#pragma unroll
+    for (int t = 0; t < T; ++t)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) red[(wave * T + t) * 256 + r * 64 + lane] = acc[t][r] - rs[r];
+    __syncthreads();
+    for (int o = threadIdx.x; o < T * 256; o += WAVES * 64) {
+        const int row = o / (16 * T), cg = o % (16 * T), t = cg >> 4, c = cg & 15;
+        const int col = (t0 + t) * kW2Cols + c;
+        if (row >= M || col >= N) continue;
+        int S = 0;
+#pragma unroll
+        for (int w = 0; w < WAVES; ++w) S += red[(w * T + t) * 256 + (row & 3) * 64 + (row >> 2) * 16 + c];
+        I8Y<TY>::put(Y + (size_t)row * ldy + col, i8_out<PRELU>(S, row_scale(row), i8_cscale(cscale, col), bias[col], a));
+    }
+}
+
 template <int T, bool ALIGNED, bool PRELU, typename TY>
 __global__ void __launch_bounds__(kDecWaves * 64) k_decode8(const int8_t* __restrict__ X,
                                                              const uint32_t* __restrict__ W2, int K, int M, int N,
@@ -304,16 +363,11 @@ __global__ void __launch_bounds__(kDecWaves * 64) k_decode8(const int8_t* __rest
     const bool row_ok = xr < M;
     const int8_t* xrow = X + (size_t)(row_ok ? xr : 0) * K;
 
-    // this wave's 16 bytes of tile (t, kb) are at wp[t] + 64 * kb (16-B units); a workgroup's last
-    // tiles past the matrix read the last tile again (uniform) and are not stored
     const u32x4* wp[T];
-#pragma unroll
-    for (int t = 0; t < T; ++t)
-        wp[t] = reinterpret_cast<const u32x4*>(W2) + (size_t)min(t0 + t, ntiles - 1) * nkb * 64 + lane;
+    decode_tile_ptrs<T>(W2, t0, ntiles, nkb, lane, wp);
 
     auto load = [&](int kb, i32x4 (&xf)[4], u32x4 (&p)[T]) {
-#pragma unroll
-        for (int t = 0; t < T; ++t) p[t] = __builtin_nontemporal_load(wp[t] + (size_t)kb * 64);
+        decode_load_w<T>(wp, kb, p);
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int k = kW2Blk * kb + 64 * i + 16 * kq;
@@ -335,7 +389,6 @@ __global__ void __launch_bounds__(kDecWaves * 64) k_decode8(const int8_t* __rest
     i32x4 acc[T], rs = i32x4{0, 0, 0, 0};
 #pragma unroll
     for (int t = 0; t < T; ++t) acc[t] = i32x4{0, 0, 0, 0};
-    const i32x4 ones = i32x4{0x01010101, 0x01010101, 0x01010101, 0x01010101};
 
     i32x4 xf[4], xn[4];
     u32x4 p[T], pn[T];
@@ -344,17 +397,7 @@ __global__ void __launch_bounds__(kDecWaves * 64) k_decode8(const int8_t* __rest
     while (kb < nkb) {  // uniform
         const int nx = kb + kDecWaves;
         if (nx < nkb) load(nx, xn, pn);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            rs = __builtin_amdgcn_mfma_i32_16x16x64_i8(xf[i], ones, rs, 0, 0, 0);
-#pragma unroll
-            for (int t = 0; t < T; ++t) {
-                const uint32_t q = p[t][i];
-                const i32x4 b = i32x4{(int)(q & 0x03030303u), (int)((q >> 2) & 0x03030303u),
-                                      (int)((q >> 4) & 0x03030303u), (int)((q >> 6) & 0x03030303u)};
-                acc[t] = __builtin_amdgcn_mfma_i32_16x16x64_i8(xf[i], b, acc[t], 0, 0, 0);
-            }
-        }
+        decode_block<T>(xf, p, acc, rs);
 #pragma unroll
         for (int i = 0; i < 4; ++i) xf[i] = xn[i];
 #pragma unroll
@@ -362,37 +405,8 @@ __global__ void __launch_bounds__(kDecWaves * 64) k_decode8(const int8_t* __rest
         kb = nx;
     }
 
-    // S of this wave's K share, in the accumulator layout (register r of lane l: row 4 (l >> 4) + r,
-    // column l & 15); a wave without blocks adds zeros
-#pragma unroll
-    for (int t = 0; t < T; ++t)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) red[(wave * T + t) * 256 + r * 64 + lane] = acc[t][r] - rs[r];
-    __syncthreads();
-    // one thread per output, a row's 16 T columns on consecutive threads
-    for (int o = threadIdx.x; o < T * 256; o += kDecWaves * 64) {
-        const int row = o / (16 * T), cg = o % (16 * T), t = cg >> 4, c = cg & 15;
-        const int col = (t0 + t) * kW2Cols + c;
-        if (row >= M || col >= N) continue;
-        int S = 0;
-#pragma unroll
-        for (int w = 0; w < kDecWaves; ++w) S += red[(w * T + t) * 256 + (row & 3) * 64 + (row >> 2) * 16 + c];
-        const float sc = scale ? scale[row] : 1.0f;
-        I8Y<TY>::put(Y + (size_t)row * ldy + col, i8_out<PRELU>(S, sc, i8_cscale(cscale, col), bias[col], a));
-    }
-}
-
-template <int T, bool ALIGNED, typename TY>
-void launch_decode(const int8_t* X, const uint32_t* w2, int K, int M, int N, const float* scale, const float* cscale,
-                   const float* B, TY* Y, int ldy, bool prelu, float a, hipStream_t st) {
-    const int ntiles = w2_col_tiles(N), nkb = w2_kblocks(K);
-    const dim3 grid((ntiles + T - 1) / T), block(kDecWaves * 64);
-    if (prelu)
-        hipLaunchKernelGGL((k_decode8<T, ALIGNED, true, TY>), grid, block, 0, st, X, w2, K, M, N, nkb, ntiles, scale,
-                           cscale, B, Y, ldy, a);
-    else
-        hipLaunchKernelGGL((k_decode8<T, ALIGNED, false, TY>), grid, block, 0, st, X, w2, K, M, N, nkb, ntiles, scale,
-                           cscale, B, Y, ldy, a);
+    decode_reduce_store<kDecWaves, T, PRELU>(
+        red, acc, rs, wave, lane, t0, M, N, [&](int row) { return scale ? scale[row] : 1.0f; }, cscale, bias, Y, ldy, a);
 }
 
 // k_decode8q: k_quant_rows_i8 and k_decode8 in one launch, for
@@ -541,9 +555,7 @@ __global__ void __launch_bounds__(kQWaves * 64) k_decode8q(const TX* __restrict_
     const int xr = lane & 15, kq = lane >> 4;
     const bool row_ok = xr < M;
     const u32x4* wp[T];
-#pragma unroll
-    for (int t = 0; t < T; ++t)
-        wp[t] = reinterpret_cast<const u32x4*>(W2) + (size_t)min(t0 + t, ntiles - 1) * nkb * 64 + lane;
+    decode_tile_ptrs<T>(W2, t0, ntiles, nkb, lane, wp);
     unsigned char* qw = smem + wave * kQWaveBytes;
 
     // the lane's four values of rows j0 .. j0 + 3 of block kb, as raw bits (fp32: one per dword; bf16: two)
@@ -641,22 +653,17 @@ __global__ void __launch_bounds__(kQWaves * 64) k_decode8q(const TX* __restrict_
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
     };
-    auto load_w = [&](int kb, u32x4 (&p)[T]) {
-#pragma unroll
-        for (int t = 0; t < T; ++t) p[t] = __builtin_nontemporal_load(wp[t] + (size_t)kb * 64);
-    };
 
     i32x4 acc[T], rs = i32x4{0, 0, 0, 0};
 #pragma unroll
     for (int t = 0; t < T; ++t) acc[t] = i32x4{0, 0, 0, 0};
-    const i32x4 ones = i32x4{0x01010101, 0x01010101, 0x01010101, 0x01010101};
 
     i32x4 xf[4];
     u32x4 p[T], pn[T];
     Raw raw[4];
     int kb = wave;
     if (kb < nkb) {
-        load_w(kb, p);
+        decode_load_w<T>(wp, kb, p);
         load_gamma(kb);
         load_rows(kb, 0, raw);
         store_rows(kb, 0, raw);
@@ -666,21 +673,11 @@ __global__ void __launch_bounds__(kQWaves * 64) k_decode8q(const TX* __restrict_
     while (kb < nkb) {  // uniform
         const int nx = kb + kQWaves;
         if (nx < nkb) {
-            load_w(nx, pn);
+            decode_load_w<T>(wp, nx, pn);
             load_gamma(nx);  // this block's staging is done: its gamma is free
             load_rows(nx, 0, raw);
         }
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            rs = __builtin_amdgcn_mfma_i32_16x16x64_i8(xf[i], ones, rs, 0, 0, 0);
-#pragma unroll
-            for (int t = 0; t < T; ++t) {
-                const uint32_t q = p[t][i];
-                const i32x4 b = i32x4{(int)(q & 0x03030303u), (int)((q >> 2) & 0x03030303u),
-                                      (int)((q >> 4) & 0x03030303u), (int)((q >> 6) & 0x03030303u)};
-                acc[t] = __builtin_amdgcn_mfma_i32_16x16x64_i8(xf[i], b, acc[t], 0, 0, 0);
-            }
-        }
+        decode_block<T>(xf, p, acc, rs);
         if (nx < nkb) {  // this block's fragments are in registers: its staging block is free
             store_rows(nx, 0, raw);
             stage_rest(nx, raw);
@@ -692,91 +689,9 @@ __global__ void __launch_bounds__(kQWaves * 64) k_decode8q(const TX* __restrict_
     }
 
     __syncthreads();  // every wave is done with its staging block: the partial sums take the memory
-    int* red = reinterpret_cast<int*>(smem);
-#pragma unroll
-    for (int t = 0; t < T; ++t)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) red[(wave * T + t) * 256 + r * 64 + lane] = acc[t][r] - rs[r];
-    __syncthreads();
-    for (int o = tid; o < T * 256; o += kThreads) {
-        const int row = o / (16 * T), cg = o % (16 * T), t = cg >> 4, c = cg & 15;
-        const int col = (t0 + t) * kW2Cols + c;
-        if (row >= M || col >= N) continue;
-        int S = 0;
-#pragma unroll
-        for (int w = 0; w < kQWaves; ++w) S += red[(w * T + t) * 256 + (row & 3) * 64 + (row >> 2) * 16 + c];
-        I8Y<TY>::put(Y + (size_t)row * ldy + col,
-                     i8_out<PRELU>(S, s_scale[row], i8_cscale(cscale, col), bias[col], a));
-    }
-}
-
-template <typename TX, int T, bool ALIGNED, typename TY>
-void launch_decode_q(const TX* X, const uint32_t* w2, int K, int M, int N, float* scale_out, const float* cscale,
-                     const float* B, TY* Y, int ldy, bool prelu, float a, hipStream_t st) {
-    const int ntiles = w2_col_tiles(N), nkb = w2_kblocks(K);
-    const dim3 grid((ntiles + T - 1) / T), block(kQWaves * 64);
-    if (prelu)
-        hipLaunchKernelGGL((k_decode8q<TX, T, ALIGNED, true, TY>), grid, block, 0, st, X, w2, K, M, N, nkb, ntiles,
-                           scale_out, cscale, B, Y, ldy, a);
-    else
-        hipLaunchKernelGGL((k_decode8q<TX, T, ALIGNED, false, TY>), grid, block, 0, st, X, w2, K, M, N, nkb, ntiles,
-                           scale_out, cscale, B, Y, ldy, a);
-}
-
-// the norm form of k_decode8q: the same grid and tiles per workgroup
-template <typename TX, int T, bool ALIGNED, typename TY>
-void launch_decode_qn(const TX* X, const float* gamma, float eps, const uint32_t* w2, int K, int M, int N,
-                      float* scale_out, const float* cscale, const float* B, TY* Y, int ldy, bool prelu, float a,
-                      hipStream_t st) {
-    const int ntiles = w2_col_tiles(N), nkb = w2_kblocks(K);
-    const dim3 grid((ntiles + T - 1) / T), block(kQWaves * 64);
-    if (prelu)
-        hipLaunchKernelGGL((k_decode8q<TX, T, ALIGNED, true, TY, true>), grid, block, 0, st, X, w2, K, M, N, nkb, ntiles,
-                           scale_out, cscale, B, Y, ldy, a, gamma, eps);
-    else
-        hipLaunchKernelGGL((k_decode8q<TX, T, ALIGNED, false, TY, true>), grid, block, 0, st, X, w2, K, M, N, nkb, ntiles,
-                           scale_out, cscale, B, Y, ldy, a, gamma, eps);
-}
-
-template <typename TX, typename TY>
-void decode_qn_typed(const TX* X, const float* gamma, float eps, const uint32_t* w2, int K, int M, int N,
-                     float* scale_out, const float* cscale, const float* B, TY* Y, int ldy, bool prelu, float a,
-                     int num_cus, hipStream_t st) {
-    const bool aligned = XSrc<TX>::vec_ok(X, K);
-    const int T = decode_tiles_per_wg(M, N, num_cus);
-#define TCSC_DECODE_QN_LAUNCH(TT)                                                                                  \
-    if (aligned)                                                                                                   \
-        launch_decode_qn<TX, TT, true>(X, gamma, eps, w2, K, M, N, scale_out, cscale, B, Y, ldy, prelu, a, st);    \
-    else                                                                                                           \
-        launch_decode_qn<TX, TT, false>(X, gamma, eps, w2, K, M, N, scale_out, cscale, B, Y, ldy, prelu, a, st)
-    if (T == 4) {
-        TCSC_DECODE_QN_LAUNCH(4);
-    } else if (T == 2) {
-        TCSC_DECODE_QN_LAUNCH(2);
-    } else {
-        TCSC_DECODE_QN_LAUNCH(1);
-    }
-#undef TCSC_DECODE_QN_LAUNCH
-}
-
-template <typename TX, typename TY>
-void decode_q_typed(const TX* X, const uint32_t* w2, int K, int M, int N, float* scale_out, const float* cscale,
-                    const float* B, TY* Y, int ldy, bool prelu, float a, int num_cus, hipStream_t st) {
-    const bool aligned = XSrc<TX>::vec_ok(X, K);
-    const int T = decode_tiles_per_wg(M, N, num_cus);
-#define TCSC_DECODE_Q_LAUNCH(TT)                                                                        \
-    if (aligned)                                                                                        \
-        launch_decode_q<TX, TT, true>(X, w2, K, M, N, scale_out, cscale, B, Y, ldy, prelu, a, st);      \
-    else                                                                                                \
-        launch_decode_q<TX, TT, false>(X, w2, K, M, N, scale_out, cscale, B, Y, ldy, prelu, a, st)
-    if (T == 4) {
-        TCSC_DECODE_Q_LAUNCH(4);
-    } else if (T == 2) {
-        TCSC_DECODE_Q_LAUNCH(2);
-    } else {
-        TCSC_DECODE_Q_LAUNCH(1);
-    }
-#undef TCSC_DECODE_Q_LAUNCH
+    decode_reduce_store<kQWaves, T, PRELU>(
+        reinterpret_cast<int*>(smem), acc, rs, wave, lane, t0, M, N, [&](int row) { return s_scale[row]; }, cscale, bias, Y,
+        ldy, a);
 }
 
 }  // namespace
@@ -856,82 +771,53 @@ int decode_tiles_per_wg(int M, int N, int num_cus) {
     return T;
 }
 
-template <typename TY>
-static void decode_typed(const int8_t* X, const uint32_t* w2, int K, int M, int N, const float* scale,
-                         const float* cscale, const float* B, TY* Y, int ldy, bool prelu, float a, int num_cus,
-                         hipStream_t st) {
-    const bool aligned = K % 16 == 0 && (reinterpret_cast<uintptr_t>(X) & 15) == 0;
-    const int T = decode_tiles_per_wg(M, N, num_cus);
-#define TCSC_DECODE_LAUNCH(TT)                                                                \
-    if (aligned)                                                                              \
-        launch_decode<TT, true>(X, w2, K, M, N, scale, cscale, B, Y, ldy, prelu, a, st);      \
-    else                                                                                      \
-        launch_decode<TT, false>(X, w2, K, M, N, scale, cscale, B, Y, ldy, prelu, a, st)
-    if (T == 4) {
-        TCSC_DECODE_LAUNCH(4);
-    } else if (T == 2) {
-        TCSC_DECODE_LAUNCH(2);
-    } else {
-        TCSC_DECODE_LAUNCH(1);
-    }
-#undef TCSC_DECODE_LAUNCH
-}
-
-hipError_t decode_gemm(const int8_t* X, const uint32_t* w2, int K, int M, int N, const float* scale, const float* B,
-                       const YOut& y, int ldy, bool prelu, float a, int num_cus, hipStream_t st) {
-    if (M < 1 || M > kDecodeMaxM || K < 1 || K >= kDecodeMaxK || N < 1 || !X || !w2 || !B || !y.Y || ldy < N)
+// The one decode launch (tcsc_internal.h).  Everything a kernel is instantiated
+// over -- Y type, tiles per workgroup, ALIGNED, PRELU, and for an X the launch
+// quantizes its type and the norm -- becomes a template argument here and
+// nowhere else; x and e are unpacked into the kernels' parameter lists.
+hipError_t decode_gemm(const DecodeX& x, const uint32_t* w2, int K, int M, int N, const I8Epi& e, int num_cus,
+                       hipStream_t st) {
+    const bool quant = x.xtype != kI8;
+    if (M < 1 || M > kDecodeMaxM || K < 1 || K >= kDecodeMaxK || N < 1 || !x.X || !w2 || (quant && !x.scale_out) || !e.B ||
+        !e.y.Y || e.ldy < N)
         return hipErrorInvalidValue;
-    if (y.ytype == kYBf16)
-        decode_typed(X, w2, K, M, N, scale, y.cscale, B, static_cast<uint16_t*>(y.Y), ldy, prelu, a, num_cus, st);
-    else
-        decode_typed(X, w2, K, M, N, scale, y.cscale, B, static_cast<float*>(y.Y), ldy, prelu, a, num_cus, st);
-    return hipGetLastError();
-}
-
-hipError_t decode_gemm_q(const void* X, bool bf16, const uint32_t* w2, int K, int M, int N, float* scale_out,
-                         const float* B, const YOut& y, int ldy, bool prelu, float a, int num_cus, hipStream_t st) {
-    if (M < 1 || M > kDecodeMaxM || K < 1 || K >= kDecodeMaxK || N < 1 || !X || !w2 || !scale_out || !B || !y.Y ||
-        ldy < N)
-        return hipErrorInvalidValue;
-#define TCSC_DECODE_Q_TYPED(TX, TY)                                                                                  \
-    decode_q_typed(static_cast<const TX*>(X), w2, K, M, N, scale_out, y.cscale, B, static_cast<TY*>(y.Y), ldy, prelu, \
-                   a, num_cus, st)
-    if (bf16) {
-        if (y.ytype == kYBf16)
-            TCSC_DECODE_Q_TYPED(uint16_t, uint16_t);
-        else
-            TCSC_DECODE_Q_TYPED(uint16_t, float);
-    } else {
-        if (y.ytype == kYBf16)
-            TCSC_DECODE_Q_TYPED(float, uint16_t);
-        else
-            TCSC_DECODE_Q_TYPED(float, float);
-    }
-#undef TCSC_DECODE_Q_TYPED
-    return hipGetLastError();
-}
-
-hipError_t decode_gemm_qn(const void* X, bool bf16, const float* gamma, float eps, const uint32_t* w2, int K, int M,
-                          int N, float* scale_out, const float* B, const YOut& y, int ldy, bool prelu, float a,
-                          int num_cus, hipStream_t st) {
-    if (M < 1 || M > kDecodeMaxM || K < 1 || K >= kDecodeMaxK || N < 1 || !X || !w2 || !scale_out || !B || !y.Y ||
-        ldy < N)
-        return hipErrorInvalidValue;
-#define TCSC_DECODE_QN_TYPED(TX, TY)                                                                                 \
-    decode_qn_typed(static_cast<const TX*>(X), gamma, eps, w2, K, M, N, scale_out, y.cscale, B, static_cast<TY*>(y.Y), \
-                    ldy, prelu, a, num_cus, st)
-    if (bf16) {
-        if (y.ytype == kYBf16)
-            TCSC_DECODE_QN_TYPED(uint16_t, uint16_t);
-        else
-            TCSC_DECODE_QN_TYPED(uint16_t, float);
-    } else {
-        if (y.ytype == kYBf16)
-            TCSC_DECODE_QN_TYPED(float, uint16_t);
-        else
-            TCSC_DECODE_QN_TYPED(float, float);
-    }
-#undef TCSC_DECODE_QN_TYPED
+    const int ntiles = w2_col_tiles(N), nkb = w2_kblocks(K), tiles = decode_tiles_per_wg(M, N, num_cus);
+    const dim3 grid((ntiles + tiles - 1) / tiles);
+    const bool aligned = x.xtype == kI8    ? XSrc<int8_t>::vec_ok(static_cast<const int8_t*>(x.X), K)
+                         : x.xtype == kBf16 ? XSrc<uint16_t>::vec_ok(static_cast<const uint16_t*>(x.X), K)
+                                            : XSrc<float>::vec_ok(static_cast<const float*>(x.X), K);
+    auto with_tiles = [&](auto&& f) {
+        if (tiles == 4) return f(std::integral_constant<int, 4>{});
+        if (tiles == 2) return f(std::integral_constant<int, 2>{});
+        return f(std::integral_constant<int, 1>{});
+    };
+    with_elem(e.y.ytype == kYBf16, [&](auto ty) {
+        using TY = typename decltype(ty)::type;
+        TY* Y = static_cast<TY*>(e.y.Y);
+        with_tiles([&](auto t) {
+            with_bool(aligned, [&](auto al) {
+                with_bool(e.prelu, [&](auto pr) {
+                    constexpr int T = decltype(t)::value;
+                    constexpr bool AL = decltype(al)::value, PR = decltype(pr)::value;
+                    if (!quant) {
+                        hipLaunchKernelGGL((k_decode8<T, AL, PR, TY>), grid, dim3(kDecWaves * 64), 0, st,
+                                           static_cast<const int8_t*>(x.X), w2, K, M, N, nkb, ntiles, e.rscale, e.y.cscale,
+                                           e.B, Y, e.ldy, e.a);
+                        return;
+                    }
+                    with_elem(x.xtype == kBf16, [&](auto tx) {
+                        using TX = typename decltype(tx)::type;
+                        with_bool(x.norm != nullptr, [&](auto nm) {
+                            hipLaunchKernelGGL((k_decode8q<TX, T, AL, PR, TY, decltype(nm)::value>), grid,
+                                               dim3(kQWaves * 64), 0, st, static_cast<const TX*>(x.X), w2, K, M, N, nkb,
+                                               ntiles, x.scale_out, e.y.cscale, e.B, Y, e.ldy, e.a,
+                                               x.norm ? x.norm->gamma : nullptr, x.norm ? x.norm->eps : 0.0f);
+                        });
+                    });
+                });
+            });
+        });
+    });
     return hipGetLastError();
 }
 

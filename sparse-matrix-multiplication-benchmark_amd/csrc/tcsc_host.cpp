@@ -58,6 +58,11 @@ using tcsc::set_error;
 using tcsc::sgemm_ws;
 using tcsc::tcsc_fingerprint;
 
+// the fp32 call of M rows that every launch of this layer is
+static tcsc::Call f32_call(const float* dX, const float* dB, float* dY, int M, int ldy, int variant, float a, void* stream) {
+    return tcsc::make_call(dX, tcsc::kF32, nullptr, dB, tcsc::YOut{dY, tcsc::kYF32, nullptr}, M, ldy, variant, a, stream);
+}
+
 // One column block of W on one device (column axis), or one device's plan of
 // the whole W (row axis: the calls split M over the devices instead).
 struct Shard {
@@ -631,8 +636,8 @@ int run_bands(int dev, DevState& ds, const Shard& sh, int m0, int M, int nb, con
         // the whole job's path (host_bands: the gather) and K split: a band of bm rows
         // chooses neither for itself, and ds.ws is sized for exactly this
         Route route;
-        if ((rc = sgemm_ws(p, xb, ds.b, ds.y + (size_t)r0 * nc, r1 - r0, nc, variant, a, st, ds.ws, ds.ws_cap, 0, pin,
-                           &route)) != TCSC_OK)
+        if ((rc = sgemm_ws(p, f32_call(xb, ds.b, ds.y + (size_t)r0 * nc, r1 - r0, nc, variant, a, st), ds.ws, ds.ws_cap, 0,
+                           pin, &route)) != TCSC_OK)
             return finish(rc);
         sh.ran_path = route.path;
         sh.ran_slices = route.slices;
@@ -711,8 +716,8 @@ int run_device(int dev, const std::vector<Job>& jobs, const float* X, const floa
         pin.path = job.path;
         pin.slices = job.slices;
         Route route;
-        if ((rc = sgemm_ws(sh->plan, ds.x, ds.b, ds.y, M, nc, variant, a, st, ds.ws, ds.ws_cap, 0, pin, &route)) !=
-            TCSC_OK)
+        if ((rc = sgemm_ws(sh->plan, f32_call(ds.x, ds.b, ds.y, M, nc, variant, a, st), ds.ws, ds.ws_cap, 0, pin,
+                           &route)) != TCSC_OK)
             return rc;
         sh->ran_path = route.path;
         sh->ran_slices = route.slices;

@@ -35,21 +35,32 @@ __device__ __forceinline__ uint16_t i8_bf16(float v) {
 }
 
 // The Y element of a call: float (TCSC_Y_F32) or bf16 bits (TCSC_Y_BF16).
-// put() stores one element; every store of either type goes through it or
-// through the 4-column forms below, so a 2-byte element is never written as
-// half of a wider store it does not wholly own.
+// put() stores one element and put4_nt() a lane's four adjacent columns as one
+// non-temporal store (16 B of floats, 8 B of bf16; dst aligned to four
+// elements): every store of either type goes through one of them, so a 2-byte
+// element is never written as half of a wider store it does not wholly own.
 template <typename TY>
 struct I8Y;
 template <>
 struct I8Y<float> {
     static __device__ __forceinline__ void put(float* dst, float v) { *dst = v; }
     static __device__ __forceinline__ void put_nt(float* dst, float v) { __builtin_nontemporal_store(v, dst); }
+    static __device__ __forceinline__ void put4_nt(float* dst, float v0, float v1, float v2, float v3) {
+        typedef float f32x4 __attribute__((ext_vector_type(4)));
+        __builtin_nontemporal_store(f32x4{v0, v1, v2, v3}, reinterpret_cast<f32x4*>(dst));
+    }
 };
 template <>
 struct I8Y<uint16_t> {
     static __device__ __forceinline__ void put(uint16_t* dst, float v) { *dst = i8_bf16(v); }
     static __device__ __forceinline__ void put_nt(uint16_t* dst, float v) {
         __builtin_nontemporal_store(i8_bf16(v), dst);
+    }
+    static __device__ __forceinline__ void put4_nt(uint16_t* dst, float v0, float v1, float v2, float v3) {
+        typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+        const u32x2 o = {(uint32_t)i8_bf16(v0) | (uint32_t)i8_bf16(v1) << 16,
+                         (uint32_t)i8_bf16(v2) | (uint32_t)i8_bf16(v3) << 16};
+        __builtin_nontemporal_store(o, reinterpret_cast<u32x2*>(dst));
     }
 };
 

@@ -5,6 +5,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 namespace tcsc {
 
 // ---- geometry of the gather kernel (DESIGN.md "Kernel K1") ---------------
@@ -210,6 +212,50 @@ struct YOut {
     bool plain() const { return ytype == kYF32 && !cscale; }  // what every route can write
     YOut rows_on(size_t r0, int ldy) const { return YOut{static_cast<char*>(Y) + r0 * ldy * elem(), ytype, cscale}; }
 };
+// What the epilogue of every int8 kernel needs (i8_out, tcsc_i8_out.h), from the
+// API layer to the one place that launches, which unpacks it into the kernel's
+// parameter list: Y[m, j] = act(fl(fl(fl(float(S) * rscale[m]) * y.cscale[j]) + B[j]))
+// in y's type.  A new epilogue input is one field here.
+struct I8Epi {
+    const float* rscale = nullptr;  // the row scales of an int8 X (null: ones); a launch that quantizes uses its own
+    const float* B = nullptr;
+    YOut y;
+    int ldy = 0;  // in y's elements
+    bool prelu = false;
+    float a = 0.f;
+};
+// The RMSNorm in front of a quantizer; gamma null = all ones
+struct RmsNorm {
+    const float* gamma = nullptr;
+    float eps = 0.f;
+};
+// The X of a decode launch: M x K of xtype, any alignment, read in place.  kI8:
+// quantized already (its row scales are the epilogue's).  kF32 / kBf16: the
+// launch quantizes it, after `norm` if one is given, and writes the
+// quantizer's scale of row m to scale_out[m].
+struct DecodeX {
+    const void* X = nullptr;
+    int xtype = kI8;
+    float* scale_out = nullptr;
+    const RmsNorm* norm = nullptr;
+};
+
+// A run-time bool, or the choice between fp32 and bf16 elements, as a
+// compile-time argument of a generic lambda: f(std::true_type) or
+// f(std::false_type); f(ElemTag<uint16_t>) or f(ElemTag<float>).  The launchers
+// nest these to write a dispatch over template parameters once.
+template <typename T>
+struct ElemTag {
+    using type = T;
+};
+template <typename F>
+auto with_bool(bool b, F&& f) {
+    return b ? f(std::true_type{}) : f(std::false_type{});
+}
+template <typename F>
+auto with_elem(bool bf16, F&& f) {
+    return bf16 ? f(ElemTag<uint16_t>{}) : f(ElemTag<float>{});
+}
 
 struct GemmArgs {
     const void* X = nullptr;        // M x K of xtype; the transpose converts it into the fp32 X^T and
@@ -443,23 +489,20 @@ hipError_t mfma8_pack_x(const int8_t* X, int M, int K, int8_t* x8, int ld8, hipS
 // column's sum of |w| >= 2^24
 hipError_t mfma8_build_w8(const uint16_t* wt, int ncols, int K, int ldw, int8_t* w8, int ld8, int* bad,
                           hipStream_t st);
-// k_gemm8 (+ k_reduce_i8 when K is split): Y = act(fl(fl(fl(float(S) * scale[m])
-// * cscale[j]) + B[j])) in y's type, S the exact i32 sum; a null scale = all ones
-hipError_t mfma8_gemm(const int8_t* x8, const int8_t* w8, int ld8, int K, int M, int N, const float* scale,
-                      const float* B, const YOut& y, int ldy, bool prelu, float a, int* slabs, size_t slab_bytes,
-                      hipStream_t st);
-// k_quant_rows_i8: per-row absmax quantization (tcsc_gpu_quantize_rows_i8)
-hipError_t quantize_rows_i8(const float* X, int M, int K, int8_t* Xq, float* scale, hipStream_t st);
-// the same on bf16 bit patterns, widened first (tcsc_gpu_quantize_rows_i8_bf16)
-hipError_t quantize_rows_i8_bf16(const uint16_t* X, int M, int K, int8_t* Xq, float* scale, hipStream_t st);
+// k_gemm8 (+ k_reduce_i8 when K is split): the epilogue `e` (I8Epi) on S, the exact i32 sum
+hipError_t mfma8_gemm(const int8_t* x8, const int8_t* w8, int ld8, int K, int M, int N, const I8Epi& e, int* slabs,
+                      size_t slab_bytes, hipStream_t st);
+// k_quant_rows_i8: per-row absmax quantization of X, fp32 (kF32) or bf16 bit
+// patterns widened first (kBf16) -- tcsc_gpu_quantize_rows_i8{,_bf16}; with a
+// norm (k_quant_rows_i8<.., NORM>, tcsc_gpu_quantize_rows_i8_norm) the bits of
+// rmsnorm_rows followed by the plain quantizer, in one launch
+hipError_t quantize_rows_i8(const void* X, int xtype, const RmsNorm* norm, int M, int K, int8_t* Xq, float* scale,
+                            hipStream_t st);
 // k_rmsnorm_rows (the arithmetic of tcsc_norm.h): Xn = fl(fl(x r)
 // gamma) in fp32, r per row into rinv where it is given; X is fp32 or bf16 bit
 // patterns, gamma fp32 or null (all ones), any alignment
 hipError_t rmsnorm_rows(const void* X, bool bf16, const float* gamma, float eps, int M, int K, float* Xn, float* rinv,
                         hipStream_t st);
-// k_quant_rows_i8<.., NORM>: the bits of rmsnorm_rows followed by quantize_rows_i8, in one launch
-hipError_t quantize_rows_i8_norm(const void* X, bool bf16, const float* gamma, float eps, int M, int K, int8_t* Xq,
-                                 float* scale, hipStream_t st);
 
 // ---- int8 decode path (tcsc_decode.hip) -------------------------
 // The 2-bit image of a ternary W: tiles of kW2Cols columns x kW2Blk k, 1 KiB
@@ -506,27 +549,20 @@ hipError_t w2_unpack_fill(const uint32_t* w2, int ncols, int K, const int* offp,
                           hipStream_t st);
 // k_gemm8w2 (tcsc_mfma.hip): mfma8_gemm with B read from the
 // 2-bit image; the same tiles, K split (mfma8_slices), slabs and bits
-hipError_t mfma8_gemm_w2(const int8_t* x8, const uint32_t* w2, int ld8, int K, int M, int N, const float* scale,
-                         const float* B, const YOut& y, int ldy, bool prelu, float a, int* slabs, size_t slab_bytes,
-                         hipStream_t st);
+hipError_t mfma8_gemm_w2(const int8_t* x8, const uint32_t* w2, int ld8, int K, int M, int N, const I8Epi& e, int* slabs,
+                         size_t slab_bytes, hipStream_t st);
 // column tiles per workgroup of a k_decode8 launch (1, 2 or 4)
 int decode_tiles_per_wg(int M, int N, int num_cus);
-// k_decode8: mfma8_gemm's Y for m < M <= 16; X is M x K int8 of any alignment,
-// read in place
-hipError_t decode_gemm(const int8_t* X, const uint32_t* w2, int K, int M, int N, const float* scale, const float* B,
-                       const YOut& y, int ldy, bool prelu, float a, int num_cus, hipStream_t st);
-// k_decode8q: the quantizer and k_decode8 in one launch.  X is
-// M x K fp32 (bf16 false) or bf16 bit patterns (bf16 true) of any alignment,
-// read in place; scale_out[m] gets the quantizer's scale of row m, and Y the
-// bits of quantize_rows_i8{,_bf16} followed by decode_gemm
-hipError_t decode_gemm_q(const void* X, bool bf16, const uint32_t* w2, int K, int M, int N, float* scale_out,
-                         const float* B, const YOut& y, int ldy, bool prelu, float a, int num_cus, hipStream_t st);
-// k_decode8q<.., NORM>: the RMSNorm in front of the quantizer as
-// well, in the same launch: the bits of rmsnorm_rows, quantize_rows_i8 and
-// decode_gemm.  gamma null = all ones
-hipError_t decode_gemm_qn(const void* X, bool bf16, const float* gamma, float eps, const uint32_t* w2, int K, int M,
-                          int N, float* scale_out, const float* B, const YOut& y, int ldy, bool prelu, float a,
-                          int num_cus, hipStream_t st);
+// The decode launch, m < M <= 16, by what x (DecodeX) says X is:
+//   kI8           k_decode8: mfma8_gemm's Y;
+//   kF32 / kBf16  k_decode8q: the quantizer and k_decode8 in one
+//                 launch -- Y gets the bits of quantize_rows_i8 followed by the
+//                 kI8 form; e.rscale is not read;
+//   with x.norm   k_decode8q<.., NORM> (§22): the RMSNorm in front of the
+//                 quantizer as well -- the bits of rmsnorm_rows, then the above.
+// The one dispatch over TX x TY x T x ALIGNED x PRELU x NORM is inside.
+hipError_t decode_gemm(const DecodeX& x, const uint32_t* w2, int K, int M, int N, const I8Epi& e, int num_cus,
+                       hipStream_t st);
 
 // Rewrites the flagged rows in k_stream's fast order (no-op when none is).
 hipError_t mfma_fixup(const uint16_t* x3, int M, int K, int ldk, const int* cq, const int* crq, int ncols,

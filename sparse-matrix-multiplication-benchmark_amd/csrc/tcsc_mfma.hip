@@ -39,6 +39,7 @@
 #include "tcsc_internal.h"
 #include "tcsc_norm.h"
 #include "tcsc_quant.h"
+#include "tcsc_w2.h"
 #include "tcsc_xsrc.h"
 
 namespace tcsc {
@@ -702,8 +703,7 @@ __global__ void __launch_bounds__(WM * WN * 64) k_gemm3(const uint16_t* __restri
 // 128-k blocks, zeros past K.  Integers are never non-finite or tiny: no row
 // flags, no fixup; the i32 sums are exact, so every K split gives one result.
 // ---------------------------------------------------------------------------
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));  // i32x4: tcsc_w2.h
 
 // The epilogue arithmetic, act(fl(fl(fl(float(S) * s) * c) + b)) as floats or
 // rounded to bf16, is i8_out and i8_bf16 of tcsc_i8_out.h:
@@ -809,16 +809,10 @@ __global__ void __launch_bounds__(256) k_reduce_i8(const int* __restrict__ ws, i
             v[u] = i8_out<PRELU>(t, sc, i8_cscale(cscale, col + u), Bias[col + u], a);
         }
         TY* dst = Y + (size_t)row * ldy + col;
-        if constexpr (!VEC) {
+        if constexpr (VEC)
+            I8Y<TY>::put4_nt(dst, v[0], v[1], v[2], v[3]);
+        else
             I8Y<TY>::put(dst, v[0]);
-        } else if constexpr (std::is_same<TY, float>::value) {
-            const f32x4 o = {v[0], v[1], v[2], v[3]};
-            __builtin_nontemporal_store(o, reinterpret_cast<f32x4*>(dst));
-        } else {  // four bf16 of this lane's own: one 8-B store
-            const u32x2 o = {(uint32_t)i8_bf16(v[0]) | (uint32_t)i8_bf16(v[1]) << 16,
-                             (uint32_t)i8_bf16(v[2]) | (uint32_t)i8_bf16(v[3]) << 16};
-            __builtin_nontemporal_store(o, reinterpret_cast<u32x2*>(dst));
-        }
     }
 }
 
@@ -884,13 +878,7 @@ __device__ __forceinline__ void gemm8_store(const i32x4 (&acc)[FI][FJ], char* ld
                 for (int u = 0; u < 4; ++u) v[u] = i8_out<PRELU>(s[u], sc, cq[u], bq[u], a);
                 TY* dst = Y + (size_t)row * ldy + col;
                 if (vec && col + 3 < N) {
-                    if constexpr (std::is_same<TY, float>::value) {
-                        __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(dst));
-                    } else {
-                        const u32x2 o = {(uint32_t)i8_bf16(v[0]) | (uint32_t)i8_bf16(v[1]) << 16,
-                                         (uint32_t)i8_bf16(v[2]) | (uint32_t)i8_bf16(v[3]) << 16};
-                        __builtin_nontemporal_store(o, reinterpret_cast<u32x2*>(dst));
-                    }
+                    I8Y<TY>::put4_nt(dst, v[0], v[1], v[2], v[3]);
                 } else {
 #pragma unroll
                     for (int u = 0; u < 4; ++u)
@@ -1064,16 +1052,6 @@ __global__ void __launch_bounds__(WM * WN * 64) k_gemm8(const int8_t* __restrict
 // epilogue are k_gemm8's.  A workgroup's column tiles past the matrix read the
 // last tile again and are not stored; an odd count of 128-k blocks ends the
 // loop inside the last 256-k image block, whose second half is never read.
-__device__ __forceinline__ i32x4 w2_frag(uint32_t p) {
-    i32x4 b;
-#pragma unroll
-    for (int d = 0; d < 4; ++d) {
-        const uint32_t c = (p >> (2 * d)) & 0x03030303u;  // selectors 0 .. 2: bytes 0 .. 2 of the table
-        b[d] = (int)__builtin_amdgcn_perm(0x000100ffu, 0x000100ffu, c);
-    }
-    return b;
-}
-
 template <int WN, int FI, int FJ, bool PRELU, bool PARTIAL, int BS = 2, typename TY = float>
 __global__ void __launch_bounds__(WN * 64) k_gemm8w2(const int8_t* __restrict__ A, const uint32_t* __restrict__ W2,
                                                     int ldk, int M, int N, int nblk, int nkb, int ntiles,
@@ -1651,86 +1629,68 @@ hipError_t mfma8_build_w8(const uint16_t* wt, int ncols, int K, int ldw, int8_t*
     return hipGetLastError();
 }
 
-template <typename TX>
-static hipError_t launch_quant_rows(const TX* X, int M, int K, int8_t* Xq, float* scale, hipStream_t st) {
-    if (M <= 0) return hipSuccess;
-    const bool vec = XSrc<TX>::vec_ok(X, K) && (reinterpret_cast<uintptr_t>(Xq) & (XSrc<TX>::kVec - 1)) == 0;
-    if (vec)
-        hipLaunchKernelGGL((k_quant_rows_i8<TX, true>), dim3(M), dim3(256), 0, st, X, M, K, Xq, scale);
-    else
-        hipLaunchKernelGGL((k_quant_rows_i8<TX, false>), dim3(M), dim3(256), 0, st, X, M, K, Xq, scale);
-    return hipGetLastError();
-}
-
-hipError_t quantize_rows_i8(const float* X, int M, int K, int8_t* Xq, float* scale, hipStream_t st) {
-    return launch_quant_rows(X, M, K, Xq, scale, st);
-}
-
 static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
-template <typename TX>
-static hipError_t launch_quant_rows_norm(const TX* X, const float* gamma, float eps, int M, int K, int8_t* Xq,
-                                         float* scale, hipStream_t st) {
+hipError_t quantize_rows_i8(const void* X, int xtype, const RmsNorm* norm, int M, int K, int8_t* Xq, float* scale,
+                            hipStream_t st) {
     if (M <= 0) return hipSuccess;
-    const bool vec = XSrc<TX>::vec_ok(X, K) && (reinterpret_cast<uintptr_t>(Xq) & (XSrc<TX>::kVec - 1)) == 0 &&
-                     aligned16(gamma);
-    if (vec)
-        hipLaunchKernelGGL((k_quant_rows_i8<TX, true, true>), dim3(M), dim3(256), 0, st, X, M, K, Xq, scale, gamma, eps);
-    else
-        hipLaunchKernelGGL((k_quant_rows_i8<TX, false, true>), dim3(M), dim3(256), 0, st, X, M, K, Xq, scale, gamma, eps);
-    return hipGetLastError();
-}
-
-hipError_t quantize_rows_i8_norm(const void* X, bool bf16, const float* gamma, float eps, int M, int K, int8_t* Xq,
-                                 float* scale, hipStream_t st) {
-    if (K < 1 || !X || !Xq || !scale) return M <= 0 ? hipSuccess : hipErrorInvalidValue;
-    return bf16 ? launch_quant_rows_norm(static_cast<const uint16_t*>(X), gamma, eps, M, K, Xq, scale, st)
-                : launch_quant_rows_norm(static_cast<const float*>(X), gamma, eps, M, K, Xq, scale, st);
-}
-
-template <typename TX>
-static hipError_t launch_rmsnorm_rows(const TX* X, const float* gamma, float eps, int M, int K, float* Xn, float* rinv,
-                                      hipStream_t st) {
-    if (M <= 0) return hipSuccess;
-    if (XSrc<TX>::vec_ok(X, K) && aligned16(Xn) && aligned16(gamma))
-        hipLaunchKernelGGL((k_rmsnorm_rows<TX, true>), dim3(M), dim3(256), 0, st, X, gamma, eps, M, K, Xn, rinv);
-    else
-        hipLaunchKernelGGL((k_rmsnorm_rows<TX, false>), dim3(M), dim3(256), 0, st, X, gamma, eps, M, K, Xn, rinv);
-    return hipGetLastError();
+    if (norm && (K < 1 || !X || !Xq || !scale)) return hipErrorInvalidValue;
+    return with_elem(xtype == kBf16, [&](auto tx) {
+        using TX = typename decltype(tx)::type;
+        const TX* x = static_cast<const TX*>(X);
+        const bool vec = XSrc<TX>::vec_ok(x, K) && (reinterpret_cast<uintptr_t>(Xq) & (XSrc<TX>::kVec - 1)) == 0 &&
+                         (!norm || aligned16(norm->gamma));
+        return with_bool(vec, [&](auto v) {
+            return with_bool(norm != nullptr, [&](auto nm) {
+                hipLaunchKernelGGL((k_quant_rows_i8<TX, decltype(v)::value, decltype(nm)::value>), dim3(M), dim3(256), 0,
+                                   st, x, M, K, Xq, scale, norm ? norm->gamma : nullptr, norm ? norm->eps : 0.0f);
+                return hipGetLastError();
+            });
+        });
+    });
 }
 
 hipError_t rmsnorm_rows(const void* X, bool bf16, const float* gamma, float eps, int M, int K, float* Xn, float* rinv,
                         hipStream_t st) {
-    if (K < 1 || !X || !Xn) return M <= 0 ? hipSuccess : hipErrorInvalidValue;
-    return bf16 ? launch_rmsnorm_rows(static_cast<const uint16_t*>(X), gamma, eps, M, K, Xn, rinv, st)
-                : launch_rmsnorm_rows(static_cast<const float*>(X), gamma, eps, M, K, Xn, rinv, st);
-}
-
-hipError_t quantize_rows_i8_bf16(const uint16_t* X, int M, int K, int8_t* Xq, float* scale, hipStream_t st) {
-    return launch_quant_rows(X, M, K, Xq, scale, st);
+    if (M <= 0) return hipSuccess;
+    if (K < 1 || !X || !Xn) return hipErrorInvalidValue;
+    return with_elem(bf16, [&](auto tx) {
+        using TX = typename decltype(tx)::type;
+        const TX* x = static_cast<const TX*>(X);
+        return with_bool(XSrc<TX>::vec_ok(x, K) && aligned16(Xn) && aligned16(gamma), [&](auto v) {
+            hipLaunchKernelGGL((k_rmsnorm_rows<TX, decltype(v)::value>), dim3(M), dim3(256), 0, st, x, gamma, eps, M, K,
+                               Xn, rinv);
+            return hipGetLastError();
+        });
+    });
 }
 
 // k_reduce_i8 on the slabs of a split int8 GEMM (k_gemm8 or k_gemm8w2)
-template <bool PRELU, typename TY>
-static hipError_t launch_reduce_i8(const int* slabs, int slices, int M, int N, const float* scale, const float* cscale,
-                                   const float* B, TY* Y, int ldy, float a, hipStream_t st) {
-    const bool vec = N % 4 == 0 && ldy % 4 == 0 && (reinterpret_cast<uintptr_t>(Y) & (4 * sizeof(TY) - 1)) == 0 &&
-                     (reinterpret_cast<uintptr_t>(slabs) & 15) == 0;
-    const long long n = (long long)M * (vec ? N / 4 : N);
-    if (vec)
-        hipLaunchKernelGGL((k_reduce_i8<PRELU, true, TY>), dim3(grid_of(n, 256)), dim3(256), 0, st, slabs, slices, M, N, scale,
-                           cscale, B, Y, ldy, a);
-    else
-        hipLaunchKernelGGL((k_reduce_i8<PRELU, false, TY>), dim3(grid_of(n, 256)), dim3(256), 0, st, slabs, slices, M, N, scale,
-                           cscale, B, Y, ldy, a);
-    return hipGetLastError();
+static hipError_t launch_reduce_i8(const int* slabs, int slices, int M, int N, const I8Epi& e, hipStream_t st) {
+    return with_elem(e.y.ytype == kYBf16, [&](auto ty) {
+        using TY = typename decltype(ty)::type;
+        TY* Y = static_cast<TY*>(e.y.Y);
+        const bool vec = N % 4 == 0 && e.ldy % 4 == 0 && (reinterpret_cast<uintptr_t>(Y) & (4 * sizeof(TY) - 1)) == 0 &&
+                         aligned16(slabs);
+        const long long n = (long long)M * (vec ? N / 4 : N);
+        return with_bool(vec, [&](auto v) {
+            return with_bool(e.prelu, [&](auto pr) {
+                hipLaunchKernelGGL((k_reduce_i8<decltype(pr)::value, decltype(v)::value, TY>), dim3(grid_of(n, 256)),
+                                   dim3(256), 0, st, slabs, slices, M, N, e.rscale, e.y.cscale, e.B, Y, e.ldy, e.a);
+                return hipGetLastError();
+            });
+        });
+    });
 }
 
 template <bool PRELU, typename TY>
-static hipError_t launch_gemm8_t(const int8_t* x8, const int8_t* w8, int ld8, int nblk, int M, int N,
-                                 const float* scale, const float* cscale, const float* B, TY* Y, int ldy, float a,
+static hipError_t launch_gemm8_t(const int8_t* x8, const int8_t* w8, int ld8, int nblk, int M, int N, const I8Epi& epi,
                                  int* slabs, int slices, hipStream_t st) {
     constexpr int kGm = 4;  // bands of 4 row tiles, as launch_gemm3_t
+    const float *scale = epi.rscale, *cscale = epi.y.cscale, *B = epi.B;  // the kernels' parameter lists
+    TY* Y = static_cast<TY*>(epi.y.Y);
+    const int ldy = epi.ldy;
+    const float a = epi.a;
     float* sl = reinterpret_cast<float*>(slabs);
     const int bps = (nblk + slices - 1) / std::max(slices, 1);
     if (mfma_big_tiles(M, N)) {
@@ -1762,7 +1722,7 @@ static hipError_t launch_gemm8_t(const int8_t* x8, const int8_t* w8, int ld8, in
     }
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess || slices <= 1) return e;
-    return launch_reduce_i8<PRELU>(slabs, slices, M, N, scale, cscale, B, Y, ldy, a, st);
+    return launch_reduce_i8(slabs, slices, M, N, epi, st);
 }
 
 // k_gemm8w2 on k_gemm8's three grids, slices and blocks per slice: 128 x 512
@@ -1770,9 +1730,12 @@ static hipError_t launch_gemm8_t(const int8_t* x8, const int8_t* w8, int ld8, in
 // of 128 x 32), so mfma_tiles and mfma8_slices count its workgroups as they are.
 template <bool PRELU, typename TY>
 static hipError_t launch_gemm8w2_t(const int8_t* x8, const uint32_t* w2, int ld8, int nblk, int K, int M, int N,
-                                   const float* scale, const float* cscale, const float* B, TY* Y, int ldy, float a,
-                                   int* slabs, int slices, hipStream_t st) {
+                                   const I8Epi& epi, int* slabs, int slices, hipStream_t st) {
     constexpr int kGm = 4;
+    const float *scale = epi.rscale, *cscale = epi.y.cscale, *B = epi.B;
+    TY* Y = static_cast<TY*>(epi.y.Y);
+    const int ldy = epi.ldy;
+    const float a = epi.a;
     float* sl = reinterpret_cast<float*>(slabs);
     const int bps = (nblk + slices - 1) / std::max(slices, 1);
     const int nkb = w2_kblocks(K), nt = w2_col_tiles(N);
@@ -1805,38 +1768,38 @@ static hipError_t launch_gemm8w2_t(const int8_t* x8, const uint32_t* w2, int ld8
     }
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess || slices <= 1) return e;
-    return launch_reduce_i8<PRELU>(slabs, slices, M, N, scale, cscale, B, Y, ldy, a, st);
+    return launch_reduce_i8(slabs, slices, M, N, epi, st);
 }
 
-// the Y type and the PReLU into template arguments
-#define TCSC_I8_DISPATCH(FN, ...)                                                                            \
-    (y.ytype == kYBf16                                                                                       \
-         ? (prelu ? FN<true>(__VA_ARGS__, static_cast<uint16_t*>(y.Y), ldy, a, slabs, slices, st)            \
-                  : FN<false>(__VA_ARGS__, static_cast<uint16_t*>(y.Y), ldy, a, slabs, slices, st))          \
-         : (prelu ? FN<true>(__VA_ARGS__, static_cast<float*>(y.Y), ldy, a, slabs, slices, st)               \
-                  : FN<false>(__VA_ARGS__, static_cast<float*>(y.Y), ldy, a, slabs, slices, st)))
+// the Y type and the PReLU of the descriptor into template arguments
+template <typename F>
+static hipError_t with_i8_epi(const I8Epi& e, F&& f) {
+    return with_elem(e.y.ytype == kYBf16, [&](auto ty) { return with_bool(e.prelu, [&](auto pr) { return f(ty, pr); }); });
+}
 
-hipError_t mfma8_gemm(const int8_t* x8, const int8_t* w8, int ld8, int K, int M, int N, const float* scale,
-                      const float* B, const YOut& y, int ldy, bool prelu, float a, int* slabs, size_t slab_bytes,
-                      hipStream_t st) {
+hipError_t mfma8_gemm(const int8_t* x8, const int8_t* w8, int ld8, int K, int M, int N, const I8Epi& e, int* slabs,
+                      size_t slab_bytes, hipStream_t st) {
     if (M <= 0 || N <= 0) return hipSuccess;
     const int nblk = mfma8_nblk(K);
-    if (nblk < 1 || ld8 != mfma8_ldw(K) || !y.Y) return hipErrorInvalidValue;
+    if (nblk < 1 || ld8 != mfma8_ldw(K) || !e.y.Y) return hipErrorInvalidValue;
     const int slices = mfma8_slices(M, N, K);
     if (slices > 1 && (!slabs || slab_bytes < mfma8_slab_bytes(M, N, K))) return hipErrorInvalidValue;
-    return TCSC_I8_DISPATCH(launch_gemm8_t, x8, w8, ld8, nblk, M, N, scale, y.cscale, B);
+    return with_i8_epi(e, [&](auto ty, auto pr) {
+        return launch_gemm8_t<decltype(pr)::value, typename decltype(ty)::type>(x8, w8, ld8, nblk, M, N, e, slabs, slices, st);
+    });
 }
 
-hipError_t mfma8_gemm_w2(const int8_t* x8, const uint32_t* w2, int ld8, int K, int M, int N, const float* scale,
-                         const float* B, const YOut& y, int ldy, bool prelu, float a, int* slabs, size_t slab_bytes,
-                         hipStream_t st) {
+hipError_t mfma8_gemm_w2(const int8_t* x8, const uint32_t* w2, int ld8, int K, int M, int N, const I8Epi& e, int* slabs,
+                         size_t slab_bytes, hipStream_t st) {
     if (M <= 0 || N <= 0) return hipSuccess;
     const int nblk = mfma8_nblk(K);
-    if (nblk < 1 || ld8 != mfma8_ldw(K) || K >= kDecodeMaxK || !w2 || !y.Y) return hipErrorInvalidValue;
+    if (nblk < 1 || ld8 != mfma8_ldw(K) || K >= kDecodeMaxK || !w2 || !e.y.Y) return hipErrorInvalidValue;
     const int slices = mfma8_slices(M, N, K);
     if (slices > 1 && (!slabs || slab_bytes < mfma8_slab_bytes(M, N, K))) return hipErrorInvalidValue;
-    return TCSC_I8_DISPATCH(launch_gemm8w2_t, x8, w2, ld8, nblk, K, M, N, scale, y.cscale, B);
+    return with_i8_epi(e, [&](auto ty, auto pr) {
+        return launch_gemm8w2_t<decltype(pr)::value, typename decltype(ty)::type>(x8, w2, ld8, nblk, K, M, N, e, slabs, slices,
+                                                                               st);
+    });
 }
-#undef TCSC_I8_DISPATCH
 
 }  // namespace tcsc

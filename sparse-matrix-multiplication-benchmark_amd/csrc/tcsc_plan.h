@@ -91,17 +91,56 @@ constexpr size_t kUnbounded = (size_t)-1;  // ws_avail: size the call, whatever 
 Route route_call(const tcsc_gpu_plan* p, int M, int dt, size_t ws_avail, const RoutePins& pin,
                  const char* who = nullptr);
 
-// One call on a caller's workspace.  dX is M x K of type dt (with the int8
-// type the row scales dScale, null for ones); the narrow types have stage 0
-// only.  *ran, if given, receives the route that ran.  Beside the activation
-// type, the output descriptor: `out`, if given, replaces dY with a Y of its own
-// type (fp32 or bf16, ldy in its elements) and the column scales (YOut,
-// tcsc_internal.h) -- the int8 call's decode and MFMA routes alone write
-// anything but {fp32, no column scale}; `as` is the call's name in messages.
-int sgemm_ws(const tcsc_gpu_plan* p, const void* dX, const float* dB, float* dY, int M, int ldy, int variant, float a,
-             void* stream, float* ws, size_t ws_bytes, int stage = 0, const RoutePins& pin = RoutePins(),
-             Route* ran = nullptr, int dt = kF32, const float* dScale = nullptr, const YOut* out = nullptr,
-             const char* as = nullptr);
+// What an entry point received: the one description of a call that travels
+// from the public functions to the launch.  X is M x K of xtype (tcsc::kF32 /
+// kBf16 / kI8; with the int8 type the row scales xscale, null for ones); y is
+// the output (YOut, tcsc_internal.h): an fp32 or bf16 call's is {Y, kYF32,
+// nullptr}, and the int8 call's decode and MFMA routes alone write anything
+// else; ldy is in y's elements.  `who` is the name the call gives itself in
+// messages (null: the activation type's own entry point).
+struct Call {
+    const void* X = nullptr;
+    int xtype = kF32;
+    const float* xscale = nullptr;
+    const float* B = nullptr;
+    YOut y;
+    int M = 0, ldy = 0, variant = 0;
+    float a = 0.f;
+    void* stream = nullptr;
+    const char* who = nullptr;
+    // rows [r0, r0 + n) of a call on a matrix of K rows as a call of their own: X (x_elem bytes an
+    // element), the row scales and Y (by the element size of its type) advance by r0 rows
+    Call rows(int r0, int n, int K, size_t x_elem) const {
+        Call c = *this;
+        c.X = X ? static_cast<const char*>(X) + (size_t)r0 * K * x_elem : nullptr;
+        c.xscale = xscale ? xscale + r0 : nullptr;
+        c.y = y.rows_on((size_t)r0, ldy);
+        c.M = n;
+        return c;
+    }
+};
+// a Call from an entry point's arguments, in the order the public prototypes list them
+inline Call make_call(const void* X, int xtype, const float* xscale, const float* B, const YOut& y, int M, int ldy,
+                      int variant, float a, void* stream, const char* who = nullptr) {
+    Call c;
+    c.X = X;
+    c.xtype = xtype;
+    c.xscale = xscale;
+    c.B = B;
+    c.y = y;
+    c.M = M;
+    c.ldy = ldy;
+    c.variant = variant;
+    c.a = a;
+    c.stream = stream;
+    c.who = who;
+    return c;
+}
+
+// One call on a caller's workspace ws; the narrow types have stage 0 only.
+// *ran, if given, receives the route that ran.
+int sgemm_ws(const tcsc_gpu_plan* p, const Call& c, float* ws, size_t ws_bytes, int stage, const RoutePins& pin,
+             Route* ran);
 
 }  // namespace tcsc
 #pragma GCC visibility pop

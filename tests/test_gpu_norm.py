@@ -249,17 +249,19 @@ def test_n_edges(gpu, oracle, env, N):
 
 def test_a_ragged_last_workgroup(gpu, oracle, env):
     """8208 columns = 513 tiles: at M = 5, 9 and 16 a workgroup owns two tiles on a 256-CU chip and the last
-    workgroup one real tile; every workgroup computes the same r and scales."""
+    workgroup one real tile; every workgroup computes the same r and scales.  16400 columns = 1025 tiles
+    (K = 260): at M = 9 and 16 a workgroup owns four (decode_tiles_per_wg(9, 16400, 256) == 4), 257 workgroups,
+    the last again with one real tile."""
     torch = gpu
-    K, N = 264, 8208
-    c = case(torch, oracle, K, N)
-    W, plan = packed_plan(c["Wd"])
     env(TCSC_QFUSE="1")
-    for xt in XTYPES:
-        for M in (5, 9, 16):
-            check(torch, plan, c, xt, M, N, cscale=M == 9, bf16=M == 16, what="N=8208")
-    plan.destroy()
-    W.free()
+    for K, N, ms in ((264, 8208, (5, 9, 16)), (260, 16400, (9, 16))):
+        c = case(torch, oracle, K, N)
+        W, plan = packed_plan(c["Wd"])
+        for xt in XTYPES:
+            for M in ms:
+                check(torch, plan, c, xt, M, N, cscale=M == 9, bf16=M == 16, what=f"N={N}")
+        plan.destroy()
+        W.free()
 
 
 @pytest.mark.parametrize("K", [256, 300])

@@ -251,17 +251,19 @@ def test_n_edges(gpu, oracle, env, N):
 
 def test_a_ragged_last_workgroup(gpu, oracle, env):
     """8208 columns = 513 tiles: at M = 5, 9 and 16 a workgroup owns two tiles on a 256-CU chip and the last
-    workgroup one real tile."""
+    workgroup one real tile.  16400 columns = 1025 tiles: at M = 9 and 16 a workgroup owns four
+    (decode_tiles_per_wg(9, 16400, 256) == 4), 257 workgroups, the last again with one real tile."""
     torch = gpu
-    K, N = 260, 8208
-    c = case(torch, oracle, K, N)
-    W, plan = packed_plan(c["Wd"])
+    K = 260
     env(TCSC_QFUSE="1")
-    for xt in XTYPES:
-        for M in (5, 9, 16):
-            check_fused(torch, plan, c, xt, M, N, what="N=8208")
-    plan.destroy()
-    W.free()
+    for N, ms in ((8208, (5, 9, 16)), (16400, (9, 16))):
+        c = case(torch, oracle, K, N)
+        W, plan = packed_plan(c["Wd"])
+        for xt in XTYPES:
+            for M in ms:
+                check_fused(torch, plan, c, xt, M, N, what=f"N={N}")
+        plan.destroy()
+        W.free()
 
 
 @pytest.mark.parametrize("K", [256, 300])

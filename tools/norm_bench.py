@@ -23,6 +23,10 @@ tree's library and on the parent's (`q8`, `q8_parent`, `q8_again`).
 
 One JSON document goes to --out (default profiles/norm_bench.json) and a summary table to stdout.  Needs a gfx950 GPU.
 
+A parent that has sgemm_q8_norm itself (an A/B across a later change) is also timed on (ii) and (iii):
+`two_launch_parent`, `fused_parent`, and per point this tree's time over them and whether it is within this tree's
+own spread.
+
     python tools/norm_bench.py --parent-pkg DIR [--reps 5] [--shapes KxN ...] [--out FILE]
 """
 import argparse
@@ -97,7 +101,15 @@ def child(mode, shapes, reps, out_path):
                     plan.sgemm_q8(X, Xq, S, B, Y, M, N, "prelu_basic", A, st)
 
                 if mode == "parent":
-                    assert not hasattr(tcsc_amd.Plan, "sgemm_q8_norm"), "the parent package is this tree's"
+                    assert not os.path.realpath(tcsc_amd.LIB_PATH).startswith(os.path.realpath(PKG) + os.sep), \
+                        "the parent package is this tree's"
+                    if hasattr(tcsc_amd.Plan, "sgemm_q8_norm"):  # a parent that has the call: its two forms as well
+                        for name, knob in (("two_launch_parent", "0"), ("fused_parent", "1")):
+                            os.environ["TCSC_QFUSE"] = knob
+                            if knob == "0" or plan.launch_info_q8_norm(M, xt)[0] == "decode":
+                                p[name] = graph_time(torch, timed, lambda st, X=X: plan.sgemm_q8_norm(
+                                    X, Xq, S, B, Y, M, N, gamma, EPS, "prelu_basic", A, st), reps)
+                        os.environ.pop("TCSC_QFUSE", None)
 
                     gw = gamma.to(X.dtype)  # a weight of x's type: torch's fused rms_norm asks for it
 
@@ -190,6 +202,13 @@ def main():
         p["q8_over_parent"] = p["q8"]["graph_ms"] / p["q8_parent"]["graph_ms"]
         p["q8_within_spread"] = bool(min(p["q8"]["graph_ms"], p["q8_again"]["graph_ms"])
                                      <= p["q8_parent"]["graph_ms"] * (1.0 + p["q8_spread"]))
+        for name in ("two_launch", "fused"):  # against a parent that has the call, within this tree's own spread
+            if name + "_parent" in b and name in p:
+                p[name + "_parent"] = b[name + "_parent"]
+                mine = min(p[name]["graph_ms"], c[name + "_again"]["graph_ms"])
+                sp = abs(c[name + "_again"]["graph_ms"] - p[name]["graph_ms"]) / p[name]["graph_ms"]
+                p[name + "_over_parent"] = p[name]["graph_ms"] / b[name + "_parent"]["graph_ms"]
+                p[name + "_within_spread"] = bool(mine <= b[name + "_parent"]["graph_ms"] * (1.0 + sp))
         p["holds"] = True
         if "fused" in p:
             p["fused_again"] = c["fused_again"]
@@ -206,6 +225,12 @@ def main():
     res["all_bits_equal"] = all(p["bits_equal"] for p in res["points"] if "bits_equal" in p)
     res["two_launch_wins_everywhere"] = all(p["two_launch_wins"] for p in res["points"])
     res["q8_within_spread_everywhere"] = all(p["q8_within_spread"] for p in res["points"])
+    for name in ("two_launch", "fused"):
+        pts = [p for p in res["points"] if name + "_within_spread" in p]
+        if pts:
+            res[name + "_within_spread_everywhere"] = all(p[name + "_within_spread"] for p in pts)
+            print(name, "over parent: max", max(p[name + "_over_parent"] for p in pts), "within spread everywhere",
+                  res[name + "_within_spread_everywhere"])
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
         json.dump(res, f, indent=1)

@@ -17,7 +17,8 @@ Three legs:
   (iii) sgemm_q8 with col_scale, the bias, the PReLU and a bf16 Y: this tree's library, the launches of (i) (`iii_new`)
 
 Three child processes, one library each, every point in each, in the order parent, new, parent_again.  The parent
-is --parent-pkg: a build of the parent commit (its `tcsc_amd/` and `lib/`; $TCSC_AMD_LIB names its library).
+is --parent-pkg: a build of the parent commit (its `tcsc_amd/` and `lib/`; $TCSC_AMD_LIB names its library).  It may
+have the feature itself (an A/B of the old entry point across a later change): legs (i) and (ii) run on any library.
 
 Per point: spread = |i_parent_again - i_parent| / i_parent;  `iii_no_slower` = iii_new <= i_parent (1 + spread);
 `i_unchanged` = |i_new - i_parent| <= spread i_parent taken over both parent measurements;  `ii_over_iii`, the
@@ -96,8 +97,10 @@ def child(mode, shapes, reps, out_path):
     tcsc_amd.require_gpu()
     for k in KNOBS:
         os.environ.pop(k, None)
-    is_new = "tcsc_gpu_sgemm_q8_out" in tcsc_amd.EXPORTED_SYMBOLS
+    # the parent may have the feature too (a later A/B of the old entry point): then it is told apart by its path
+    is_new = os.path.realpath(tcsc_amd.LIB_PATH).startswith(os.path.realpath(PKG) + os.sep)
     assert is_new == (mode == "new"), f"mode {mode} on the wrong library ({tcsc_amd.LIB_PATH})"
+    assert not is_new or "tcsc_gpu_sgemm_q8_out" in tcsc_amd.EXPORTED_SYMBOLS
     dev = torch.device("cuda:0")
     res = {"mode": mode, "lib": tcsc_amd.LIB_PATH, "device": torch.cuda.get_device_name(0), "points": []}
     for K, N in shapes:
