@@ -760,6 +760,93 @@ int tcsc_gpu_launch_info_q8_norm(const tcsc_gpu_plan *plan, int M, int xtype,
                                  int *path, int *slices, int *fused);
 int tcsc_gpu_norm_fuse_pays(int M, int K, int N, int xtype);   /* host arithmetic */
 
+/* ---- Gated FFN in the int8 call ---------------------------------
+ * The FFN of a BitNet-style block is down(quant(subnorm(act(gate(x)) * up(x)))).
+ * The gate and up projections share X, its row scales and its quantizer, and
+ * their outputs meet element by element: these calls compute
+ *   Y = act(X Wg) * (X Wu)
+ * on two plans, so that a whole FFN is two library calls -- a gated call into a
+ * bf16 Y, and tcsc_gpu_sgemm_q8_norm on that Y.
+ *
+ * The arithmetic is pinned; every step is one rounded fp32 operation and no step
+ * is contracted with another.  With Sg, Su the exact i32 sums against the gate
+ * and up weights, s[m] the row scale, cg, cu the column scales (NULL: all ones)
+ * and bg, bu the biases:
+ *   g = fl(fl(fl(float(Sg) s[m]) cg[j]) + bg[j])      tcsc_gpu_sgemm_i8_out's value,
+ *   u = fl(fl(fl(float(Su) s[m]) cu[j]) + bu[j])      no PReLU
+ *   TCSC_GLU_RELU2:  r = g < 0 ? 0 : g;  h = fl(fl(r r) u)
+ *   TCSC_GLU_SILU:   h = fl(fl(g / fl(1 + expf(-g))) u)    IEEE division, the
+ *                    device math library's expf (1 ulp)
+ *   Y[m, j] = h (TCSC_Y_F32) or h rounded to bf16, nearest even (TCSC_Y_BF16)
+ * Every route gives the same bits: TCSC_GLU_RELU2 those of two
+ * tcsc_gpu_sgemm_i8_out calls into fp32 followed by torch's
+ * relu(g).square() * u (and .to(bfloat16)).  Inputs are finite.  Only rows < M
+ * and columns < cols are written, with the store rules of tcsc_gpu_sgemm_i8_out.
+ *
+ * gate, up: two plans with the same rows (K) and cols (H) on one device, each
+ *   holding the 2-bit image: a packed plan, or an ordinary plan after
+ *   tcsc_gpu_plan_enable_w2.  Two plans rather than one of 2 H columns: H needs
+ *   no alignment, the image format and its save / load do not change, and the
+ *   plans of existing layers serve.
+ * dG: the caller's scratch for the gate values, M x H floats at pitch H, as dXq
+ *   is the quantizer's.  Needed where the route is TCSC_PATH_MFMA; untouched,
+ *   and allowed to be NULL, where it is TCSC_PATH_DECODE.
+ * dY: M x ldy of ytype, ldy >= H in elements.
+ *
+ * Routes (tcsc_gpu_launch_info_glu), by M alone -- the cost models, $TCSC_PATH
+ * and $TCSC_DECODE are not asked:
+ *   M <= 16  TCSC_PATH_DECODE: one launch (k_decode8g) that streams both images
+ *            against one set of X fragments.  tcsc_gpu_sgemm_q8_glu runs the
+ *            quantizer inside it (k_decode8qg: *fused = 1) where
+ *            tcsc_gpu_glu_fuse_pays says so or $TCSC_QFUSE=1 is set ($TCSC_QFUSE=0:
+ *            never); otherwise the quantizer (with the norm: its norm form) into
+ *            dXq, then k_decode8g.
+ *   M >= 17  TCSC_PATH_MFMA: k_pack8 once, then k_gemm8w2 twice on the gate
+ *            plan's workspace (slabs included: *slices is the K split of each) --
+ *            the gate half through the plain epilogue into dG, the up half
+ *            through the gated one.  tcsc_gpu_plan_reserve(gate, max_M) covers it;
+ *            a call on a smaller workspace grows it first, as tcsc_gpu_sgemm_i8
+ *            does.  Once reserved, no call allocates or synchronises, and all
+ *            can be captured.
+ *
+ * tcsc_gpu_sgemm_q8_glu takes an fp32 or bf16 X (xtype as in tcsc_gpu_sgemm_q8),
+ * writes the row scales to dScale and uses dXq as tcsc_gpu_sgemm_q8 does (NULL
+ * allowed where the call is fused).  eps == 0.0f exactly, with a NULL dGamma,
+ * means no norm; any other eps is checked as tcsc_gpu_sgemm_q8_norm checks it
+ * and the RMSNorm of that call runs in front of the quantizer.
+ *
+ * tcsc_gpu_glu_fuse_pays (host arithmetic: no plan, no device): the rule of
+ * tcsc_gpu_quant_fuse_pays with the gated launch's own workgroup count W =
+ * ceil(ceil(H / 16) / TG): 1 for 1 <= M <= 4 and W M K <= 2^23; with norm != 0
+ * tcsc_gpu_norm_fuse_pays's, which is 0 everywhere.  tcsc_gpu_launch_info_glu
+ * reports *fused for a call without the norm.
+ *
+ * TCSC_E_ARG with a message naming the call, before any HIP call, for: a NULL
+ * plan, dY, bias or X; a plan without the 2-bit image; plans whose K, cols or
+ * device differ; an act or ytype out of range; a NULL dG on the MFMA route; a
+ * NULL dXq where the call is not fused; dGamma given with eps == 0; ldy < cols.
+ *
+ * Out of scope: one GEMM launch over both images at M >= 17 (the next lever);
+ * gating on the gather and small-M routes and on the fp32 and bf16 calls; an
+ * int8 Y; other gate activations; a host-pointer version. */
+enum tcsc_glu_act { TCSC_GLU_RELU2 = 0, TCSC_GLU_SILU = 1 };
+int tcsc_gpu_sgemm_i8_glu(const tcsc_gpu_plan *gate, const tcsc_gpu_plan *up,
+                          const void *dXq, const float *dScale,
+                          const float *dColScaleG, const float *dBG,
+                          const float *dColScaleU, const float *dBU,
+                          float *dG /* may be NULL at M <= 16 */, void *dY, int ytype,
+                          int M, int ldy, int act, void *stream);
+int tcsc_gpu_sgemm_q8_glu(const tcsc_gpu_plan *gate, const tcsc_gpu_plan *up,
+                          const void *dX, int xtype, const float *dGamma, float eps,
+                          void *dXq, float *dScale,
+                          const float *dColScaleG, const float *dBG,
+                          const float *dColScaleU, const float *dBU,
+                          float *dG /* may be NULL at M <= 16 */, void *dY, int ytype,
+                          int M, int ldy, int act, void *stream);
+int tcsc_gpu_launch_info_glu(const tcsc_gpu_plan *gate, const tcsc_gpu_plan *up, int M, int xtype,
+                             int *path, int *slices, int *fused);
+int tcsc_gpu_glu_fuse_pays(int M, int K, int N, int xtype, int norm);   /* host arithmetic */
+
 /* Device-side tcsc_from_dense: dense K x N row-major float matrix on the
  * device -> TCSC arrays on the device, bit-exact with the reference builder
  * (tcsc.c:6-66).  Two calls: first with the four output pointers NULL to

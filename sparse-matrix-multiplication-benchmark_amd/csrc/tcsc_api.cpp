@@ -2301,6 +2301,230 @@ int tcsc_gpu_sgemm_q8_norm(const tcsc_gpu_plan* p, const void* dX, int xtype, co
                          who, dXq, dScale, &norm);
 }
 
+// ---- the gated FFN call -----------------------------------------
+// Y = act(X Wg) (X Wu) on two plans with the 2-bit image and the same K and H.  The route is fixed by
+// M alone, whatever the cost models, $TCSC_PATH or $TCSC_DECODE say: up to 16 rows the one gated decode
+// launch, above k_pack8 once and k_gemm8w2 twice on the gate plan's workspace -- the gate half into the
+// caller's G through the plain epilogue, the up half with the gated one.
+static_assert(TCSC_GLU_RELU2 == tcsc::kGluRelu2 && TCSC_GLU_SILU == tcsc::kGluSilu, "the public gate activations are i8_glu's");
+
+// The fusing rule of the gated q8 call: §20's (and with the norm §22's, which is 0 everywhere) with the
+// gated launch's own workgroup count.
+static bool glu_fuse_pays(int M, int K, int N, int xtype, bool norm) {
+    const int max_M = norm ? kNFuseMaxM : kQFuseMaxM;
+    const long long values = norm ? kNFuseValues : kQFuseValues;
+    if (M < 1 || M > max_M || K < 1 || N < 1 || (xtype != TCSC_X_F32 && xtype != TCSC_X_BF16)) return false;
+    const int TG = tcsc::decode_glu_tiles_per_wg(M, N, 0);  // the grid on a 256-CU chip
+    const long long wgs = (tcsc::w2_col_tiles(N) + TG - 1) / TG;
+    return wgs * M * K <= values;
+}
+int tcsc_gpu_glu_fuse_pays(int M, int K, int N, int xtype, int norm) { return glu_fuse_pays(M, K, N, xtype, norm != 0) ? 1 : 0; }
+
+// what every gated entry point checks of its plans, ahead of any HIP call
+static int glu_plans(const char* who, const tcsc_gpu_plan* gate, const tcsc_gpu_plan* up) {
+    if (!gate || !up) {
+        set_error("%s: NULL %s plan", who, !gate ? "gate" : "up");
+        return TCSC_E_ARG;
+    }
+    if (!gate->w2 || !up->w2) {
+        set_error("%s: the %s plan has no 2-bit image (a packed plan, or tcsc_gpu_plan_enable_w2 on an ordinary one)", who,
+                  !gate->w2 ? "gate" : "up");
+        return TCSC_E_ARG;
+    }
+    if (gate->rows != up->rows || gate->cols != up->cols || gate->device != up->device) {
+        set_error("%s: the gate plan is K=%d x cols=%d on device %d and the up plan K=%d x cols=%d on device %d", who,
+                  gate->rows, gate->cols, gate->device, up->rows, up->cols, up->device);
+        return TCSC_E_ARG;
+    }
+    return TCSC_OK;
+}
+static int glu_args(const char* who, const tcsc_gpu_plan* gate, const tcsc_gpu_plan* up, const float* dBG,
+                    const float* dBU, const void* dY, int ytype, int act) {
+    if (ytype != TCSC_Y_F32 && ytype != TCSC_Y_BF16) {
+        set_error("%s: ytype=%d is neither TCSC_Y_F32 (0) nor TCSC_Y_BF16 (1)", who, ytype);
+        return TCSC_E_ARG;
+    }
+    if (act != TCSC_GLU_RELU2 && act != TCSC_GLU_SILU) {
+        set_error("%s: act=%d is neither TCSC_GLU_RELU2 (0) nor TCSC_GLU_SILU (1)", who, act);
+        return TCSC_E_ARG;
+    }
+    const int rc = glu_plans(who, gate, up);
+    if (rc != TCSC_OK) return rc;
+    if (!dY || !dBG || !dBU) {
+        set_error("%s: NULL %s", who, !dY ? "dY" : !dBG ? "dBG" : "dBU");
+        return TCSC_E_ARG;
+    }
+    return TCSC_OK;
+}
+// the MFMA workspace of M rows of a gated call: the int8 call's on the gate plan (the slabs serve both GEMMs in turn)
+static size_t glu_ws_bytes(const tcsc_gpu_plan* gate, int M) {
+    return mfma_ws(kI8, std::min(M, kMaxLaunchRows), gate->rows, gate->cols).bytes;
+}
+
+// A gated call on an int8 X (c.xtype == kI8; c.glu.up set; the plans and pointers checked by glu_args).
+static int sgemm_glu_i8(const tcsc_gpu_plan* gate, const Call& c) {
+    const char* who = c.who;
+    const tcsc_gpu_plan* up = c.glu.up;
+    const int M = c.M, K = gate->rows, H = gate->cols;
+    if (M < 0 || c.ldy < H) {
+        set_error("%s: bad arguments (M=%d ldy=%d cols=%d)", who, M, c.ldy, H);
+        return TCSC_E_ARG;
+    }
+    if (M == 0 || H == 0) return TCSC_OK;
+    if (!c.X) {
+        set_error("%s: NULL X", who);
+        return TCSC_E_ARG;
+    }
+    hipStream_t st = static_cast<hipStream_t>(c.stream);
+    I8Epi eg, eu;  // the two halves: the gate's own epilogue, and the up half's with the gate beside it
+    eg.rscale = eu.rscale = c.xscale;
+    eg.B = c.B;
+    eg.y = YOut{c.glu.G, kYF32, c.y.cscale};
+    eg.ldy = c.glu.ldg;
+    eu.B = c.glu.B;
+    eu.y = YOut{c.y.Y, c.y.ytype, c.glu.cscale};
+    eu.ldy = c.ldy;
+    eu.act = c.glu.act;
+    if (M <= tcsc::kDecodeMaxM) {  // TCSC_PATH_DECODE: one launch, G untouched
+        HIP_TRY(tcsc::decode_glu(tcsc::DecodeX{c.X, kI8, nullptr, nullptr}, gate->w2, up->w2, K, M, H, eg, eu, gate->num_cus,
+                                 st));
+        return TCSC_OK;
+    }
+    if (!c.glu.G) {
+        set_error("%s: NULL dG on the MFMA route (M=%d > %d)", who, M, tcsc::kDecodeMaxM);
+        return TCSC_E_ARG;
+    }
+    if (gate->ws_bytes < glu_ws_bytes(gate, M)) {  // grown on first use, as every tcsc_gpu_sgemm* does
+        const int rc = tcsc_gpu_plan_reserve(const_cast<tcsc_gpu_plan*>(gate), M);
+        if (rc != TCSC_OK) return rc;
+    }
+    const_cast<tcsc_gpu_plan*>(gate)->staged_M = -1;
+    for (int r0 = 0; r0 < M; r0 += kMaxLaunchRows) {  // pieces of at most kMaxLaunchRows rows on one workspace
+        const Call q = c.rows(r0, std::min(kMaxLaunchRows, M - r0), K, 1);
+        const MfmaWs w = mfma_ws(kI8, q.M, K, H);
+        if (!gate->ws || gate->ws_bytes < w.bytes) {
+            set_error("%s: workspace of %zu bytes < %zu needed for M=%d", who, gate->ws ? gate->ws_bytes : (size_t)0, w.bytes,
+                      q.M);
+            return TCSC_E_ARG;
+        }
+        char* base = reinterpret_cast<char*>(gate->ws);
+        int8_t* x8 = reinterpret_cast<int8_t*>(base);
+        int* slabs = reinterpret_cast<int*>(base + w.slabs_off);
+        const size_t slab_bytes = gate->ws_bytes - w.slabs_off;
+        const int ld8 = tcsc::mfma8_ldw(K);
+        eg.rscale = eu.rscale = q.xscale;
+        eg.y.Y = q.glu.G;
+        eu.y.Y = q.y.Y;
+        eu.G = q.glu.G;
+        eu.ldg = q.glu.ldg;
+        HIP_TRY(tcsc::mfma8_pack_x(static_cast<const int8_t*>(q.X), q.M, K, x8, ld8, st));
+        HIP_TRY(tcsc::mfma8_gemm_w2(x8, gate->w2, ld8, K, q.M, H, eg, slabs, slab_bytes, st));
+        HIP_TRY(tcsc::mfma8_gemm_w2(x8, up->w2, ld8, K, q.M, H, eu, slabs, slab_bytes, st));
+    }
+    return TCSC_OK;
+}
+
+static Call glu_call(const char* who, const void* X, int xtype, const float* xscale, const tcsc_gpu_plan* up,
+                     const float* cg, const float* bg, const float* cu, const float* bu, float* dG, void* dY, int ytype,
+                     int M, int ldy, int H, int act, void* stream) {
+    Call c = make_call(X, xtype, xscale, bg, y_out(dY, ytype, cg), M, ldy, TCSC_VARIANT_BASIC, 0.f, stream, who);
+    c.glu = tcsc::GluUp{up, cu, bu, dG, H, act};
+    return c;
+}
+
+int tcsc_gpu_sgemm_i8_glu(const tcsc_gpu_plan* gate, const tcsc_gpu_plan* up, const void* dXq, const float* dScale,
+                          const float* dColScaleG, const float* dBG, const float* dColScaleU, const float* dBU, float* dG,
+                          void* dY, int ytype, int M, int ldy, int act, void* stream) {
+    const char* who = "tcsc_gpu_sgemm_i8_glu";
+    const int rc = glu_args(who, gate, up, dBG, dBU, dY, ytype, act);
+    if (rc != TCSC_OK) return rc;
+    return sgemm_glu_i8(gate, glu_call(who, dXq, kI8, dScale, up, dColScaleG, dBG, dColScaleU, dBU, dG, dY, ytype, M, ldy,
+                                       gate->cols, act, stream));
+}
+
+// whether a gated q8 call of M rows fuses the quantizer (norm: and the norm) into the decode launch
+static bool glu_fused(int M, int K, int H, int xtype, bool norm) {
+    if (M < 1 || M > tcsc::kDecodeMaxM) return false;
+    const int knob = qfuse_knob();
+    return knob >= 0 ? knob == 1 : glu_fuse_pays(M, K, H, xtype, norm);
+}
+
+int tcsc_gpu_sgemm_q8_glu(const tcsc_gpu_plan* gate, const tcsc_gpu_plan* up, const void* dX, int xtype,
+                          const float* dGamma, float eps, void* dXq, float* dScale, const float* dColScaleG,
+                          const float* dBG, const float* dColScaleU, const float* dBU, float* dG, void* dY, int ytype,
+                          int M, int ldy, int act, void* stream) {
+    const char* who = "tcsc_gpu_sgemm_q8_glu";
+    if (xtype != TCSC_X_F32 && xtype != TCSC_X_BF16) {
+        set_error("%s: xtype=%d is neither TCSC_X_F32 (0) nor TCSC_X_BF16 (1)", who, xtype);
+        return TCSC_E_ARG;
+    }
+    const bool has_norm = eps != 0.0f;  // eps == 0 exactly: no norm in front
+    if (!has_norm && dGamma) {
+        set_error("%s: dGamma given with eps == 0 (no norm): pass the norm's eps, or a NULL dGamma", who);
+        return TCSC_E_ARG;
+    }
+    int rc = has_norm ? norm_args(who, xtype, eps, gate ? gate->rows : 1) : TCSC_OK;
+    if (rc != TCSC_OK) return rc;
+    rc = glu_args(who, gate, up, dBG, dBU, dY, ytype, act);
+    if (rc != TCSC_OK) return rc;
+    const int K = gate->rows, H = gate->cols;
+    if (M < 0 || ldy < H) {
+        set_error("%s: bad arguments (M=%d ldy=%d cols=%d)", who, M, ldy, H);
+        return TCSC_E_ARG;
+    }
+    if (M == 0 || H == 0) return TCSC_OK;
+    if (!dX || !dScale) {
+        set_error("%s: NULL %s", who, !dX ? "dX" : "dScale");
+        return TCSC_E_ARG;
+    }
+    const RmsNorm norm{dGamma, eps};
+    Call c = glu_call(who, dX, xtype, nullptr, up, dColScaleG, dBG, dColScaleU, dBU, dG, dY, ytype, M, ldy, H, act, stream);
+    if (glu_fused(M, K, H, xtype, has_norm)) {
+        I8Epi eg, eu;
+        eg.B = dBG;
+        eg.y.cscale = dColScaleG;
+        eu.B = dBU;
+        eu.y = c.y;
+        eu.y.cscale = dColScaleU;
+        eu.ldy = ldy;
+        eu.act = act;
+        HIP_TRY(tcsc::decode_glu(tcsc::DecodeX{dX, xtype, dScale, has_norm ? &norm : nullptr}, gate->w2, up->w2, K, M, H, eg,
+                                 eu, gate->num_cus, static_cast<hipStream_t>(stream)));
+        return TCSC_OK;
+    }
+    if (!dXq) {
+        set_error("%s: NULL dXq on a route that is not fused (M=%d)", who, M);
+        return TCSC_E_ARG;
+    }
+    if (M > tcsc::kDecodeMaxM && !dG) {  // ahead of the quantizer's launch
+        set_error("%s: NULL dG on the MFMA route (M=%d > %d)", who, M, tcsc::kDecodeMaxM);
+        return TCSC_E_ARG;
+    }
+    rc = has_norm ? tcsc_gpu_quantize_rows_i8_norm(dX, xtype, dGamma, eps, M, K, dXq, dScale, stream)
+                  : quantize_rows(xtype, dX, M, K, dXq, dScale, stream);
+    if (rc != TCSC_OK) return rc;
+    c.X = dXq;
+    c.xtype = kI8;
+    c.xscale = dScale;
+    return sgemm_glu_i8(gate, c);
+}
+
+int tcsc_gpu_launch_info_glu(const tcsc_gpu_plan* gate, const tcsc_gpu_plan* up, int M, int xtype, int* path, int* slices,
+                             int* fused) {
+    const char* who = "tcsc_gpu_launch_info_glu";
+    if (M < 0 || !path || !slices || !fused || (xtype != TCSC_X_F32 && xtype != TCSC_X_BF16)) {
+        set_error("%s: bad arguments (M=%d xtype=%d)", who, M, xtype);
+        return TCSC_E_ARG;
+    }
+    const int rc = glu_plans(who, gate, up);
+    if (rc != TCSC_OK) return rc;
+    const bool decode = M <= tcsc::kDecodeMaxM;
+    *path = decode ? TCSC_PATH_DECODE : TCSC_PATH_MFMA;
+    *slices = decode ? 1 : tcsc::mfma8_slices(std::min(M, kMaxLaunchRows), gate->cols, gate->rows);
+    *fused = glu_fused(M, gate->rows, gate->cols, xtype, false) ? 1 : 0;
+    return TCSC_OK;
+}
+
 int tcsc_gpu_workspace_bound_i8(int M, int K, int N, size_t* i8_bytes, size_t* f32_bytes) {
     if (M < 0 || K < 1 || N < 0) {
         set_error("tcsc_gpu_workspace_bound_i8: bad arguments (M=%d K=%d N=%d)", M, K, N);

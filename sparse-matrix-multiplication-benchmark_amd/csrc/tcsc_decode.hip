@@ -694,6 +694,365 @@ __global__ void __launch_bounds__(kQWaves * 64) k_decode8q(const TX* __restrict_
         ldy, a);
 }
 
+// ---- the gated forms: act(X Wg) (X Wu) in one launch ---------------
+// k_decode8g and k_decode8qg are k_decode8 and k_decode8q on two images of one
+// K x N shape: a workgroup owns TG column tiles and streams the 2 TG tiles of the
+// gate and the up image against one set of X fragments and one row-sum MFMA per
+// step (decode_load_w / decode_block at T = 2 TG), and the tail multiplies the
+// two values.  k_decode8 and k_decode8q above are left as they are, text and
+// code: their bodies up to the tail are repeated below (decode8g_sums,
+// decode8qg_body) because the same text behind a function boundary moved the
+// register allocation of the existing instantiations (a few VGPRs, and 36 B of
+// scratch back into the T = 4 norm form), which §24 rules out.
+//
+// The gated tail: `red` holds the shares of a workgroup's TG gate
+// tiles (t < TG) and then of its TG up tiles, and one thread per output adds the
+// WAVES shares of Sg and of Su, applies i8_out to each and i8_glu to the pair, and
+// does the one store.  Every thread of the workgroup calls this.
+struct GluEpi {
+    const float *cg, *bg, *cu, *bu;  // the column scales (null: ones) and biases of the gate and up halves
+    int act;
+};
+template <int WAVES, int TG, typename TY, typename RowScale>
+__device__ __forceinline__ void decode_reduce_store_glu(int* red, const i32x4 (&acc)[2 * TG], const i32x4& rs, int wave,
+                                                        int lane, int t0, int M, int N, RowScale row_scale,
+                                                        const GluEpi& e, TY* __restrict__ Y, int ldy) {
+    constexpr int T = 2 * TG;
+#pragma unroll
+    for (int t = 0; t < T; ++t)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) red[(wave * T + t) * 256 + r * 64 + lane] = acc[t][r] - rs[r];
+    __syncthreads();
+    for (int o = threadIdx.x; o < TG * 256; o += WAVES * 64) {
+        const int row = o / (16 * TG), cg = o % (16 * TG), t = cg >> 4, c = cg & 15;
+        const int col = (t0 + t) * kW2Cols + c;
+        if (row >= M || col >= N) continue;
+        int Sg = 0, Su = 0;
+#pragma unroll
+        for (int w = 0; w < WAVES; ++w) {
+            Sg += red[(w * T + t) * 256 + (row & 3) * 64 + (row >> 2) * 16 + c];
+            Su += red[(w * T + TG + t) * 256 + (row & 3) * 64 + (row >> 2) * 16 + c];
+        }
+        const float s = row_scale(row);
+        const float g = i8_out<false>(Sg, s, i8_cscale(e.cg, col), e.bg[col], 0.0f);
+        const float u = i8_out<false>(Su, s, i8_cscale(e.cu, col), e.bu[col], 0.0f);
+        I8Y<TY>::put(Y + (size_t)row * ldy + col, i8_glu(g, u, e.act));
+    }
+}
+
+// The two images of a gated launch: a workgroup's tiles are TG adjacent ones of
+// the gate image (wp[0 .. TG)) and the same TG of the up image (wp[TG .. 2 TG)),
+// decode_tile_ptrs once per image.  t0 is the workgroup's first column tile.
+template <int TG>
+struct DecodeImg2 {
+    static constexpr int T = 2 * TG, kColTiles = TG;
+    const uint32_t *Wg, *Wu;
+    __device__ __forceinline__ void ptrs(int t0, int ntiles, int nkb, int lane, const u32x4* (&wp)[T]) const {
+        const u32x4 *g[TG], *u[TG];
+        decode_tile_ptrs<TG>(Wg, t0, ntiles, nkb, lane, g);
+        decode_tile_ptrs<TG>(Wu, t0, ntiles, nkb, lane, u);
+#pragma unroll
+        for (int t = 0; t < TG; ++t) wp[t] = g[t], wp[TG + t] = u[t];
+    }
+};
+
+// k_decode8's body up to the tail: this wave's share of sum q c of the workgroup's
+// IMG::T tiles in acc and of the row sums in rs.
+template <bool ALIGNED, typename IMG>
+__device__ __forceinline__ void decode8g_sums(const int8_t* __restrict__ X, const IMG& img, int K, int M, int nkb,
+                                             int ntiles, int t0, int wave, int lane, i32x4 (&acc)[IMG::T], i32x4& rs) {
+    constexpr int T = IMG::T;
+    const int xr = lane & 15, kq = lane >> 4;
+    const bool row_ok = xr < M;
+    const int8_t* xrow = X + (size_t)(row_ok ? xr : 0) * K;
+
+    const u32x4* wp[T];
+    img.ptrs(t0, ntiles, nkb, lane, wp);
+
+    auto load = [&](int kb, i32x4 (&xf)[4], u32x4 (&p)[T]) {
+        decode_load_w<T>(wp, kb, p);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int k = kW2Blk * kb + 64 * i + 16 * kq;
+            xf[i] = i32x4{0, 0, 0, 0};
+            if constexpr (ALIGNED) {
+                if (row_ok && k < K) xf[i] = *reinterpret_cast<const i32x4*>(xrow + k);
+            } else {
+                if (row_ok && k < K) {
+#pragma unroll
+                    for (int j = 0; j < 16; ++j) {
+                        const uint32_t b = k + j < K ? (uint32_t)(uint8_t)xrow[k + j] : 0u;
+                        xf[i][j >> 2] |= (int)(b << (8 * (j & 3)));
+                    }
+                }
+            }
+        }
+    };
+
+    rs = i32x4{0, 0, 0, 0};
+#pragma unroll
+    for (int t = 0; t < T; ++t) acc[t] = i32x4{0, 0, 0, 0};
+
+    i32x4 xf[4], xn[4];
+    u32x4 p[T], pn[T];
+    int kb = wave;
+    if (kb < nkb) load(kb, xf, p);
+    while (kb < nkb) {  // uniform
+        const int nx = kb + kDecWaves;
+        if (nx < nkb) load(nx, xn, pn);
+        decode_block<T>(xf, p, acc, rs);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) xf[i] = xn[i];
+#pragma unroll
+        for (int t = 0; t < T; ++t) p[t] = pn[t];
+        kb = nx;
+    }
+}
+
+// The gated k_decode8; act is a uniform branch in the tail.
+template <int TG, bool ALIGNED, typename TY>
+__global__ void __launch_bounds__(kDecWaves * 64) k_decode8g(const int8_t* __restrict__ X,
+                                                              const uint32_t* __restrict__ Wg,
+                                                              const uint32_t* __restrict__ Wu, int K, int M, int N,
+                                                              int nkb, int ntiles, const float* __restrict__ scale,
+                                                              GluEpi e, TY* __restrict__ Y, int ldy) {
+    __shared__ int red[kDecWaves * 2 * TG * 256];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int t0 = blockIdx.x * TG;
+    i32x4 acc[2 * TG], rs;
+    decode8g_sums<ALIGNED>(X, DecodeImg2<TG>{Wg, Wu}, K, M, nkb, ntiles, t0, wave, lane, acc, rs);
+    decode_reduce_store_glu<kDecWaves, TG>(
+        red, acc, rs, wave, lane, t0, M, N, [&](int row) { return scale ? scale[row] : 1.0f; }, e, Y, ldy);
+}
+
+// k_decode8q's body up to the tail -- phase A and the whole of phase B, the norm
+// form included, run once for both matrices: tail(red, s_scale, acc, rs, wave,
+// lane, t0) gets the LDS the partial sums take, the rows' scales in the LDS and
+// this wave's sums.
+template <typename TX, bool ALIGNED, bool NORM, typename IMG, typename Tail>
+__device__ __forceinline__ void decode8qg_body(const TX* __restrict__ X, const IMG& img, int K, int M, int nkb,
+                                              int ntiles, float* __restrict__ scale_out,
+                                              const float* __restrict__ gamma, float eps, Tail tail) {
+    using XS = XSrc<TX>;
+    constexpr int T = IMG::T;
+    constexpr int kThreads = kQWaves * 64, kHalves = kThreads / 32;
+    constexpr int kRedBytes = kQWaves * T * 256 * 4, kStageBytes = kQWaves * kQWaveBytes;
+    // the waves' staging blocks during the K loop, the partial sums after it (and, in the norm form's
+    // phase A, the teams' 512 tree nodes)
+    __shared__ __attribute__((aligned(16))) unsigned char smem[kRedBytes > kStageBytes ? kRedBytes : kStageBytes];
+    __shared__ float s_part[kHalves], s_scale[kDecodeMaxM], s_inv[kDecodeMaxM];
+    __shared__ float s_r[NORM ? kDecodeMaxM : 1];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int t0 = blockIdx.x * IMG::kColTiles;
+
+    // ---- phase A: the row maxima, scales and inverses
+    {
+        int sh = 0;  // Mp = 1 << sh
+        while ((1 << sh) < M) ++sh;
+        const int gl = 9 - sh;  // log2 of the threads per row: 512 .. 32
+        static_assert(kThreads == 512 && kDecodeMaxM == 16, "512 threads over at most 16 rows: half-waves do not mix rows");
+        const int arow = tid >> gl, asub = tid & ((1 << gl) - 1), G = 1 << gl;
+        float am = 0.0f;
+        if constexpr (NORM) {
+            static_assert(kThreads == kNormPartials && kStageBytes >= kNormPartials * 4, "one thread per partial at M = 1");
+            float* part = reinterpret_cast<float*>(smem);
+            float r;
+            switch (sh) {  // uniform
+                case 0: decode_norm_sweeps<TX, ALIGNED, 1>(X, gamma, eps, K, M, tid, part, r, am); break;
+                case 1: decode_norm_sweeps<TX, ALIGNED, 2>(X, gamma, eps, K, M, tid, part, r, am); break;
+                case 2: decode_norm_sweeps<TX, ALIGNED, 4>(X, gamma, eps, K, M, tid, part, r, am); break;
+                case 3: decode_norm_sweeps<TX, ALIGNED, 8>(X, gamma, eps, K, M, tid, part, r, am); break;
+                default: decode_norm_sweeps<TX, ALIGNED, 16>(X, gamma, eps, K, M, tid, part, r, am); break;
+            }
+            if (arow < M && asub == 0) s_r[arow] = r;
+        } else if (arow < M) {
+            const TX* src = X + (size_t)arow * K;
+            if constexpr (ALIGNED) {
+                for (int q = asub; q < K / XS::kVec; q += G) {
+                    float f[XS::kVec];
+                    XS::unpack(*reinterpret_cast<const uint4*>(src + (size_t)q * XS::kVec), 1.0f, f);
+#pragma unroll
+                    for (int e = 0; e < XS::kVec; ++e) am = fmaxf(am, fabsf(f[e]));
+                }
+            } else {
+                for (int k = asub; k < K; k += G) am = fmaxf(am, fabsf(XS::conv(src[k], 1.0f)));
+            }
+        }
+#pragma unroll
+        for (int d = 16; d >= 1; d >>= 1) am = fmaxf(am, __shfl_xor(am, d, 64));  // stays inside the half-wave
+        if ((tid & 31) == 0) s_part[tid >> 5] = am;
+        __syncthreads();
+        if (tid < M) {
+            const int h = G >> 5;  // half-waves per row
+            float m = 0.0f;
+            for (int q = 0; q < h; ++q) m = fmaxf(m, s_part[tid * h + q]);
+            float sc, inv;
+            quant_scales(m, sc, inv);
+            s_scale[tid] = sc;
+            s_inv[tid] = inv;
+            if (blockIdx.x == 0) scale_out[tid] = sc;
+        }
+        __syncthreads();
+    }
+
+    // ---- phase B: k_decode8's loop on fragments quantized through the LDS
+    const int xr = lane & 15, kq = lane >> 4;
+    const bool row_ok = xr < M;
+    const u32x4* wp[T];
+    img.ptrs(t0, ntiles, nkb, lane, wp);
+    unsigned char* qw = smem + wave * kQWaveBytes;
+
+    // the lane's four values of rows j0 .. j0 + 3 of block kb, as raw bits (fp32: one per dword; bf16: two)
+    constexpr int kRaw = (int)sizeof(TX);  // dwords of four values
+    struct Raw {
+        uint32_t w[kRaw];
+    };
+    auto load_rows = [&](int kb, int j0, Raw (&raw)[4]) {
+        const int k = kW2Blk * kb + 4 * lane;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+#pragma unroll
+            for (int d = 0; d < kRaw; ++d) raw[u].w[d] = 0;
+            if (j0 + u >= M || k >= K) continue;  // the first is uniform
+            const TX* src = X + (size_t)(j0 + u) * K + k;
+            if constexpr (ALIGNED) {  // K % 4 == 0: the four values lie wholly below K
+                if constexpr (kRaw == 4) {
+                    const uint4 v = *reinterpret_cast<const uint4*>(src);
+                    raw[u].w[0] = v.x, raw[u].w[1] = v.y, raw[u].w[2] = v.z, raw[u].w[3] = v.w;
+                } else {
+                    const uint2 v = *reinterpret_cast<const uint2*>(src);
+                    raw[u].w[0] = v.x, raw[u].w[1] = v.y;
+                }
+            } else {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    if (k + e >= K) continue;
+                    if constexpr (kRaw == 4)
+                        raw[u].w[e] = __float_as_uint(src[e]);
+                    else
+                        raw[u].w[e >> 1] |= (uint32_t)src[e] << (16 * (e & 1));
+                }
+            }
+        }
+    };
+    // the norm form: gamma of the lane's four k of block kb, shared by all rows (ones past K, unused)
+    [[maybe_unused]] float gm[4] = {1.0f, 1.0f, 1.0f, 1.0f};
+    [[maybe_unused]] const bool gvec = NORM && K % 4 == 0 && (reinterpret_cast<uintptr_t>(gamma) & 15) == 0;
+    auto load_gamma = [&](int kb) {
+        if constexpr (NORM) {
+            const int k = kW2Blk * kb + 4 * lane;
+            if (!gamma) return;  // uniform
+            if (gvec) {          // uniform; the four lie wholly below K or wholly past it
+                if (k < K) {
+                    const float4 g = *reinterpret_cast<const float4*>(gamma + k);
+                    gm[0] = g.x, gm[1] = g.y, gm[2] = g.z, gm[3] = g.w;
+                }
+            } else {
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                    if (k + e < K) gm[e] = gamma[k + e];
+            }
+        }
+    };
+    // quantized and stored: byte e of the dword is value k + e, zero at k + e >= K
+    auto store_rows = [&](int kb, int j0, const Raw (&raw)[4]) {
+        const int k = kW2Blk * kb + 4 * lane;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int row = j0 + u;
+            if (row >= M) break;  // uniform
+            const float inv = s_inv[row];
+            [[maybe_unused]] const float r = NORM ? s_r[row] : 1.0f;
+            uint32_t o = 0;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                float x;
+                if constexpr (kRaw == 4)
+                    x = __uint_as_float(raw[u].w[e]);
+                else
+                    x = XS::conv((TX)(raw[u].w[e >> 1] >> (16 * (e & 1))), 1.0f);
+                if constexpr (NORM) x = gamma ? norm_apply(x, r, gm[e]) : norm_apply(x, r);
+                const uint32_t q = (uint32_t)quant_i8(x, inv) & 0xffu;
+                if (ALIGNED ? k < K : k + e < K) o |= q << (8 * e);
+            }
+            *reinterpret_cast<uint32_t*>(qw + row * kW2Blk + (((lane >> 2) ^ row) << 4) + 4 * (lane & 3)) = o;
+        }
+    };
+    auto stage_rest = [&](int kb, Raw (&raw)[4]) {  // rows 4 .. M - 1, four at a time
+        for (int j0 = 4; j0 < M; j0 += 4) {
+            load_rows(kb, j0, raw);
+            store_rows(kb, j0, raw);
+        }
+    };
+    // the wave's own stores, read by its other lanes: LDS operations of one wave execute in order
+    auto fragments = [&](i32x4 (&xf)[4]) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            xf[i] = i32x4{0, 0, 0, 0};
+            if (row_ok) xf[i] = *reinterpret_cast<const i32x4*>(qw + xr * kW2Blk + (((4 * i + kq) ^ xr) << 4));
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+    };
+
+    i32x4 acc[T], rs = i32x4{0, 0, 0, 0};
+#pragma unroll
+    for (int t = 0; t < T; ++t) acc[t] = i32x4{0, 0, 0, 0};
+
+    i32x4 xf[4];
+    u32x4 p[T], pn[T];
+    Raw raw[4];
+    int kb = wave;
+    if (kb < nkb) {
+        decode_load_w<T>(wp, kb, p);
+        load_gamma(kb);
+        load_rows(kb, 0, raw);
+        store_rows(kb, 0, raw);
+        stage_rest(kb, raw);
+        fragments(xf);
+    }
+    while (kb < nkb) {  // uniform
+        const int nx = kb + kQWaves;
+        if (nx < nkb) {
+            decode_load_w<T>(wp, nx, pn);
+            load_gamma(nx);  // this block's staging is done: its gamma is free
+            load_rows(nx, 0, raw);
+        }
+        decode_block<T>(xf, p, acc, rs);
+        if (nx < nkb) {  // this block's fragments are in registers: its staging block is free
+            store_rows(nx, 0, raw);
+            stage_rest(nx, raw);
+            fragments(xf);
+#pragma unroll
+            for (int t = 0; t < T; ++t) p[t] = pn[t];
+        }
+        kb = nx;
+    }
+
+    __syncthreads();  // every wave is done with its staging block: the partial sums take the memory
+    tail(reinterpret_cast<int*>(smem), s_scale, acc, rs, wave, lane, t0);
+}
+
+// The gated k_decode8q.
+template <typename TX, int TG, bool ALIGNED, typename TY, bool NORM>
+__global__ void __launch_bounds__(kQWaves * 64) k_decode8qg(const TX* __restrict__ X, const uint32_t* __restrict__ Wg,
+                                                            const uint32_t* __restrict__ Wu, int K, int M, int N,
+                                                            int nkb, int ntiles, float* __restrict__ scale_out,
+                                                            GluEpi e, TY* __restrict__ Y, int ldy,
+                                                            const float* __restrict__ gamma, float eps) {
+    decode8qg_body<TX, ALIGNED, NORM>(
+        X, DecodeImg2<TG>{Wg, Wu}, K, M, nkb, ntiles, scale_out, gamma, eps,
+        [&](int* red, const float* s_scale, const i32x4(&acc)[2 * TG], const i32x4& rs, int wave, int lane, int t0) {
+            decode_reduce_store_glu<kQWaves, TG>(
+                red, acc, rs, wave, lane, t0, M, N, [&](int row) { return s_scale[row]; }, e, Y, ldy);
+        });
+}
+
 }  // namespace
 
 hipError_t decode_build_w2(const int8_t* w8, int ncols, int K, int ld8, uint32_t* w2, int* bad, hipStream_t st) {
@@ -813,6 +1172,58 @@ hipError_t decode_gemm(const DecodeX& x, const uint32_t* w2, int K, int M, int N
                                                ntiles, x.scale_out, e.y.cscale, e.B, Y, e.ldy, e.a,
                                                x.norm ? x.norm->gamma : nullptr, x.norm ? x.norm->eps : 0.0f);
                         });
+                    });
+                });
+            });
+        });
+    });
+    return hipGetLastError();
+}
+
+// Column tiles per workgroup of a gated launch: decode_tiles_per_wg's rule on
+// the 2 TG image tiles the workgroup streams (a workgroup holds at most four),
+// the grid being its ceil(tiles / TG) workgroups.
+int decode_glu_tiles_per_wg(int M, int N, int num_cus) {
+    if (kDecTiles) return kDecTiles == 4 ? 2 : 1;
+    const int ntiles = w2_col_tiles(N), cus = num_cus > 0 ? num_cus : 256;
+    int T = M > 8 ? 4 : 2;  // the rule's 1 is below one tile of each image
+    while (T > 2 && (ntiles + T / 2 - 1) / (T / 2) < cus) T >>= 1;
+    return T / 2;
+}
+
+// The gated decode launch (tcsc_internal.h): decode_gemm's dispatch without the
+// PReLU axis and over TG in {1, 2}; the activation is a kernel argument.
+hipError_t decode_glu(const DecodeX& x, const uint32_t* wg, const uint32_t* wu, int K, int M, int N, const I8Epi& gate,
+                      const I8Epi& up, int num_cus, hipStream_t st) {
+    const bool quant = x.xtype != kI8;
+    if (M < 1 || M > kDecodeMaxM || K < 1 || K >= kDecodeMaxK || N < 1 || !x.X || !wg || !wu || (quant && !x.scale_out) ||
+        !gate.B || !up.B || !up.y.Y || up.ldy < N || (up.act != kGluRelu2 && up.act != kGluSilu))
+        return hipErrorInvalidValue;
+    const int ntiles = w2_col_tiles(N), nkb = w2_kblocks(K), tiles = decode_glu_tiles_per_wg(M, N, num_cus);
+    const dim3 grid((ntiles + tiles - 1) / tiles);
+    const bool aligned = x.xtype == kI8    ? XSrc<int8_t>::vec_ok(static_cast<const int8_t*>(x.X), K)
+                         : x.xtype == kBf16 ? XSrc<uint16_t>::vec_ok(static_cast<const uint16_t*>(x.X), K)
+                                            : XSrc<float>::vec_ok(static_cast<const float*>(x.X), K);
+    const GluEpi e{gate.y.cscale, gate.B, up.y.cscale, up.B, up.act};
+    with_elem(up.y.ytype == kYBf16, [&](auto ty) {
+        using TY = typename decltype(ty)::type;
+        TY* Y = static_cast<TY*>(up.y.Y);
+        with_bool(tiles == 2, [&](auto t2) {
+            with_bool(aligned, [&](auto al) {
+                constexpr int TG = decltype(t2)::value ? 2 : 1;
+                constexpr bool AL = decltype(al)::value;
+                if (!quant) {
+                    hipLaunchKernelGGL((k_decode8g<TG, AL, TY>), grid, dim3(kDecWaves * 64), 0, st,
+                                       static_cast<const int8_t*>(x.X), wg, wu, K, M, N, nkb, ntiles, up.rscale, e, Y,
+                                       up.ldy);
+                    return;
+                }
+                with_elem(x.xtype == kBf16, [&](auto tx) {
+                    using TX = typename decltype(tx)::type;
+                    with_bool(x.norm != nullptr, [&](auto nm) {
+                        hipLaunchKernelGGL((k_decode8qg<TX, TG, AL, TY, decltype(nm)::value>), grid, dim3(kQWaves * 64),
+                                           0, st, static_cast<const TX*>(x.X), wg, wu, K, M, N, nkb, ntiles, x.scale_out,
+                                           e, Y, up.ldy, x.norm ? x.norm->gamma : nullptr, x.norm ? x.norm->eps : 0.0f);
                     });
                 });
             });

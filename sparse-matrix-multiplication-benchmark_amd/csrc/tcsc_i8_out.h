@@ -1,10 +1,14 @@
 // tcsc_i8_out.h -- the epilogue arithmetic of the int8 call (DESIGN.md §16,
 // §21), shared by every kernel that turns an exact i32 sum into Y: k_gemm8,
 // k_gemm8w2 and k_reduce_i8 (tcsc_mfma.hip), k_decode8 and k_decode8q
-// (tcsc_decode.hip).  One definition, so the paths give the same bits.
+// (tcsc_decode.hip), and the gate of the gated forms (§24: k_decode8g,
+// k_decode8qg, gemm8_store and k_reduce_i8 with GLU).  One definition, so the
+// paths give the same bits.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include "tcsc_internal.h"
 
 namespace tcsc {
 
@@ -20,6 +24,25 @@ __device__ __forceinline__ float i8_out(int S, float s, float c, float b, float 
     const float q = p * c;
     const float v = q + b;
     return PRELU ? ((v < 0.0f) ? a * v : v) : v;
+}
+
+// The gate of a gated call: g and u are i8_out<false> of the gate
+// and up sums, act the run-time activation (enum tcsc_glu_act) as a uniform
+// branch.  Every step is one rounded fp32 operation, none contracted:
+//   kGluRelu2  r = g < 0 ? 0 : g;  fl(fl(r r) u)           torch relu(g).square() * u
+//   kGluSilu   fl(fl(g / fl(1 + expf(-g))) u)              IEEE division, the math library's expf
+// (a very negative g gives expf = inf, g / inf = -0 and a zero of u's sign).
+__device__ __forceinline__ float i8_glu(float g, float u, int act) {
+#pragma clang fp contract(off)
+    if (act == kGluRelu2) {
+        const float r = g < 0.0f ? 0.0f : g;
+        const float r2 = r * r;
+        return r2 * u;
+    }
+    const float e = expf(-g);
+    const float d = 1.0f + e;
+    const float s = __fdiv_rn(g, d);
+    return s * u;
 }
 
 // c[j] of a call (null: all ones)

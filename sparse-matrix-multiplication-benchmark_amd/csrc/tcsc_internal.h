@@ -223,7 +223,14 @@ struct I8Epi {
     int ldy = 0;  // in y's elements
     bool prelu = false;
     float a = 0.f;
+    // The up half of a gated call: Y[m, j] = i8_glu(g, u, act) with u this
+    // epilogue's value (no PReLU) and g = G[m * ldg + j], the gate half's fp32 output
+    // (k_gemm8w2, k_reduce_i8); the decode launch computes g itself and reads act only.
+    const float* G = nullptr;
+    int ldg = 0;
+    int act = 0;  // kGluRelu2 / kGluSilu: TCSC_GLU_RELU2 / TCSC_GLU_SILU
 };
+enum { kGluRelu2 = 0, kGluSilu = 1 };  // the gate activations of i8_glu (tcsc_i8_out.h)
 // The RMSNorm in front of a quantizer; gamma null = all ones
 struct RmsNorm {
     const float* gamma = nullptr;
@@ -548,7 +555,9 @@ hipError_t w2_unpack_col_start(const int* offp, const int* offn, int ncols, int 
 hipError_t w2_unpack_fill(const uint32_t* w2, int ncols, int K, const int* offp, const int* offn, int* rip, int* rin,
                           hipStream_t st);
 // k_gemm8w2 (tcsc_mfma.hip): mfma8_gemm with B read from the
-// 2-bit image; the same tiles, K split (mfma8_slices), slabs and bits
+// 2-bit image; the same tiles, K split (mfma8_slices), slabs and bits.  With
+// e.G set it is the up half of a gated call: the store, or the
+// reduce of a split K, writes i8_glu(G[m, j], value, e.act); e.prelu must be off
 hipError_t mfma8_gemm_w2(const int8_t* x8, const uint32_t* w2, int ld8, int K, int M, int N, const I8Epi& e, int* slabs,
                          size_t slab_bytes, hipStream_t st);
 // column tiles per workgroup of a k_decode8 launch (1, 2 or 4)
@@ -563,6 +572,15 @@ int decode_tiles_per_wg(int M, int N, int num_cus);
 // The one dispatch over TX x TY x T x ALIGNED x PRELU x NORM is inside.
 hipError_t decode_gemm(const DecodeX& x, const uint32_t* w2, int K, int M, int N, const I8Epi& e, int num_cus,
                        hipStream_t st);
+// The gated decode launch, k_decode8g / k_decode8qg: one launch
+// that streams the images wg and wu (both K x N) against one X and stores
+// Y = i8_glu(g, u, up.act), g and u being i8_out on the two sums with `gate`'s and
+// `up`'s column scales and biases (neither's PReLU is read).  Y, its type and
+// pitch are up's; x as in decode_gemm.  decode_glu_tiles_per_wg: the column
+// tiles TG of a workgroup (1 or 2; it streams 2 TG image tiles).
+int decode_glu_tiles_per_wg(int M, int N, int num_cus);
+hipError_t decode_glu(const DecodeX& x, const uint32_t* wg, const uint32_t* wu, int K, int M, int N, const I8Epi& gate,
+                      const I8Epi& up, int num_cus, hipStream_t st);
 
 // Rewrites the flagged rows in k_stream's fast order (no-op when none is).
 hipError_t mfma_fixup(const uint16_t* x3, int M, int K, int ldk, const int* cq, const int* crq, int ncols,

@@ -773,12 +773,16 @@ __global__ void __launch_bounds__(256) k_w8_from(const uint16_t* __restrict__ WT
 // Split K: the i32 slabs added as integers (any order gives the same sum),
 // then the unsplit epilogue's arithmetic.  VEC: 4 columns per thread (N % 4 ==
 // 0, ldy % 4 == 0, 16-B aligned slabs, Y aligned to 4 of its elements), all
-// slices' loads in flight.  TY: float, or uint16_t for a bf16 Y (§21).
-template <bool PRELU, bool VEC, typename TY>
+// slices' loads in flight.  TY: float, or uint16_t for a bf16 Y (§21).  GLU (§24):
+// the value is the up half of a gated call and Y = i8_glu(G[row, col], value, act);
+// VEC then asks 16-B alignment and ldg % 4 == 0 of G too.
+template <bool PRELU, bool VEC, typename TY, bool GLU = false>
 __global__ void __launch_bounds__(256) k_reduce_i8(const int* __restrict__ ws, int slices, int M, int N,
                                                    const float* __restrict__ scale,
                                                    const float* __restrict__ cscale, const float* __restrict__ Bias,
-                                                   TY* __restrict__ Y, int ldy, float a) {
+                                                   TY* __restrict__ Y, int ldy, float a,
+                                                   const float* __restrict__ G = nullptr, int ldg = 0, int act = 0) {
+    static_assert(!(GLU && PRELU), "the halves of a gated call have no PReLU");
     constexpr int W = VEC ? 4 : 1;
     const int nq = N / W;
     const long long total = (long long)M * nq;
@@ -808,6 +812,16 @@ __global__ void __launch_bounds__(256) k_reduce_i8(const int* __restrict__ ws, i
                 if (s < slices) t += p[s][u];
             v[u] = i8_out<PRELU>(t, sc, i8_cscale(cscale, col + u), Bias[col + u], a);
         }
+        if constexpr (GLU) {
+            const float* gp = G + (size_t)row * ldg + col;
+            if constexpr (VEC) {
+                const f32x4 g = *reinterpret_cast<const f32x4*>(gp);
+#pragma unroll
+                for (int u = 0; u < 4; ++u) v[u] = i8_glu(g[u], v[u], act);
+            } else {
+                v[0] = i8_glu(gp[0], v[0], act);
+            }
+        }
         TY* dst = Y + (size_t)row * ldy + col;
         if constexpr (VEC)
             I8Y<TY>::put4_nt(dst, v[0], v[1], v[2], v[3]);
@@ -822,12 +836,16 @@ __global__ void __launch_bounds__(256) k_reduce_i8(const int* __restrict__ ws, i
 // bias[col]), as floats or (TY = uint16_t) bf16 bits.  A lane's four columns go
 // out as one store -- 16 B of floats, 8 B of bf16 -- where Y is aligned to four
 // of its elements and ldy % 4 == 0, else element by element, each guarded.
-template <int WM, int WN, int FI, int FJ, bool PRELU, bool PARTIAL, int LDSB, typename TY>
+// GLU (§24): the value is the up half of a gated call, and what is stored is
+// i8_glu(G[row, col], value, act), G the gate half's fp32 output at pitch ldg.
+template <int WM, int WN, int FI, int FJ, bool PRELU, bool PARTIAL, int LDSB, bool GLU = false, typename TY>
 __device__ __forceinline__ void gemm8_store(const i32x4 (&acc)[FI][FJ], char* lds, int lane, int wr, int wc, int m0,
                                             int n0, int M, int N, const float* __restrict__ scale,
                                             const float* __restrict__ cscale, const float* __restrict__ bias,
-                                            TY* __restrict__ Y, int ldy, float a) {
+                                            TY* __restrict__ Y, int ldy, float a,
+                                            const float* __restrict__ G = nullptr, int ldg = 0, int act = 0) {
     static_assert(!PARTIAL || std::is_same<TY, float>::value, "the i32 slabs travel as the float instantiation");
+    static_assert(!GLU || (!PARTIAL && !PRELU), "a gated store is a final one, and its halves have no PReLU");
     constexpr int TM = WM * FI * 16, TN = WN * FJ * 16, NW = WM * WN;
     constexpr int PR = 64, SROW = TN + 4, LPR = TN / 4;  // rows per pass, staged row, lanes per row
     static_assert(PR * SROW * 4 <= LDSB && TM % PR == 0 && (64 % LPR == 0 || LPR % 64 == 0), "epilogue staging");
@@ -876,6 +894,12 @@ __device__ __forceinline__ void gemm8_store(const i32x4 (&acc)[FI][FJ], char* ld
                 f32x4 v;
 #pragma unroll
                 for (int u = 0; u < 4; ++u) v[u] = i8_out<PRELU>(s[u], sc, cq[u], bq[u], a);
+                if constexpr (GLU) {
+                    const float* gp = G + (size_t)row * ldg + col;
+#pragma unroll
+                    for (int u = 0; u < 4; ++u)
+                        if (col + u < N) v[u] = i8_glu(gp[u], v[u], act);
+                }
                 TY* dst = Y + (size_t)row * ldy + col;
                 if (vec && col + 3 < N) {
                     I8Y<TY>::put4_nt(dst, v[0], v[1], v[2], v[3]);
@@ -1052,12 +1076,13 @@ __global__ void __launch_bounds__(WM * WN * 64) k_gemm8(const int8_t* __restrict
 // epilogue are k_gemm8's.  A workgroup's column tiles past the matrix read the
 // last tile again and are not stored; an odd count of 128-k blocks ends the
 // loop inside the last 256-k image block, whose second half is never read.
-template <int WN, int FI, int FJ, bool PRELU, bool PARTIAL, int BS = 2, typename TY = float>
+template <int WN, int FI, int FJ, bool PRELU, bool PARTIAL, int BS = 2, typename TY = float, bool GLU = false>
 __global__ void __launch_bounds__(WN * 64) k_gemm8w2(const int8_t* __restrict__ A, const uint32_t* __restrict__ W2,
                                                     int ldk, int M, int N, int nblk, int nkb, int ntiles,
                                                     const float* __restrict__ scale, const float* __restrict__ cscale,
                                                     const float* __restrict__ bias, TY* __restrict__ Y, int ldy,
-                                                    float a, int tiles_m, int tiles_n, int gm, int bps) {
+                                                    float a, int tiles_m, int tiles_n, int gm, int bps,
+                                                    const float* __restrict__ G = nullptr, int ldg = 0, int act = 0) {
     static_assert(!(PARTIAL && PRELU), "a partial slab carries raw sums");
     constexpr int TM = FI * 16, TN = WN * FJ * 16, NW = WN;
     constexpr int PA = TM / 8, ASLOT = PA * 1024, PAW = PA / NW;
@@ -1197,8 +1222,8 @@ __global__ void __launch_bounds__(WN * 64) k_gemm8w2(const int8_t* __restrict__ 
     __syncthreads();
 
     TY* out = PARTIAL ? reinterpret_cast<TY*>(reinterpret_cast<int*>(Y) + (size_t)blockIdx.y * M * ldy) : Y;
-    gemm8_store<1, WN, FI, FJ, PRELU, PARTIAL, LDSB>(acc, lds, lane, 0, wave, m0, n0, M, N, scale, cscale, bias, out, ldy,
-                                                     a);
+    gemm8_store<1, WN, FI, FJ, PRELU, PARTIAL, LDSB, GLU>(acc, lds, lane, 0, wave, m0, n0, M, N, scale, cscale, bias, out,
+                                                          ldy, a, G, ldg, act);
 }
 
 // tcsc_gpu_quantize_rows_i8{,_bf16}: per row, amax = max |x|, scale = amax /
@@ -1671,9 +1696,14 @@ static hipError_t launch_reduce_i8(const int* slabs, int slices, int M, int N, c
         using TY = typename decltype(ty)::type;
         TY* Y = static_cast<TY*>(e.y.Y);
         const bool vec = N % 4 == 0 && e.ldy % 4 == 0 && (reinterpret_cast<uintptr_t>(Y) & (4 * sizeof(TY) - 1)) == 0 &&
-                         aligned16(slabs);
+                         aligned16(slabs) && (!e.G || (e.ldg % 4 == 0 && aligned16(e.G)));
         const long long n = (long long)M * (vec ? N / 4 : N);
         return with_bool(vec, [&](auto v) {
+            if (e.G) {  // the up half of a gated call (never with a PReLU: mfma8_gemm_w2 refuses it)
+                hipLaunchKernelGGL((k_reduce_i8<false, decltype(v)::value, TY, true>), dim3(grid_of(n, 256)), dim3(256), 0,
+                                   st, slabs, slices, M, N, e.rscale, e.y.cscale, e.B, Y, e.ldy, e.a, e.G, e.ldg, e.act);
+                return hipGetLastError();
+            }
             return with_bool(e.prelu, [&](auto pr) {
                 hipLaunchKernelGGL((k_reduce_i8<decltype(pr)::value, decltype(v)::value, TY>), dim3(grid_of(n, 256)),
                                    dim3(256), 0, st, slabs, slices, M, N, e.rscale, e.y.cscale, e.B, Y, e.ldy, e.a);
@@ -1728,7 +1758,7 @@ static hipError_t launch_gemm8_t(const int8_t* x8, const int8_t* w8, int ld8, in
 // k_gemm8w2 on k_gemm8's three grids, slices and blocks per slice: 128 x 512
 // (8 waves of 128 x 64), 64 x 256 (4 waves of 64 x 64) and 128 x 128 (4 waves
 // of 128 x 32), so mfma_tiles and mfma8_slices count its workgroups as they are.
-template <bool PRELU, typename TY>
+template <bool PRELU, typename TY, bool GLU = false>
 static hipError_t launch_gemm8w2_t(const int8_t* x8, const uint32_t* w2, int ld8, int nblk, int K, int M, int N,
                                    const I8Epi& epi, int* slabs, int slices, hipStream_t st) {
     constexpr int kGm = 4;
@@ -1743,16 +1773,16 @@ static hipError_t launch_gemm8w2_t(const int8_t* x8, const uint32_t* w2, int ld8
         const int tm = (M + 127) / 128, tn = (N + 511) / 512;
         const int gm = std::min(kGm, tm);
         if (slices <= 1)
-            hipLaunchKernelGGL((k_gemm8w2<8, 8, 4, PRELU, false, 1, TY>), dim3(tm * tn), dim3(512), 0, st, x8, w2, ld8, M, N, nblk,
-                               nkb, nt, scale, cscale, B, Y, ldy, a, tm, tn, gm, nblk);
+            hipLaunchKernelGGL((k_gemm8w2<8, 8, 4, PRELU, false, 1, TY, GLU>), dim3(tm * tn), dim3(512), 0, st, x8, w2, ld8, M, N,
+                               nblk, nkb, nt, scale, cscale, B, Y, ldy, a, tm, tn, gm, nblk, epi.G, epi.ldg, epi.act);
         else
             hipLaunchKernelGGL((k_gemm8w2<8, 8, 4, false, true, 1>), dim3(tm * tn, slices), dim3(512), 0, st, x8, w2, ld8, M,
                                N, nblk, nkb, nt, nullptr, nullptr, nullptr, sl, N, 0.0f, tm, tn, gm, bps);
     } else if (mfma_narrow_tiles(M, N)) {
         const int tn = (N + 255) / 256;
         if (slices <= 1)
-            hipLaunchKernelGGL((k_gemm8w2<4, 4, 4, PRELU, false, 2, TY>), dim3(tn), dim3(256), 0, st, x8, w2, ld8, M, N, nblk, nkb,
-                               nt, scale, cscale, B, Y, ldy, a, 1, tn, 1, nblk);
+            hipLaunchKernelGGL((k_gemm8w2<4, 4, 4, PRELU, false, 2, TY, GLU>), dim3(tn), dim3(256), 0, st, x8, w2, ld8, M, N, nblk,
+                               nkb, nt, scale, cscale, B, Y, ldy, a, 1, tn, 1, nblk, epi.G, epi.ldg, epi.act);
         else
             hipLaunchKernelGGL((k_gemm8w2<4, 4, 4, false, true>), dim3(tn, slices), dim3(256), 0, st, x8, w2, ld8, M, N,
                                nblk, nkb, nt, nullptr, nullptr, nullptr, sl, N, 0.0f, 1, tn, 1, bps);
@@ -1760,8 +1790,8 @@ static hipError_t launch_gemm8w2_t(const int8_t* x8, const uint32_t* w2, int ld8
         const int tm = (M + 127) / 128, tn = (N + 127) / 128;
         const int gm = std::min(kGm, tm);
         if (slices <= 1)
-            hipLaunchKernelGGL((k_gemm8w2<4, 8, 2, PRELU, false, 2, TY>), dim3(tm * tn), dim3(256), 0, st, x8, w2, ld8, M, N, nblk,
-                               nkb, nt, scale, cscale, B, Y, ldy, a, tm, tn, gm, nblk);
+            hipLaunchKernelGGL((k_gemm8w2<4, 8, 2, PRELU, false, 2, TY, GLU>), dim3(tm * tn), dim3(256), 0, st, x8, w2, ld8, M, N,
+                               nblk, nkb, nt, scale, cscale, B, Y, ldy, a, tm, tn, gm, nblk, epi.G, epi.ldg, epi.act);
         else
             hipLaunchKernelGGL((k_gemm8w2<4, 8, 2, false, true>), dim3(tm * tn, slices), dim3(256), 0, st, x8, w2, ld8, M,
                                N, nblk, nkb, nt, nullptr, nullptr, nullptr, sl, N, 0.0f, tm, tn, gm, bps);
@@ -1781,7 +1811,7 @@ hipError_t mfma8_gemm(const int8_t* x8, const int8_t* w8, int ld8, int K, int M,
                       size_t slab_bytes, hipStream_t st) {
     if (M <= 0 || N <= 0) return hipSuccess;
     const int nblk = mfma8_nblk(K);
-    if (nblk < 1 || ld8 != mfma8_ldw(K) || !e.y.Y) return hipErrorInvalidValue;
+    if (nblk < 1 || ld8 != mfma8_ldw(K) || !e.y.Y || e.G) return hipErrorInvalidValue;  // a gated call runs k_gemm8w2
     const int slices = mfma8_slices(M, N, K);
     if (slices > 1 && (!slabs || slab_bytes < mfma8_slab_bytes(M, N, K))) return hipErrorInvalidValue;
     return with_i8_epi(e, [&](auto ty, auto pr) {
@@ -1796,6 +1826,12 @@ hipError_t mfma8_gemm_w2(const int8_t* x8, const uint32_t* w2, int ld8, int K, i
     if (nblk < 1 || ld8 != mfma8_ldw(K) || K >= kDecodeMaxK || !w2 || !e.y.Y) return hipErrorInvalidValue;
     const int slices = mfma8_slices(M, N, K);
     if (slices > 1 && (!slabs || slab_bytes < mfma8_slab_bytes(M, N, K))) return hipErrorInvalidValue;
+    if (e.G) {  // the up half of a gated call: no PReLU, G at a pitch of at least N, a known activation
+        if (e.prelu || e.ldg < N || (e.act != kGluRelu2 && e.act != kGluSilu)) return hipErrorInvalidValue;
+        return with_elem(e.y.ytype == kYBf16, [&](auto ty) {
+            return launch_gemm8w2_t<false, typename decltype(ty)::type, true>(x8, w2, ld8, nblk, K, M, N, e, slabs, slices, st);
+        });
+    }
     return with_i8_epi(e, [&](auto ty, auto pr) {
         return launch_gemm8w2_t<decltype(pr)::value, typename decltype(ty)::type>(x8, w2, ld8, nblk, K, M, N, e, slabs, slices,
                                                                                st);

@@ -98,6 +98,17 @@ Route route_call(const tcsc_gpu_plan* p, int M, int dt, size_t ws_avail, const R
 // nullptr}, and the int8 call's decode and MFMA routes alone write anything
 // else; ldy is in y's elements.  `who` is the name the call gives itself in
 // messages (null: the activation type's own entry point).
+// The up half of a gated call (tcsc_gpu_sgemm_i8_glu): the call's own plan, B and
+// y.cscale are the gate's, Y = i8_glu(gate value, up value, act) in y's type.  G is the caller's
+// scratch for the gate values of the MFMA route, M x ldg floats.  up == null: not a gated call.
+struct GluUp {
+    const tcsc_gpu_plan* up = nullptr;
+    const float* cscale = nullptr;
+    const float* B = nullptr;
+    float* G = nullptr;
+    int ldg = 0;
+    int act = 0;
+};
 struct Call {
     const void* X = nullptr;
     int xtype = kF32;
@@ -108,13 +119,15 @@ struct Call {
     float a = 0.f;
     void* stream = nullptr;
     const char* who = nullptr;
+    GluUp glu;
     // rows [r0, r0 + n) of a call on a matrix of K rows as a call of their own: X (x_elem bytes an
-    // element), the row scales and Y (by the element size of its type) advance by r0 rows
+    // element), the row scales, Y (by the element size of its type) and a gated call's G advance by r0 rows
     Call rows(int r0, int n, int K, size_t x_elem) const {
         Call c = *this;
         c.X = X ? static_cast<const char*>(X) + (size_t)r0 * K * x_elem : nullptr;
         c.xscale = xscale ? xscale + r0 : nullptr;
         c.y = y.rows_on((size_t)r0, ldy);
+        c.glu.G = glu.G ? glu.G + (size_t)r0 * glu.ldg : nullptr;
         c.M = n;
         return c;
     }

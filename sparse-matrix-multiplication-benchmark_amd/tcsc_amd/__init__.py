@@ -60,6 +60,7 @@ EXPORTED_SYMBOLS = (
     "tcsc_gpu_sgemm_i8_out", "tcsc_gpu_sgemm_q8_out",
     "tcsc_gpu_rmsnorm_rows", "tcsc_gpu_quantize_rows_i8_norm", "tcsc_gpu_sgemm_q8_norm",
     "tcsc_gpu_launch_info_q8_norm", "tcsc_gpu_norm_fuse_pays",
+    "tcsc_gpu_sgemm_i8_glu", "tcsc_gpu_sgemm_q8_glu", "tcsc_gpu_launch_info_glu", "tcsc_gpu_glu_fuse_pays",
     # include/sparse/bcsr.h
     "bcsr_from_dense", "bcsr_sgemm_basic", "bcsr_sgemm_prelu_basic", "bcsr_sgemm_avx", "bcsr_sgemm_prelu_avx",
     "bcsr_sgemm_avx2", "bcsr_free",
@@ -193,6 +194,10 @@ def lib():
     L.tcsc_gpu_sgemm_q8_norm.argtypes = [vp, vp, i, vp, f, vp, vp, vp, vp, vp, i, i, i, i, f, vp]
     L.tcsc_gpu_launch_info_q8_norm.argtypes = [vp, i, i, C.POINTER(i), C.POINTER(i), C.POINTER(i)]
     L.tcsc_gpu_norm_fuse_pays.argtypes = [i, i, i, i]
+    L.tcsc_gpu_sgemm_i8_glu.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, i, vp]
+    L.tcsc_gpu_sgemm_q8_glu.argtypes = [vp, vp, vp, i, vp, f, vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, i, vp]
+    L.tcsc_gpu_launch_info_glu.argtypes = [vp, vp, i, i, C.POINTER(i), C.POINTER(i), C.POINTER(i)]
+    L.tcsc_gpu_glu_fuse_pays.argtypes = [i, i, i, i, i]
     L.tcsc_gpu_prepare_x.argtypes = [vp, vp, i, vp]
     L.tcsc_gpu_sgemm_prepared.argtypes = [vp, vp, vp, i, i, i, f, vp]
     L.tcsc_gpu_from_dense.argtypes = [vp, i, i, vp, vp, vp, vp, C.POINTER(i), C.POINTER(i), vp]
@@ -946,6 +951,76 @@ def norm_fuse_pays(M: int, K: int, N: int, dtype="f32") -> bool:
     arithmetic): whether :meth:`Plan.sgemm_q8_norm` of M rows of that dtype on a K x N decode route runs one
     kernel."""
     return bool(lib().tcsc_gpu_norm_fuse_pays(int(M), int(K), int(N), _xtype(dtype)))
+
+
+GLU_ACT_ID = {"relu2": 0, "silu": 1}
+
+
+def _glu_act(act) -> int:
+    """enum tcsc_glu_act of 'relu2' / 'silu', or the enum's own integer (passed on as it is)."""
+    if isinstance(act, int):
+        return act
+    if act in GLU_ACT_ID:
+        return GLU_ACT_ID[act]
+    raise TcscError(f"the gate activation must be one of {sorted(GLU_ACT_ID)}, got {act!r}")
+
+
+def launch_info_glu(gate_plan, up_plan, M: int, dtype="f32") -> tuple[str, int, bool]:
+    """(path, K slices, fused) of a gated call of M rows (tcsc_gpu_launch_info_glu): 'decode' up to 16 rows and
+    'mfma' above; fused: whether :func:`sgemm_q8_glu` of that dtype, without a norm, quantizes inside the launch."""
+    path, slices, fused = C.c_int(), C.c_int(), C.c_int()
+    _check(lib().tcsc_gpu_launch_info_glu(gate_plan.handle, up_plan.handle, int(M), _xtype(dtype), C.byref(path),
+                                          C.byref(slices), C.byref(fused)), "tcsc_gpu_launch_info_glu")
+    return ("gather", "fused", "mfma", "small", "decode")[path.value], slices.value, bool(fused.value)
+
+
+def _glu_scratch(gate_plan, up_plan, M: int, Y, G):
+    """dG of a gated call: the caller's, or M x cols floats beside a tensor Y where the route is the MFMA one."""
+    if G is not None or launch_info_glu(gate_plan, up_plan, M)[0] != "mfma" or not hasattr(Y, "new_empty"):
+        return G
+    import torch
+
+    return Y.new_empty((int(M), gate_plan.info()["cols"]), dtype=torch.float32)
+
+
+def sgemm_i8_glu(gate_plan, up_plan, Xq, scale, bias_gate, bias_up, Y, M: int, ldy: int, act="relu2",
+                 col_scale_gate=None, col_scale_up=None, G=None, stream: int = 0, ytype=None) -> None:
+    """Y = act(g) * u for int8 activations (tcsc_gpu_sgemm_i8_glu): g and u are :meth:`Plan.sgemm_i8` of Xq on the
+    gate and the up plan (same K and cols, both with the 2-bit image) with their own column scales and biases
+    and no PReLU; act is 'relu2' (relu(g)^2) or 'silu'.  Y is fp32 or bf16 by the tensor's dtype (a raw pointer:
+    ytype).  G, the fp32 scratch for g (M x cols) on the MFMA route (M > 16), is allocated here when it is None
+    and Y is a tensor; a captured call passes its own."""
+    yt = _ytype_of(Y) if ytype is None else _ytype(ytype)
+    G = _glu_scratch(gate_plan, up_plan, M, Y, G)
+    _check(lib().tcsc_gpu_sgemm_i8_glu(gate_plan.handle, up_plan.handle, C.c_void_p(_ptr(Xq)), C.c_void_p(_ptr(scale)),
+                                       C.c_void_p(_ptr(col_scale_gate)), C.c_void_p(_ptr(bias_gate)),
+                                       C.c_void_p(_ptr(col_scale_up)), C.c_void_p(_ptr(bias_up)), C.c_void_p(_ptr(G)),
+                                       C.c_void_p(_ptr(Y)), yt, int(M), int(ldy), _glu_act(act), C.c_void_p(stream)),
+           "tcsc_gpu_sgemm_i8_glu")
+
+
+def sgemm_q8_glu(gate_plan, up_plan, X, Xq, scale, bias_gate, bias_up, Y, M: int, ldy: int, act="relu2",
+                 col_scale_gate=None, col_scale_up=None, norm_weight=None, norm_eps=None, G=None, stream: int = 0,
+                 xtype=None, ytype=None) -> None:
+    """The quantizer and :func:`sgemm_i8_glu` in one call (tcsc_gpu_sgemm_q8_glu): X is M x K fp32 or bf16, scale
+    (M floats) is written and Xq (M x K int8) is scratch, untouched where the call is fused
+    (:func:`launch_info_glu`).  norm_eps None: no norm (norm_weight must be None too); otherwise the RMSNorm of
+    :meth:`Plan.sgemm_q8_norm` runs in front of the quantizer."""
+    xt = _xtype_of(X) if xtype is None else _xtype(xtype)
+    yt = _ytype_of(Y) if ytype is None else _ytype(ytype)
+    G = _glu_scratch(gate_plan, up_plan, M, Y, G)
+    _check(lib().tcsc_gpu_sgemm_q8_glu(gate_plan.handle, up_plan.handle, C.c_void_p(_ptr(X)), xt,
+                                       C.c_void_p(_ptr(norm_weight)), 0.0 if norm_eps is None else float(norm_eps),
+                                       C.c_void_p(_ptr(Xq)), C.c_void_p(_ptr(scale)), C.c_void_p(_ptr(col_scale_gate)),
+                                       C.c_void_p(_ptr(bias_gate)), C.c_void_p(_ptr(col_scale_up)),
+                                       C.c_void_p(_ptr(bias_up)), C.c_void_p(_ptr(G)), C.c_void_p(_ptr(Y)), yt, int(M),
+                                       int(ldy), _glu_act(act), C.c_void_p(stream)), "tcsc_gpu_sgemm_q8_glu")
+
+
+def glu_fuse_pays(M: int, K: int, N: int, dtype="f32", norm: bool = False) -> bool:
+    """The default rule for fusing the quantizer (norm: and the norm) into the gated decode launch
+    (tcsc_gpu_glu_fuse_pays; host arithmetic)."""
+    return bool(lib().tcsc_gpu_glu_fuse_pays(int(M), int(K), int(N), _xtype(dtype), int(bool(norm))))
 
 
 def w2_image_bytes(K: int, N: int) -> int:

@@ -19,7 +19,7 @@ import numpy as np
 
 from . import Plan, TcscError, TcscMatrix, prelu_backward, ternarize_absmean, w2_image_bytes
 
-__all__ = ["TernaryLinear", "PackedTernaryLinear"]
+__all__ = ["TernaryLinear", "PackedTernaryLinear", "PackedTernaryGLU", "PackedTernaryMLP"]
 
 _classes = None
 
@@ -414,7 +414,186 @@ def _define():
                     + ("" if self.norm_eps is None else f", norm_eps={self.norm_eps}, "
                        f"norm_weight={self.norm_weight is not None}"))
 
-    return {"TernaryLinear": TernaryLinear, "PackedTernaryLinear": PackedTernaryLinear}
+    class PackedTernaryGLU(torch.nn.Module):
+        """Inference-only gated pair ``y = act(g) * u`` on two packed plans, with
+        ``g = scale * weight_scale_gate * (q . Wg) + bias_gate`` and u the same on Wu: one
+        ``tcsc_amd.sgemm_q8_glu`` call -- up to 16 rows a single decode launch that streams both 2-bit images,
+        k_gemm8w2 twice on one packed X above.
+
+        Wg, Wu: K x H each, as :class:`PackedTernaryLinear` takes W.  bias_*, weight_scale_*: as its bias and
+        weight_scale, one per half.  act: 'relu2' (``relu(g)**2``) or 'silu'.  norm_weight, norm_eps, out_dtype,
+        device: as there.  ``state_dict()`` carries ``w2_gate`` and ``w2_up`` beside the buffers the layer has
+        (an absent buffer is None and is not saved); ``empty(K, H).load_state_dict(...)`` and ``reserve(rows)``
+        work as in :class:`PackedTernaryLinear`."""
+
+        _HALVES = ("gate", "up")
+
+        def __init__(self, Wg, Wu, bias_gate=None, bias_up=None, weight_scale_gate=None, weight_scale_up=None,
+                     act: str = "relu2", norm_weight=None, norm_eps: float | None = None, out_dtype=torch.float32,
+                     device: int = 0):
+            super().__init__()
+            mats = [_ternary_matrix(W, "PackedTernaryGLU") for W in (Wg, Wu)]
+            if (mats[0].rows, mats[0].cols) != (mats[1].rows, mats[1].cols):
+                raise TcscError(f"PackedTernaryGLU: Wg is {mats[0].rows} x {mats[0].cols}, Wu {mats[1].rows} x "
+                                f"{mats[1].cols}")
+            self._init_common(mats[0].rows, mats[0].cols, act, norm_eps, out_dtype, device)
+            dev = torch.device("cuda", self.device_index)
+            self.register_buffer("bias_gate", _bias_tensor(bias_gate, self.out_features, dev, "PackedTernaryGLU"))
+            self.register_buffer("bias_up", _bias_tensor(bias_up, self.out_features, dev, "PackedTernaryGLU"))
+            self.register_buffer("weight_scale_gate", _weight_scale_tensor(weight_scale_gate, self.out_features, dev))
+            self.register_buffer("weight_scale_up", _weight_scale_tensor(weight_scale_up, self.out_features, dev))
+            nw, _ = _norm_args(norm_weight, norm_eps, self.in_features, dev)
+            self.register_buffer("norm_weight", nw)
+            self.plans = [Plan.packed(m, 0, self.out_features, self.device_index, _stream(dev)) for m in mats]
+
+        def _init_common(self, K: int, H: int, act, norm_eps, out_dtype, device):
+            from . import GLU_ACT_ID
+
+            if act not in GLU_ACT_ID:
+                raise TcscError(f"PackedTernaryGLU: act must be one of {sorted(GLU_ACT_ID)}, got {act!r}")
+            self.in_features, self.out_features, self.act = int(K), int(H), act
+            self.device_index = int(device)
+            self.out_dtype = _out_dtype(out_dtype)
+            _, self.norm_eps = _norm_args(None, norm_eps, self.in_features, torch.device("cuda", self.device_index))
+            self.plans = None
+            self._rows, self._xq, self._scale, self._g = 0, None, None, None
+
+        @classmethod
+        def from_float(cls, Wg, Wu, bias_gate=None, bias_up=None, act: str = "relu2", norm_weight=None,
+                       norm_eps: float | None = None, out_dtype=torch.float32, device: int = 0):
+            """The layer of two float matrices (K x H each): each ternarized by ``tcsc_amd.ternarize_absmean``, its
+            beta the half's per-tensor weight scale."""
+            tb = [ternarize_absmean(W.detach().cpu().numpy() if torch.is_tensor(W) else W) for W in (Wg, Wu)]
+            return cls(tb[0][0], tb[1][0], bias_gate, bias_up, float(tb[0][1]), float(tb[1][1]), act, norm_weight,
+                       norm_eps, out_dtype, device)
+
+        @classmethod
+        def empty(cls, in_features: int, out_features: int, act: str = "relu2", norm_eps: float | None = None,
+                  out_dtype=torch.float32, device: int = 0):
+            """A layer of this shape with zero biases, no weight scales and no plans yet, for ``load_state_dict``."""
+            self = cls.__new__(cls)
+            torch.nn.Module.__init__(self)
+            self._init_common(in_features, out_features, act, norm_eps, out_dtype, device)
+            dev = torch.device("cuda", self.device_index)
+            for h in cls._HALVES:
+                self.register_buffer("bias_" + h, torch.zeros(self.out_features, dtype=torch.float32, device=dev))
+                self.register_buffer("weight_scale_" + h, None)
+            self.register_buffer("norm_weight", None)
+            return self
+
+        def _loaded_plans(self, what: str):
+            if self.plans is None:
+                raise TcscError(f"PackedTernaryGLU.{what}: the layer is empty (PackedTernaryGLU.empty): load a "
+                                "state_dict first")
+            return self.plans
+
+        def _save_to_state_dict(self, destination, prefix, keep_vars):
+            super()._save_to_state_dict(destination, prefix, keep_vars)
+            st = _stream(torch.device("cuda", self.device_index))
+            for h, plan in zip(self._HALVES, self._loaded_plans("state_dict")):
+                destination[prefix + "w2_" + h] = plan.w2_image(st)
+
+        def _load_from_state_dict(self, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys,
+                                  error_msgs):
+            """Rebuilds both plans from ``w2_gate`` and ``w2_up``; they and the two biases must be there, whatever
+            ``strict`` says (TcscError otherwise, the layer unchanged); the weight scales and ``norm_weight`` are
+            taken when present and the layer has none afterwards when absent."""
+            who, K, H = "PackedTernaryGLU.load_state_dict", self.in_features, self.out_features
+            dev = torch.device("cuda", self.device_index)
+            want = w2_image_bytes(K, H)
+            for h in self._HALVES:
+                for key in ("bias_" + h, "w2_" + h):
+                    if prefix + key not in state_dict:
+                        raise TcscError(f"{who}: missing key {prefix + key!r}")
+                b, w2 = state_dict[prefix + "bias_" + h], state_dict[prefix + "w2_" + h]
+                if not torch.is_tensor(b) or b.numel() != H:
+                    raise TcscError(f"{who}: {prefix}bias_{h} must hold {H} values")
+                if not torch.is_tensor(w2) or w2.dtype != torch.uint8 or w2.numel() != want:
+                    raise TcscError(f"{who}: {prefix}w2_{h} must hold the {want} uint8 values of a {K} x {H} image")
+                ws = state_dict.get(prefix + "weight_scale_" + h)
+                if ws is not None and (not torch.is_tensor(ws) or ws.numel() != H):
+                    raise TcscError(f"{who}: {prefix}weight_scale_{h} must hold {H} values")
+            nw = state_dict.get(prefix + "norm_weight")
+            if nw is not None and (not torch.is_tensor(nw) or nw.numel() != K or self.norm_eps is None):
+                raise TcscError(f"{who}: {prefix}norm_weight must hold {K} values, on a layer made with norm_eps")
+            plans = [Plan.packed_from_image(state_dict[prefix + "w2_" + h].detach().to(dev).contiguous(), K, H, 0,
+                                            self.device_index, _stream(dev)) for h in self._HALVES]
+            for h in self._HALVES:  # the base class copies into the buffers the layer has: one of the state's kind
+                has = state_dict.get(prefix + "weight_scale_" + h) is not None
+                setattr(self, "weight_scale_" + h, torch.empty(H, dtype=torch.float32, device=dev) if has else None)
+            self.norm_weight = None if nw is None else torch.empty(K, dtype=torch.float32, device=dev)
+            super()._load_from_state_dict(state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys,
+                                          error_msgs)
+            for h in self._HALVES:
+                if prefix + "w2_" + h in unexpected_keys:
+                    unexpected_keys.remove(prefix + "w2_" + h)
+            old, self.plans = self.plans, plans
+            for p in old or ():
+                p.destroy()
+
+        def _scratch(self, rows: int):
+            if self._rows < rows:
+                dev = torch.device("cuda", self.device_index)
+                self._xq = torch.empty((rows, self.in_features), dtype=torch.int8, device=dev)
+                self._scale = torch.empty(rows, dtype=torch.float32, device=dev)
+                # the gate values of the MFMA route (more than 16 rows); the decode launch needs none
+                self._g = torch.empty((rows, self.out_features), dtype=torch.float32, device=dev) if rows > 16 else None
+                self._rows = rows
+            return self._xq, self._scale, self._g
+
+        def reserve(self, max_rows: int) -> None:
+            """The gate plan's workspace and the layer's scratch (the quantized X, the row scales and, above 16
+            rows, the gate values) for up to max_rows rows: afterwards a forward allocates nothing but its output."""
+            self._loaded_plans("reserve")[0].reserve(max_rows)
+            self._scratch(max_rows)
+
+        def forward(self, x):
+            from . import sgemm_q8_glu
+
+            gate, up = self._loaded_plans("forward")
+            if not torch.is_tensor(x) or x.dtype not in (torch.float32, torch.bfloat16) or not x.is_cuda:
+                raise TcscError("PackedTernaryGLU: x must be an fp32 or bf16 CUDA tensor")
+            if torch.is_grad_enabled() and x.requires_grad:
+                raise TcscError("PackedTernaryGLU is inference only: x requires grad")
+            if x.device.index != self.device_index or x.dim() < 1 or x.shape[-1] != self.in_features:
+                raise TcscError(f"PackedTernaryGLU: x has shape {tuple(x.shape)} on {x.device}, expected (..., "
+                                f"{self.in_features}) on cuda:{self.device_index}")
+            lead = x.shape[:-1]
+            x2 = x.detach().reshape(-1, self.in_features).contiguous()
+            M, H = x2.shape[0], self.out_features
+            xq, scale, g = self._scratch(M)
+            y = torch.empty((M, H), dtype=self.out_dtype, device=x.device)
+            sgemm_q8_glu(gate, up, x2, xq, scale, self.bias_gate, self.bias_up, y, M, H, self.act,
+                         self.weight_scale_gate, self.weight_scale_up, self.norm_weight, self.norm_eps, g,
+                         _stream(x.device))
+            return y.reshape(*lead, H)
+
+        def extra_repr(self) -> str:
+            return (f"in_features={self.in_features}, out_features={self.out_features}, act={self.act}, "
+                    f"out_dtype={self.out_dtype}" + ("" if self.norm_eps is None else f", norm_eps={self.norm_eps}"))
+
+    class PackedTernaryMLP(torch.nn.Module):
+        """The two-call FFN of a BitNet-style block: ``down(subnorm(act(gate(norm(x))) * up(norm(x))))`` as a
+        :class:`PackedTernaryGLU` with a bf16 output (``glu``) and a :class:`PackedTernaryLinear` with its own
+        RMSNorm in front (``down``: K = the hidden width).  Both are built by the caller; ``reserve`` and the
+        state dict are the two layers'."""
+
+        def __init__(self, glu: PackedTernaryGLU, down: PackedTernaryLinear):
+            super().__init__()
+            if down.in_features != glu.out_features:
+                raise TcscError(f"PackedTernaryMLP: the GLU gives {glu.out_features} columns, down takes "
+                                f"{down.in_features}")
+            self.glu, self.down = glu, down
+
+        def reserve(self, max_rows: int) -> None:
+            self.glu.reserve(max_rows)
+            self.down.reserve(max_rows)
+
+        def forward(self, x):
+            return self.down(self.glu(x))
+
+    return {"TernaryLinear": TernaryLinear, "PackedTernaryLinear": PackedTernaryLinear,
+            "PackedTernaryGLU": PackedTernaryGLU, "PackedTernaryMLP": PackedTernaryMLP}
 
 
 def __getattr__(name):
