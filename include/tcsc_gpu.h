@@ -847,6 +847,96 @@ int tcsc_gpu_launch_info_glu(const tcsc_gpu_plan *gate, const tcsc_gpu_plan *up,
                              int *path, int *slices, int *fused);
 int tcsc_gpu_glu_fuse_pays(int M, int K, int N, int xtype, int norm);   /* host arithmetic */
 
+/* ---- Grouped int8 call: several matrices on one X ---------------
+ * The Q, K and V projections of an attention block read the same
+ * quant(RMSNorm(x) gamma), the same row scales and the same int8 X, as do any
+ * projections that share an input.  These calls run up to TCSC_GROUP_MAX of them
+ * as one: member i's output is, bit for bit, what
+ *   tcsc_gpu_sgemm_i8_out(members[i].plan, dXq, dScale, dColScale_i, dB_i, dY_i,
+ *                         ytype, M, ldy_i, TCSC_VARIANT_BASIC, 0, stream)
+ * writes -- that call stays the definition of the arithmetic -- and the q8 form
+ * equals the norm, the quantizer and the i8 form, as tcsc_gpu_sgemm_q8 /
+ * tcsc_gpu_sgemm_q8_norm do.  There is no PReLU on this call.
+ *
+ * members: count (1 .. TCSC_GROUP_MAX) of
+ *   plan       a plan that holds the 2-bit image (a packed plan, or an ordinary
+ *              one after tcsc_gpu_plan_enable_w2).  All members have the same
+ *              rows (K) and device; the column counts are free, with no
+ *              alignment to the 16-column tile.
+ *   dColScale  cols floats, NULL: all ones;  dB: cols floats
+ *   dY, ldy    M x ldy of the call's ytype, ldy >= cols in elements.  The members'
+ *              dY may point into one tensor at different column offsets with a
+ *              common pitch (a fused qkv tensor): the store rules are
+ *              tcsc_gpu_sgemm_i8_out's, any element alignment.  Overlapping
+ *              outputs are the caller's mistake and are not checked.
+ * A group of one gives the single call's bits with the single call's grid.
+ *
+ * Routes (tcsc_gpu_launch_info_group), by M alone -- the cost models, $TCSC_PATH
+ * and $TCSC_DECODE are not asked:
+ *   M <= 16  TCSC_PATH_DECODE: one launch (k_decode8m) whose grid is the
+ *            concatenation of the members' workgroups: member i owns
+ *            ceil(ceil(cols_i / 16) / T) consecutive workgroups of T column tiles
+ *            each, T being one value per launch -- 4 above 8 rows, 2 above 4, else
+ *            1, halved while the whole grid W = sum_i ceil(tiles_i / T) is below
+ *            the CU count.  tcsc_gpu_sgemm_q8_group without the norm runs the
+ *            quantizer inside that launch (k_decode8qm: *fused = 1) where
+ *            tcsc_gpu_group_fuse_pays says so or $TCSC_QFUSE=1 is set
+ *            ($TCSC_QFUSE=0: never); otherwise the quantizer into dXq, then
+ *            k_decode8m.  The fused kernel has no norm form (the norm inside the
+ *            decode launch lost at 37 of 40 measured points): a
+ *            grouped call with the norm always runs the norm form of the
+ *            quantizer into dXq and then k_decode8m, whatever $TCSC_QFUSE says,
+ *            and needs dXq.
+ *   M >= 17  TCSC_PATH_MFMA: the quantizer (with the norm: its norm form) once,
+ *            k_pack8 once into the first member's workspace, and k_gemm8w2 once
+ *            per member, each GEMM's K-split slabs in its own plan's workspace
+ *            (slices[i] is member i's K split).  tcsc_gpu_plan_reserve(plan,
+ *            max_M) on every member covers the call; a smaller workspace is grown
+ *            first, as every int8 call does.  Once reserved, no call allocates or
+ *            synchronises, and all can be captured.
+ *
+ * tcsc_gpu_sgemm_q8_group takes an fp32 or bf16 X (xtype as in tcsc_gpu_sgemm_q8),
+ * writes the row scales to dScale and uses dXq as tcsc_gpu_sgemm_q8 does (NULL
+ * allowed where the call is fused).  eps == 0.0f exactly, with a NULL dGamma,
+ * means no norm; any other eps is checked as tcsc_gpu_sgemm_q8_norm checks it
+ * and the RMSNorm of that call runs in front of the quantizer.
+ *
+ * tcsc_gpu_group_fuse_pays (host arithmetic: no plan, no device): the rule of
+ * tcsc_gpu_quant_fuse_pays with the grouped launch's workgroup count W: 1 for
+ * 1 <= M <= 4 and W M K <= 2^23; 0 with norm != 0.  For one member it is
+ * tcsc_gpu_quant_fuse_pays.  tcsc_gpu_launch_info_group reports *fused for a
+ * call without the norm; slices receives count ints.
+ *
+ * TCSC_E_ARG with a message naming the call and, where it applies, the member's
+ * index, before any HIP call, for: count outside 1 .. TCSC_GROUP_MAX; NULL
+ * members; a ytype or xtype out of range; a NULL plan, dB or dY of a member; a
+ * member plan without the 2-bit image; members whose K or device differ; ldy <
+ * cols; M < 0; a NULL X; on the q8 form a bad eps, dGamma given with eps == 0,
+ * a NULL dScale, and a NULL dXq where the call is not fused.  M == 0 is TCSC_OK.
+ *
+ * Out of scope: one GEMM launch over all images at M >= 17; a norm form of the
+ * fused grouped kernel; PReLU or gating on this call; the gather and small-M
+ * routes; a host-pointer version. */
+#define TCSC_GROUP_MAX 4
+typedef struct tcsc_gpu_group_member {
+    const tcsc_gpu_plan *plan;   /* holds the 2-bit image */
+    const float *dColScale;      /* cols floats, NULL: ones */
+    const float *dB;             /* cols floats */
+    void *dY;                    /* M x ldy of the call's ytype */
+    int ldy;                     /* >= plan cols, in elements */
+} tcsc_gpu_group_member;
+
+int tcsc_gpu_sgemm_i8_group(const tcsc_gpu_group_member *members, int count,
+                            const void *dXq, const float *dScale,
+                            int ytype, int M, void *stream);
+int tcsc_gpu_sgemm_q8_group(const tcsc_gpu_group_member *members, int count,
+                            const void *dX, int xtype, const float *dGamma, float eps,
+                            void *dXq, float *dScale,
+                            int ytype, int M, void *stream);
+int tcsc_gpu_launch_info_group(const tcsc_gpu_group_member *members, int count, int M, int xtype,
+                               int *path, int *slices /* count ints */, int *fused);
+int tcsc_gpu_group_fuse_pays(int M, int K, const int *cols, int count, int xtype, int norm); /* host arithmetic */
+
 /* Device-side tcsc_from_dense: dense K x N row-major float matrix on the
  * device -> TCSC arrays on the device, bit-exact with the reference builder
  * (tcsc.c:6-66).  Two calls: first with the four output pointers NULL to

@@ -2525,6 +2525,261 @@ int tcsc_gpu_launch_info_glu(const tcsc_gpu_plan* gate, const tcsc_gpu_plan* up,
     return TCSC_OK;
 }
 
+// ---- the grouped call -------------------------------------------
+// Up to TCSC_GROUP_MAX plans with the 2-bit image and one K on one X: member i gets the bits of
+// tcsc_gpu_sgemm_i8_out on its own plan.  The route is fixed by M alone, as the gated call's: up to 16
+// rows one grouped decode launch, above k_pack8 once (into the first member's workspace) and k_gemm8w2
+// once per member, each GEMM's slabs in its own plan's workspace.
+static_assert(TCSC_GROUP_MAX == tcsc::kGroupMax, "the public group size is the launch table's");
+
+// The fusing rule of the grouped q8 call: §20's with the grouped launch's own workgroup count.  The
+// grouped launch has no norm form, so with the norm the answer is 0 (as §22's rule is everywhere).
+static bool group_fuse_pays(int M, int K, const int* cols, int count, int xtype, bool norm) {
+    if (norm || M < 1 || M > kQFuseMaxM || K < 1 || !cols || count < 1 || count > TCSC_GROUP_MAX ||
+        (xtype != TCSC_X_F32 && xtype != TCSC_X_BF16))
+        return false;
+    for (int i = 0; i < count; ++i)
+        if (cols[i] < 1) return false;
+    const int T = tcsc::decode_group_tiles_per_wg(M, cols, count, 0);  // the grid on a 256-CU chip
+    return tcsc::decode_group_wgs(cols, count, T) * M * K <= kQFuseValues;
+}
+int tcsc_gpu_group_fuse_pays(int M, int K, const int* cols, int count, int xtype, int norm) {
+    return group_fuse_pays(M, K, cols, count, xtype, norm != 0) ? 1 : 0;
+}
+
+// what every grouped entry point checks of its group, ahead of any HIP call (group_plans' outputs: with the
+// members' dB, dY and ldy)
+static int group_members(const char* who, const tcsc_gpu_group_member* m, int count) {
+    if (count < 1 || count > TCSC_GROUP_MAX) {
+        set_error("%s: count=%d is outside 1 .. %d (TCSC_GROUP_MAX)", who, count, TCSC_GROUP_MAX);
+        return TCSC_E_ARG;
+    }
+    if (!m) {
+        set_error("%s: NULL members", who);
+        return TCSC_E_ARG;
+    }
+    return TCSC_OK;
+}
+static int group_plans(const char* who, const tcsc_gpu_group_member* m, int count, bool outputs) {
+    for (int i = 0; i < count; ++i) {
+        if (!m[i].plan || (outputs && (!m[i].dB || !m[i].dY))) {
+            set_error("%s: member %d: NULL %s", who, i, !m[i].plan ? "plan" : !m[i].dB ? "dB" : "dY");
+            return TCSC_E_ARG;
+        }
+    }
+    for (int i = 0; i < count; ++i) {
+        if (!m[i].plan->w2) {
+            set_error("%s: member %d: the plan has no 2-bit image (a packed plan, or tcsc_gpu_plan_enable_w2 on an ordinary "
+                      "one)", who, i);
+            return TCSC_E_ARG;
+        }
+    }
+    for (int i = 1; i < count; ++i) {
+        if (m[i].plan->rows != m[0].plan->rows || m[i].plan->device != m[0].plan->device) {
+            set_error("%s: member %d: the plan has K=%d on device %d and member 0's K=%d on device %d", who, i,
+                      m[i].plan->rows, m[i].plan->device, m[0].plan->rows, m[0].plan->device);
+            return TCSC_E_ARG;
+        }
+    }
+    if (!outputs) return TCSC_OK;
+    for (int i = 0; i < count; ++i) {
+        if (m[i].ldy < m[i].plan->cols) {
+            set_error("%s: member %d: ldy=%d < cols=%d", who, i, m[i].ldy, m[i].plan->cols);
+            return TCSC_E_ARG;
+        }
+    }
+    return TCSC_OK;
+}
+static int group_ytype(const char* who, int ytype) {
+    if (ytype == TCSC_Y_F32 || ytype == TCSC_Y_BF16) return TCSC_OK;
+    set_error("%s: ytype=%d is neither TCSC_Y_F32 (0) nor TCSC_Y_BF16 (1)", who, ytype);
+    return TCSC_E_ARG;
+}
+static int group_xtype(const char* who, int xtype) {
+    if (xtype == TCSC_X_F32 || xtype == TCSC_X_BF16) return TCSC_OK;
+    set_error("%s: xtype=%d is neither TCSC_X_F32 (0) nor TCSC_X_BF16 (1)", who, xtype);
+    return TCSC_E_ARG;
+}
+
+// the members of a call in one list: member 0 from the call's own fields, the rest from c.group
+struct GroupView {
+    int count = 0;
+    const tcsc_gpu_plan* plan[TCSC_GROUP_MAX];
+    tcsc::DecodeMember m[TCSC_GROUP_MAX];
+};
+static GroupView group_view(const tcsc_gpu_plan* first, const Call& c) {
+    GroupView v;
+    for (int i = 0; i <= c.group.count; ++i) {
+        const tcsc_gpu_plan* p = i ? c.group.m[i - 1].plan : first;
+        if (p->cols == 0) continue;  // nothing to write
+        tcsc::DecodeMember& d = v.m[v.count];
+        v.plan[v.count++] = p;
+        d.w2 = p->w2;
+        d.N = p->cols;
+        d.e.rscale = c.xscale;
+        d.e.B = i ? c.group.m[i - 1].B : c.B;
+        d.e.y = i ? c.group.m[i - 1].y : c.y;
+        d.e.ldy = i ? c.group.m[i - 1].ldy : c.ldy;
+    }
+    return v;
+}
+
+// A grouped call on an int8 X (c.xtype == kI8; the members checked by group_plans).
+static int sgemm_group_i8(const tcsc_gpu_plan* first, const Call& c) {
+    const char* who = c.who;
+    const int M = c.M, K = first->rows;
+    if (M < 0) {
+        set_error("%s: bad arguments (M=%d)", who, M);
+        return TCSC_E_ARG;
+    }
+    if (M == 0) return TCSC_OK;
+    if (!c.X) {
+        set_error("%s: NULL X", who);
+        return TCSC_E_ARG;
+    }
+    hipStream_t st = static_cast<hipStream_t>(c.stream);
+    if (M <= tcsc::kDecodeMaxM) {  // TCSC_PATH_DECODE: one launch
+        const GroupView v = group_view(first, c);
+        if (!v.count) return TCSC_OK;
+        HIP_TRY(tcsc::decode_group(tcsc::DecodeX{c.X, kI8, nullptr, nullptr}, v.m, v.count, K, M, first->num_cus, st));
+        return TCSC_OK;
+    }
+    {  // every member's workspace, grown on first use as every tcsc_gpu_sgemm* does
+        const GroupView v = group_view(first, c);
+        for (int i = 0; i < v.count; ++i) {
+            tcsc_gpu_plan* p = const_cast<tcsc_gpu_plan*>(v.plan[i]);
+            if (p->ws_bytes < mfma_ws(kI8, std::min(M, kMaxLaunchRows), K, p->cols).bytes) {
+                const int rc = tcsc_gpu_plan_reserve(p, M);
+                if (rc != TCSC_OK) return rc;
+            }
+            p->staged_M = -1;
+        }
+    }
+    for (int r0 = 0; r0 < M; r0 += kMaxLaunchRows) {  // pieces of at most kMaxLaunchRows rows on the same workspaces
+        const Call q = c.rows(r0, std::min(kMaxLaunchRows, M - r0), K, 1);
+        const GroupView v = group_view(first, q);
+        if (!v.count) return TCSC_OK;
+        const int ld8 = tcsc::mfma8_ldw(K);
+        for (int i = 0; i < v.count; ++i) {
+            const tcsc_gpu_plan* p = v.plan[i];
+            const size_t need = mfma_ws(kI8, q.M, K, p->cols).bytes;
+            if (!p->ws || p->ws_bytes < need) {
+                set_error("%s: member %d: workspace of %zu bytes < %zu needed for M=%d", who, i,
+                          p->ws ? p->ws_bytes : (size_t)0, need, q.M);
+                return TCSC_E_ARG;
+            }
+        }
+        int8_t* x8 = reinterpret_cast<int8_t*>(v.plan[0]->ws);  // the packed X of all members' GEMMs
+        HIP_TRY(tcsc::mfma8_pack_x(static_cast<const int8_t*>(q.X), q.M, K, x8, ld8, st));
+        for (int i = 0; i < v.count; ++i) {
+            const tcsc_gpu_plan* p = v.plan[i];
+            const MfmaWs w = mfma_ws(kI8, q.M, K, p->cols);  // the slabs where the member's own call has them
+            char* base = reinterpret_cast<char*>(p->ws);
+            HIP_TRY(tcsc::mfma8_gemm_w2(x8, p->w2, ld8, K, q.M, p->cols, v.m[i].e, reinterpret_cast<int*>(base + w.slabs_off),
+                                        p->ws_bytes - w.slabs_off, st));
+        }
+    }
+    return TCSC_OK;
+}
+
+static Call group_call(const char* who, const tcsc_gpu_group_member* m, int count, const void* X, int xtype,
+                       const float* xscale, int ytype, int M, void* stream) {
+    Call c = make_call(X, xtype, xscale, m[0].dB, y_out(m[0].dY, ytype, m[0].dColScale), M, m[0].ldy, TCSC_VARIANT_BASIC,
+                       0.f, stream, who);
+    c.group.count = count - 1;
+    for (int i = 1; i < count; ++i)
+        c.group.m[i - 1] = tcsc::GroupRest::Member{m[i].plan, m[i].dB, y_out(m[i].dY, ytype, m[i].dColScale), m[i].ldy};
+    return c;
+}
+
+int tcsc_gpu_sgemm_i8_group(const tcsc_gpu_group_member* members, int count, const void* dXq, const float* dScale,
+                            int ytype, int M, void* stream) {
+    const char* who = "tcsc_gpu_sgemm_i8_group";
+    int rc = group_members(who, members, count);
+    if (rc == TCSC_OK) rc = group_ytype(who, ytype);
+    if (rc == TCSC_OK) rc = group_plans(who, members, count, true);
+    if (rc != TCSC_OK) return rc;
+    return sgemm_group_i8(members[0].plan, group_call(who, members, count, dXq, kI8, dScale, ytype, M, stream));
+}
+
+// whether a grouped q8 call of M rows without the norm quantizes inside the decode launch
+static bool group_fused(const tcsc_gpu_group_member* m, int count, int M, int xtype) {
+    if (M < 1 || M > tcsc::kDecodeMaxM) return false;
+    int cols[TCSC_GROUP_MAX], n = 0;
+    for (int i = 0; i < count; ++i)
+        if (m[i].plan->cols > 0) cols[n++] = m[i].plan->cols;
+    if (!n) return false;
+    const int knob = qfuse_knob();
+    return knob >= 0 ? knob == 1 : group_fuse_pays(M, m[0].plan->rows, cols, n, xtype, false);
+}
+
+int tcsc_gpu_sgemm_q8_group(const tcsc_gpu_group_member* members, int count, const void* dX, int xtype,
+                            const float* dGamma, float eps, void* dXq, float* dScale, int ytype, int M, void* stream) {
+    const char* who = "tcsc_gpu_sgemm_q8_group";
+    int rc = group_members(who, members, count);
+    if (rc == TCSC_OK) rc = group_ytype(who, ytype);
+    if (rc == TCSC_OK) rc = group_xtype(who, xtype);
+    if (rc != TCSC_OK) return rc;
+    const bool has_norm = eps != 0.0f;  // eps == 0 exactly: no norm in front
+    if (has_norm) rc = norm_args(who, xtype, eps, members[0].plan ? members[0].plan->rows : 1);
+    if (rc != TCSC_OK) return rc;
+    if (!has_norm && dGamma) {
+        set_error("%s: dGamma given with eps == 0 (no norm): pass the norm's eps, or a NULL dGamma", who);
+        return TCSC_E_ARG;
+    }
+    rc = group_plans(who, members, count, true);
+    if (rc != TCSC_OK) return rc;
+    const int K = members[0].plan->rows;
+    if (M < 0) {
+        set_error("%s: bad arguments (M=%d)", who, M);
+        return TCSC_E_ARG;
+    }
+    if (M == 0) return TCSC_OK;
+    if (!dX || !dScale) {
+        set_error("%s: NULL %s", who, !dX ? "dX" : "dScale");
+        return TCSC_E_ARG;
+    }
+    Call c = group_call(who, members, count, dX, xtype, nullptr, ytype, M, stream);
+    if (!has_norm && group_fused(members, count, M, xtype)) {  // the grouped launch has no norm form
+        const GroupView v = group_view(members[0].plan, c);
+        HIP_TRY(tcsc::decode_group(tcsc::DecodeX{dX, xtype, dScale, nullptr}, v.m, v.count, K, M, members[0].plan->num_cus,
+                                   static_cast<hipStream_t>(stream)));
+        return TCSC_OK;
+    }
+    if (!dXq) {
+        set_error("%s: NULL dXq on a route that is not fused (M=%d)", who, M);
+        return TCSC_E_ARG;
+    }
+    rc = has_norm ? tcsc_gpu_quantize_rows_i8_norm(dX, xtype, dGamma, eps, M, K, dXq, dScale, stream)
+                  : quantize_rows(xtype, dX, M, K, dXq, dScale, stream);
+    if (rc != TCSC_OK) return rc;
+    c.X = dXq;
+    c.xtype = kI8;
+    c.xscale = dScale;
+    return sgemm_group_i8(members[0].plan, c);
+}
+
+int tcsc_gpu_launch_info_group(const tcsc_gpu_group_member* members, int count, int M, int xtype, int* path, int* slices,
+                               int* fused) {
+    const char* who = "tcsc_gpu_launch_info_group";
+    int rc = group_members(who, members, count);
+    if (rc != TCSC_OK) return rc;
+    if (M < 0 || !path || !slices || !fused || (xtype != TCSC_X_F32 && xtype != TCSC_X_BF16)) {
+        set_error("%s: bad arguments (M=%d xtype=%d)", who, M, xtype);
+        return TCSC_E_ARG;
+    }
+    rc = group_plans(who, members, count, false);
+    if (rc != TCSC_OK) return rc;
+    const bool decode = M <= tcsc::kDecodeMaxM;
+    *path = decode ? TCSC_PATH_DECODE : TCSC_PATH_MFMA;
+    for (int i = 0; i < count; ++i)
+        slices[i] = decode || members[i].plan->cols == 0
+                        ? 1
+                        : tcsc::mfma8_slices(std::min(M, kMaxLaunchRows), members[i].plan->cols, members[i].plan->rows);
+    *fused = group_fused(members, count, M, xtype) ? 1 : 0;
+    return TCSC_OK;
+}
+
 int tcsc_gpu_workspace_bound_i8(int M, int K, int N, size_t* i8_bytes, size_t* f32_bytes) {
     if (M < 0 || K < 1 || N < 0) {
         set_error("tcsc_gpu_workspace_bound_i8: bad arguments (M=%d K=%d N=%d)", M, K, N);

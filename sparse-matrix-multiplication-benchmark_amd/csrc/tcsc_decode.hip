@@ -1053,6 +1053,96 @@ __global__ void __launch_bounds__(kQWaves * 64) k_decode8qg(const TX* __restrict
         });
 }
 
+// ---- the grouped forms: up to four matrices on one X in one launch ----
+// k_decode8m and k_decode8qm are k_decode8 and k_decode8q (without PReLU and
+// without the norm) on a grid that is the concatenation of the members'
+// workgroups: member i owns ceil(tiles_i / T) consecutive blocks from
+// m[i].first on, and all T tiles of a block lie in one member (its last block
+// reads its last tile again: decode_tile_ptrs).  The members differ in image,
+// column count, column scales, bias, Y and pitch; K, M, X, the row scales and
+// the Y type are the launch's.  The table is a kernel argument by value and a
+// block finds its member by comparing blockIdx.x with the first blocks of
+// members 1 .. 3 (INT_MAX for a slot past the group's count): compares and
+// selects over the four slots, so every field stays in scalar registers -- an
+// array indexed by a run-time member number would be copied to scratch.
+// From there the bodies are decode8g_sums / decode8qg_body on one image and
+// decode_reduce_store as the tail.
+struct GroupSlot {
+    const uint32_t* W2;
+    const float *cscale, *bias;
+    void* Y;
+    int N, ntiles, ldy, first;
+};
+struct GroupTable {
+    GroupSlot m[kGroupMax];
+};
+static_assert(kGroupMax == 4, "decode_group_slot selects over four slots");
+__device__ __forceinline__ GroupSlot decode_group_slot(const GroupTable& g, int block) {
+    const bool a1 = block >= g.m[1].first, a2 = block >= g.m[2].first, a3 = block >= g.m[3].first;  // uniform
+    // The empty asm pins each chosen value in scalar registers here: without it the selects sink to the
+    // tail and all four slots stay live across the K loop (SGPR spills in k_decode8qm).
+    auto pick = [&](auto s0, auto s1, auto s2, auto s3) {
+        auto v = a3 ? s3 : a2 ? s2 : a1 ? s1 : s0;
+        asm volatile("" : "+s"(v));
+        return v;
+    };
+    GroupSlot s;
+    s.W2 = pick(g.m[0].W2, g.m[1].W2, g.m[2].W2, g.m[3].W2);
+    s.cscale = pick(g.m[0].cscale, g.m[1].cscale, g.m[2].cscale, g.m[3].cscale);
+    s.bias = pick(g.m[0].bias, g.m[1].bias, g.m[2].bias, g.m[3].bias);
+    s.Y = pick(g.m[0].Y, g.m[1].Y, g.m[2].Y, g.m[3].Y);
+    s.N = pick(g.m[0].N, g.m[1].N, g.m[2].N, g.m[3].N);
+    s.ntiles = pick(g.m[0].ntiles, g.m[1].ntiles, g.m[2].ntiles, g.m[3].ntiles);
+    s.ldy = pick(g.m[0].ldy, g.m[1].ldy, g.m[2].ldy, g.m[3].ldy);
+    s.first = pick(0, g.m[1].first, g.m[2].first, g.m[3].first);
+    return s;
+}
+
+// The one image of a grouped workgroup: TT adjacent tiles of the member's image.
+// tbase is the tile number the body gives the member's first tile (blockIdx.x
+// * TT there): ptrs takes it off again.
+template <int TT>
+struct DecodeImg1 {
+    static constexpr int T = TT, kColTiles = TT;
+    const uint32_t* W;
+    int tbase;
+    __device__ __forceinline__ void ptrs(int t0, int ntiles, int nkb, int lane, const u32x4* (&wp)[T]) const {
+        decode_tile_ptrs<TT>(W, t0 - tbase, ntiles, nkb, lane, wp);
+    }
+};
+
+// The grouped k_decode8.
+template <int T, bool ALIGNED, typename TY>
+__global__ void __launch_bounds__(kDecWaves * 64) k_decode8m(const int8_t* __restrict__ X, GroupTable g, int K, int M,
+                                                              int nkb, const float* __restrict__ scale) {
+    __shared__ int red[kDecWaves * T * 256];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const GroupSlot s = decode_group_slot(g, blockIdx.x);
+    const int t0 = (blockIdx.x - s.first) * T;  // in the member's own tiles
+    i32x4 acc[T], rs;
+    decode8g_sums<ALIGNED>(X, DecodeImg1<T>{s.W2, 0}, K, M, nkb, s.ntiles, t0, wave, lane, acc, rs);
+    decode_reduce_store<kDecWaves, T, false>(
+        red, acc, rs, wave, lane, t0, M, s.N, [&](int row) { return scale ? scale[row] : 1.0f; }, s.cscale, s.bias,
+        static_cast<TY*>(s.Y), s.ldy, 0.0f);
+}
+
+// The grouped k_decode8q: phase A and phase B are k_decode8q's, and the launch's
+// block 0 stores the row scales once.  No norm form.
+template <typename TX, int T, bool ALIGNED, typename TY>
+__global__ void __launch_bounds__(kQWaves * 64) k_decode8qm(const TX* __restrict__ X, GroupTable g, int K, int M,
+                                                            int nkb, float* __restrict__ scale_out) {
+    const GroupSlot s = decode_group_slot(g, blockIdx.x);
+    const int tbase = s.first * T;
+    decode8qg_body<TX, ALIGNED, false>(
+        X, DecodeImg1<T>{s.W2, tbase}, K, M, nkb, s.ntiles, scale_out, nullptr, 0.0f,
+        [&](int* red, const float* s_scale, const i32x4(&acc)[T], const i32x4& rs, int wave, int lane, int t0) {
+            decode_reduce_store<kQWaves, T, false>(
+                red, acc, rs, wave, lane, t0 - tbase, M, s.N, [&](int row) { return s_scale[row]; }, s.cscale, s.bias,
+                static_cast<TY*>(s.Y), s.ldy, 0.0f);
+        });
+}
+
 }  // namespace
 
 hipError_t decode_build_w2(const int8_t* w8, int ncols, int K, int ld8, uint32_t* w2, int* bad, hipStream_t st) {
@@ -1225,6 +1315,79 @@ hipError_t decode_glu(const DecodeX& x, const uint32_t* wg, const uint32_t* wu, 
                                            0, st, static_cast<const TX*>(x.X), wg, wu, K, M, N, nkb, ntiles, x.scale_out,
                                            e, Y, up.ldy, x.norm ? x.norm->gamma : nullptr, x.norm ? x.norm->eps : 0.0f);
                     });
+                });
+            });
+        });
+    });
+    return hipGetLastError();
+}
+
+// Column tiles per workgroup of a grouped launch, one value for all members:
+// decode_tiles_per_wg's rule on the whole grid, the sum of the members'
+// ceil(tiles_i / T) workgroups.  One member: decode_tiles_per_wg itself.
+long long decode_group_wgs(const int* cols, int count, int T) {
+    long long w = 0;
+    for (int i = 0; i < count; ++i) w += (w2_col_tiles(cols[i]) + T - 1) / T;
+    return w;
+}
+int decode_group_tiles_per_wg(int M, const int* cols, int count, int num_cus) {
+    if (kDecTiles) return kDecTiles;
+    const int cus = num_cus > 0 ? num_cus : 256;
+    int T = M > 8 ? 4 : M > 4 ? 2 : 1;
+    while (T > 1 && decode_group_wgs(cols, count, T) < cus) T >>= 1;
+    return T;
+}
+
+// The grouped decode launch (tcsc_internal.h): decode_gemm's dispatch without
+// the PReLU and norm axes; the members travel as one table by value.
+hipError_t decode_group(const DecodeX& x, const DecodeMember* m, int count, int K, int M, int num_cus, hipStream_t st) {
+    const bool quant = x.xtype != kI8;
+    if (M < 1 || M > kDecodeMaxM || K < 1 || K >= kDecodeMaxK || count < 1 || count > kGroupMax || !m || !x.X ||
+        (quant && !x.scale_out) || x.norm)
+        return hipErrorInvalidValue;
+    int cols[kGroupMax];
+    for (int i = 0; i < count; ++i) {
+        if (m[i].N < 1 || !m[i].w2 || !m[i].e.B || !m[i].e.y.Y || m[i].e.ldy < m[i].N || m[i].e.y.ytype != m[0].e.y.ytype ||
+            m[i].e.prelu)
+            return hipErrorInvalidValue;
+        cols[i] = m[i].N;
+    }
+    const int nkb = w2_kblocks(K), tiles = decode_group_tiles_per_wg(M, cols, count, num_cus);
+    const long long wgs = decode_group_wgs(cols, count, tiles);
+    if (wgs > 0x7fffffffLL) return hipErrorInvalidValue;
+    GroupTable g{};
+    int first = 0;
+    for (int i = 0; i < kGroupMax; ++i) {
+        g.m[i].first = 0x7fffffff;  // a slot past the group: no block is at or beyond it
+        if (i >= count) continue;
+        const int ntiles = w2_col_tiles(m[i].N);
+        g.m[i] = GroupSlot{m[i].w2, m[i].e.y.cscale, m[i].e.B, m[i].e.y.Y, m[i].N, ntiles, m[i].e.ldy, first};
+        first += (ntiles + tiles - 1) / tiles;
+    }
+    const dim3 grid((unsigned)wgs);
+    const bool aligned = x.xtype == kI8    ? XSrc<int8_t>::vec_ok(static_cast<const int8_t*>(x.X), K)
+                         : x.xtype == kBf16 ? XSrc<uint16_t>::vec_ok(static_cast<const uint16_t*>(x.X), K)
+                                            : XSrc<float>::vec_ok(static_cast<const float*>(x.X), K);
+    auto with_tiles = [&](auto&& f) {
+        if (tiles == 4) return f(std::integral_constant<int, 4>{});
+        if (tiles == 2) return f(std::integral_constant<int, 2>{});
+        return f(std::integral_constant<int, 1>{});
+    };
+    with_elem(m[0].e.y.ytype == kYBf16, [&](auto ty) {
+        using TY = typename decltype(ty)::type;
+        with_tiles([&](auto t) {
+            with_bool(aligned, [&](auto al) {
+                constexpr int T = decltype(t)::value;
+                constexpr bool AL = decltype(al)::value;
+                if (!quant) {
+                    hipLaunchKernelGGL((k_decode8m<T, AL, TY>), grid, dim3(kDecWaves * 64), 0, st,
+                                       static_cast<const int8_t*>(x.X), g, K, M, nkb, m[0].e.rscale);
+                    return;
+                }
+                with_elem(x.xtype == kBf16, [&](auto tx) {
+                    using TX = typename decltype(tx)::type;
+                    hipLaunchKernelGGL((k_decode8qm<TX, T, AL, TY>), grid, dim3(kQWaves * 64), 0, st,
+                                       static_cast<const TX*>(x.X), g, K, M, nkb, x.scale_out);
                 });
             });
         });

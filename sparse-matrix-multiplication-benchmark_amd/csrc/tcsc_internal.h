@@ -581,6 +581,23 @@ hipError_t decode_gemm(const DecodeX& x, const uint32_t* w2, int K, int M, int N
 int decode_glu_tiles_per_wg(int M, int N, int num_cus);
 hipError_t decode_glu(const DecodeX& x, const uint32_t* wg, const uint32_t* wu, int K, int M, int N, const I8Epi& gate,
                       const I8Epi& up, int num_cus, hipStream_t st);
+// The grouped decode launch, k_decode8m / k_decode8qm: `count`
+// (1 .. kGroupMax) images of K rows and any column counts against one X in one
+// launch whose grid is the concatenation of the members' workgroups.  Member i
+// gets decode_gemm's Y of (w2, N, e) -- e.prelu off, one Y type for all, the
+// row scales of an int8 X those of m[0].e.  x as in decode_gemm, without a norm
+// (the grouped launch has no norm form).  decode_group_tiles_per_wg: the one T
+// of the launch (1, 2 or 4), decode_tiles_per_wg's rule on the whole grid of
+// decode_group_wgs(cols, count, T) workgroups.
+constexpr int kGroupMax = 4;  // TCSC_GROUP_MAX
+struct DecodeMember {
+    const uint32_t* w2 = nullptr;
+    int N = 0;
+    I8Epi e;
+};
+long long decode_group_wgs(const int* cols, int count, int T);
+int decode_group_tiles_per_wg(int M, const int* cols, int count, int num_cus);
+hipError_t decode_group(const DecodeX& x, const DecodeMember* m, int count, int K, int M, int num_cus, hipStream_t st);
 
 // Rewrites the flagged rows in k_stream's fast order (no-op when none is).
 hipError_t mfma_fixup(const uint16_t* x3, int M, int K, int ldk, const int* cq, const int* crq, int ncols,

@@ -109,6 +109,19 @@ struct GluUp {
     int ldg = 0;
     int act = 0;
 };
+// The members beyond the first of a grouped call (tcsc_gpu_sgemm_i8_group): the call's own
+// plan, B, y and ldy are member 0's, and every further member has a plan, bias, output (y.ytype the
+// call's) and pitch of its own.  count == 0: not a grouped call.
+struct GroupRest {
+    struct Member {
+        const tcsc_gpu_plan* plan = nullptr;
+        const float* B = nullptr;
+        YOut y;
+        int ldy = 0;
+    };
+    int count = 0;
+    Member m[kGroupMax - 1];
+};
 struct Call {
     const void* X = nullptr;
     int xtype = kF32;
@@ -120,14 +133,17 @@ struct Call {
     void* stream = nullptr;
     const char* who = nullptr;
     GluUp glu;
+    GroupRest group;
     // rows [r0, r0 + n) of a call on a matrix of K rows as a call of their own: X (x_elem bytes an
-    // element), the row scales, Y (by the element size of its type) and a gated call's G advance by r0 rows
+    // element), the row scales, Y (by the element size of its type), a gated call's G and every
+    // further member's Y of a grouped call advance by r0 rows
     Call rows(int r0, int n, int K, size_t x_elem) const {
         Call c = *this;
         c.X = X ? static_cast<const char*>(X) + (size_t)r0 * K * x_elem : nullptr;
         c.xscale = xscale ? xscale + r0 : nullptr;
         c.y = y.rows_on((size_t)r0, ldy);
         c.glu.G = glu.G ? glu.G + (size_t)r0 * glu.ldg : nullptr;
+        for (int i = 0; i < group.count; ++i) c.group.m[i].y = group.m[i].y.rows_on((size_t)r0, group.m[i].ldy);
         c.M = n;
         return c;
     }

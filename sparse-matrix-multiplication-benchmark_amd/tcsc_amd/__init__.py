@@ -61,6 +61,7 @@ EXPORTED_SYMBOLS = (
     "tcsc_gpu_rmsnorm_rows", "tcsc_gpu_quantize_rows_i8_norm", "tcsc_gpu_sgemm_q8_norm",
     "tcsc_gpu_launch_info_q8_norm", "tcsc_gpu_norm_fuse_pays",
     "tcsc_gpu_sgemm_i8_glu", "tcsc_gpu_sgemm_q8_glu", "tcsc_gpu_launch_info_glu", "tcsc_gpu_glu_fuse_pays",
+    "tcsc_gpu_sgemm_i8_group", "tcsc_gpu_sgemm_q8_group", "tcsc_gpu_launch_info_group", "tcsc_gpu_group_fuse_pays",
     # include/sparse/bcsr.h
     "bcsr_from_dense", "bcsr_sgemm_basic", "bcsr_sgemm_prelu_basic", "bcsr_sgemm_avx", "bcsr_sgemm_prelu_avx",
     "bcsr_sgemm_avx2", "bcsr_free",
@@ -92,6 +93,17 @@ class plan_info_t(C.Structure):
         ("nnz", C.c_longlong), ("n_pos", C.c_longlong), ("n_neg", C.c_longlong),
         ("chunk_k", C.c_int), ("n_chunks", C.c_int), ("device_bytes", C.c_size_t), ("order", C.c_int),
         ("mfma_min_M", C.c_int),
+    ]
+
+
+GROUP_MAX = 4  # TCSC_GROUP_MAX
+
+
+class group_member_t(C.Structure):
+    """Layout of tcsc_gpu_group_member (include/tcsc_gpu.h): one matrix of a grouped int8 call."""
+
+    _fields_ = [
+        ("plan", C.c_void_p), ("dColScale", C.c_void_p), ("dB", C.c_void_p), ("dY", C.c_void_p), ("ldy", C.c_int),
     ]
 
 
@@ -198,6 +210,11 @@ def lib():
     L.tcsc_gpu_sgemm_q8_glu.argtypes = [vp, vp, vp, i, vp, f, vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, i, vp]
     L.tcsc_gpu_launch_info_glu.argtypes = [vp, vp, i, i, C.POINTER(i), C.POINTER(i), C.POINTER(i)]
     L.tcsc_gpu_glu_fuse_pays.argtypes = [i, i, i, i, i]
+    gm = C.POINTER(group_member_t)
+    L.tcsc_gpu_sgemm_i8_group.argtypes = [gm, i, vp, vp, i, i, vp]
+    L.tcsc_gpu_sgemm_q8_group.argtypes = [gm, i, vp, i, vp, f, vp, vp, i, i, vp]
+    L.tcsc_gpu_launch_info_group.argtypes = [gm, i, i, i, C.POINTER(i), C.POINTER(i), C.POINTER(i)]
+    L.tcsc_gpu_group_fuse_pays.argtypes = [i, i, C.POINTER(i), i, i, i]
     L.tcsc_gpu_prepare_x.argtypes = [vp, vp, i, vp]
     L.tcsc_gpu_sgemm_prepared.argtypes = [vp, vp, vp, i, i, i, f, vp]
     L.tcsc_gpu_from_dense.argtypes = [vp, i, i, vp, vp, vp, vp, C.POINTER(i), C.POINTER(i), vp]
@@ -1021,6 +1038,85 @@ def glu_fuse_pays(M: int, K: int, N: int, dtype="f32", norm: bool = False) -> bo
     """The default rule for fusing the quantizer (norm: and the norm) into the gated decode launch
     (tcsc_gpu_glu_fuse_pays; host arithmetic)."""
     return bool(lib().tcsc_gpu_glu_fuse_pays(int(M), int(K), int(N), _xtype(dtype), int(bool(norm))))
+
+
+def _group_members(plans, biases=None, Ys=None, ldys=None, col_scales=None):
+    """The tcsc_gpu_group_member array of a grouped call (and its length, passed on as it is: the library
+    refuses a count outside 1 .. GROUP_MAX).  ldys None: every Y's own row pitch (a tensor's stride(0)), else
+    the plan's column count."""
+    n = len(plans)
+    arr = (group_member_t * max(n, 1))()
+    for k, plan in enumerate(plans):
+        m = arr[k]
+        m.plan = plan.handle if plan is not None else None
+        m.dColScale = _ptr(col_scales[k]) if col_scales is not None and col_scales[k] is not None else None
+        m.dB = _ptr(biases[k]) if biases is not None and biases[k] is not None else None
+        Y = Ys[k] if Ys is not None else None
+        m.dY = _ptr(Y) if Y is not None else None
+        if ldys is not None:
+            m.ldy = int(ldys[k])
+        elif hasattr(Y, "stride") and hasattr(Y, "dim") and Y.dim() == 2:
+            m.ldy = int(Y.stride(0))
+        elif plan is not None and Ys is not None:
+            m.ldy = plan.info()["cols"]
+    return arr, n
+
+
+def launch_info_group(plans, M: int, dtype="f32") -> tuple[str, list[int], bool]:
+    """(path, [K slices of each member], fused) of a grouped call of M rows (tcsc_gpu_launch_info_group): 'decode'
+    up to 16 rows and 'mfma' above; fused: whether :func:`sgemm_q8_group` of that dtype, without a norm,
+    quantizes inside the launch (with a norm it never does)."""
+    arr, n = _group_members(plans)
+    path, fused = C.c_int(), C.c_int()
+    slices = (C.c_int * max(n, 1))()
+    _check(lib().tcsc_gpu_launch_info_group(arr, n, int(M), _xtype(dtype), C.byref(path), slices, C.byref(fused)),
+           "tcsc_gpu_launch_info_group")
+    return ("gather", "fused", "mfma", "small", "decode")[path.value], [slices[k] for k in range(n)], bool(fused.value)
+
+
+def _group_ytype(Ys, ytype) -> int:
+    if ytype is not None:
+        return _ytype(ytype)
+    yts = {_ytype_of(Y) for Y in Ys}
+    if not yts:  # an empty group: the library's refusal
+        return 0
+    if len(yts) != 1:
+        raise TcscError("a grouped call writes one Y type: the outputs must share a dtype")
+    return yts.pop()
+
+
+def sgemm_i8_group(plans, Xq, scale, biases, Ys, M: int, ldys=None, col_scales=None, stream: int = 0,
+                   ytype=None) -> None:
+    """Several matrices on one int8 X in one call (tcsc_gpu_sgemm_i8_group): Ys[k] gets the bits of
+    :meth:`Plan.sgemm_i8` of Xq on plans[k] (1 .. GROUP_MAX plans of one K, each with the 2-bit image) with
+    biases[k], col_scales[k] (None: ones) and no PReLU.  The Ys are fp32 or bf16 alike, by the tensors' dtype
+    (raw pointers: ytype), and may be column slices of one tensor; ldys None takes each tensor's row pitch.  Up
+    to 16 rows it is one decode launch over all members, above one k_pack8 and one GEMM per member."""
+    arr, n = _group_members(plans, biases, Ys, ldys, col_scales)
+    _check(lib().tcsc_gpu_sgemm_i8_group(arr, n, C.c_void_p(_ptr(Xq)), C.c_void_p(_ptr(scale)), _group_ytype(Ys, ytype),
+                                         int(M), C.c_void_p(stream)), "tcsc_gpu_sgemm_i8_group")
+
+
+def sgemm_q8_group(plans, X, Xq, scale, biases, Ys, M: int, ldys=None, col_scales=None, norm_weight=None,
+                   norm_eps=None, stream: int = 0, xtype=None, ytype=None) -> None:
+    """The quantizer and :func:`sgemm_i8_group` in one call (tcsc_gpu_sgemm_q8_group): X is M x K fp32 or bf16,
+    scale (M floats) is written and Xq (M x K int8) is scratch, untouched where the call is fused
+    (:func:`launch_info_group`).  norm_eps None: no norm (norm_weight must be None too); otherwise the RMSNorm of
+    :meth:`Plan.sgemm_q8_norm` runs in front of the quantizer, always in the quantizer's own launch."""
+    xt = _xtype_of(X) if xtype is None else _xtype(xtype)
+    arr, n = _group_members(plans, biases, Ys, ldys, col_scales)
+    _check(lib().tcsc_gpu_sgemm_q8_group(arr, n, C.c_void_p(_ptr(X)), xt, C.c_void_p(_ptr(norm_weight)),
+                                         0.0 if norm_eps is None else float(norm_eps), C.c_void_p(_ptr(Xq)),
+                                         C.c_void_p(_ptr(scale)), _group_ytype(Ys, ytype), int(M), C.c_void_p(stream)),
+           "tcsc_gpu_sgemm_q8_group")
+
+
+def group_fuse_pays(M: int, K: int, cols, dtype="f32", norm: bool = False) -> bool:
+    """The default rule for fusing the quantizer into the grouped decode launch of members with these column
+    counts (tcsc_gpu_group_fuse_pays; host arithmetic); False with the norm."""
+    cols = [int(c) for c in cols]
+    arr = (C.c_int * max(len(cols), 1))(*cols)
+    return bool(lib().tcsc_gpu_group_fuse_pays(int(M), int(K), arr, len(cols), _xtype(dtype), int(bool(norm))))
 
 
 def w2_image_bytes(K: int, N: int) -> int:

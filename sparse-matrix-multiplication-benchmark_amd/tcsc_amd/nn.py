@@ -19,7 +19,7 @@ import numpy as np
 
 from . import Plan, TcscError, TcscMatrix, prelu_backward, ternarize_absmean, w2_image_bytes
 
-__all__ = ["TernaryLinear", "PackedTernaryLinear", "PackedTernaryGLU", "PackedTernaryMLP"]
+__all__ = ["TernaryLinear", "PackedTernaryLinear", "PackedTernaryGLU", "PackedTernaryMLP", "PackedTernaryGroup"]
 
 _classes = None
 
@@ -592,8 +592,177 @@ def _define():
         def forward(self, x):
             return self.down(self.glu(x))
 
+    class PackedTernaryGroup(torch.nn.Module):
+        """Inference-only group of 1 to 4 ternary matrices on one input, the Q, K and V
+        projections of an attention block for instance: ``y_i = scale * weight_scale_i * (q . W_i) + bias_i`` for
+        every member in one ``tcsc_amd.sgemm_q8_group`` call -- up to 16 rows a single decode launch over all
+        the 2-bit images, one packed X and one k_gemm8w2 per member above.  Each y_i has the bits of a
+        :class:`PackedTernaryLinear` (a None) built from the same inputs.
+
+        Ws: the matrices, K x N_i each, as :class:`PackedTernaryLinear` takes W; the N_i are free.  biases,
+        weight_scales: None, or one entry per member (each as that layer's bias / weight_scale).  norm_weight,
+        norm_eps, out_dtype, device: shared, as there.  ``forward(x)`` writes one ``[rows, sum N_i]`` tensor and
+        returns the members' column slices of it as a tuple (views of one allocation: ``torch.cat`` is free).
+        ``state_dict()`` carries ``w2_<i>`` beside ``bias_<i>`` and, where the member has one,
+        ``weight_scale_<i>``; ``empty(K, [N_i]).load_state_dict(...)`` and ``reserve(rows)`` work as in
+        :class:`PackedTernaryLinear`."""
+
+        def __init__(self, Ws, biases=None, weight_scales=None, norm_weight=None, norm_eps: float | None = None,
+                     out_dtype=torch.float32, device: int = 0):
+            super().__init__()
+            from . import GROUP_MAX
+
+            Ws = list(Ws)
+            if not 1 <= len(Ws) <= GROUP_MAX:
+                raise TcscError(f"PackedTernaryGroup: {len(Ws)} matrices, a group holds 1 to {GROUP_MAX}")
+            mats = [_ternary_matrix(W, "PackedTernaryGroup") for W in Ws]
+            if any(m.rows != mats[0].rows for m in mats):
+                raise TcscError(f"PackedTernaryGroup: the matrices have {[m.rows for m in mats]} rows, one K is needed")
+            biases = [None] * len(mats) if biases is None else list(biases)
+            weight_scales = [None] * len(mats) if weight_scales is None else list(weight_scales)
+            if len(biases) != len(mats) or len(weight_scales) != len(mats):
+                raise TcscError("PackedTernaryGroup: biases and weight_scales take one entry per matrix")
+            self._init_common(mats[0].rows, [m.cols for m in mats], norm_eps, out_dtype, device)
+            dev = torch.device("cuda", self.device_index)
+            for k, n in enumerate(self.out_features_list):
+                self.register_buffer(f"bias_{k}", _bias_tensor(biases[k], n, dev, "PackedTernaryGroup"))
+                self.register_buffer(f"weight_scale_{k}", _weight_scale_tensor(weight_scales[k], n, dev))
+            nw, _ = _norm_args(norm_weight, norm_eps, self.in_features, dev)
+            self.register_buffer("norm_weight", nw)
+            self.plans = [Plan.packed(m, 0, m.cols, self.device_index, _stream(dev)) for m in mats]
+
+        def _init_common(self, K: int, cols, norm_eps, out_dtype, device):
+            from . import GROUP_MAX
+
+            cols = [int(n) for n in cols]
+            if not 1 <= len(cols) <= GROUP_MAX:
+                raise TcscError(f"PackedTernaryGroup: {len(cols)} members, a group holds 1 to {GROUP_MAX}")
+            self.in_features, self.out_features_list = int(K), cols
+            self.out_features = sum(cols)
+            self.device_index = int(device)
+            self.out_dtype = _out_dtype(out_dtype)
+            _, self.norm_eps = _norm_args(None, norm_eps, self.in_features, torch.device("cuda", self.device_index))
+            self.plans = None
+            self._rows, self._xq, self._scale = 0, None, None
+
+        @classmethod
+        def from_float(cls, Wfs, biases=None, norm_weight=None, norm_eps: float | None = None,
+                       out_dtype=torch.float32, device: int = 0):
+            """The layer of float matrices (K x N_i): each ternarized by ``tcsc_amd.ternarize_absmean``, its beta the
+            member's per-tensor weight scale."""
+            tb = [ternarize_absmean(W.detach().cpu().numpy() if torch.is_tensor(W) else W) for W in Wfs]
+            return cls([t for t, _ in tb], biases, [float(b) for _, b in tb], norm_weight, norm_eps, out_dtype, device)
+
+        @classmethod
+        def empty(cls, in_features: int, out_features_list, norm_eps: float | None = None, out_dtype=torch.float32,
+                  device: int = 0):
+            """A layer of these shapes with zero biases, no weight scales and no plans yet, for ``load_state_dict``."""
+            self = cls.__new__(cls)
+            torch.nn.Module.__init__(self)
+            self._init_common(in_features, out_features_list, norm_eps, out_dtype, device)
+            dev = torch.device("cuda", self.device_index)
+            for k, n in enumerate(self.out_features_list):
+                self.register_buffer(f"bias_{k}", torch.zeros(n, dtype=torch.float32, device=dev))
+                self.register_buffer(f"weight_scale_{k}", None)
+            self.register_buffer("norm_weight", None)
+            return self
+
+        def _loaded_plans(self, what: str):
+            if self.plans is None:
+                raise TcscError(f"PackedTernaryGroup.{what}: the layer is empty (PackedTernaryGroup.empty): load a "
+                                "state_dict first")
+            return self.plans
+
+        def _save_to_state_dict(self, destination, prefix, keep_vars):
+            super()._save_to_state_dict(destination, prefix, keep_vars)
+            st = _stream(torch.device("cuda", self.device_index))
+            for k, plan in enumerate(self._loaded_plans("state_dict")):
+                destination[f"{prefix}w2_{k}"] = plan.w2_image(st)
+
+        def _load_from_state_dict(self, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys,
+                                  error_msgs):
+            """Rebuilds every plan from its ``w2_<i>``; the images and the biases must be there, whatever
+            ``strict`` says (TcscError otherwise, the layer unchanged); the weight scales and ``norm_weight`` are
+            taken when present and the layer has none afterwards when absent."""
+            who, K = "PackedTernaryGroup.load_state_dict", self.in_features
+            dev = torch.device("cuda", self.device_index)
+            for k, n in enumerate(self.out_features_list):
+                for key in (f"bias_{k}", f"w2_{k}"):
+                    if prefix + key not in state_dict:
+                        raise TcscError(f"{who}: missing key {prefix + key!r}")
+                b, w2 = state_dict[f"{prefix}bias_{k}"], state_dict[f"{prefix}w2_{k}"]
+                want = w2_image_bytes(K, n)
+                if not torch.is_tensor(b) or b.numel() != n:
+                    raise TcscError(f"{who}: {prefix}bias_{k} must hold {n} values")
+                if not torch.is_tensor(w2) or w2.dtype != torch.uint8 or w2.numel() != want:
+                    raise TcscError(f"{who}: {prefix}w2_{k} must hold the {want} uint8 values of a {K} x {n} image")
+                ws = state_dict.get(f"{prefix}weight_scale_{k}")
+                if ws is not None and (not torch.is_tensor(ws) or ws.numel() != n):
+                    raise TcscError(f"{who}: {prefix}weight_scale_{k} must hold {n} values")
+            nw = state_dict.get(prefix + "norm_weight")
+            if nw is not None and (not torch.is_tensor(nw) or nw.numel() != K or self.norm_eps is None):
+                raise TcscError(f"{who}: {prefix}norm_weight must hold {K} values, on a layer made with norm_eps")
+            plans = [Plan.packed_from_image(state_dict[f"{prefix}w2_{k}"].detach().to(dev).contiguous(), K, n, 0,
+                                            self.device_index, _stream(dev))
+                     for k, n in enumerate(self.out_features_list)]
+            for k, n in enumerate(self.out_features_list):  # the base class copies into the buffers the layer has
+                has = state_dict.get(f"{prefix}weight_scale_{k}") is not None
+                setattr(self, f"weight_scale_{k}", torch.empty(n, dtype=torch.float32, device=dev) if has else None)
+            self.norm_weight = None if nw is None else torch.empty(K, dtype=torch.float32, device=dev)
+            super()._load_from_state_dict(state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys,
+                                          error_msgs)
+            for k in range(len(self.out_features_list)):
+                if f"{prefix}w2_{k}" in unexpected_keys:
+                    unexpected_keys.remove(f"{prefix}w2_{k}")
+            old, self.plans = self.plans, plans
+            for p in old or ():
+                p.destroy()
+
+        def _scratch(self, rows: int):
+            if self._rows < rows:
+                dev = torch.device("cuda", self.device_index)
+                self._xq = torch.empty((rows, self.in_features), dtype=torch.int8, device=dev)
+                self._scale = torch.empty(rows, dtype=torch.float32, device=dev)
+                self._rows = rows
+            return self._xq, self._scale
+
+        def reserve(self, max_rows: int) -> None:
+            """Every member plan's workspace and the layer's scratch (the quantized X and the row scales) for up
+            to max_rows rows: afterwards a forward allocates nothing but its output."""
+            for plan in self._loaded_plans("reserve"):
+                plan.reserve(max_rows)
+            self._scratch(max_rows)
+
+        def forward(self, x):
+            from . import sgemm_q8_group
+
+            plans = self._loaded_plans("forward")
+            if not torch.is_tensor(x) or x.dtype not in (torch.float32, torch.bfloat16) or not x.is_cuda:
+                raise TcscError("PackedTernaryGroup: x must be an fp32 or bf16 CUDA tensor")
+            if torch.is_grad_enabled() and x.requires_grad:
+                raise TcscError("PackedTernaryGroup is inference only: x requires grad")
+            if x.device.index != self.device_index or x.dim() < 1 or x.shape[-1] != self.in_features:
+                raise TcscError(f"PackedTernaryGroup: x has shape {tuple(x.shape)} on {x.device}, expected (..., "
+                                f"{self.in_features}) on cuda:{self.device_index}")
+            lead = x.shape[:-1]
+            x2 = x.detach().reshape(-1, self.in_features).contiguous()
+            M, n = x2.shape[0], len(plans)
+            xq, scale = self._scratch(M)
+            y = torch.empty((M, self.out_features), dtype=self.out_dtype, device=x.device)
+            ys = list(torch.split(y, self.out_features_list, dim=1))
+            sgemm_q8_group(plans, x2, xq, scale, [getattr(self, f"bias_{k}") for k in range(n)], ys, M,
+                           [self.out_features] * n, [getattr(self, f"weight_scale_{k}") for k in range(n)],
+                           self.norm_weight, self.norm_eps, _stream(x.device))
+            # the leading dimensions of x back on the row axis: views still (a reshape of a column slice would copy)
+            return tuple(v.unflatten(0, tuple(lead)) if lead else v[0] for v in ys)
+
+        def extra_repr(self) -> str:
+            return (f"in_features={self.in_features}, out_features={self.out_features_list}, "
+                    f"out_dtype={self.out_dtype}" + ("" if self.norm_eps is None else f", norm_eps={self.norm_eps}"))
+
     return {"TernaryLinear": TernaryLinear, "PackedTernaryLinear": PackedTernaryLinear,
-            "PackedTernaryGLU": PackedTernaryGLU, "PackedTernaryMLP": PackedTernaryMLP}
+            "PackedTernaryGLU": PackedTernaryGLU, "PackedTernaryMLP": PackedTernaryMLP,
+            "PackedTernaryGroup": PackedTernaryGroup}
 
 
 def __getattr__(name):
