@@ -937,6 +937,76 @@ int tcsc_gpu_launch_info_group(const tcsc_gpu_group_member *members, int count, 
                                int *path, int *slices /* count ints */, int *fused);
 int tcsc_gpu_group_fuse_pays(int M, int K, const int *cols, int count, int xtype, int norm); /* host arithmetic */
 
+/* ---- Residual add in the int8 epilogue: Y = R + X W --------------
+ * The output and down projections of a transformer block end in a skip
+ * connection, h = h + proj(x).  These calls add the residual where the value
+ * still sits in registers, instead of a second launch that reads Y and R and
+ * writes Y again.  With S the exact i32 sum of row m and column j:
+ *   v = fl(fl(fl(float(S) * dScale[m]) * dColScale[j]) + dB[j])
+ *                               tcsc_gpu_sgemm_i8_out's value, TCSC_VARIANT_BASIC
+ *   r = dR[m * ldr + j]         of ytype; a bf16 r is widened exactly
+ *   y = fl(v + r)               one rounded fp32 add, never contracted
+ *   dY[m * ldy + j] = y (TCSC_Y_F32), or y rounded to nearest even (TCSC_Y_BF16)
+ * R has the type of Y: the residual stream is what the call writes.  There is
+ * no PReLU, no `variant` and no `a` on these calls.
+ *
+ * Every route gives the same bits -- decode and MFMA, both GEMM tile shapes,
+ * every K split, packed and ordinary plans, the quantizer fused or not, the
+ * norm in front or not:
+ *   fp32 Y   tcsc_gpu_sgemm_i8_out into an fp32 Y0, then the fp32 add Y0 + R;
+ *   bf16 Y   bf16(Y0 + float(R)) with that fp32 Y0: ONE rounding to bf16.
+ * This is not what a bf16 layer followed by a bf16 add gives: that composition
+ * rounds v to bf16 first and the sum a second time, and differs from this call
+ * in the last bit of many elements.
+ *
+ * In place.  dR == dY with ldr == ldy is allowed: every output element is read
+ * and written by the same thread, the read first, and elements past the matrix
+ * are neither read nor written.  dR == dY with ldr != ldy is refused.  Any other
+ * overlap of R, Y, X and Xq is the caller's mistake and is not checked.
+ *
+ * Reads and stores.  Only rows < M and columns < cols of R are read; R is never
+ * written unless it is Y.  The store rules of tcsc_gpu_sgemm_i8_out hold for Y.
+ * A lane's four adjacent columns travel as one access where ldy % 4 == 0 and Y
+ * is aligned to four of its elements and, on these calls, ldr % 4 == 0 and R is
+ * aligned to four elements as well; otherwise element by element, each guarded.
+ *
+ * tcsc_gpu_sgemm_q8_res is tcsc_gpu_sgemm_q8_out -- with a norm,
+ * tcsc_gpu_sgemm_q8_norm -- followed by the add: X is fp32 or bf16 (xtype), the
+ * row scales are written to dScale and dXq is used as those calls use it (NULL
+ * allowed where the call is fused).  eps == 0.0f exactly, with a NULL dGamma,
+ * means no norm (tcsc_gpu_sgemm_q8_glu's convention); any other eps is checked
+ * as tcsc_gpu_sgemm_q8_norm checks it.
+ *
+ * Routing, fusing, workspace and capture are those of the calls extended: the
+ * route is what tcsc_gpu_launch_info_i8 / _q8 / _q8_norm report for the plan and
+ * M; the quantizer is fused under tcsc_gpu_quant_fuse_pays (with the norm:
+ * tcsc_gpu_norm_fuse_pays); $TCSC_DECODE, $TCSC_QFUSE, $TCSC_W2GEMM and
+ * $TCSC_MFMA_WGS keep their meaning.  The calls are served on TCSC_PATH_DECODE
+ * and TCSC_PATH_MFMA; where M routes to the gather or the small-M path they
+ * return TCSC_E_ARG with a message naming the call and the path, as the _out
+ * calls do for a typed Y.  After tcsc_gpu_plan_reserve(plan, max_M) a call of
+ * M <= max_M allocates nothing, does not synchronise and can be captured; a
+ * captured in-place call applied n times adds n products to R.
+ *
+ * TCSC_E_ARG with a message naming the call, before any HIP call, in this
+ * order: (q8 form) an xtype out of range, dGamma given with eps == 0, a bad
+ * eps; a ytype out of range; a NULL plan; a NULL dY or dB; a NULL dR;
+ * ldr < cols; dR == dY with ldr != ldy; then the checks of the calls extended
+ * (M < 0, ldy < cols, a NULL X or dScale, a NULL dXq where not fused).
+ *
+ * Out of scope: a residual on the gated and grouped calls; a residual of
+ * another type than Y's; PReLU with a residual; the gather and small-M routes;
+ * the next layer's norm-quantizer behind the add; a host-pointer version. */
+int tcsc_gpu_sgemm_i8_res(const tcsc_gpu_plan *plan, const void *dXq, const float *dScale,
+                          const float *dColScale, const float *dB,
+                          const void *dR, int ldr, void *dY, int ytype,
+                          int M, int ldy, void *stream);
+int tcsc_gpu_sgemm_q8_res(const tcsc_gpu_plan *plan, const void *dX, int xtype,
+                          const float *dGamma, float eps, void *dXq, float *dScale,
+                          const float *dColScale, const float *dB,
+                          const void *dR, int ldr, void *dY, int ytype,
+                          int M, int ldy, void *stream);
+
 /* Device-side tcsc_from_dense: dense K x N row-major float matrix on the
  * device -> TCSC arrays on the device, bit-exact with the reference builder
  * (tcsc.c:6-66).  Two calls: first with the four output pointers NULL to

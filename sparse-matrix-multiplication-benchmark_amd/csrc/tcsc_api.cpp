@@ -1017,6 +1017,8 @@ I8Epi i8_epi(const Call& c) {
     e.ldy = c.ldy;
     e.prelu = is_prelu(c.variant);
     e.a = c.a;
+    e.R = c.R;
+    e.ldr = c.ldr;
     return e;
 }
 
@@ -1105,6 +1107,13 @@ static bool refuse_out(const char* who, int path, const YOut& y, int M) {
               y.cscale ? "a column scale" : "", M, path_name(path), path);
     return true;
 }
+// A residual is added in the epilogues of the same two routes.
+static bool refuse_res(const char* who, int path, const void* R, int M) {
+    if (!R || path == TCSC_PATH_DECODE || path == TCSC_PATH_MFMA) return false;
+    set_error("%s: a residual needs the decode or the MFMA path, and M=%d routes to the %s path (%d), which has no "
+              "residual add", who, M, path_name(path), path);
+    return true;
+}
 
 // One call on the workspace ws: routed once (route_call, with what `pin`
 // fixes and what the pointers allow), then launched as routed.
@@ -1121,6 +1130,10 @@ int tcsc::sgemm_ws(const tcsc_gpu_plan* p, const Call& c, float* ws, size_t ws_b
     void* stream = c.stream;
     if (dt != kI8 && !y.plain()) {
         set_error("%s: only the int8 call has a typed Y and column scales", who);
+        return TCSC_E_ARG;
+    }
+    if (c.R && (dt != kI8 || stage != 0 || is_prelu(variant) || c.glu.up || c.group.count)) {
+        set_error("%s: a residual goes with the plain int8 call alone (no PReLU, not gated, not grouped)", who);
         return TCSC_E_ARG;
     }
     if (dt != kF32 && stage != 0) {
@@ -1170,7 +1183,7 @@ int tcsc::sgemm_ws(const tcsc_gpu_plan* p, const Call& c, float* ws, size_t ws_b
         set_error("%s: the plan cannot run M=%d on the pinned path %d", who, M, r.path);
         return TCSC_E_ARG;
     }
-    if (refuse_out(who, r.path, y, M)) return TCSC_E_ARG;
+    if (refuse_out(who, r.path, y, M) || refuse_res(who, r.path, c.R, M)) return TCSC_E_ARG;
     if (r.path == TCSC_PATH_DECODE) {
         HIP_TRY(tcsc::decode_gemm(tcsc::DecodeX{dX, kI8, nullptr, nullptr}, p->w2, p->rows, M, p->cols, i8_epi(c),
                                   p->num_cus, static_cast<hipStream_t>(stream)));
@@ -1921,9 +1934,11 @@ int tcsc_gpu_launch_combine(const tcsc_gpu_plan* p, int M, int* in_launch) {
 static int sgemm_entry(const tcsc_gpu_plan* p, const Call& c) {
     const int dt = c.xtype, M = c.M;
     if (dt != kI8 && refuse_packed(p, kXTypes[dt].sgemm)) return TCSC_E_ARG;
-    if (!c.y.plain() && p && M > 0 && p->cols > 0 &&
-        refuse_out(c.who ? c.who : kXTypes[dt].sgemm, route_call(p, M, dt, p->ws_bytes, RoutePins()).path, c.y, M))
-        return TCSC_E_ARG;
+    if ((!c.y.plain() || c.R) && p && M > 0 && p->cols > 0) {
+        const char* who = c.who ? c.who : kXTypes[dt].sgemm;
+        const int path = route_call(p, M, dt, p->ws_bytes, RoutePins()).path;
+        if (refuse_out(who, path, c.y, M) || refuse_res(who, path, c.R, M)) return TCSC_E_ARG;
+    }
     if (p && M > 0 && p->cols > 0 && p->ws_bytes < wanted_workspace(p, M, dt)) {
         const int rc = tcsc_gpu_plan_reserve(const_cast<tcsc_gpu_plan*>(p), M);
         if (rc != TCSC_OK) return rc;
@@ -2188,7 +2203,10 @@ static int sgemm_q8_impl(const tcsc_gpu_plan* p, const Call& c, const char* inne
         return TCSC_E_ARG;
     }
     bool fused = false;
-    if (p->cols > 0 && refuse_out(who, route_q8(p, M, xtype, &fused, norm != nullptr).path, c.y, M)) return TCSC_E_ARG;
+    if (p->cols > 0) {
+        const int path = route_q8(p, M, xtype, &fused, norm != nullptr).path;
+        if (refuse_out(who, path, c.y, M) || refuse_res(who, path, c.R, M)) return TCSC_E_ARG;
+    }
     if (!fused) {  // the quantizer into the caller's scratch, then the int8 call as it is: two or three launches
         if (!dXq && p->rows > 0) {
             set_error("%s: NULL dXq on a route that is not fused (M=%d)", who, M);
@@ -2299,6 +2317,65 @@ int tcsc_gpu_sgemm_q8_norm(const tcsc_gpu_plan* p, const void* dX, int xtype, co
     const RmsNorm norm{dGamma, eps};
     return sgemm_q8_impl(p, make_call(dX, xtype, nullptr, dB, y_out(dY, ytype, dColScale), M, ldy, variant, a, stream, who),
                          who, dXq, dScale, &norm);
+}
+
+// ---- the residual add in the epilogue ---------------------------
+// Y = R + X W: the _out and _q8_out / _q8_norm calls without PReLU, with R[m * ldr + j] (of Y's type)
+// added to the value in the epilogue of the decode and MFMA routes.  What the calls check on top of
+// out_args, ahead of any HIP call and in this order: a NULL dR, ldr < cols, and an R that is Y at
+// another pitch than Y's.
+static int res_args(const char* who, const tcsc_gpu_plan* p, const float* dB, const void* dR, int ldr, const void* dY,
+                    int ytype, int ldy) {
+    const int rc = out_args(who, p, dB, dY, ytype);
+    if (rc != TCSC_OK) return rc;
+    if (!dR) {
+        set_error("%s: NULL dR", who);
+        return TCSC_E_ARG;
+    }
+    if (ldr < p->cols) {
+        set_error("%s: ldr=%d < cols=%d", who, ldr, p->cols);
+        return TCSC_E_ARG;
+    }
+    if (dR == dY && ldr != ldy) {
+        set_error("%s: dR == dY (in place) with ldr=%d != ldy=%d", who, ldr, ldy);
+        return TCSC_E_ARG;
+    }
+    return TCSC_OK;
+}
+
+int tcsc_gpu_sgemm_i8_res(const tcsc_gpu_plan* p, const void* dXq, const float* dScale, const float* dColScale,
+                          const float* dB, const void* dR, int ldr, void* dY, int ytype, int M, int ldy, void* stream) {
+    const char* who = "tcsc_gpu_sgemm_i8_res";
+    const int rc = res_args(who, p, dB, dR, ldr, dY, ytype, ldy);
+    if (rc != TCSC_OK) return rc;
+    Call c = make_call(dXq, kI8, dScale, dB, y_out(dY, ytype, dColScale), M, ldy, TCSC_VARIANT_BASIC, 0.f, stream, who);
+    c.R = dR;
+    c.ldr = ldr;
+    return sgemm_entry(p, c);
+}
+
+int tcsc_gpu_sgemm_q8_res(const tcsc_gpu_plan* p, const void* dX, int xtype, const float* dGamma, float eps, void* dXq,
+                          float* dScale, const float* dColScale, const float* dB, const void* dR, int ldr, void* dY,
+                          int ytype, int M, int ldy, void* stream) {
+    const char* who = "tcsc_gpu_sgemm_q8_res";
+    if (xtype != TCSC_X_F32 && xtype != TCSC_X_BF16) {
+        set_error("%s: xtype=%d is neither TCSC_X_F32 (0) nor TCSC_X_BF16 (1)", who, xtype);
+        return TCSC_E_ARG;
+    }
+    const bool has_norm = eps != 0.0f;  // eps == 0 exactly: no norm in front (tcsc_gpu_sgemm_q8_glu's convention)
+    if (!has_norm && dGamma) {
+        set_error("%s: dGamma given with eps == 0 (no norm): pass the norm's eps, or a NULL dGamma", who);
+        return TCSC_E_ARG;
+    }
+    int rc = has_norm ? norm_args(who, xtype, eps, p ? p->rows : 1) : TCSC_OK;
+    if (rc != TCSC_OK) return rc;
+    rc = res_args(who, p, dB, dR, ldr, dY, ytype, ldy);
+    if (rc != TCSC_OK) return rc;
+    const RmsNorm norm{dGamma, eps};
+    Call c = make_call(dX, xtype, nullptr, dB, y_out(dY, ytype, dColScale), M, ldy, TCSC_VARIANT_BASIC, 0.f, stream, who);
+    c.R = dR;
+    c.ldr = ldr;
+    return sgemm_q8_impl(p, c, who, dXq, dScale, has_norm ? &norm : nullptr);
 }
 
 // ---- the gated FFN call -----------------------------------------

@@ -327,11 +327,18 @@ __device__ __forceinline__ void decode_block(const i32x4 (&xf)[4], const u32x4 (
 // columns on consecutive threads -- adds the WAVES shares and stores
 // i8_out(S, row_scale(row), ...).  The kernels differ in WAVES and in where
 // the row scale comes from.  Every thread of the workgroup calls this.
-template <int WAVES, int T, bool PRELU, typename TY, typename RowScale>
+// RES: what is stored is i8_res(value, R[row * ldr + col]), R of
+// Y's type.  The thread that stores an element is the one that reads it, the
+// read first, and outputs past the matrix are neither read nor stored, so
+// R == Y (with ldr == ldy) reads every element once, before its store.  Y
+// carries no restrict here: the kernels' own Y parameter does, except in the
+// residual instantiations (I8YPtr).
+template <int WAVES, int T, bool PRELU, bool RES = false, typename TY, typename RowScale>
 __device__ __forceinline__ void decode_reduce_store(int* red, const i32x4 (&acc)[T], const i32x4& rs, int wave, int lane,
                                                     int t0, int M, int N, RowScale row_scale,
                                                     const float* __restrict__ cscale, const float* __restrict__ bias,
-                                                    TY* __restrict__ Y, int ldy, float a) {
+                                                    TY* Y, int ldy, float a, const TY* R = nullptr, int ldr = 0) {
+    static_assert(!(RES && PRELU), "a residual call has no PReLU");
 #pragma unroll
     for (int t = 0; t < T; ++t)
 #pragma unroll
@@ -344,17 +351,23 @@ __device__ __forceinline__ void decode_reduce_store(int* red, const i32x4 (&acc)
         int S = 0;
 #pragma unroll
         for (int w = 0; w < WAVES; ++w) S += red[(w * T + t) * 256 + (row & 3) * 64 + (row >> 2) * 16 + c];
-        I8Y<TY>::put(Y + (size_t)row * ldy + col, i8_out<PRELU>(S, row_scale(row), i8_cscale(cscale, col), bias[col], a));
+        if constexpr (RES) {
+            const float r = I8Y<TY>::get(R + (size_t)row * ldr + col);
+            const float v = i8_out<false>(S, row_scale(row), i8_cscale(cscale, col), bias[col], 0.0f);
+            I8Y<TY>::put(Y + (size_t)row * ldy + col, i8_res(v, r));
+        } else {
+            I8Y<TY>::put(Y + (size_t)row * ldy + col, i8_out<PRELU>(S, row_scale(row), i8_cscale(cscale, col), bias[col], a));
+        }
     }
 }
 
-template <int T, bool ALIGNED, bool PRELU, typename TY>
+template <int T, bool ALIGNED, bool PRELU, typename TY, bool RES = false>
 __global__ void __launch_bounds__(kDecWaves * 64) k_decode8(const int8_t* __restrict__ X,
                                                              const uint32_t* __restrict__ W2, int K, int M, int N,
                                                              int nkb, int ntiles, const float* __restrict__ scale,
                                                              const float* __restrict__ cscale,
-                                                             const float* __restrict__ bias, TY* __restrict__ Y,
-                                                             int ldy, float a) {
+                                                             const float* __restrict__ bias, I8YPtr<TY, RES> Y,
+                                                             int ldy, float a, const TY* R = nullptr, int ldr = 0) {
     __shared__ int red[kDecWaves * T * 256];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -405,8 +418,9 @@ __global__ void __launch_bounds__(kDecWaves * 64) k_decode8(const int8_t* __rest
         kb = nx;
     }
 
-    decode_reduce_store<kDecWaves, T, PRELU>(
-        red, acc, rs, wave, lane, t0, M, N, [&](int row) { return scale ? scale[row] : 1.0f; }, cscale, bias, Y, ldy, a);
+    decode_reduce_store<kDecWaves, T, PRELU, RES>(
+        red, acc, rs, wave, lane, t0, M, N, [&](int row) { return scale ? scale[row] : 1.0f; }, cscale, bias, Y, ldy, a,
+        R, ldr);
 }
 
 // k_decode8q: k_quant_rows_i8 and k_decode8 in one launch, for
@@ -481,14 +495,14 @@ __device__ __forceinline__ void decode_norm_sweeps(const TX* __restrict__ X, con
     }
 }
 
-template <typename TX, int T, bool ALIGNED, bool PRELU, typename TY, bool NORM = false>
+template <typename TX, int T, bool ALIGNED, bool PRELU, typename TY, bool NORM = false, bool RES = false>
 __global__ void __launch_bounds__(kQWaves * 64) k_decode8q(const TX* __restrict__ X, const uint32_t* __restrict__ W2,
                                                            int K, int M, int N, int nkb, int ntiles,
                                                            float* __restrict__ scale_out,
                                                            const float* __restrict__ cscale,
-                                                           const float* __restrict__ bias, TY* __restrict__ Y,
+                                                           const float* __restrict__ bias, I8YPtr<TY, RES> Y,
                                                            int ldy, float a, const float* __restrict__ gamma = nullptr,
-                                                           float eps = 0.0f) {
+                                                           float eps = 0.0f, const TY* R = nullptr, int ldr = 0) {
     using XS = XSrc<TX>;
     constexpr int kThreads = kQWaves * 64, kHalves = kThreads / 32;
     constexpr int kRedBytes = kQWaves * T * 256 * 4, kStageBytes = kQWaves * kQWaveBytes;
@@ -689,9 +703,9 @@ __global__ void __launch_bounds__(kQWaves * 64) k_decode8q(const TX* __restrict_
     }
 
     __syncthreads();  // every wave is done with its staging block: the partial sums take the memory
-    decode_reduce_store<kQWaves, T, PRELU>(
+    decode_reduce_store<kQWaves, T, PRELU, RES>(
         reinterpret_cast<int*>(smem), acc, rs, wave, lane, t0, M, N, [&](int row) { return s_scale[row]; }, cscale, bias, Y,
-        ldy, a);
+        ldy, a, R, ldr);
 }
 
 // ---- the gated forms: act(X Wg) (X Wu) in one launch ---------------
@@ -1221,14 +1235,15 @@ int decode_tiles_per_wg(int M, int N, int num_cus) {
 }
 
 // The one decode launch (tcsc_internal.h).  Everything a kernel is instantiated
-// over -- Y type, tiles per workgroup, ALIGNED, PRELU, and for an X the launch
-// quantizes its type and the norm -- becomes a template argument here and
-// nowhere else; x and e are unpacked into the kernels' parameter lists.
+// over -- Y type, tiles per workgroup, ALIGNED, PRELU or the residual (§26: the
+// two exclude each other), and for an X the launch quantizes its type and the
+// norm -- becomes a template argument here and nowhere else; x and e are
+// unpacked into the kernels' parameter lists.
 hipError_t decode_gemm(const DecodeX& x, const uint32_t* w2, int K, int M, int N, const I8Epi& e, int num_cus,
                        hipStream_t st) {
     const bool quant = x.xtype != kI8;
     if (M < 1 || M > kDecodeMaxM || K < 1 || K >= kDecodeMaxK || N < 1 || !x.X || !w2 || (quant && !x.scale_out) || !e.B ||
-        !e.y.Y || e.ldy < N)
+        !e.y.Y || e.ldy < N || (e.R && (e.prelu || e.ldr < N || (e.R == e.y.Y && e.ldr != e.ldy))))
         return hipErrorInvalidValue;
     const int ntiles = w2_col_tiles(N), nkb = w2_kblocks(K), tiles = decode_tiles_per_wg(M, N, num_cus);
     const dim3 grid((ntiles + tiles - 1) / tiles);
@@ -1240,27 +1255,34 @@ hipError_t decode_gemm(const DecodeX& x, const uint32_t* w2, int K, int M, int N
         if (tiles == 2) return f(std::integral_constant<int, 2>{});
         return f(std::integral_constant<int, 1>{});
     };
+    // the tail: 0 plain, 1 PReLU, 2 the residual
+    auto with_tail = [&](auto&& f) {
+        if (e.R) return f(std::integral_constant<int, 2>{});
+        if (e.prelu) return f(std::integral_constant<int, 1>{});
+        return f(std::integral_constant<int, 0>{});
+    };
     with_elem(e.y.ytype == kYBf16, [&](auto ty) {
         using TY = typename decltype(ty)::type;
         TY* Y = static_cast<TY*>(e.y.Y);
+        const TY* R = static_cast<const TY*>(e.R);
         with_tiles([&](auto t) {
             with_bool(aligned, [&](auto al) {
-                with_bool(e.prelu, [&](auto pr) {
+                with_tail([&](auto tl) {
                     constexpr int T = decltype(t)::value;
-                    constexpr bool AL = decltype(al)::value, PR = decltype(pr)::value;
+                    constexpr bool AL = decltype(al)::value, PR = decltype(tl)::value == 1, RS = decltype(tl)::value == 2;
                     if (!quant) {
-                        hipLaunchKernelGGL((k_decode8<T, AL, PR, TY>), grid, dim3(kDecWaves * 64), 0, st,
+                        hipLaunchKernelGGL((k_decode8<T, AL, PR, TY, RS>), grid, dim3(kDecWaves * 64), 0, st,
                                            static_cast<const int8_t*>(x.X), w2, K, M, N, nkb, ntiles, e.rscale, e.y.cscale,
-                                           e.B, Y, e.ldy, e.a);
+                                           e.B, Y, e.ldy, e.a, R, e.ldr);
                         return;
                     }
                     with_elem(x.xtype == kBf16, [&](auto tx) {
                         using TX = typename decltype(tx)::type;
                         with_bool(x.norm != nullptr, [&](auto nm) {
-                            hipLaunchKernelGGL((k_decode8q<TX, T, AL, PR, TY, decltype(nm)::value>), grid,
+                            hipLaunchKernelGGL((k_decode8q<TX, T, AL, PR, TY, decltype(nm)::value, RS>), grid,
                                                dim3(kQWaves * 64), 0, st, static_cast<const TX*>(x.X), w2, K, M, N, nkb,
                                                ntiles, x.scale_out, e.y.cscale, e.B, Y, e.ldy, e.a,
-                                               x.norm ? x.norm->gamma : nullptr, x.norm ? x.norm->eps : 0.0f);
+                                               x.norm ? x.norm->gamma : nullptr, x.norm ? x.norm->eps : 0.0f, R, e.ldr);
                         });
                     });
                 });

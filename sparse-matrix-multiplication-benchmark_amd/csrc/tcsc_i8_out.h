@@ -2,11 +2,13 @@
 // §21), shared by every kernel that turns an exact i32 sum into Y: k_gemm8,
 // k_gemm8w2 and k_reduce_i8 (tcsc_mfma.hip), k_decode8 and k_decode8q
 // (tcsc_decode.hip), and the gate of the gated forms (§24: k_decode8g,
-// k_decode8qg, gemm8_store and k_reduce_i8 with GLU).  One definition, so the
-// paths give the same bits.
+// k_decode8qg, gemm8_store and k_reduce_i8 with GLU), and the residual add of
+// the residual forms (§26).  One definition, so the paths give the same bits.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include <type_traits>
 
 #include "tcsc_internal.h"
 
@@ -45,6 +47,15 @@ __device__ __forceinline__ float i8_glu(float g, float u, int act) {
     return s * u;
 }
 
+// The residual add of a residual call: v is i8_out<false> of the
+// sum and r the element of R, of Y's type and widened exactly (I8Y<TY>::get).
+// One rounded fp32 add, whatever stands around it: fl(v + r).
+__device__ __forceinline__ float i8_res(float v, float r) {
+#pragma clang fp contract(off)
+    const float y = v + r;
+    return y;
+}
+
 // c[j] of a call (null: all ones)
 __device__ __forceinline__ float i8_cscale(const float* __restrict__ c, int j) { return c ? c[j] : 1.0f; }
 
@@ -62,6 +73,9 @@ __device__ __forceinline__ uint16_t i8_bf16(float v) {
 // non-temporal store (16 B of floats, 8 B of bf16; dst aligned to four
 // elements): every store of either type goes through one of them, so a 2-byte
 // element is never written as half of a wider store it does not wholly own.
+// get() and get4() are the reads of a residual R of the same type (§26): one
+// element, or a lane's four adjacent columns as one load (src aligned to four
+// elements), widened to fp32 exactly.
 template <typename TY>
 struct I8Y;
 template <>
@@ -71,6 +85,12 @@ struct I8Y<float> {
     static __device__ __forceinline__ void put4_nt(float* dst, float v0, float v1, float v2, float v3) {
         typedef float f32x4 __attribute__((ext_vector_type(4)));
         __builtin_nontemporal_store(f32x4{v0, v1, v2, v3}, reinterpret_cast<f32x4*>(dst));
+    }
+    static __device__ __forceinline__ float get(const float* src) { return *src; }
+    static __device__ __forceinline__ void get4(const float* src, float (&r)[4]) {
+        typedef float f32x4 __attribute__((ext_vector_type(4)));
+        const f32x4 q = *reinterpret_cast<const f32x4*>(src);
+        r[0] = q[0], r[1] = q[1], r[2] = q[2], r[3] = q[3];
     }
 };
 template <>
@@ -85,6 +105,19 @@ struct I8Y<uint16_t> {
                          (uint32_t)i8_bf16(v2) | (uint32_t)i8_bf16(v3) << 16};
         __builtin_nontemporal_store(o, reinterpret_cast<u32x2*>(dst));
     }
+    static __device__ __forceinline__ float get(const uint16_t* src) { return __uint_as_float((uint32_t)*src << 16); }
+    static __device__ __forceinline__ void get4(const uint16_t* src, float (&r)[4]) {
+        typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+        const u32x2 q = *reinterpret_cast<const u32x2*>(src);
+        r[0] = __uint_as_float(q[0] << 16), r[1] = __uint_as_float(q[0] & 0xffff0000u);
+        r[2] = __uint_as_float(q[1] << 16), r[3] = __uint_as_float(q[1] & 0xffff0000u);
+    }
 };
+
+// The Y parameter of a kernel with a residual form: restrict-qualified as ever
+// where there is no residual, and plain where there is one, because an
+// in-place call passes one pointer as R and as Y (§26).
+template <typename TY, bool RES>
+using I8YPtr = std::conditional_t<RES, TY*, TY* __restrict__>;
 
 }  // namespace tcsc

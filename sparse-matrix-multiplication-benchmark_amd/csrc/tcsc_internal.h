@@ -229,6 +229,11 @@ struct I8Epi {
     const float* G = nullptr;
     int ldg = 0;
     int act = 0;  // kGluRelu2 / kGluSilu: TCSC_GLU_RELU2 / TCSC_GLU_SILU
+    // The residual of a residual call: Y[m, j] = i8_res(v, R[m * ldr + j]) with v this
+    // epilogue's value (no PReLU, not gated) and R of y's type, ldr in its elements.  R may be y.Y
+    // itself with ldr == ldy: every element is read by the thread that stores it, ahead of the store.
+    const void* R = nullptr;
+    int ldr = 0;
 };
 enum { kGluRelu2 = 0, kGluSilu = 1 };  // the gate activations of i8_glu (tcsc_i8_out.h)
 // The RMSNorm in front of a quantizer; gamma null = all ones

@@ -775,21 +775,36 @@ __global__ void __launch_bounds__(256) k_w8_from(const uint16_t* __restrict__ WT
 // 0, ldy % 4 == 0, 16-B aligned slabs, Y aligned to 4 of its elements), all
 // slices' loads in flight.  TY: float, or uint16_t for a bf16 Y (§21).  GLU (§24):
 // the value is the up half of a gated call and Y = i8_glu(G[row, col], value, act);
-// VEC then asks 16-B alignment and ldg % 4 == 0 of G too.
-template <bool PRELU, bool VEC, typename TY, bool GLU = false>
+// VEC then asks 16-B alignment and ldg % 4 == 0 of G too.  RES (§26): what is
+// stored is i8_res(value, R[row, col]), R of Y's type at pitch ldr and read by
+// the thread that stores the element, ahead of the store (R == Y is allowed, so
+// neither carries restrict); VEC then asks R aligned to four elements and
+// ldr % 4 == 0 as well.
+template <bool PRELU, bool VEC, typename TY, bool GLU = false, bool RES = false>
 __global__ void __launch_bounds__(256) k_reduce_i8(const int* __restrict__ ws, int slices, int M, int N,
                                                    const float* __restrict__ scale,
                                                    const float* __restrict__ cscale, const float* __restrict__ Bias,
-                                                   TY* __restrict__ Y, int ldy, float a,
-                                                   const float* __restrict__ G = nullptr, int ldg = 0, int act = 0) {
+                                                   I8YPtr<TY, RES> Y, int ldy, float a,
+                                                   const float* __restrict__ G = nullptr, int ldg = 0, int act = 0,
+                                                   const TY* R = nullptr, int ldr = 0) {
     static_assert(!(GLU && PRELU), "the halves of a gated call have no PReLU");
+    static_assert(!(RES && (GLU || PRELU)), "a residual call is neither gated nor has it a PReLU");
     constexpr int W = VEC ? 4 : 1;
     const int nq = N / W;
     const long long total = (long long)M * nq;
+    const int nslices = slices;
     for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total;
          i += (long long)gridDim.x * blockDim.x) {
+        // The loop's own copies of the slice count and the slab size.  RES: the empty asm makes them values
+        // of this iteration, so the 16 compares `s < slices` and the 15 products s * slab are made where they
+        // are used; hoisted out of the loop they are 16 masks and 15 offsets in some 60 SGPRs that live
+        // across it, and with R and ldr on top the residual form spilled 6 to 12 SGPRs.  The other forms
+        // keep their code (and the spills they had).
+        int slices = nslices;
+        size_t slab = (size_t)M * N;
+        if constexpr (RES) asm volatile("" : "+s"(slices), "+s"(slab));
         const int row = (int)(i / nq), col = W * (int)(i % nq);
-        const size_t slab = (size_t)M * N, e = (size_t)row * N + col;
+        const size_t e = (size_t)row * N + col;
         int p[16][W];
 #pragma unroll
         for (int s = 0; s < 16; ++s)
@@ -822,6 +837,17 @@ __global__ void __launch_bounds__(256) k_reduce_i8(const int* __restrict__ ws, i
                 v[0] = i8_glu(gp[0], v[0], act);
             }
         }
+        if constexpr (RES) {
+            const TY* rp = R + (size_t)row * ldr + col;
+            if constexpr (VEC) {
+                float r[4];
+                I8Y<TY>::get4(rp, r);
+#pragma unroll
+                for (int u = 0; u < 4; ++u) v[u] = i8_res(v[u], r[u]);
+            } else {
+                v[0] = i8_res(v[0], I8Y<TY>::get(rp));
+            }
+        }
         TY* dst = Y + (size_t)row * ldy + col;
         if constexpr (VEC)
             I8Y<TY>::put4_nt(dst, v[0], v[1], v[2], v[3]);
@@ -838,20 +864,30 @@ __global__ void __launch_bounds__(256) k_reduce_i8(const int* __restrict__ ws, i
 // of its elements and ldy % 4 == 0, else element by element, each guarded.
 // GLU (§24): the value is the up half of a gated call, and what is stored is
 // i8_glu(G[row, col], value, act), G the gate half's fp32 output at pitch ldg.
-template <int WM, int WN, int FI, int FJ, bool PRELU, bool PARTIAL, int LDSB, bool GLU = false, typename TY>
+// RES (§26): what is stored is i8_res(value, R[row, col]), R of Y's type at pitch
+// ldr.  A lane reads the four columns it stores, ahead of the store -- as one
+// load where the store is one and R is aligned to four elements with ldr % 4 ==
+// 0 too, else element by element, each guarded -- so R == Y (ldr == ldy) reads
+// every element once.  Y carries no restrict here: the kernels' own Y parameter
+// does, except in the residual instantiations (I8YPtr).
+template <int WM, int WN, int FI, int FJ, bool PRELU, bool PARTIAL, int LDSB, bool GLU = false, bool RES = false,
+          typename TY>
 __device__ __forceinline__ void gemm8_store(const i32x4 (&acc)[FI][FJ], char* lds, int lane, int wr, int wc, int m0,
                                             int n0, int M, int N, const float* __restrict__ scale,
                                             const float* __restrict__ cscale, const float* __restrict__ bias,
-                                            TY* __restrict__ Y, int ldy, float a,
-                                            const float* __restrict__ G = nullptr, int ldg = 0, int act = 0) {
+                                            TY* Y, int ldy, float a,
+                                            const float* __restrict__ G = nullptr, int ldg = 0, int act = 0,
+                                            const TY* R = nullptr, int ldr = 0) {
     static_assert(!PARTIAL || std::is_same<TY, float>::value, "the i32 slabs travel as the float instantiation");
     static_assert(!GLU || (!PARTIAL && !PRELU), "a gated store is a final one, and its halves have no PReLU");
+    static_assert(!RES || (!PARTIAL && !PRELU && !GLU), "a residual store is a final one, not gated and without PReLU");
     constexpr int TM = WM * FI * 16, TN = WN * FJ * 16, NW = WM * WN;
     constexpr int PR = 64, SROW = TN + 4, LPR = TN / 4;  // rows per pass, staged row, lanes per row
     static_assert(PR * SROW * 4 <= LDSB && TM % PR == 0 && (64 % LPR == 0 || LPR % 64 == 0), "epilogue staging");
     static_assert((NW * 64) % LPR == 0, "a lane keeps its columns across the read-back");
     int* stg = reinterpret_cast<int*>(lds);
-    const bool vec = (ldy & 3) == 0 && (reinterpret_cast<uintptr_t>(Y) & (4 * sizeof(TY) - 1)) == 0;
+    bool vec = (ldy & 3) == 0 && (reinterpret_cast<uintptr_t>(Y) & (4 * sizeof(TY) - 1)) == 0;
+    if constexpr (RES) vec = vec && (ldr & 3) == 0 && (reinterpret_cast<uintptr_t>(R) & (4 * sizeof(TY) - 1)) == 0;
     const int c4 = 4 * (threadIdx.x % LPR), col = n0 + c4;
     f32x4 bq = f32x4{0.f, 0.f, 0.f, 0.f}, cq = f32x4{1.f, 1.f, 1.f, 1.f};
     if (!PARTIAL) {
@@ -900,6 +936,19 @@ __device__ __forceinline__ void gemm8_store(const i32x4 (&acc)[FI][FJ], char* ld
                     for (int u = 0; u < 4; ++u)
                         if (col + u < N) v[u] = i8_glu(gp[u], v[u], act);
                 }
+                if constexpr (RES) {
+                    const TY* rp = R + (size_t)row * ldr + col;
+                    float r[4] = {0.f, 0.f, 0.f, 0.f};
+                    if (vec && col + 3 < N) {
+                        I8Y<TY>::get4(rp, r);
+                    } else {
+#pragma unroll
+                        for (int u = 0; u < 4; ++u)
+                            if (col + u < N) r[u] = I8Y<TY>::get(rp + u);
+                    }
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) v[u] = i8_res(v[u], r[u]);
+                }
                 TY* dst = Y + (size_t)row * ldy + col;
                 if (vec && col + 3 < N) {
                     I8Y<TY>::put4_nt(dst, v[0], v[1], v[2], v[3]);
@@ -923,13 +972,14 @@ __device__ __forceinline__ void gemm8_store(const i32x4 (&acc)[FI][FJ], char* ld
 // k values whichever they are, and an integer dot product does not depend on
 // their order.  ldk = ldw = mfma8_ldw(K) bytes.  PARTIAL: raw i32 sums into
 // slab blockIdx.y of Y (M x ldy ints), added by k_reduce_i8.
-template <int WM, int WN, int FI, int FJ, bool PRELU, bool PARTIAL, typename TY = float>
+template <int WM, int WN, int FI, int FJ, bool PRELU, bool PARTIAL, typename TY = float, bool RES = false>
 __global__ void __launch_bounds__(WM * WN * 64) k_gemm8(const int8_t* __restrict__ A, const int8_t* __restrict__ Bt,
                                                       int ldk, int ldw, int M, int N, int nblk,
                                                       const float* __restrict__ scale,
                                                       const float* __restrict__ cscale,
-                                                      const float* __restrict__ bias, TY* __restrict__ Y, int ldy,
-                                                      float a, int tiles_m, int tiles_n, int gm, int bps) {
+                                                      const float* __restrict__ bias, I8YPtr<TY, RES> Y, int ldy,
+                                                      float a, int tiles_m, int tiles_n, int gm, int bps,
+                                                      const TY* R = nullptr, int ldr = 0) {
     static_assert(!(PARTIAL && PRELU), "a partial slab carries raw sums");
     constexpr int TM = WM * FI * 16, TN = WN * FJ * 16, NW = WM * WN;
     constexpr int PA = TM / 8, PB = TN / 8;  // 1-KiB pieces of a slot
@@ -1054,8 +1104,9 @@ __global__ void __launch_bounds__(WM * WN * 64) k_gemm8(const int8_t* __restrict
     __syncthreads();
 
     TY* out = PARTIAL ? reinterpret_cast<TY*>(reinterpret_cast<int*>(Y) + (size_t)blockIdx.y * M * ldy) : Y;
-    gemm8_store<WM, WN, FI, FJ, PRELU, PARTIAL, 2 * ASLOT + 2 * BSLOT>(acc, lds, lane, wr, wc, m0, n0, M, N, scale, cscale, bias,
-                                                                       out, ldy, a);
+    gemm8_store<WM, WN, FI, FJ, PRELU, PARTIAL, 2 * ASLOT + 2 * BSLOT, false, RES>(acc, lds, lane, wr, wc, m0, n0, M, N, scale,
+                                                                                   cscale, bias, out, ldy, a, nullptr, 0, 0,
+                                                                                   R, ldr);
 }
 
 // k_gemm8w2: k_gemm8 with the B operand read from the 2-bit
@@ -1076,13 +1127,15 @@ __global__ void __launch_bounds__(WM * WN * 64) k_gemm8(const int8_t* __restrict
 // epilogue are k_gemm8's.  A workgroup's column tiles past the matrix read the
 // last tile again and are not stored; an odd count of 128-k blocks ends the
 // loop inside the last 256-k image block, whose second half is never read.
-template <int WN, int FI, int FJ, bool PRELU, bool PARTIAL, int BS = 2, typename TY = float, bool GLU = false>
+template <int WN, int FI, int FJ, bool PRELU, bool PARTIAL, int BS = 2, typename TY = float, bool GLU = false,
+          bool RES = false>
 __global__ void __launch_bounds__(WN * 64) k_gemm8w2(const int8_t* __restrict__ A, const uint32_t* __restrict__ W2,
                                                     int ldk, int M, int N, int nblk, int nkb, int ntiles,
                                                     const float* __restrict__ scale, const float* __restrict__ cscale,
-                                                    const float* __restrict__ bias, TY* __restrict__ Y, int ldy,
+                                                    const float* __restrict__ bias, I8YPtr<TY, RES> Y, int ldy,
                                                     float a, int tiles_m, int tiles_n, int gm, int bps,
-                                                    const float* __restrict__ G = nullptr, int ldg = 0, int act = 0) {
+                                                    const float* __restrict__ G = nullptr, int ldg = 0, int act = 0,
+                                                    const TY* R = nullptr, int ldr = 0) {
     static_assert(!(PARTIAL && PRELU), "a partial slab carries raw sums");
     constexpr int TM = FI * 16, TN = WN * FJ * 16, NW = WN;
     constexpr int PA = TM / 8, ASLOT = PA * 1024, PAW = PA / NW;
@@ -1222,8 +1275,8 @@ __global__ void __launch_bounds__(WN * 64) k_gemm8w2(const int8_t* __restrict__ 
     __syncthreads();
 
     TY* out = PARTIAL ? reinterpret_cast<TY*>(reinterpret_cast<int*>(Y) + (size_t)blockIdx.y * M * ldy) : Y;
-    gemm8_store<1, WN, FI, FJ, PRELU, PARTIAL, LDSB, GLU>(acc, lds, lane, 0, wave, m0, n0, M, N, scale, cscale, bias, out,
-                                                          ldy, a, G, ldg, act);
+    gemm8_store<1, WN, FI, FJ, PRELU, PARTIAL, LDSB, GLU, RES>(acc, lds, lane, 0, wave, m0, n0, M, N, scale, cscale, bias,
+                                                               out, ldy, a, G, ldg, act, R, ldr);
 }
 
 // tcsc_gpu_quantize_rows_i8{,_bf16}: per row, amax = max |x|, scale = amax /
@@ -1695,10 +1748,18 @@ static hipError_t launch_reduce_i8(const int* slabs, int slices, int M, int N, c
     return with_elem(e.y.ytype == kYBf16, [&](auto ty) {
         using TY = typename decltype(ty)::type;
         TY* Y = static_cast<TY*>(e.y.Y);
+        const TY* R = static_cast<const TY*>(e.R);
         const bool vec = N % 4 == 0 && e.ldy % 4 == 0 && (reinterpret_cast<uintptr_t>(Y) & (4 * sizeof(TY) - 1)) == 0 &&
-                         aligned16(slabs) && (!e.G || (e.ldg % 4 == 0 && aligned16(e.G)));
+                         aligned16(slabs) && (!e.G || (e.ldg % 4 == 0 && aligned16(e.G))) &&
+                         (!R || (e.ldr % 4 == 0 && (reinterpret_cast<uintptr_t>(R) & (4 * sizeof(TY) - 1)) == 0));
         const long long n = (long long)M * (vec ? N / 4 : N);
         return with_bool(vec, [&](auto v) {
+            if (R) {  // a residual call (never gated, never with a PReLU: mfma8_gemm and mfma8_gemm_w2 refuse both)
+                hipLaunchKernelGGL((k_reduce_i8<false, decltype(v)::value, TY, false, true>), dim3(grid_of(n, 256)), dim3(256),
+                                   0, st, slabs, slices, M, N, e.rscale, e.y.cscale, e.B, Y, e.ldy, e.a, nullptr, 0, 0, R,
+                                   e.ldr);
+                return hipGetLastError();
+            }
             if (e.G) {  // the up half of a gated call (never with a PReLU: mfma8_gemm_w2 refuses it)
                 hipLaunchKernelGGL((k_reduce_i8<false, decltype(v)::value, TY, true>), dim3(grid_of(n, 256)), dim3(256), 0,
                                    st, slabs, slices, M, N, e.rscale, e.y.cscale, e.B, Y, e.ldy, e.a, e.G, e.ldg, e.act);
@@ -1713,12 +1774,13 @@ static hipError_t launch_reduce_i8(const int* slabs, int slices, int M, int N, c
     });
 }
 
-template <bool PRELU, typename TY>
+template <bool PRELU, typename TY, bool RES = false>
 static hipError_t launch_gemm8_t(const int8_t* x8, const int8_t* w8, int ld8, int nblk, int M, int N, const I8Epi& epi,
                                  int* slabs, int slices, hipStream_t st) {
     constexpr int kGm = 4;  // bands of 4 row tiles, as launch_gemm3_t
     const float *scale = epi.rscale, *cscale = epi.y.cscale, *B = epi.B;  // the kernels' parameter lists
     TY* Y = static_cast<TY*>(epi.y.Y);
+    const TY* R = static_cast<const TY*>(epi.R);
     const int ldy = epi.ldy;
     const float a = epi.a;
     float* sl = reinterpret_cast<float*>(slabs);
@@ -1727,16 +1789,16 @@ static hipError_t launch_gemm8_t(const int8_t* x8, const int8_t* w8, int ld8, in
         const int tm = (M + 127) / 128, tn = (N + 511) / 512;
         const int gm = std::min(kGm, tm);
         if (slices <= 1)
-            hipLaunchKernelGGL((k_gemm8<1, 8, 8, 4, PRELU, false, TY>), dim3(tm * tn), dim3(512), 0, st, x8, w8, ld8, ld8, M, N,
-                               nblk, scale, cscale, B, Y, ldy, a, tm, tn, gm, nblk);
+            hipLaunchKernelGGL((k_gemm8<1, 8, 8, 4, PRELU, false, TY, RES>), dim3(tm * tn), dim3(512), 0, st, x8, w8, ld8, ld8, M, N,
+                               nblk, scale, cscale, B, Y, ldy, a, tm, tn, gm, nblk, R, epi.ldr);
         else
             hipLaunchKernelGGL((k_gemm8<1, 8, 8, 4, false, true>), dim3(tm * tn, slices), dim3(512), 0, st, x8, w8, ld8,
                                ld8, M, N, nblk, nullptr, nullptr, nullptr, sl, N, 0.0f, tm, tn, gm, bps);
     } else if (mfma_narrow_tiles(M, N)) {
         const int tn = (N + 255) / 256;
         if (slices <= 1)
-            hipLaunchKernelGGL((k_gemm8<1, 4, 4, 4, PRELU, false, TY>), dim3(tn), dim3(256), 0, st, x8, w8, ld8, ld8, M, N, nblk,
-                               scale, cscale, B, Y, ldy, a, 1, tn, 1, nblk);
+            hipLaunchKernelGGL((k_gemm8<1, 4, 4, 4, PRELU, false, TY, RES>), dim3(tn), dim3(256), 0, st, x8, w8, ld8, ld8, M, N, nblk,
+                               scale, cscale, B, Y, ldy, a, 1, tn, 1, nblk, R, epi.ldr);
         else
             hipLaunchKernelGGL((k_gemm8<1, 4, 4, 4, false, true>), dim3(tn, slices), dim3(256), 0, st, x8, w8, ld8, ld8, M,
                                N, nblk, nullptr, nullptr, nullptr, sl, N, 0.0f, 1, tn, 1, bps);
@@ -1744,8 +1806,8 @@ static hipError_t launch_gemm8_t(const int8_t* x8, const int8_t* w8, int ld8, in
         const int tm = (M + 127) / 128, tn = (N + 127) / 128;
         const int gm = std::min(kGm, tm);
         if (slices <= 1)
-            hipLaunchKernelGGL((k_gemm8<2, 2, 4, 4, PRELU, false, TY>), dim3(tm * tn), dim3(256), 0, st, x8, w8, ld8, ld8, M, N,
-                               nblk, scale, cscale, B, Y, ldy, a, tm, tn, gm, nblk);
+            hipLaunchKernelGGL((k_gemm8<2, 2, 4, 4, PRELU, false, TY, RES>), dim3(tm * tn), dim3(256), 0, st, x8, w8, ld8, ld8, M, N,
+                               nblk, scale, cscale, B, Y, ldy, a, tm, tn, gm, nblk, R, epi.ldr);
         else
             hipLaunchKernelGGL((k_gemm8<2, 2, 4, 4, false, true>), dim3(tm * tn, slices), dim3(256), 0, st, x8, w8, ld8,
                                ld8, M, N, nblk, nullptr, nullptr, nullptr, sl, N, 0.0f, tm, tn, gm, bps);
@@ -1758,12 +1820,13 @@ static hipError_t launch_gemm8_t(const int8_t* x8, const int8_t* w8, int ld8, in
 // k_gemm8w2 on k_gemm8's three grids, slices and blocks per slice: 128 x 512
 // (8 waves of 128 x 64), 64 x 256 (4 waves of 64 x 64) and 128 x 128 (4 waves
 // of 128 x 32), so mfma_tiles and mfma8_slices count its workgroups as they are.
-template <bool PRELU, typename TY, bool GLU = false>
+template <bool PRELU, typename TY, bool GLU = false, bool RES = false>
 static hipError_t launch_gemm8w2_t(const int8_t* x8, const uint32_t* w2, int ld8, int nblk, int K, int M, int N,
                                    const I8Epi& epi, int* slabs, int slices, hipStream_t st) {
     constexpr int kGm = 4;
     const float *scale = epi.rscale, *cscale = epi.y.cscale, *B = epi.B;
     TY* Y = static_cast<TY*>(epi.y.Y);
+    const TY* R = static_cast<const TY*>(epi.R);
     const int ldy = epi.ldy;
     const float a = epi.a;
     float* sl = reinterpret_cast<float*>(slabs);
@@ -1773,16 +1836,16 @@ static hipError_t launch_gemm8w2_t(const int8_t* x8, const uint32_t* w2, int ld8
         const int tm = (M + 127) / 128, tn = (N + 511) / 512;
         const int gm = std::min(kGm, tm);
         if (slices <= 1)
-            hipLaunchKernelGGL((k_gemm8w2<8, 8, 4, PRELU, false, 1, TY, GLU>), dim3(tm * tn), dim3(512), 0, st, x8, w2, ld8, M, N,
-                               nblk, nkb, nt, scale, cscale, B, Y, ldy, a, tm, tn, gm, nblk, epi.G, epi.ldg, epi.act);
+            hipLaunchKernelGGL((k_gemm8w2<8, 8, 4, PRELU, false, 1, TY, GLU, RES>), dim3(tm * tn), dim3(512), 0, st, x8, w2, ld8, M, N,
+                               nblk, nkb, nt, scale, cscale, B, Y, ldy, a, tm, tn, gm, nblk, epi.G, epi.ldg, epi.act, R, epi.ldr);
         else
             hipLaunchKernelGGL((k_gemm8w2<8, 8, 4, false, true, 1>), dim3(tm * tn, slices), dim3(512), 0, st, x8, w2, ld8, M,
                                N, nblk, nkb, nt, nullptr, nullptr, nullptr, sl, N, 0.0f, tm, tn, gm, bps);
     } else if (mfma_narrow_tiles(M, N)) {
         const int tn = (N + 255) / 256;
         if (slices <= 1)
-            hipLaunchKernelGGL((k_gemm8w2<4, 4, 4, PRELU, false, 2, TY, GLU>), dim3(tn), dim3(256), 0, st, x8, w2, ld8, M, N, nblk,
-                               nkb, nt, scale, cscale, B, Y, ldy, a, 1, tn, 1, nblk, epi.G, epi.ldg, epi.act);
+            hipLaunchKernelGGL((k_gemm8w2<4, 4, 4, PRELU, false, 2, TY, GLU, RES>), dim3(tn), dim3(256), 0, st, x8, w2, ld8, M, N, nblk,
+                               nkb, nt, scale, cscale, B, Y, ldy, a, 1, tn, 1, nblk, epi.G, epi.ldg, epi.act, R, epi.ldr);
         else
             hipLaunchKernelGGL((k_gemm8w2<4, 4, 4, false, true>), dim3(tn, slices), dim3(256), 0, st, x8, w2, ld8, M, N,
                                nblk, nkb, nt, nullptr, nullptr, nullptr, sl, N, 0.0f, 1, tn, 1, bps);
@@ -1790,8 +1853,8 @@ static hipError_t launch_gemm8w2_t(const int8_t* x8, const uint32_t* w2, int ld8
         const int tm = (M + 127) / 128, tn = (N + 127) / 128;
         const int gm = std::min(kGm, tm);
         if (slices <= 1)
-            hipLaunchKernelGGL((k_gemm8w2<4, 8, 2, PRELU, false, 2, TY, GLU>), dim3(tm * tn), dim3(256), 0, st, x8, w2, ld8, M, N,
-                               nblk, nkb, nt, scale, cscale, B, Y, ldy, a, tm, tn, gm, nblk, epi.G, epi.ldg, epi.act);
+            hipLaunchKernelGGL((k_gemm8w2<4, 8, 2, PRELU, false, 2, TY, GLU, RES>), dim3(tm * tn), dim3(256), 0, st, x8, w2, ld8, M, N,
+                               nblk, nkb, nt, scale, cscale, B, Y, ldy, a, tm, tn, gm, nblk, epi.G, epi.ldg, epi.act, R, epi.ldr);
         else
             hipLaunchKernelGGL((k_gemm8w2<4, 8, 2, false, true>), dim3(tm * tn, slices), dim3(256), 0, st, x8, w2, ld8, M,
                                N, nblk, nkb, nt, nullptr, nullptr, nullptr, sl, N, 0.0f, tm, tn, gm, bps);
@@ -1799,6 +1862,12 @@ static hipError_t launch_gemm8w2_t(const int8_t* x8, const uint32_t* w2, int ld8
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess || slices <= 1) return e;
     return launch_reduce_i8(slabs, slices, M, N, epi, st);
+}
+
+// what a residual epilogue must be: no PReLU, not gated, R at a pitch of at least N, and
+// an R that is Y at Y's pitch
+static bool i8_res_ok(const I8Epi& e, int N) {
+    return !e.prelu && !e.G && e.ldr >= N && (e.R != e.y.Y || e.ldr == e.ldy);
 }
 
 // the Y type and the PReLU of the descriptor into template arguments
@@ -1812,8 +1881,13 @@ hipError_t mfma8_gemm(const int8_t* x8, const int8_t* w8, int ld8, int K, int M,
     if (M <= 0 || N <= 0) return hipSuccess;
     const int nblk = mfma8_nblk(K);
     if (nblk < 1 || ld8 != mfma8_ldw(K) || !e.y.Y || e.G) return hipErrorInvalidValue;  // a gated call runs k_gemm8w2
+    if (e.R && !i8_res_ok(e, N)) return hipErrorInvalidValue;
     const int slices = mfma8_slices(M, N, K);
     if (slices > 1 && (!slabs || slab_bytes < mfma8_slab_bytes(M, N, K))) return hipErrorInvalidValue;
+    if (e.R)
+        return with_elem(e.y.ytype == kYBf16, [&](auto ty) {
+            return launch_gemm8_t<false, typename decltype(ty)::type, true>(x8, w8, ld8, nblk, M, N, e, slabs, slices, st);
+        });
     return with_i8_epi(e, [&](auto ty, auto pr) {
         return launch_gemm8_t<decltype(pr)::value, typename decltype(ty)::type>(x8, w8, ld8, nblk, M, N, e, slabs, slices, st);
     });
@@ -1826,6 +1900,13 @@ hipError_t mfma8_gemm_w2(const int8_t* x8, const uint32_t* w2, int ld8, int K, i
     if (nblk < 1 || ld8 != mfma8_ldw(K) || K >= kDecodeMaxK || !w2 || !e.y.Y) return hipErrorInvalidValue;
     const int slices = mfma8_slices(M, N, K);
     if (slices > 1 && (!slabs || slab_bytes < mfma8_slab_bytes(M, N, K))) return hipErrorInvalidValue;
+    if (e.R) {  // a residual call: no PReLU, not gated, R at a pitch of at least N
+        if (!i8_res_ok(e, N)) return hipErrorInvalidValue;
+        return with_elem(e.y.ytype == kYBf16, [&](auto ty) {
+            return launch_gemm8w2_t<false, typename decltype(ty)::type, false, true>(x8, w2, ld8, nblk, K, M, N, e, slabs, slices,
+                                                                                    st);
+        });
+    }
     if (e.G) {  // the up half of a gated call: no PReLU, G at a pitch of at least N, a known activation
         if (e.prelu || e.ldg < N || (e.act != kGluRelu2 && e.act != kGluSilu)) return hipErrorInvalidValue;
         return with_elem(e.y.ytype == kYBf16, [&](auto ty) {

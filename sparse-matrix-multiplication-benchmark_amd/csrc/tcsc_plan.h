@@ -134,15 +134,21 @@ struct Call {
     const char* who = nullptr;
     GluUp glu;
     GroupRest group;
+    // The residual of a residual call (tcsc_gpu_sgemm_i8_res): M x ldr elements of y's
+    // type, added to the call's value in the epilogue; it may be y.Y itself with ldr == ldy.  Null:
+    // not a residual call.  Only the decode and MFMA routes of the int8 call serve one.
+    const void* R = nullptr;
+    int ldr = 0;
     // rows [r0, r0 + n) of a call on a matrix of K rows as a call of their own: X (x_elem bytes an
-    // element), the row scales, Y (by the element size of its type), a gated call's G and every
-    // further member's Y of a grouped call advance by r0 rows
+    // element), the row scales, Y and a residual call's R (by the element size of their type), a gated
+    // call's G and every further member's Y of a grouped call advance by r0 rows
     Call rows(int r0, int n, int K, size_t x_elem) const {
         Call c = *this;
         c.X = X ? static_cast<const char*>(X) + (size_t)r0 * K * x_elem : nullptr;
         c.xscale = xscale ? xscale + r0 : nullptr;
         c.y = y.rows_on((size_t)r0, ldy);
         c.glu.G = glu.G ? glu.G + (size_t)r0 * glu.ldg : nullptr;
+        c.R = R ? static_cast<const char*>(R) + (size_t)r0 * ldr * y.elem() : nullptr;
         for (int i = 0; i < group.count; ++i) c.group.m[i].y = group.m[i].y.rows_on((size_t)r0, group.m[i].ldy);
         c.M = n;
         return c;

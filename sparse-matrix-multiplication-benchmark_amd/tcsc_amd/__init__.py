@@ -62,6 +62,7 @@ EXPORTED_SYMBOLS = (
     "tcsc_gpu_launch_info_q8_norm", "tcsc_gpu_norm_fuse_pays",
     "tcsc_gpu_sgemm_i8_glu", "tcsc_gpu_sgemm_q8_glu", "tcsc_gpu_launch_info_glu", "tcsc_gpu_glu_fuse_pays",
     "tcsc_gpu_sgemm_i8_group", "tcsc_gpu_sgemm_q8_group", "tcsc_gpu_launch_info_group", "tcsc_gpu_group_fuse_pays",
+    "tcsc_gpu_sgemm_i8_res", "tcsc_gpu_sgemm_q8_res",
     # include/sparse/bcsr.h
     "bcsr_from_dense", "bcsr_sgemm_basic", "bcsr_sgemm_prelu_basic", "bcsr_sgemm_avx", "bcsr_sgemm_prelu_avx",
     "bcsr_sgemm_avx2", "bcsr_free",
@@ -215,6 +216,8 @@ def lib():
     L.tcsc_gpu_sgemm_q8_group.argtypes = [gm, i, vp, i, vp, f, vp, vp, i, i, vp]
     L.tcsc_gpu_launch_info_group.argtypes = [gm, i, i, i, C.POINTER(i), C.POINTER(i), C.POINTER(i)]
     L.tcsc_gpu_group_fuse_pays.argtypes = [i, i, C.POINTER(i), i, i, i]
+    L.tcsc_gpu_sgemm_i8_res.argtypes = [vp, vp, vp, vp, vp, vp, i, vp, i, i, i, vp]
+    L.tcsc_gpu_sgemm_q8_res.argtypes = [vp, vp, i, vp, f, vp, vp, vp, vp, vp, i, vp, i, i, i, vp]
     L.tcsc_gpu_prepare_x.argtypes = [vp, vp, i, vp]
     L.tcsc_gpu_sgemm_prepared.argtypes = [vp, vp, vp, i, i, i, f, vp]
     L.tcsc_gpu_from_dense.argtypes = [vp, i, i, vp, vp, vp, vp, C.POINTER(i), C.POINTER(i), vp]
@@ -754,27 +757,44 @@ class Plan:
         return bool(lib().tcsc_gpu_plan_has_w2(self.handle))
 
     def sgemm_i8(self, Xq, scale, B, Y, M: int, ldy: int, variant: str = "prelu_basic", a: float = 0.2,
-                 stream: int = 0, col_scale=None, ytype=None) -> None:
+                 stream: int = 0, col_scale=None, ytype=None, residual=None, ldr=None) -> None:
         """Y = act(scale[m] * col_scale[j] * (Xq . W) + B) for int8 activations (tcsc_gpu_sgemm_i8_out): Xq is
         M x K contiguous int8 (a torch.int8 tensor or a pointer), scale M floats or None for all ones, col_scale
         the plan's cols floats or None for all ones; B is fp32.  Y is fp32 or bf16, ldy in its elements: a
         tensor's dtype says which, a raw pointer is fp32 unless ytype ('f32' / 'bf16') says otherwise.  A
-        col_scale or a bf16 Y needs the decode or the MFMA route (:meth:`launch_info_i8`): TcscError elsewhere."""
+        col_scale or a bf16 Y needs the decode or the MFMA route (:meth:`launch_info_i8`): TcscError elsewhere.
+
+        residual (tcsc_gpu_sgemm_i8_res): M x ldr elements of Y's type (ldr defaults to ldy), added to the value
+        in the epilogue as one fp32 add ahead of the one rounding to Y's type; it may be Y itself with ldr ==
+        ldy (in place).  The variant must then be 'basic', and the route decode or MFMA."""
         yt = _ytype_of(Y) if ytype is None else _ytype(ytype)
+        if residual is not None:
+            _res_check(residual, yt, variant)
+            _check(lib().tcsc_gpu_sgemm_i8_res(self.handle, C.c_void_p(_ptr(Xq)), C.c_void_p(_ptr(scale)),
+                                               C.c_void_p(_ptr(col_scale)), C.c_void_p(_ptr(B)),
+                                               C.c_void_p(_ptr(residual)), int(ldy if ldr is None else ldr),
+                                               C.c_void_p(_ptr(Y)), yt, int(M), int(ldy), C.c_void_p(stream)),
+                   "tcsc_gpu_sgemm_i8_res")
+            return
         _check(lib().tcsc_gpu_sgemm_i8_out(self.handle, C.c_void_p(_ptr(Xq)), C.c_void_p(_ptr(scale)),
                                            C.c_void_p(_ptr(col_scale)), C.c_void_p(_ptr(B)), C.c_void_p(_ptr(Y)), yt,
                                            int(M), int(ldy), VARIANT_ID[variant], float(a), C.c_void_p(stream)),
                "tcsc_gpu_sgemm_i8_out")
 
     def sgemm_q8(self, X, Xq, scale, B, Y, M: int, ldy: int, variant: str = "prelu_basic", a: float = 0.2,
-                 stream: int = 0, xtype=None, col_scale=None, ytype=None) -> None:
+                 stream: int = 0, xtype=None, col_scale=None, ytype=None, residual=None, ldr=None) -> None:
         """The quantizer and :meth:`sgemm_i8` in one call (tcsc_gpu_sgemm_q8_out): X is M x K contiguous fp32 or
         bf16 (a torch tensor, whose dtype says which, or a pointer with xtype 'f32' / 'bf16'), scale (M floats) is
         written, Xq (M x K int8) is scratch -- untouched, and allowed to be None, where the call is fused
         (:meth:`launch_info_q8`).  Y and scale get the bits of :func:`quantize_rows_i8` + :meth:`sgemm_i8`;
-        col_scale, the type of Y and ytype as there."""
+        col_scale, the type of Y, ytype, residual and ldr as there (tcsc_gpu_sgemm_q8_res)."""
         xt = _xtype_of(X) if xtype is None else _xtype(xtype)
         yt = _ytype_of(Y) if ytype is None else _ytype(ytype)
+        if residual is not None:
+            _res_check(residual, yt, variant)
+            self._sgemm_q8_res(X, xt, None, 0.0, Xq, scale, col_scale, B, residual, ldy if ldr is None else ldr, Y, yt,
+                               M, ldy, stream)
+            return
         _check(lib().tcsc_gpu_sgemm_q8_out(self.handle, C.c_void_p(_ptr(X)), xt, C.c_void_p(_ptr(Xq)),
                                            C.c_void_p(_ptr(scale)), C.c_void_p(_ptr(col_scale)), C.c_void_p(_ptr(B)),
                                            C.c_void_p(_ptr(Y)), yt, int(M), int(ldy), VARIANT_ID[variant], float(a),
@@ -791,18 +811,34 @@ class Plan:
 
     def sgemm_q8_norm(self, X, Xq, scale, B, Y, M: int, ldy: int, norm_weight=None, eps: float = 1e-6,
                       variant: str = "prelu_basic", a: float = 0.2, stream: int = 0, xtype=None, col_scale=None,
-                      ytype=None) -> None:
+                      ytype=None, residual=None, ldr=None) -> None:
         """:meth:`sgemm_q8` on RMSNorm(X) * norm_weight (tcsc_gpu_sgemm_q8_norm): norm_weight is K floats or None
         for all ones.  Y and scale get the bits of :func:`rmsnorm_rows` + :func:`quantize_rows_i8` +
         :meth:`sgemm_i8`; one launch where the call is fused (:meth:`launch_info_q8_norm`: Xq is then untouched and
-        may be None), :func:`quantize_rows_i8_norm` into Xq and the int8 call elsewhere."""
+        may be None), :func:`quantize_rows_i8_norm` into Xq and the int8 call elsewhere.  residual and ldr as in
+        :meth:`sgemm_i8` (tcsc_gpu_sgemm_q8_res with the norm; eps must not be 0 there)."""
         xt = _xtype_of(X) if xtype is None else _xtype(xtype)
         yt = _ytype_of(Y) if ytype is None else _ytype(ytype)
+        if residual is not None:
+            _res_check(residual, yt, variant)
+            if float(eps) == 0.0:
+                raise TcscError("sgemm_q8_norm: eps == 0 means no norm on the residual call; use sgemm_q8")
+            self._sgemm_q8_res(X, xt, norm_weight, eps, Xq, scale, col_scale, B, residual, ldy if ldr is None else ldr,
+                               Y, yt, M, ldy, stream)
+            return
         _check(lib().tcsc_gpu_sgemm_q8_norm(self.handle, C.c_void_p(_ptr(X)), xt, C.c_void_p(_ptr(norm_weight)),
                                             float(eps), C.c_void_p(_ptr(Xq)), C.c_void_p(_ptr(scale)),
                                             C.c_void_p(_ptr(col_scale)), C.c_void_p(_ptr(B)), C.c_void_p(_ptr(Y)), yt,
                                             int(M), int(ldy), VARIANT_ID[variant], float(a), C.c_void_p(stream)),
                "tcsc_gpu_sgemm_q8_norm")
+
+    def _sgemm_q8_res(self, X, xt, norm_weight, eps, Xq, scale, col_scale, B, residual, ldr, Y, yt, M, ldy,
+                      stream) -> None:
+        _check(lib().tcsc_gpu_sgemm_q8_res(self.handle, C.c_void_p(_ptr(X)), xt, C.c_void_p(_ptr(norm_weight)),
+                                           float(eps), C.c_void_p(_ptr(Xq)), C.c_void_p(_ptr(scale)),
+                                           C.c_void_p(_ptr(col_scale)), C.c_void_p(_ptr(B)),
+                                           C.c_void_p(_ptr(residual)), int(ldr), C.c_void_p(_ptr(Y)), yt, int(M),
+                                           int(ldy), C.c_void_p(stream)), "tcsc_gpu_sgemm_q8_res")
 
     def launch_info_q8_norm(self, M: int, dtype="f32") -> tuple[str, int, bool]:
         """(path, K slices, fused) of an :meth:`sgemm_q8_norm` launch of M rows of that dtype
@@ -912,6 +948,14 @@ def _ytype_of(Y) -> int:
     """enum tcsc_ytype of an output buffer: a tensor's dtype says; a raw pointer or None counts as fp32."""
     dt = getattr(Y, "dtype", None)
     return 0 if dt is None else _ytype(dt)
+
+
+def _res_check(residual, yt: int, variant: str) -> None:
+    """What a residual asks of a Plan.sgemm_i8 / sgemm_q8 / sgemm_q8_norm call: no PReLU, and Y's dtype."""
+    if variant != "basic":
+        raise TcscError(f"a residual goes with variant 'basic' alone (no PReLU), not {variant!r}")
+    if hasattr(residual, "dtype") and _ytype_of(residual) != yt:
+        raise TcscError(f"the residual's dtype {residual.dtype} is not Y's")
 
 
 def ternarize_absmean(Wf):

@@ -257,6 +257,12 @@ def _define():
         library's pinned arithmetic (``tcsc_amd.rmsnorm_rows``) inside the quantizer's launch, or inside the one
         decode launch where fusing pays.  norm_weight is a buffer: ``state_dict()`` carries it when the layer has
         one; norm_eps is a constructor argument, as ``a`` is.  Without norm_eps the layer is what it was.
+        ``forward(x, residual=r)`` returns ``r + layer(x)`` from the same launches (``tcsc_gpu_sgemm_q8_res``): r has
+        shape (..., N), dtype out_dtype, the layer's device and a unit last stride (contiguous, or two-dimensional
+        with a row pitch), and must not require grad.  The add is one fp32 add ahead of the one rounding to
+        out_dtype, so a bf16 layer gives ``(fp32 layer(x) + r.float()).to(bfloat16)``, not the twice-rounded
+        ``layer(x) + r``.  ``inplace=True`` writes the sum into r and returns r.  A layer with ``a`` set (PReLU)
+        refuses a residual.
         There is no backward and no transposed plan: it raises when grad is enabled and x requires grad.
         """
 
@@ -382,7 +388,26 @@ def _define():
             self._loaded_plan("reserve").reserve(max_rows)
             self._quant_buffers(max_rows)
 
-        def forward(self, x):
+        def _residual_2d(self, residual, lead, M: int, x):
+            """(pointer holder, pitch) of a residual of shape (*lead, N) as M rows of one pitch."""
+            N = self.out_features
+            if self.a is not None:
+                raise TcscError("PackedTernaryLinear: a layer with a PReLU (a is set) takes no residual")
+            if not torch.is_tensor(residual) or residual.dtype != self.out_dtype or residual.device != x.device:
+                raise TcscError(f"PackedTernaryLinear: the residual must be a {self.out_dtype} tensor on {x.device}")
+            if tuple(residual.shape) != (*lead, N):
+                raise TcscError(f"PackedTernaryLinear: the residual has shape {tuple(residual.shape)}, expected "
+                                f"{(*lead, N)}")
+            if residual.requires_grad:
+                raise TcscError("PackedTernaryLinear is inference only: the residual requires grad")
+            if residual.is_contiguous():
+                return residual, N
+            if residual.dim() == 2 and residual.stride(1) == 1 and residual.stride(0) >= N:
+                return residual, residual.stride(0)
+            raise TcscError("PackedTernaryLinear: the residual must be contiguous, or two-dimensional with a unit "
+                            f"last stride and a row pitch of at least {N} (strides {tuple(residual.stride())})")
+
+        def forward(self, x, residual=None, inplace: bool = False):
             plan = self._loaded_plan("forward")
             if not torch.is_tensor(x) or x.dtype not in (torch.float32, torch.bfloat16) or not x.is_cuda:
                 raise TcscError("PackedTernaryLinear: x must be an fp32 or bf16 CUDA tensor")
@@ -399,6 +424,18 @@ def _define():
             M, K, N = x2.shape[0], self.in_features, self.out_features
             xq, scale = self._quant_buffers(M)
             stream = _stream(x.device)
+            if residual is not None:
+                r, ldr = self._residual_2d(residual, lead, M, x)
+                y, ldy = (r, ldr) if inplace else (torch.empty((M, N), dtype=self.out_dtype, device=x.device), N)
+                if self.norm_eps is None:
+                    plan.sgemm_q8(x2, xq, scale, self.bias, y, M, ldy, "basic", 0.0, stream,
+                                  col_scale=self.weight_scale, residual=r, ldr=ldr)
+                else:
+                    plan.sgemm_q8_norm(x2, xq, scale, self.bias, y, M, ldy, self.norm_weight, self.norm_eps, "basic",
+                                       0.0, stream, col_scale=self.weight_scale, residual=r, ldr=ldr)
+                return residual if inplace else y.reshape(*lead, N)
+            if inplace:
+                raise TcscError("PackedTernaryLinear: inplace=True needs a residual to write into")
             y = torch.empty((M, N), dtype=self.out_dtype, device=x.device)
             variant, a = ("basic", 0.0) if self.a is None else ("prelu_basic", self.a)
             if self.norm_eps is None:
@@ -576,7 +613,8 @@ def _define():
         """The two-call FFN of a BitNet-style block: ``down(subnorm(act(gate(norm(x))) * up(norm(x))))`` as a
         :class:`PackedTernaryGLU` with a bf16 output (``glu``) and a :class:`PackedTernaryLinear` with its own
         RMSNorm in front (``down``: K = the hidden width).  Both are built by the caller; ``reserve`` and the
-        state dict are the two layers'."""
+        state dict are the two layers'.  ``forward(x, residual=r, inplace=...)`` passes the residual to ``down``
+        (:class:`PackedTernaryLinear`): the FFN with its skip connection in two library calls."""
 
         def __init__(self, glu: PackedTernaryGLU, down: PackedTernaryLinear):
             super().__init__()
@@ -589,8 +627,8 @@ def _define():
             self.glu.reserve(max_rows)
             self.down.reserve(max_rows)
 
-        def forward(self, x):
-            return self.down(self.glu(x))
+        def forward(self, x, residual=None, inplace: bool = False):
+            return self.down(self.glu(x), residual=residual, inplace=inplace)
 
     class PackedTernaryGroup(torch.nn.Module):
         """Inference-only group of 1 to 4 ternary matrices on one input, the Q, K and V
