@@ -128,7 +128,8 @@ enum tcsc_path {
     TCSC_PATH_FUSED = 1, /* retired (round 5): the persistent k_fused left the library; never returned */
     TCSC_PATH_MFMA = 2,
     TCSC_PATH_SMALL = 3,
-    TCSC_PATH_DECODE = 4 /* k_decode8: int8 calls of M <= 16 rows on a plan with the 2-bit image
+    TCSC_PATH_DECODE = 4 /* k_decode8: int8 calls of M <= 16 rows (k_decode8r: up to 64 where the plan's
+                            tcsc_gpu_plan_set_decode_rows setting admits them) on a plan with the 2-bit image
                             (tcsc_gpu_plan_enable_w2); never an fp32 or bf16 call */
 };
 int tcsc_gpu_launch_info(const tcsc_gpu_plan *plan, int M, int *path, int *slices);
@@ -405,7 +406,8 @@ int tcsc_gpu_workspace_bound_i8(int M, int K, int N, size_t *i8_bytes, size_t *f
  * are stored, with pitch ldy.
  *
  * Routing: only int8 calls on a plan with the 2-bit image take the path, and
- * only at 1 <= M <= 16.  By default it is taken where tcsc_gpu_decode_pays
+ * only at 1 <= M <= 16 unless the plan's decode_rows setting (below, "int8
+ * decode up to 64 rows") admits more.  By default it is taken where tcsc_gpu_decode_pays
  * (host arithmetic) says 1:
  *   1 <= M <= 16 and (M > 4, or the small-M path does not fit this (M, K), or
  *   16 nnz > K N)
@@ -418,7 +420,8 @@ int tcsc_gpu_workspace_bound_i8(int M, int K, int N, size_t *i8_bytes, size_t *f
  *
  * Out of scope: int8 Y; a host-pointer version.  (M > 16 on the image,
  * plans that hold nothing else, and the image without the int8 one: packed
- * plans, below.) */
+ * plans, below; M up to 64 on the decode path itself: the decode_rows setting,
+ * below.) */
 int tcsc_gpu_plan_enable_w2(tcsc_gpu_plan *plan, void *stream);
 int tcsc_gpu_plan_has_w2(const tcsc_gpu_plan *plan);
 int tcsc_gpu_w2_image_bytes(int K, int N, size_t *bytes);
@@ -453,6 +456,9 @@ int tcsc_gpu_decode_pays(int M, int K, int N, long long nnz);
  *   1 <= M <= 16  TCSC_PATH_DECODE, k_decode8 as it is -- whatever
  *                 tcsc_gpu_decode_pays or $TCSC_DECODE say: there is nothing
  *                 else to run
+ *   17 <= M <= 64 TCSC_PATH_DECODE too, k_decode8r, where the plan's decode_rows
+ *                 setting admits M (tcsc_gpu_plan_set_decode_rows; by default
+ *                 it admits none and the next line holds from 17 rows)
  *   M >= 17       TCSC_PATH_MFMA: k_pack8 (X -> X8), then k_gemm8w2, k_gemm8
  *                 with the B fragments loaded from the 2-bit image straight
  *                 into registers and turned into signed bytes there (no row
@@ -1006,6 +1012,60 @@ int tcsc_gpu_sgemm_q8_res(const tcsc_gpu_plan *plan, const void *dX, int xtype,
                           const float *dColScale, const float *dB,
                           const void *dR, int ldr, void *dY, int ytype,
                           int M, int ldy, void *stream);
+
+/* ---- int8 decode up to 64 rows: a per-plan setting ---------------
+ * k_decode8r is k_decode8 with two or four 16-row tiles per workgroup: one
+ * launch that reads X in place and streams the 2-bit image once, every expanded
+ * fragment of the image feeding one MFMA per row tile.  Same sums, same
+ * epilogue (row and column scales, bias, PReLU or the residual, fp32 or bf16
+ * Y, R == Y in place): the bits of the MFMA route at the same M.  No workspace,
+ * no allocation, no synchronisation: capturable.
+ *
+ * tcsc_gpu_plan_set_decode_rows(plan, rows): the most rows an int8 call on this
+ * plan takes to TCSC_PATH_DECODE.  rows is 16 .. 64 or TCSC_DECODE_ROWS_AUTO;
+ * the default is 16, which routes every call as before.  With a number, int8
+ * calls of 16 < M <= rows take the decode path; with AUTO, those for which
+ * tcsc_gpu_decode_rows_pays(M, K, cols, CUs of the device) says 1, asked per
+ * call.  TCSC_E_ARG for a NULL plan, any other value, or a plan without the
+ * 2-bit image.  On an ordinary plan $TCSC_DECODE=0 still vetoes the path and a
+ * pinned TCSC_PATH_MFMA still wins; M <= 16 is untouched in every respect.
+ * Setting it allocates and frees nothing and does not synchronise, and it is no
+ * part of a saved plan.  tcsc_gpu_plan_decode_rows reads it back (TCSC_E_ARG,
+ * which is no value of the setting, for a NULL plan).
+ *
+ * Served: tcsc_gpu_sgemm_i8, _i8_out, _i8_res, and behind the quantizer's own
+ * launch tcsc_gpu_sgemm_q8, _q8_out, _q8_norm, _q8_res -- above 16 rows a q8
+ * call is never fused, whatever $TCSC_QFUSE says; tcsc_gpu_launch_info_i8 /
+ * _q8 / _q8_norm report the route.  The gated and grouped calls read no
+ * setting: M <= 16 decodes, anything above is the MFMA route.
+ *
+ * Workspace: tcsc_gpu_plan_workspace(plan, M, TCSC_PATH_AUTO) reports the need
+ * of the route the setting gives, 0 on the decode route.  tcsc_gpu_plan_reserve
+ * sizes every M > 16 for the MFMA route whatever the setting is: the setting
+ * may change afterwards, and the gated and grouped calls borrow the workspace.
+ *
+ * tcsc_gpu_decode_rows_pays (host arithmetic: no plan, no device): the rule
+ * fitted to profiles/decode_rows_bench.json,
+ *   17 <= M <= 32 and K N <= 2^26
+ * -- with two row tiles the launch beat k_pack8 + k_gemm8w2 at every measured
+ * shape (2560^2 .. 8192^2: 1.2x to 2.2x); with four (M >= 33) it won at the
+ * square shapes and lost at 2560 x 6912 and 6912 x 2560, so the rule is 0
+ * there and 33 .. 64 rows are an explicit opt-in.  num_cus is not read today.
+ *
+ * tcsc_gpu_launch_info_decode: what a decode launch of M rows on this plan
+ * would run, whether or not the setting routes M there: *row_tiles (1 up to 16
+ * rows, 2 up to 32, 4 up to 64), *col_tiles (column tiles of 16 per workgroup:
+ * 1, 2 or 4) and *workgroups (the grid).  TCSC_E_ARG for a NULL argument, a plan
+ * without the image, M < 1 or M > 64.
+ *
+ * Out of scope: the gated and grouped calls above 16 rows; the quantizer inside
+ * the launch above 16 rows; more than 64 rows. */
+#define TCSC_DECODE_ROWS_AUTO (-1)
+int tcsc_gpu_plan_set_decode_rows(tcsc_gpu_plan *plan, int rows);
+int tcsc_gpu_plan_decode_rows(const tcsc_gpu_plan *plan);
+int tcsc_gpu_decode_rows_pays(int M, int K, int N, int num_cus);
+int tcsc_gpu_launch_info_decode(const tcsc_gpu_plan *plan, int M, int *row_tiles, int *col_tiles,
+                                long long *workgroups);
 
 /* Device-side tcsc_from_dense: dense K x N row-major float matrix on the
  * device -> TCSC arrays on the device, bit-exact with the reference builder

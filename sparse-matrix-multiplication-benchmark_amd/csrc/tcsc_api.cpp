@@ -63,6 +63,10 @@ struct tcsc_gpu_plan {
     // it (k_decode8)
     uint32_t* w2 = nullptr;
     size_t w2_bytes = 0;
+    // the most rows an int8 call takes to the decode path (tcsc_gpu_plan_set_decode_rows):
+    // 16 .. 64, above 16 the row-tiled k_decode8r, or TCSC_DECODE_ROWS_AUTO: wherever
+    // tcsc_gpu_decode_rows_pays says so.  A setting only: it owns no memory
+    int decode_rows = tcsc::kDecodeMaxM;
     // the column range's rebased CSC (fast-order plans): the small-M path
     // walks it, the MFMA path's fixup recomputes flagged rows from it
     // (crq: each column's +1 / -1 rows merged in ascending k, in the quad
@@ -559,13 +563,35 @@ bool w2gemm_knob() {
     const char* e = std::getenv("TCSC_W2GEMM");
     return e && std::atoi(e) != 0;
 }
+// The row-tiled launches (k_decode8r): where one launch of 16 < M <= 64 rows beats k_pack8 +
+// k_gemm8w2, fitted to profiles/decode_rows_bench.json: 1 for 17 <= M <= 32 and K N <= 2^26.  With two row
+// tiles the launch beat the GEMM beyond the run's spread at every measured point (five shapes from 2560^2 to
+// 8192^2, M = 17, 24, 32: 1.23x to 2.23x).  With four (M >= 33) it won at 2560^2, 4096^2 and 8192^2 and lost
+// at 2560 x 6912 and 6912 x 2560 (0.83x to 0.98x), and nothing monotone in M, K, N and the CU count separates
+// those, so the rule is 0 from 33 rows on.  K N <= 2^26 is the largest shape measured (the margin falls with
+// the size of W: 2.2x at 2560^2, 1.23x at 8192^2, M = 32); below the smallest the GEMM's two launches cost 11 us
+// whatever the shape and the one decode launch less than half of it.  num_cus does not enter.
+constexpr long long kDecodeRowsMaxKN = 1LL << 26;
+constexpr int kDecodeRowsPaysM = 32;
+bool decode_rows_pays(int M, int K, int N, int num_cus) {
+    (void)num_cus;
+    if (M <= tcsc::kDecodeMaxM || M > kDecodeRowsPaysM || K < 1 || K >= tcsc::kDecodeMaxK || N < 1) return false;
+    return (long long)K * N <= kDecodeRowsMaxKN;
+}
+// the plan's setting admits M rows (M > 16) to the decode path
+bool decode_rows_on(const tcsc_gpu_plan* p, int M) {
+    if (M <= tcsc::kDecodeMaxM || M > tcsc::kDecodeRowsMax) return false;
+    if (p->decode_rows == TCSC_DECODE_ROWS_AUTO) return decode_rows_pays(M, p->rows, p->cols, p->num_cus);
+    return M <= p->decode_rows;
+}
 bool has_decode(const tcsc_gpu_plan* p, int M, int dt) {  // the plan can run M rows of type dt on the decode path
-    return dt == kI8 && p->w2 && M >= 1 && M <= tcsc::kDecodeMaxM;
+    return dt == kI8 && p->w2 && M >= 1 && (M <= tcsc::kDecodeMaxM || decode_rows_on(p, M));
 }
 bool use_decode(const tcsc_gpu_plan* p, int M, int dt) {
     if (!has_decode(p, M, dt)) return false;
     if (p->packed) return true;  // nothing else serves M <= 16 there: neither the rule nor $TCSC_DECODE is asked
     const int knob = decode_knob();
+    if (M > tcsc::kDecodeMaxM) return knob != 0;  // the plan's setting decides; $TCSC_DECODE=0 still vetoes
     return knob >= 0 ? knob == 1 : decode_pays(M, p->rows, p->cols, p->n_pos + p->n_neg);
 }
 
@@ -965,10 +991,10 @@ Route tcsc::route_call(const tcsc_gpu_plan* p, int M, int dt, size_t ws_avail, c
     r.path = pin.path != TCSC_PATH_AUTO ? pin.path : launch_path(p, M, dt);
     r.rows = std::min(M, kMaxLaunchRows);
     if (p->packed) {
-        // The 2-bit image is the plan's only format: k_decode8 up to 16 rows, k_gemm8w2 above, whatever the
-        // cost models, $TCSC_PATH or $TCSC_DECODE say.  More than kMaxLaunchRows rows run in pieces of that
+        // The 2-bit image is the plan's only format: k_decode8 up to 16 rows (k_decode8r up to the plan's
+        // decode_rows setting, §27), k_gemm8w2 above, whatever the cost models, $TCSC_PATH or $TCSC_DECODE say.  More than kMaxLaunchRows rows run in pieces of that
         // many on one workspace; every piece computes the same bits on either kernel and any K split.
-        if (pin.path == TCSC_PATH_AUTO) r.path = M <= tcsc::kDecodeMaxM ? TCSC_PATH_DECODE : TCSC_PATH_MFMA;
+        if (pin.path == TCSC_PATH_AUTO) r.path = use_decode(p, M, dt) ? TCSC_PATH_DECODE : TCSC_PATH_MFMA;
         if (r.path != TCSC_PATH_MFMA || !has_mfma(p, r.rows, dt)) return r;  // no workspace, or nothing to run
         r.slices = d.slices(r.rows, N, K);
         r.ws_bytes = mfma_ws(dt, r.rows, K, N).bytes;
@@ -1992,6 +2018,53 @@ int tcsc_gpu_plan_enable_i8(tcsc_gpu_plan* p, void* stream) {
     return rc;
 }
 
+int tcsc_gpu_plan_set_decode_rows(tcsc_gpu_plan* p, int rows) {
+    if (!p) {
+        set_error("tcsc_gpu_plan_set_decode_rows: NULL plan");
+        return TCSC_E_ARG;
+    }
+    if (rows != TCSC_DECODE_ROWS_AUTO && (rows < tcsc::kDecodeMaxM || rows > tcsc::kDecodeRowsMax)) {
+        set_error("tcsc_gpu_plan_set_decode_rows: rows=%d is neither %d .. %d nor TCSC_DECODE_ROWS_AUTO", rows,
+                  tcsc::kDecodeMaxM, tcsc::kDecodeRowsMax);
+        return TCSC_E_ARG;
+    }
+    if (!p->w2) {
+        set_error("tcsc_gpu_plan_set_decode_rows: the plan has no 2-bit image (tcsc_gpu_plan_enable_w2, or a packed plan)");
+        return TCSC_E_ARG;
+    }
+    p->decode_rows = rows;  // read per call by route_call: nothing is allocated, freed or synchronised
+    return TCSC_OK;
+}
+
+int tcsc_gpu_plan_decode_rows(const tcsc_gpu_plan* p) {
+    if (!p) {
+        set_error("tcsc_gpu_plan_decode_rows: NULL plan");
+        return TCSC_E_ARG;
+    }
+    return p->decode_rows;
+}
+
+int tcsc_gpu_decode_rows_pays(int M, int K, int N, int num_cus) { return decode_rows_pays(M, K, N, num_cus) ? 1 : 0; }
+
+int tcsc_gpu_launch_info_decode(const tcsc_gpu_plan* p, int M, int* row_tiles, int* col_tiles, long long* workgroups) {
+    if (!p || !row_tiles || !col_tiles || !workgroups) {
+        set_error("tcsc_gpu_launch_info_decode: bad arguments");
+        return TCSC_E_ARG;
+    }
+    if (!p->w2 || M < 1 || M > tcsc::kDecodeRowsMax) {
+        set_error("tcsc_gpu_launch_info_decode: no decode launch of M=%d rows (1 .. %d on a plan with the 2-bit image)", M,
+                  tcsc::kDecodeRowsMax);
+        return TCSC_E_ARG;
+    }
+    const int rt = tcsc::decode_row_tiles(M);
+    const int t = rt > 1 ? tcsc::decode_rows_tiles_per_wg(M, p->cols, p->num_cus)
+                         : tcsc::decode_tiles_per_wg(M, p->cols, p->num_cus);
+    *row_tiles = rt;
+    *col_tiles = t;
+    *workgroups = (tcsc::w2_col_tiles(p->cols) + t - 1) / t;
+    return TCSC_OK;
+}
+
 int tcsc_gpu_plan_has_i8(const tcsc_gpu_plan* p) {
     if (!p) {
         set_error("tcsc_gpu_plan_has_i8: NULL plan");
@@ -2158,7 +2231,7 @@ static bool q8_fuse_pays(int M, int K, int N, int xtype, bool norm) {
 static Route route_q8(const tcsc_gpu_plan* p, int M, int xtype, bool* fused, bool norm) {
     const Route r = route_call(p, M, kI8, p->ws_bytes, RoutePins());
     *fused = false;
-    if (r.path == TCSC_PATH_DECODE && has_decode(p, M, kI8)) {
+    if (r.path == TCSC_PATH_DECODE && has_decode(p, M, kI8) && M <= tcsc::kDecodeMaxM) {  // never fused above 16 rows
         const int knob = qfuse_knob();
         *fused = knob >= 0 ? knob == 1 : q8_fuse_pays(M, p->rows, p->cols, xtype, norm);
     }

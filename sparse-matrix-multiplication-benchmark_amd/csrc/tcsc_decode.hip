@@ -49,6 +49,17 @@ constexpr int kDecWaves = TCSC_DEC_WAVES;
 constexpr int kDecTiles = TCSC_DEC_TILES;
 static_assert(kDecWaves >= 1 && kDecWaves <= 16 && kDecWaves * 4 * 1024 <= 64 * 1024, "the LDS reduce of 4 tiles");
 static_assert(kDecTiles == 0 || kDecTiles == 1 || kDecTiles == 2 || kDecTiles == 4, "1, 2 or 4 tiles");
+// The row-tiled kernel (k_decode8r): accumulator tiles (row tiles
+// x column tiles) a workgroup may hold -- 8 in registers, and kDecWaves of each
+// parked in 64 KiB of LDS -- and, for A/B builds, a fixed number of column tiles
+// per workgroup (0: decode_rows_tiles_per_wg's rule; capped by the first).
+#ifndef TCSC_DECR_TILES
+#define TCSC_DECR_TILES 0
+#endif
+constexpr int kDecRowsAcc = 64 / kDecWaves < 8 ? 64 / kDecWaves : 8;
+constexpr int kDecRowsTiles = TCSC_DECR_TILES;
+static_assert(kDecRowsAcc >= 4, "four row tiles of one column tile");
+static_assert(kDecRowsTiles == 0 || kDecRowsTiles == 1 || kDecRowsTiles == 2 || kDecRowsTiles == 4, "1, 2 or 4 tiles");
 
 // The 2-bit image from the int8 one (W8: ncols x ld8 bytes, zeros past K).  One
 // thread per dword of the image, so a wave writes 1 KiB of contiguous memory;
@@ -1157,6 +1168,178 @@ __global__ void __launch_bounds__(kQWaves * 64) k_decode8qm(const TX* __restrict
         });
 }
 
+// ---- the row-tiled form: 17 .. 64 rows in one pass over the image ----
+// k_decode8r is k_decode8 with RT 16-row tiles per workgroup: the grid, the K
+// split over the waves, the image loads and w2_codes are k_decode8's, and every
+// expanded fragment of the image feeds RT MFMAs instead of one.  Per 256-k block
+// a wave loads RT x 4 X fragments -- lane l reads rows 16 rt + (l & 15), rows
+// >= M and k >= K are zeros and never read -- and its T image pieces; the row
+// sums take one MFMA per step and row tile (rs[RT]), the codes one per step,
+// row tile and column tile (acc[RT][T]).  A row tile without a row below M
+// issues no MFMA (a uniform branch: M is the launch's).
+// The prefetch: X travels in batches of H steps with two sets of registers, one
+// in use and one in flight.  At RT = 2 a batch is the block (H = 4): the next
+// block's X and image are issued before this block's MFMAs, k_decode8's
+// pipeline, the two sets swapping roles from block to block (the loop is
+// unrolled by two instead of copying 32 registers).  At RT = 4 two sets of a
+// whole block are 128 registers and the kernel spilled (the 512 threads leave
+// 256 a wave), so a batch is half a block (H = 2): the second half's fragments
+// are in flight during the first half's MFMAs and the next block's first half
+// during the second's; the image stays one block ahead.
+// RT T <= 8 (kDecRowsAcc): the partial sums of all row tiles are parked at once in 8 RT T KiB
+// of the LDS, 64 KiB at the most, so the tail has k_decode8's one barrier.
+// k_decode8 and its siblings above are left as they are, text and code.
+template <int RT, int T, int H, int B>  // steps H B .. H B + H - 1 of a block: batch B of its X
+__device__ __forceinline__ void decode_steps_rows(const i32x4 (&xf)[RT][H], const u32x4 (&p)[T], int M,
+                                                  i32x4 (&acc)[RT][T], i32x4 (&rs)[RT]) {
+    const i32x4 ones = i32x4{0x01010101, 0x01010101, 0x01010101, 0x01010101};
+#pragma unroll
+    for (int ii = 0; ii < H; ++ii) {
+        i32x4 c[T];
+#pragma unroll
+        for (int t = 0; t < T; ++t) c[t] = w2_codes(p[t][H * B + ii]);
+#pragma unroll
+        for (int rt = 0; rt < RT; ++rt) {
+            if (16 * rt >= M) continue;  // uniform
+            rs[rt] = __builtin_amdgcn_mfma_i32_16x16x64_i8(xf[rt][ii], ones, rs[rt], 0, 0, 0);
+#pragma unroll
+            for (int t = 0; t < T; ++t) acc[rt][t] = __builtin_amdgcn_mfma_i32_16x16x64_i8(xf[rt][ii], c[t], acc[rt][t], 0, 0, 0);
+        }
+    }
+}
+
+// decode_reduce_store over RT row tiles: row r of tile rt is row 16 rt + r of Y
+// and of R.  `red` holds WAVES x RT x T accumulator tiles; one thread per
+// output -- a row's 16 T columns on consecutive threads -- adds the WAVES
+// shares, reads R first where there is one, and stores.
+template <int WAVES, int RT, int T, bool PRELU, bool RES, typename TY>
+__device__ __forceinline__ void decode_reduce_store_rows(int* red, const i32x4 (&acc)[RT][T], const i32x4 (&rs)[RT],
+                                                         int wave, int lane, int t0, int M, int N,
+                                                         const float* __restrict__ scale,
+                                                         const float* __restrict__ cscale,
+                                                         const float* __restrict__ bias, TY* Y, int ldy, float a,
+                                                         const TY* R, int ldr) {
+    static_assert(!(RES && PRELU), "a residual call has no PReLU");
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+        for (int t = 0; t < T; ++t)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) red[((wave * RT + rt) * T + t) * 256 + r * 64 + lane] = acc[rt][t][r] - rs[rt][r];
+    __syncthreads();
+    for (int o = threadIdx.x; o < RT * T * 256; o += WAVES * 64) {
+        const int row = o / (16 * T), cg = o % (16 * T), t = cg >> 4, c = cg & 15;
+        const int col = (t0 + t) * kW2Cols + c;
+        if (row >= M || col >= N) continue;
+        const int rt = row >> 4, r = row & 15;
+        int S = 0;
+#pragma unroll
+        for (int w = 0; w < WAVES; ++w) S += red[((w * RT + rt) * T + t) * 256 + (r & 3) * 64 + (r >> 2) * 16 + c];
+        const float rsc = scale ? scale[row] : 1.0f;
+        if constexpr (RES) {
+            const float res = I8Y<TY>::get(R + (size_t)row * ldr + col);
+            const float v = i8_out<false>(S, rsc, i8_cscale(cscale, col), bias[col], 0.0f);
+            I8Y<TY>::put(Y + (size_t)row * ldy + col, i8_res(v, res));
+        } else {
+            I8Y<TY>::put(Y + (size_t)row * ldy + col, i8_out<PRELU>(S, rsc, i8_cscale(cscale, col), bias[col], a));
+        }
+    }
+}
+
+template <int RT, int T, bool ALIGNED, bool PRELU, typename TY, bool RES = false>
+__global__ void __launch_bounds__(kDecWaves * 64) k_decode8r(const int8_t* __restrict__ X,
+                                                              const uint32_t* __restrict__ W2, int K, int M, int N,
+                                                              int nkb, int ntiles, const float* __restrict__ scale,
+                                                              const float* __restrict__ cscale,
+                                                              const float* __restrict__ bias, I8YPtr<TY, RES> Y,
+                                                              int ldy, float a, const TY* R = nullptr, int ldr = 0) {
+    static_assert(RT >= 2 && RT * T <= kDecRowsAcc, "all row tiles' sums at once in 64 KiB");
+    __shared__ int red[kDecWaves * RT * T * 256];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int t0 = blockIdx.x * T;
+    const int xr = lane & 15, kq = lane >> 4;
+    bool row_ok[RT];
+    const int8_t* xrow[RT];
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt) {
+        row_ok[rt] = 16 * rt + xr < M;
+        xrow[rt] = X + (size_t)(row_ok[rt] ? 16 * rt + xr : 0) * K;
+    }
+
+    const u32x4* wp[T];
+    decode_tile_ptrs<T>(W2, t0, ntiles, nkb, lane, wp);
+
+    constexpr int H = RT > 2 ? 2 : 4;  // steps of an X batch
+    auto load_x = [&](int kb, int batch, i32x4 (&xf)[RT][H]) {
+#pragma unroll
+        for (int rt = 0; rt < RT; ++rt) {
+#pragma unroll
+            for (int ii = 0; ii < H; ++ii) {
+                const int k = kW2Blk * kb + 64 * (H * batch + ii) + 16 * kq;
+                xf[rt][ii] = i32x4{0, 0, 0, 0};
+                if constexpr (ALIGNED) {
+                    if (row_ok[rt] && k < K) xf[rt][ii] = *reinterpret_cast<const i32x4*>(xrow[rt] + k);
+                } else {
+                    if (row_ok[rt] && k < K) {
+#pragma unroll
+                        for (int j = 0; j < 16; ++j) {
+                            const uint32_t b = k + j < K ? (uint32_t)(uint8_t)xrow[rt][k + j] : 0u;
+                            xf[rt][ii][j >> 2] |= (int)(b << (8 * (j & 3)));
+                        }
+                    }
+                }
+            }
+        }
+    };
+
+    i32x4 acc[RT][T], rs[RT];
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt) {
+        rs[rt] = i32x4{0, 0, 0, 0};
+#pragma unroll
+        for (int t = 0; t < T; ++t) acc[rt][t] = i32x4{0, 0, 0, 0};
+    }
+
+    i32x4 xa[RT][H], xb[RT][H];
+    u32x4 pa[T], pb[T];
+    int kb = wave;
+    if (kb < nkb) {
+        decode_load_w<T>(wp, kb, pa);
+        load_x(kb, 0, xa);
+    }
+    while (kb < nkb) {  // uniform
+        int nx = kb + kDecWaves;
+        if constexpr (H == 4) {  // two blocks a round: a's, then b's
+            if (nx < nkb) {
+                decode_load_w<T>(wp, nx, pb);
+                load_x(nx, 0, xb);
+            }
+            decode_steps_rows<RT, T, 4, 0>(xa, pa, M, acc, rs);
+            kb = nx;
+            if (kb >= nkb) break;
+            nx = kb + kDecWaves;
+            if (nx < nkb) {
+                decode_load_w<T>(wp, nx, pa);
+                load_x(nx, 0, xa);
+            }
+            decode_steps_rows<RT, T, 4, 0>(xb, pb, M, acc, rs);
+        } else {  // one block a round: its first half in a, its second in b
+            load_x(kb, 1, xb);
+            if (nx < nkb) decode_load_w<T>(wp, nx, pb);
+            decode_steps_rows<RT, T, 2, 0>(xa, pa, M, acc, rs);
+            if (nx < nkb) load_x(nx, 0, xa);
+            decode_steps_rows<RT, T, 2, 1>(xb, pa, M, acc, rs);
+#pragma unroll
+            for (int t = 0; t < T; ++t) pa[t] = pb[t];
+        }
+        kb = nx;
+    }
+
+    decode_reduce_store_rows<kDecWaves, RT, T, PRELU, RES, TY>(red, acc, rs, wave, lane, t0, M, N, scale, cscale, bias, Y,
+                                                               ldy, a, R, ldr);
+}
+
 }  // namespace
 
 hipError_t decode_build_w2(const int8_t* w8, int ncols, int K, int ld8, uint32_t* w2, int* bad, hipStream_t st) {
@@ -1234,18 +1417,40 @@ int decode_tiles_per_wg(int M, int N, int num_cus) {
     return T;
 }
 
+// Row tiles and column tiles per workgroup of a launch of 17 .. 64 rows
+// (k_decode8r).  RT: two 16-row tiles up to 32 rows, four above
+// (at 33 .. 48 rows the fourth issues no MFMA).  T: a workgroup reads all of X
+// from the L2 whatever T is, so the launch's X traffic falls as 1 / T and the
+// rule starts from the most the LDS holds, RT T = 8 (kDecRowsAcc); the other constraint is
+// decode_tiles_per_wg's -- below one workgroup per CU the stream of the image
+// has too few loads in flight -- so T is halved until the grid covers the chip
+// (or T = 1).
+int decode_row_tiles(int M) { return M <= kDecodeMaxM ? 1 : M <= 32 ? 2 : 4; }
+int decode_rows_tiles_per_wg(int M, int N, int num_cus) {
+    const int ntiles = w2_col_tiles(N), cus = num_cus > 0 ? num_cus : 256;
+    int T = kDecRowsAcc / decode_row_tiles(M);
+    if (kDecRowsTiles) return kDecRowsTiles < T ? kDecRowsTiles : T;
+    while (T > 1 && (ntiles + T - 1) / T < cus) T >>= 1;
+    return T;
+}
+
 // The one decode launch (tcsc_internal.h).  Everything a kernel is instantiated
 // over -- Y type, tiles per workgroup, ALIGNED, PRELU or the residual (§26: the
 // two exclude each other), and for an X the launch quantizes its type and the
 // norm -- becomes a template argument here and nowhere else; x and e are
-// unpacked into the kernels' parameter lists.
+// unpacked into the kernels' parameter lists.  Above 16 rows (§27) the kernel is
+// k_decode8r over (RT, T) in {(2, 4), (2, 2), (2, 1), (4, 2), (4, 1)}, on an int8 X
+// alone: the forms that quantize inside are not extended.
 hipError_t decode_gemm(const DecodeX& x, const uint32_t* w2, int K, int M, int N, const I8Epi& e, int num_cus,
                        hipStream_t st) {
     const bool quant = x.xtype != kI8;
-    if (M < 1 || M > kDecodeMaxM || K < 1 || K >= kDecodeMaxK || N < 1 || !x.X || !w2 || (quant && !x.scale_out) || !e.B ||
-        !e.y.Y || e.ldy < N || (e.R && (e.prelu || e.ldr < N || (e.R == e.y.Y && e.ldr != e.ldy))))
+    if (M < 1 || M > kDecodeRowsMax || (quant && M > kDecodeMaxM) || K < 1 || K >= kDecodeMaxK || N < 1 || !x.X || !w2 ||
+        (quant && !x.scale_out) || !e.B || !e.y.Y || e.ldy < N ||
+        (e.R && (e.prelu || e.ldr < N || (e.R == e.y.Y && e.ldr != e.ldy))))
         return hipErrorInvalidValue;
-    const int ntiles = w2_col_tiles(N), nkb = w2_kblocks(K), tiles = decode_tiles_per_wg(M, N, num_cus);
+    const int rtiles = decode_row_tiles(M);
+    const int ntiles = w2_col_tiles(N), nkb = w2_kblocks(K);
+    const int tiles = rtiles > 1 ? decode_rows_tiles_per_wg(M, N, num_cus) : decode_tiles_per_wg(M, N, num_cus);
     const dim3 grid((ntiles + tiles - 1) / tiles);
     const bool aligned = x.xtype == kI8    ? XSrc<int8_t>::vec_ok(static_cast<const int8_t*>(x.X), K)
                          : x.xtype == kBf16 ? XSrc<uint16_t>::vec_ok(static_cast<const uint16_t*>(x.X), K)
@@ -1261,6 +1466,29 @@ hipError_t decode_gemm(const DecodeX& x, const uint32_t* w2, int K, int M, int N
         if (e.prelu) return f(std::integral_constant<int, 1>{});
         return f(std::integral_constant<int, 0>{});
     };
+    if (rtiles > 1) {
+        with_elem(e.y.ytype == kYBf16, [&](auto ty) {
+            using TY = typename decltype(ty)::type;
+            TY* Y = static_cast<TY*>(e.y.Y);
+            const TY* R = static_cast<const TY*>(e.R);
+            with_tiles([&](auto t) {
+                with_bool(aligned, [&](auto al) {
+                    with_tail([&](auto tl) {
+                        with_bool(rtiles == 4, [&](auto r4) {
+                            constexpr int T = decltype(t)::value, RT = decltype(r4)::value ? 4 : 2;
+                            constexpr bool AL = decltype(al)::value, PR = decltype(tl)::value == 1,
+                                           RS = decltype(tl)::value == 2;
+                            if constexpr (RT * T <= kDecRowsAcc)  // the rule never asks for more
+                                hipLaunchKernelGGL((k_decode8r<RT, T, AL, PR, TY, RS>), grid, dim3(kDecWaves * 64), 0, st,
+                                                   static_cast<const int8_t*>(x.X), w2, K, M, N, nkb, ntiles, e.rscale,
+                                                   e.y.cscale, e.B, Y, e.ldy, e.a, R, e.ldr);
+                        });
+                    });
+                });
+            });
+        });
+        return hipGetLastError();
+    }
     with_elem(e.y.ytype == kYBf16, [&](auto ty) {
         using TY = typename decltype(ty)::type;
         TY* Y = static_cast<TY*>(e.y.Y);

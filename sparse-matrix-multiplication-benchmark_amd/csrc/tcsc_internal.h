@@ -529,6 +529,7 @@ constexpr int kW2Cols = 16;
 constexpr int kW2Blk = 256;
 constexpr int kW2TileBytes = 1024;
 constexpr int kDecodeMaxM = 16;      // one 16-row MFMA tile
+constexpr int kDecodeRowsMax = 64;   // the row-tiled kernel's limit: four of them (k_decode8r)
 constexpr int kDecodeMaxK = 1 << 22; // K below it: |sum q c| <= 128 * 2 * K < 2^31
 __host__ __device__ inline int w2_col_tiles(int N) { return (N + kW2Cols - 1) / kW2Cols; }
 __host__ __device__ inline int w2_kblocks(int K) { return (K + kW2Blk - 1) / kW2Blk; }
@@ -567,14 +568,20 @@ hipError_t mfma8_gemm_w2(const int8_t* x8, const uint32_t* w2, int ld8, int K, i
                          size_t slab_bytes, hipStream_t st);
 // column tiles per workgroup of a k_decode8 launch (1, 2 or 4)
 int decode_tiles_per_wg(int M, int N, int num_cus);
-// The decode launch, m < M <= 16, by what x (DecodeX) says X is:
+// a k_decode8r launch of 16 < M <= kDecodeRowsMax rows: its row tiles per workgroup
+// (2 up to 32 rows, 4 above; 1 at M <= 16, k_decode8's) and its column tiles (1, 2 or 4, at most 8 / row tiles)
+int decode_row_tiles(int M);
+int decode_rows_tiles_per_wg(int M, int N, int num_cus);
+// The decode launch, 1 <= M <= 16, by what x (DecodeX) says X is:
 //   kI8           k_decode8: mfma8_gemm's Y;
 //   kF32 / kBf16  k_decode8q: the quantizer and k_decode8 in one
 //                 launch -- Y gets the bits of quantize_rows_i8 followed by the
 //                 kI8 form; e.rscale is not read;
 //   with x.norm   k_decode8q<.., NORM> (§22): the RMSNorm in front of the
 //                 quantizer as well -- the bits of rmsnorm_rows, then the above.
-// The one dispatch over TX x TY x T x ALIGNED x PRELU x NORM is inside.
+// With a kI8 x, 16 < M <= kDecodeRowsMax rows run k_decode8r (§27), the same Y; the
+// other forms stop at 16 rows (hipErrorInvalidValue above).
+// The one dispatch over TX x TY x RT x T x ALIGNED x PRELU x NORM is inside.
 hipError_t decode_gemm(const DecodeX& x, const uint32_t* w2, int K, int M, int N, const I8Epi& e, int num_cus,
                        hipStream_t st);
 // The gated decode launch, k_decode8g / k_decode8qg: one launch

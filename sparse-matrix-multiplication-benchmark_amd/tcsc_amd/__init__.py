@@ -63,6 +63,8 @@ EXPORTED_SYMBOLS = (
     "tcsc_gpu_sgemm_i8_glu", "tcsc_gpu_sgemm_q8_glu", "tcsc_gpu_launch_info_glu", "tcsc_gpu_glu_fuse_pays",
     "tcsc_gpu_sgemm_i8_group", "tcsc_gpu_sgemm_q8_group", "tcsc_gpu_launch_info_group", "tcsc_gpu_group_fuse_pays",
     "tcsc_gpu_sgemm_i8_res", "tcsc_gpu_sgemm_q8_res",
+    "tcsc_gpu_plan_set_decode_rows", "tcsc_gpu_plan_decode_rows", "tcsc_gpu_decode_rows_pays",
+    "tcsc_gpu_launch_info_decode",
     # include/sparse/bcsr.h
     "bcsr_from_dense", "bcsr_sgemm_basic", "bcsr_sgemm_prelu_basic", "bcsr_sgemm_avx", "bcsr_sgemm_prelu_avx",
     "bcsr_sgemm_avx2", "bcsr_free",
@@ -98,6 +100,7 @@ class plan_info_t(C.Structure):
 
 
 GROUP_MAX = 4  # TCSC_GROUP_MAX
+DECODE_ROWS_AUTO = -1  # TCSC_DECODE_ROWS_AUTO
 
 
 class group_member_t(C.Structure):
@@ -218,6 +221,10 @@ def lib():
     L.tcsc_gpu_group_fuse_pays.argtypes = [i, i, C.POINTER(i), i, i, i]
     L.tcsc_gpu_sgemm_i8_res.argtypes = [vp, vp, vp, vp, vp, vp, i, vp, i, i, i, vp]
     L.tcsc_gpu_sgemm_q8_res.argtypes = [vp, vp, i, vp, f, vp, vp, vp, vp, vp, i, vp, i, i, i, vp]
+    L.tcsc_gpu_plan_set_decode_rows.argtypes = [vp, i]
+    L.tcsc_gpu_plan_decode_rows.argtypes = [vp]
+    L.tcsc_gpu_decode_rows_pays.argtypes = [i, i, i, i]
+    L.tcsc_gpu_launch_info_decode.argtypes = [vp, i, C.POINTER(i), C.POINTER(i), C.POINTER(C.c_longlong)]
     L.tcsc_gpu_prepare_x.argtypes = [vp, vp, i, vp]
     L.tcsc_gpu_sgemm_prepared.argtypes = [vp, vp, vp, i, i, i, f, vp]
     L.tcsc_gpu_from_dense.argtypes = [vp, i, i, vp, vp, vp, vp, C.POINTER(i), C.POINTER(i), vp]
@@ -756,6 +763,26 @@ class Plan:
     def has_w2(self) -> bool:
         return bool(lib().tcsc_gpu_plan_has_w2(self.handle))
 
+    def set_decode_rows(self, rows: int) -> None:
+        """The most rows an int8 call on this plan takes to the decode path (tcsc_gpu_plan_set_decode_rows):
+        16 .. 64 -- above 16 the row-tiled k_decode8r, one launch and no workspace -- or
+        :data:`DECODE_ROWS_AUTO` for wherever :func:`decode_rows_pays` says so.  The default, 16, routes every
+        call as before.  Needs the 2-bit image; allocates nothing and does not synchronise."""
+        _check(lib().tcsc_gpu_plan_set_decode_rows(self.handle, int(rows)), "tcsc_gpu_plan_set_decode_rows")
+
+    @property
+    def decode_rows(self) -> int:
+        """The setting of :meth:`set_decode_rows` (tcsc_gpu_plan_decode_rows)."""
+        return int(lib().tcsc_gpu_plan_decode_rows(self.handle))
+
+    def launch_info_decode(self, M: int) -> tuple[int, int, int]:
+        """(row tiles, column tiles per workgroup, workgroups) of a decode launch of M rows on this plan
+        (tcsc_gpu_launch_info_decode), whether or not M routes there: 1 <= M <= 64 on a plan with the image."""
+        rt, ct, wg = C.c_int(0), C.c_int(0), C.c_longlong(0)
+        _check(lib().tcsc_gpu_launch_info_decode(self.handle, int(M), C.byref(rt), C.byref(ct), C.byref(wg)),
+               "tcsc_gpu_launch_info_decode")
+        return rt.value, ct.value, wg.value
+
     def sgemm_i8(self, Xq, scale, B, Y, M: int, ldy: int, variant: str = "prelu_basic", a: float = 0.2,
                  stream: int = 0, col_scale=None, ytype=None, residual=None, ldr=None) -> None:
         """Y = act(scale[m] * col_scale[j] * (Xq . W) + B) for int8 activations (tcsc_gpu_sgemm_i8_out): Xq is
@@ -1177,6 +1204,12 @@ def decode_pays(M: int, K: int, N: int, nnz: int) -> bool:
     return bool(lib().tcsc_gpu_decode_pays(int(M), int(K), int(N), int(nnz)))
 
 
+def decode_rows_pays(M: int, K: int, N: int, num_cus: int = 0) -> bool:
+    """Where a row-tiled decode launch of 16 < M <= 64 rows beats the MFMA route (tcsc_gpu_decode_rows_pays; host
+    arithmetic): what a plan set to :data:`DECODE_ROWS_AUTO` asks per call."""
+    return bool(lib().tcsc_gpu_decode_rows_pays(int(M), int(K), int(N), int(num_cus)))
+
+
 def w2_to_tcsc(image, rows: int, cols: int, stream: int = 0):
     """The TCSC arrays of the rows x cols matrix a 2-bit image on the device encodes (tcsc_gpu_w2_to_tcsc):
     (col_start_pos, col_start_neg, row_index_pos, row_index_neg) as torch.int32 tensors on the image's device, bit
@@ -1257,7 +1290,8 @@ def save_packed(plan: Plan, path) -> None:
 def load_packed(path, device: int = 0, stream: int = 0) -> Plan:
     """The packed plan of a file :func:`save_packed` wrote (np.load with allow_pickle=False).  The version, the
     image's dtype and its size for (rows, cols) are checked first: a file that fails raises TcscError before the
-    library is called."""
+    library is called.  The file carries no runtime setting: :meth:`Plan.set_decode_rows` on the plan returned
+    sets one."""
     with np.load(path, allow_pickle=False) as z:
         missing = [k for k in ("image", "rows", "cols", "col_begin", "version") if k not in z.files]
         if missing:

@@ -263,11 +263,15 @@ def _define():
         out_dtype, so a bf16 layer gives ``(fp32 layer(x) + r.float()).to(bfloat16)``, not the twice-rounded
         ``layer(x) + r``.  ``inplace=True`` writes the sum into r and returns r.  A layer with ``a`` set (PReLU)
         refuses a residual.
+        decode_rows: None, 16 .. 64 or ``tcsc_amd.DECODE_ROWS_AUTO``: the plan's ``Plan.set_decode_rows`` setting,
+        the most rows a forward sends through the one-launch decode kernel after the quantizer (None: the
+        library's default, 16).  A runtime setting: the same bits either way, not part of ``state_dict()``, and
+        kept across ``load_state_dict``.
         There is no backward and no transposed plan: it raises when grad is enabled and x requires grad.
         """
 
         def __init__(self, W, bias=None, a: float | None = None, device: int = 0, weight_scale=None,
-                     out_dtype=torch.float32, norm_weight=None, norm_eps: float | None = None):
+                     out_dtype=torch.float32, norm_weight=None, norm_eps: float | None = None, decode_rows=None):
             super().__init__()
             Wm = _ternary_matrix(W, "PackedTernaryLinear")  # only read here: the plan keeps no reference to it
             self.in_features, self.out_features, self.nnz = Wm.rows, Wm.cols, Wm.nnz
@@ -281,10 +285,19 @@ def _define():
             self.register_buffer("norm_weight", nw)
             self.plan = Plan.packed(Wm, 0, self.out_features, self.device_index, _stream(dev))
             self._rows, self._xq, self._scale = 0, None, None
+            self.decode_rows = None
+            self.set_decode_rows(decode_rows)
+
+        def set_decode_rows(self, decode_rows) -> None:
+            """Sets ``decode_rows`` (None keeps the plan as it is) on the plan the layer has, and on every plan a
+            ``load_state_dict`` gives it later."""
+            self.decode_rows = None if decode_rows is None else int(decode_rows)
+            if self.plan is not None and self.decode_rows is not None:
+                self.plan.set_decode_rows(self.decode_rows)
 
         @classmethod
         def from_float(cls, Wf, bias=None, a: float | None = None, device: int = 0, out_dtype=torch.float32,
-                       norm_weight=None, norm_eps: float | None = None):
+                       norm_weight=None, norm_eps: float | None = None, decode_rows=None):
             """The layer of a float weight matrix Wf (K x N): ``T, beta = tcsc_amd.ternarize_absmean(Wf)``, then
             the packed plan of T with the per-tensor ``weight_scale = beta``, so that the layer computes
             ``act(x . (beta T) + bias)`` on the quantized x."""
@@ -292,11 +305,11 @@ def _define():
                 Wf = Wf.detach().cpu().numpy()
             T, beta = ternarize_absmean(Wf)
             return cls(T, bias, a, device, weight_scale=float(beta), out_dtype=out_dtype, norm_weight=norm_weight,
-                       norm_eps=norm_eps)
+                       norm_eps=norm_eps, decode_rows=decode_rows)
 
         @classmethod
         def empty(cls, in_features: int, out_features: int, a: float | None = None, device: int = 0,
-                  out_dtype=torch.float32, norm_eps: float | None = None):
+                  out_dtype=torch.float32, norm_eps: float | None = None, decode_rows=None):
             """A layer of this shape with a zero bias, no weight scale and no plan yet: ``load_state_dict`` fills it
             from a ``state_dict()`` of a layer of the same shape (its ``weight_scale`` and ``norm_weight`` included,
             when it has them; a state with a ``norm_weight`` needs a layer made with norm_eps).
@@ -314,6 +327,7 @@ def _define():
             self.register_buffer("norm_weight", None)
             self.plan = None
             self._rows, self._xq, self._scale = 0, None, None
+            self.decode_rows = None if decode_rows is None else int(decode_rows)  # set on the plan a load builds
             return self
 
         def _loaded_plan(self, what: str) -> Plan:
@@ -362,6 +376,8 @@ def _define():
                                 "norm_eps")
             image = w2.detach().to(dev).contiguous()
             plan = Plan.packed_from_image(image, self.in_features, self.out_features, 0, self.device_index, _stream(dev))
+            if getattr(self, "decode_rows", None) is not None:
+                plan.set_decode_rows(self.decode_rows)
             # the base class copies into the buffers the layer has: give it one of the state's kind
             self.weight_scale = None if ws is None else torch.empty(self.out_features, dtype=torch.float32, device=dev)
             self.norm_weight = None if nw is None else torch.empty(self.in_features, dtype=torch.float32, device=dev)
@@ -614,14 +630,18 @@ def _define():
         :class:`PackedTernaryGLU` with a bf16 output (``glu``) and a :class:`PackedTernaryLinear` with its own
         RMSNorm in front (``down``: K = the hidden width).  Both are built by the caller; ``reserve`` and the
         state dict are the two layers'.  ``forward(x, residual=r, inplace=...)`` passes the residual to ``down``
-        (:class:`PackedTernaryLinear`): the FFN with its skip connection in two library calls."""
+        (:class:`PackedTernaryLinear`): the FFN with its skip connection in two library calls.
+        decode_rows, if given, is set on ``down`` alone (``PackedTernaryLinear.set_decode_rows``): the gated call
+        reads no such setting."""
 
-        def __init__(self, glu: PackedTernaryGLU, down: PackedTernaryLinear):
+        def __init__(self, glu: PackedTernaryGLU, down: PackedTernaryLinear, decode_rows=None):
             super().__init__()
             if down.in_features != glu.out_features:
                 raise TcscError(f"PackedTernaryMLP: the GLU gives {glu.out_features} columns, down takes "
                                 f"{down.in_features}")
             self.glu, self.down = glu, down
+            if decode_rows is not None:
+                down.set_decode_rows(decode_rows)
 
         def reserve(self, max_rows: int) -> None:
             self.glu.reserve(max_rows)

@@ -60,6 +60,13 @@ lib/abl/libtcsc_amd_dec%.so: $(SRC)/tcsc_decode.hip $(call ab_rest,$(OBJ)/tcsc_d
 	$(HIPCC) $(HIPFLAGS) -DTCSC_DEC_WAVES=$(word 1,$(subst _, ,$*)) -DTCSC_DEC_TILES=$(word 2,$(subst _, ,$*)) -c $(SRC)/tcsc_decode.hip -o $(OBJ)/abl/dec$*.o
 	$(call ab_link,$(OBJ)/tcsc_decode.o,$(OBJ)/abl/dec$*.o)
 
+# the row-tiled decode kernel's column tiles (A/B): lib/abl/libtcsc_amd_decr<tiles>.so, column tiles
+# per workgroup of k_decode8r (capped at 8 / row tiles; 0 = the product's rule); the same results, other timings
+lib/abl/libtcsc_amd_decr%.so: $(SRC)/tcsc_decode.hip $(call ab_rest,$(OBJ)/tcsc_decode.o) $(HDRS)
+	@mkdir -p lib/abl $(OBJ)/abl
+	$(HIPCC) $(HIPFLAGS) -DTCSC_DECR_TILES=$* -c $(SRC)/tcsc_decode.hip -o $(OBJ)/abl/decr$*.o
+	$(call ab_link,$(OBJ)/tcsc_decode.o,$(OBJ)/abl/decr$*.o)
+
 # the same without the X staging (gather cost alone): lib/abl/libtcsc_amd_abl<N>_nd.so
 ablation-nodma: $(foreach a,0 1 3 4 5,lib/abl/libtcsc_amd_abl$(a)_nd.so)
 
