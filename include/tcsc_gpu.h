@@ -323,8 +323,10 @@ int tcsc_gpu_launch_info_bf16(const tcsc_gpu_plan *plan, int M, int *path, int *
  * Numerics, per path:
  *   MFMA   (the plan has the int8 image and the router picks it):
  *          Y = act(fl(fl(float(S) * s[m]) + b[j])), S the exact i32 sum,
- *          float(S) rounded to nearest, one multiply, one add (never fused
- *          with it), then v < 0 ? a * v : v.  The same bits for every variant
+ *          float(S) rounded to nearest, ties to even (it rounds where |S| >
+ *          2^24: an odd sum below 2^25 goes to the neighbour whose mantissa
+ *          is even), one multiply, one add (never fused with it), then
+ *          v < 0 ? a * v : v (a NaN and -0 pass).  The same bits for every variant
  *          and every K split.  Kernels: k_pack8 (X -> X8, zero padded),
  *          k_gemm8 (v_mfma_i32_16x16x64_i8, 128-k sub-steps; the epilogue in
  *          its store), with K split raw i32 slabs and k_reduce_i8.  No row
@@ -344,7 +346,13 @@ int tcsc_gpu_launch_info_bf16(const tcsc_gpu_plan *plan, int M, int *path, int *
  *   amax = max_k |x|, dScale[m] = amax / 127.0f, inv = 127.0f / amax,
  *   q = clamp(rintf(x * inv), -127, 127)   (amax = 0: q = 0, scale = 0)
  * every step one rounded fp32 operation, so a host restatement gives the same
- * bits.  Inputs must be finite (a non-finite x gives unspecified values, never
+ * bits.  A row whose maximum is so small that fl(127.0f / amax) is +inf --
+ * amax <= 127 * 2^-128 = 0x02FE0000, about 3.73e-37, and every subnormal
+ * maximum -- counts as a row of zeros: q = 0, scale = 0 (x * inf would be NaN
+ * for x = 0 and +-127 for everything else); the loss is at most K * 3.8e-37
+ * per output.  In one line: zero = !(amax > 0) || isinf(127.0f / amax).
+ * Inputs must be finite (a non-finite x gives unspecified values in its own
+ * row -- Xq, scale and that row of Y -- and touches no other row; never
  * a fault).  Allocates nothing, asynchronous on `stream`, capturable.
  *
  * tcsc_gpu_workspace_bound_i8 (host arithmetic, no plan, no device): the MFMA
@@ -782,7 +790,9 @@ int tcsc_gpu_norm_fuse_pays(int M, int K, int N, int xtype);   /* host arithmeti
  *   u = fl(fl(fl(float(Su) s[m]) cu[j]) + bu[j])      no PReLU
  *   TCSC_GLU_RELU2:  r = g < 0 ? 0 : g;  h = fl(fl(r r) u)
  *   TCSC_GLU_SILU:   h = fl(fl(g / fl(1 + expf(-g))) u)    IEEE division, the
- *                    device math library's expf (1 ulp)
+ *                    device math library's expf (1 ulp); a very negative
+ *                    finite g gives expf = inf and g / inf = -0, g = -inf
+ *                    gives -inf / inf = NaN
  *   Y[m, j] = h (TCSC_Y_F32) or h rounded to bf16, nearest even (TCSC_Y_BF16)
  * Every route gives the same bits: TCSC_GLU_RELU2 those of two
  * tcsc_gpu_sgemm_i8_out calls into fp32 followed by torch's

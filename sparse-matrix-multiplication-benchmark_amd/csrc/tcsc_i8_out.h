@@ -14,7 +14,7 @@
 
 namespace tcsc {
 
-// act(fl(fl(fl(float(S) * s) * c) + b)): one conversion (round to nearest), the
+// act(fl(fl(fl(float(S) * s) * c) + b)): one conversion (round to nearest even), the
 // row scale, the column scale, one add that must not contract with either
 // multiply, then the PReLU.  A call without column scales passes c = 1.0f:
 // x * 1.0f == x for every x, so its bits are those of the two-step form.
@@ -33,7 +33,8 @@ __device__ __forceinline__ float i8_out(int S, float s, float c, float b, float 
 // branch.  Every step is one rounded fp32 operation, none contracted:
 //   kGluRelu2  r = g < 0 ? 0 : g;  fl(fl(r r) u)           torch relu(g).square() * u
 //   kGluSilu   fl(fl(g / fl(1 + expf(-g))) u)              IEEE division, the math library's expf
-// (a very negative g gives expf = inf, g / inf = -0 and a zero of u's sign).
+// (a very negative finite g gives expf = inf, g / inf = -0 and a zero of the sign
+// of -u; g = -inf gives -inf / inf, a NaN, as a NaN g does).
 __device__ __forceinline__ float i8_glu(float g, float u, int act) {
 #pragma clang fp contract(off)
     if (act == kGluRelu2) {

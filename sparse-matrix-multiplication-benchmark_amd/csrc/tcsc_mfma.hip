@@ -1280,8 +1280,8 @@ __global__ void __launch_bounds__(WN * 64) k_gemm8w2(const int8_t* __restrict__ 
 }
 
 // tcsc_gpu_quantize_rows_i8{,_bf16}: per row, amax = max |x|, scale = amax /
-// 127, inv = 127 / amax, q = clamp(rint(x * inv), -127, 127); amax = 0: q = 0,
-// scale = 0 (quant_scales and quant_i8, tcsc_quant.h).  Every step is one
+// 127, inv = 127 / amax, q = clamp(rint(x * inv), -127, 127); amax = 0, or so
+// small that 127 / amax is inf: q = 0, scale = 0 (quant_scales and quant_i8, tcsc_quant.h).  Every step is one
 // correctly rounded fp32 operation; TX = uint16_t is bf16 bit patterns, widened
 // first (XSrc, exact).  One workgroup per row, the row read twice (the second
 // time from the L2).  VEC (K a multiple of the kVec elements of a 16-B load, X

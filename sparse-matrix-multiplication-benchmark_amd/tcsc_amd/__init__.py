@@ -1001,8 +1001,9 @@ def ternarize_absmean(Wf):
 def quantize_rows_i8(X, Xq, scale, M: int, K: int, stream: int = 0) -> None:
     """Per-row absmax quantization on the device (tcsc_gpu_quantize_rows_i8, or _bf16 for a torch.bfloat16 X):
     X is M x K contiguous fp32 or bf16; Xq (M x K int8) and scale (M floats) are written: scale = amax / 127,
-    q = clamp(rint(x * (127 / amax)), -127, 127), a row of zeros gives q = 0 and scale = 0.  bf16 values are
-    widened to fp32 first (exact)."""
+    q = clamp(rint(x * (127 / amax)), -127, 127), a row of zeros gives q = 0 and scale = 0, and so does a row whose
+    maximum is so small that 127 / amax is inf in fp32 (amax <= 127 * 2^-128, about 3.73e-37, and every subnormal
+    maximum): zero = not (amax > 0) or isinf(127 / amax).  bf16 values are widened to fp32 first (exact)."""
     name = "tcsc_gpu_quantize_rows_i8_bf16" if _xtype_of(X) else "tcsc_gpu_quantize_rows_i8"
     _check(getattr(lib(), name)(C.c_void_p(_ptr(X)), int(M), int(K), C.c_void_p(_ptr(Xq)),
                                 C.c_void_p(_ptr(scale)), C.c_void_p(stream)), name)

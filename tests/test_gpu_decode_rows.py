@@ -391,9 +391,10 @@ def test_an_ordinary_plan(gpu, oracle, env):
 def np_quantize(x):
     x = np.ascontiguousarray(x, np.float32)
     amax = np.max(np.abs(x), axis=1).astype(np.float32)
-    with np.errstate(divide="ignore", invalid="ignore"):
-        scale = np.where(amax > 0, amax / np.float32(127.0), np.float32(0)).astype(np.float32)
-        inv = np.where(amax > 0, np.float32(127.0) / amax, np.float32(0)).astype(np.float32)
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        live = (amax > 0) & ~np.isinf(np.float32(127.0) / amax)  # a row whose 127 / amax is inf counts as a row of zeros
+        scale = np.where(live, amax / np.float32(127.0), np.float32(0)).astype(np.float32)
+        inv = np.where(live, np.float32(127.0) / amax, np.float32(0)).astype(np.float32)
     r = np.rint((x * inv[:, None]).astype(np.float32))
     return np.clip(r, -127, 127).astype(np.int8), scale
 
