@@ -809,15 +809,19 @@ int tcsc_gpu_norm_fuse_pays(int M, int K, int N, int xtype);   /* host arithmeti
  *   and allowed to be NULL, where it is TCSC_PATH_DECODE.
  * dY: M x ldy of ytype, ldy >= H in elements.
  *
- * Routes (tcsc_gpu_launch_info_glu), by M alone -- the cost models, $TCSC_PATH
- * and $TCSC_DECODE are not asked:
+ * Routes (tcsc_gpu_launch_info_glu), by M and, from 17 to 64 rows, the two
+ * plans' decode_rows_multi setting ("gated and grouped calls at 17 .. 64 rows"
+ * below; by default everything above 16 rows is the MFMA route) --
+ * the cost models, $TCSC_PATH and $TCSC_DECODE are not asked:
  *   M <= 16  TCSC_PATH_DECODE: one launch (k_decode8g) that streams both images
  *            against one set of X fragments.  tcsc_gpu_sgemm_q8_glu runs the
  *            quantizer inside it (k_decode8qg: *fused = 1) where
  *            tcsc_gpu_glu_fuse_pays says so or $TCSC_QFUSE=1 is set ($TCSC_QFUSE=0:
  *            never); otherwise the quantizer (with the norm: its norm form) into
  *            dXq, then k_decode8g.
- *   M >= 17  TCSC_PATH_MFMA: k_pack8 once, then k_gemm8w2 twice on the gate
+ *   17 <= M <= 64, where both plans' setting admits M: TCSC_PATH_DECODE too, one
+ *            launch (k_decode8gr) on the quantized X; dG untouched.
+ *   M >= 17  otherwise TCSC_PATH_MFMA: k_pack8 once, then k_gemm8w2 twice on the gate
  *            plan's workspace (slabs included: *slices is the K split of each) --
  *            the gate half through the plain epilogue into dG, the up half
  *            through the gated one.  tcsc_gpu_plan_reserve(gate, max_M) covers it;
@@ -842,7 +846,7 @@ int tcsc_gpu_norm_fuse_pays(int M, int K, int N, int xtype);   /* host arithmeti
  * device differ; an act or ytype out of range; a NULL dG on the MFMA route; a
  * NULL dXq where the call is not fused; dGamma given with eps == 0; ldy < cols.
  *
- * Out of scope: one GEMM launch over both images at M >= 17 (the next lever);
+ * Out of scope: one GEMM launch over both images on the MFMA route;
  * gating on the gather and small-M routes and on the fp32 and bf16 calls; an
  * int8 Y; other gate activations; a host-pointer version. */
 enum tcsc_glu_act { TCSC_GLU_RELU2 = 0, TCSC_GLU_SILU = 1 };
@@ -850,14 +854,14 @@ int tcsc_gpu_sgemm_i8_glu(const tcsc_gpu_plan *gate, const tcsc_gpu_plan *up,
                           const void *dXq, const float *dScale,
                           const float *dColScaleG, const float *dBG,
                           const float *dColScaleU, const float *dBU,
-                          float *dG /* may be NULL at M <= 16 */, void *dY, int ytype,
+                          float *dG /* may be NULL on the decode route */, void *dY, int ytype,
                           int M, int ldy, int act, void *stream);
 int tcsc_gpu_sgemm_q8_glu(const tcsc_gpu_plan *gate, const tcsc_gpu_plan *up,
                           const void *dX, int xtype, const float *dGamma, float eps,
                           void *dXq, float *dScale,
                           const float *dColScaleG, const float *dBG,
                           const float *dColScaleU, const float *dBU,
-                          float *dG /* may be NULL at M <= 16 */, void *dY, int ytype,
+                          float *dG /* may be NULL on the decode route */, void *dY, int ytype,
                           int M, int ldy, int act, void *stream);
 int tcsc_gpu_launch_info_glu(const tcsc_gpu_plan *gate, const tcsc_gpu_plan *up, int M, int xtype,
                              int *path, int *slices, int *fused);
@@ -887,8 +891,10 @@ int tcsc_gpu_glu_fuse_pays(int M, int K, int N, int xtype, int norm);   /* host 
  *              outputs are the caller's mistake and are not checked.
  * A group of one gives the single call's bits with the single call's grid.
  *
- * Routes (tcsc_gpu_launch_info_group), by M alone -- the cost models, $TCSC_PATH
- * and $TCSC_DECODE are not asked:
+ * Routes (tcsc_gpu_launch_info_group), by M and, from 17 to 64 rows, the members'
+ * decode_rows_multi setting ("gated and grouped calls at 17 .. 64 rows" below,
+ * DESIGN.md §28; by default everything above 16 rows is the MFMA route) -- the
+ * cost models, $TCSC_PATH and $TCSC_DECODE are not asked:
  *   M <= 16  TCSC_PATH_DECODE: one launch (k_decode8m) whose grid is the
  *            concatenation of the members' workgroups: member i owns
  *            ceil(ceil(cols_i / 16) / T) consecutive workgroups of T column tiles
@@ -903,7 +909,10 @@ int tcsc_gpu_glu_fuse_pays(int M, int K, int N, int xtype, int norm);   /* host 
  *            grouped call with the norm always runs the norm form of the
  *            quantizer into dXq and then k_decode8m, whatever $TCSC_QFUSE says,
  *            and needs dXq.
- *   M >= 17  TCSC_PATH_MFMA: the quantizer (with the norm: its norm form) once,
+ *   17 <= M <= 64, where every member's setting admits M: TCSC_PATH_DECODE too,
+ *            the quantizer (with the norm: its norm form) into dXq and then one
+ *            launch (k_decode8mr) on k_decode8m's grid.
+ *   M >= 17  otherwise TCSC_PATH_MFMA: the quantizer (with the norm: its norm form) once,
  *            k_pack8 once into the first member's workspace, and k_gemm8w2 once
  *            per member, each GEMM's K-split slabs in its own plan's workspace
  *            (slices[i] is member i's K split).  tcsc_gpu_plan_reserve(plan,
@@ -930,7 +939,7 @@ int tcsc_gpu_glu_fuse_pays(int M, int K, int N, int xtype, int norm);   /* host 
  * cols; M < 0; a NULL X; on the q8 form a bad eps, dGamma given with eps == 0,
  * a NULL dScale, and a NULL dXq where the call is not fused.  M == 0 is TCSC_OK.
  *
- * Out of scope: one GEMM launch over all images at M >= 17; a norm form of the
+ * Out of scope: one GEMM launch over all images on the MFMA route; a norm form of the
  * fused grouped kernel; PReLU or gating on this call; the gather and small-M
  * routes; a host-pointer version. */
 #define TCSC_GROUP_MAX 4
@@ -1046,8 +1055,8 @@ int tcsc_gpu_sgemm_q8_res(const tcsc_gpu_plan *plan, const void *dX, int xtype,
  * Served: tcsc_gpu_sgemm_i8, _i8_out, _i8_res, and behind the quantizer's own
  * launch tcsc_gpu_sgemm_q8, _q8_out, _q8_norm, _q8_res -- above 16 rows a q8
  * call is never fused, whatever $TCSC_QFUSE says; tcsc_gpu_launch_info_i8 /
- * _q8 / _q8_norm report the route.  The gated and grouped calls read no
- * setting: M <= 16 decodes, anything above is the MFMA route.
+ * _q8 / _q8_norm report the route.  The gated and grouped calls do not read
+ * this setting: they have one of their own, decode_rows_multi (below, §28).
  *
  * Workspace: tcsc_gpu_plan_workspace(plan, M, TCSC_PATH_AUTO) reports the need
  * of the route the setting gives, 0 on the decode route.  tcsc_gpu_plan_reserve
@@ -1068,14 +1077,78 @@ int tcsc_gpu_sgemm_q8_res(const tcsc_gpu_plan *plan, const void *dX, int xtype,
  * 1, 2 or 4) and *workgroups (the grid).  TCSC_E_ARG for a NULL argument, a plan
  * without the image, M < 1 or M > 64.
  *
- * Out of scope: the gated and grouped calls above 16 rows; the quantizer inside
- * the launch above 16 rows; more than 64 rows. */
+ * Out of scope: the quantizer inside the launch above 16 rows; more than 64
+ * rows.  (The gated and grouped calls above 16 rows: §28, below.) */
 #define TCSC_DECODE_ROWS_AUTO (-1)
 int tcsc_gpu_plan_set_decode_rows(tcsc_gpu_plan *plan, int rows);
 int tcsc_gpu_plan_decode_rows(const tcsc_gpu_plan *plan);
 int tcsc_gpu_decode_rows_pays(int M, int K, int N, int num_cus);
 int tcsc_gpu_launch_info_decode(const tcsc_gpu_plan *plan, int M, int *row_tiles, int *col_tiles,
                                 long long *workgroups);
+
+/* ---- gated and grouped calls at 17 .. 64 rows: a second per-plan setting
+ * k_decode8gr and k_decode8mr are k_decode8g and k_decode8m with two or four
+ * 16-row tiles per workgroup, as k_decode8r is k_decode8's: one launch on an
+ * int8 X that streams the 2-bit images once, without a workspace and without
+ * dG, and gives the bits of the MFMA route at the same M.
+ *
+ * tcsc_gpu_plan_set_decode_rows_multi(plan, rows): the most rows a gated or
+ * grouped call takes to TCSC_PATH_DECODE as far as this plan is concerned.  rows
+ * is 16 .. 64 or TCSC_DECODE_ROWS_AUTO; the default is 16, which routes every
+ * call as before.  A call of 16 < M <= 64 rows decodes when EVERY plan of the
+ * call -- gate and up, or all members -- admits M: a plan set to a number
+ * admits M <= rows, a plan set to AUTO admits M where the call's own rule
+ * (tcsc_gpu_glu_rows_pays(M, K, H, CUs), or tcsc_gpu_group_rows_pays over the
+ * members' column counts) says 1, asked per call.  Otherwise the call routes
+ * as before.  $TCSC_PATH, $TCSC_DECODE and the cost models are not asked, as
+ * on these calls everywhere; M <= 16 is untouched in every respect; the
+ * decode_rows setting of §27 is not read.  TCSC_E_ARG for a NULL plan, any
+ * other value, or a plan without the 2-bit image.  Setting it writes one int:
+ * it allocates and frees nothing, does not synchronise, and is no part of a
+ * saved plan.  tcsc_gpu_plan_decode_rows_multi reads it back (TCSC_E_ARG, which
+ * is no value of the setting, for a NULL plan).
+ *
+ * On the decode route: tcsc_gpu_launch_info_glu / _group report *path =
+ * TCSC_PATH_DECODE, slices of 1 and, above 16 rows, *fused = 0; dG may be NULL
+ * and is untouched (the "NULL dG on the MFMA route" refusal follows the route,
+ * not M); the q8 forms above 16 rows run the quantizer's launch (with a norm:
+ * its norm form) and then the kernel -- never fused, whatever $TCSC_QFUSE says
+ * -- and need dXq.  tcsc_gpu_plan_reserve is unchanged: it sizes M > 16 for the
+ * MFMA route, because the setting may change afterwards.
+ *
+ * tcsc_gpu_glu_rows_pays, tcsc_gpu_group_rows_pays (host arithmetic: no plan, no
+ * device): the rules fitted to profiles/multi_rows_bench.json
+ * (tools/multi_rows_bench.py) alone,
+ *   gated    17 <= M <= 64 and K H <= 2^26
+ *   grouped  17 <= M <= 64 and K (sum of the members' columns) <= 8192 * 10240
+ * -- the one launch beat both samples of the MFMA route at all 36 measured
+ * points of 17 .. 64 rows, with two row tiles and with four (gated 1.15x to
+ * 2.40x at 2560 x 6912, 4096^2, 8192^2; grouped 1.19x to 3.45x at 2560 +
+ * 640 + 640, 3 x 4096 and 8192 + 1024 + 1024 columns), the margin falling with
+ * the size of W, so each rule stops at the largest shape measured.  0 elsewhere:
+ * M <= 16, M > 64, K < 1 or >= 2^22, a column count < 1, a count outside
+ * 1 .. TCSC_GROUP_MAX.  num_cus is not read today.  The default setting stays
+ * 16: AUTO is the caller's choice.
+ *
+ * tcsc_gpu_launch_info_glu_decode / _group_decode: what a decode launch of M
+ * rows (1 .. 64) of these plans would run, whether or not M routes there:
+ * *row_tiles (1, 2 or 4), *col_tiles (per workgroup; gated: TG of each image,
+ * 2 or 1 at two row tiles and 1 at four; grouped: 4, 2 or 1 at two row tiles, 2
+ * or 1 at four -- from the most eight accumulator tiles allow, halved while the
+ * grid is below the CU count) and *workgroups.  TCSC_E_ARG as the calls' own
+ * plan checks, for a NULL output and for M outside 1 .. 64.
+ *
+ * Out of scope: the quantizer or the norm inside the launch above 16 rows; more
+ * than 64 rows; one MFMA GEMM launch over several images; a residual or PReLU
+ * on the gated and grouped calls. */
+int tcsc_gpu_plan_set_decode_rows_multi(tcsc_gpu_plan *plan, int rows);  /* 16 .. 64 or TCSC_DECODE_ROWS_AUTO */
+int tcsc_gpu_plan_decode_rows_multi(const tcsc_gpu_plan *plan);
+int tcsc_gpu_glu_rows_pays(int M, int K, int H, int num_cus);                       /* host arithmetic */
+int tcsc_gpu_group_rows_pays(int M, int K, const int *cols, int count, int num_cus); /* host arithmetic */
+int tcsc_gpu_launch_info_glu_decode(const tcsc_gpu_plan *gate, const tcsc_gpu_plan *up, int M,
+                                    int *row_tiles, int *col_tiles, long long *workgroups);
+int tcsc_gpu_launch_info_group_decode(const tcsc_gpu_group_member *members, int count, int M,
+                                      int *row_tiles, int *col_tiles, long long *workgroups);
 
 /* Device-side tcsc_from_dense: dense K x N row-major float matrix on the
  * device -> TCSC arrays on the device, bit-exact with the reference builder

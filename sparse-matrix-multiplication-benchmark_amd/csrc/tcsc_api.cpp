@@ -67,6 +67,9 @@ struct tcsc_gpu_plan {
     // 16 .. 64, above 16 the row-tiled k_decode8r, or TCSC_DECODE_ROWS_AUTO: wherever
     // tcsc_gpu_decode_rows_pays says so.  A setting only: it owns no memory
     int decode_rows = tcsc::kDecodeMaxM;
+    // the same for the gated and grouped calls (tcsc_gpu_plan_set_decode_rows_multi): a call of
+    // 16 < M <= 64 rows decodes (k_decode8gr / k_decode8mr) where every plan of the call admits M
+    int decode_rows_multi = tcsc::kDecodeMaxM;
     // the column range's rebased CSC (fast-order plans): the small-M path
     // walks it, the MFMA path's fixup recomputes flagged rows from it
     // (crq: each column's +1 / -1 rows merged in ascending k, in the quad
@@ -583,6 +586,47 @@ bool decode_rows_on(const tcsc_gpu_plan* p, int M) {
     if (M <= tcsc::kDecodeMaxM || M > tcsc::kDecodeRowsMax) return false;
     if (p->decode_rows == TCSC_DECODE_ROWS_AUTO) return decode_rows_pays(M, p->rows, p->cols, p->num_cus);
     return M <= p->decode_rows;
+}
+// The gated and grouped row-tiled launches (k_decode8gr / k_decode8mr): where the one launch of
+// 16 < M <= 64 rows beats k_pack8 + one k_gemm8w2 per matrix, fitted to profiles/multi_rows_bench.json
+// (tools/multi_rows_bench.py) and to nothing else.  The one launch beat both samples of the parent at all 36
+// measured points of 17 .. 64 rows, with two row tiles and with four: the gated call 1.15x to 2.40x (2560 x 6912,
+// 4096^2, 8192^2), the grouped one 1.19x to 3.45x (2560: 2560 + 640 + 640, 4096: 3 x 4096, 8192: 8192 + 1024 + 1024).
+// The margin falls with the size of W and with M (8192^2 at M = 64: 1.15x; 8192 x 10240 at M = 64: 1.19x), so each rule
+// stops at the largest shape measured: gated 1 for 17 <= M <= 64 and K H <= 2^26, grouped 1 for 17 <= M <= 64 and
+// K (sum of the members' columns) <= 8192 * 10240.  Below the smallest shape measured the MFMA route's launches cost
+// 25 us (gated) and 32 us (grouped) whatever the shape and the one decode launch 9 to 15 us.  num_cus does not enter.
+constexpr long long kGluRowsMaxKH = 1LL << 26;
+constexpr long long kGroupRowsMaxKN = 8192LL * 10240LL;
+bool glu_rows_pays(int M, int K, int H, int num_cus) {
+    (void)num_cus;
+    if (M <= tcsc::kDecodeMaxM || M > tcsc::kDecodeRowsMax || K < 1 || K >= tcsc::kDecodeMaxK || H < 1) return false;
+    return (long long)K * H <= kGluRowsMaxKH;
+}
+bool group_rows_pays(int M, int K, const int* cols, int count, int num_cus) {
+    (void)num_cus;
+    if (M <= tcsc::kDecodeMaxM || M > tcsc::kDecodeRowsMax || K < 1 || K >= tcsc::kDecodeMaxK || !cols || count < 1 ||
+        count > tcsc::kGroupMax)
+        return false;
+    long long total = 0;
+    for (int i = 0; i < count; ++i) {
+        if (cols[i] < 1) return false;
+        total += cols[i];
+    }
+    return (long long)K * total <= kGroupRowsMaxKN;
+}
+// the plan's decode_rows_multi setting admits M rows (M > 16); `pays` is the call's own rule, asked under AUTO
+bool multi_rows_admits(const tcsc_gpu_plan* p, int M, bool pays) {
+    if (M <= tcsc::kDecodeMaxM || M > tcsc::kDecodeRowsMax) return false;
+    if (p->decode_rows_multi == TCSC_DECODE_ROWS_AUTO) return pays;
+    return M <= p->decode_rows_multi;
+}
+// a gated call of M rows takes TCSC_PATH_DECODE: up to 16 rows always, above where gate and up admit M
+bool glu_decodes(const tcsc_gpu_plan* gate, const tcsc_gpu_plan* up, int M) {
+    if (M <= tcsc::kDecodeMaxM) return true;
+    if (M > tcsc::kDecodeRowsMax) return false;
+    const bool pays = glu_rows_pays(M, gate->rows, gate->cols, gate->num_cus);
+    return multi_rows_admits(gate, M, pays) && multi_rows_admits(up, M, pays);
 }
 bool has_decode(const tcsc_gpu_plan* p, int M, int dt) {  // the plan can run M rows of type dt on the decode path
     return dt == kI8 && p->w2 && M >= 1 && (M <= tcsc::kDecodeMaxM || decode_rows_on(p, M));
@@ -2065,6 +2109,38 @@ int tcsc_gpu_launch_info_decode(const tcsc_gpu_plan* p, int M, int* row_tiles, i
     return TCSC_OK;
 }
 
+int tcsc_gpu_plan_set_decode_rows_multi(tcsc_gpu_plan* p, int rows) {
+    if (!p) {
+        set_error("tcsc_gpu_plan_set_decode_rows_multi: NULL plan");
+        return TCSC_E_ARG;
+    }
+    if (rows != TCSC_DECODE_ROWS_AUTO && (rows < tcsc::kDecodeMaxM || rows > tcsc::kDecodeRowsMax)) {
+        set_error("tcsc_gpu_plan_set_decode_rows_multi: rows=%d is neither %d .. %d nor TCSC_DECODE_ROWS_AUTO", rows,
+                  tcsc::kDecodeMaxM, tcsc::kDecodeRowsMax);
+        return TCSC_E_ARG;
+    }
+    if (!p->w2) {
+        set_error("tcsc_gpu_plan_set_decode_rows_multi: the plan has no 2-bit image (tcsc_gpu_plan_enable_w2, or a packed "
+                  "plan)");
+        return TCSC_E_ARG;
+    }
+    p->decode_rows_multi = rows;  // read per gated / grouped call: nothing is allocated, freed or synchronised
+    return TCSC_OK;
+}
+
+int tcsc_gpu_plan_decode_rows_multi(const tcsc_gpu_plan* p) {
+    if (!p) {
+        set_error("tcsc_gpu_plan_decode_rows_multi: NULL plan");
+        return TCSC_E_ARG;
+    }
+    return p->decode_rows_multi;
+}
+
+int tcsc_gpu_glu_rows_pays(int M, int K, int H, int num_cus) { return glu_rows_pays(M, K, H, num_cus) ? 1 : 0; }
+int tcsc_gpu_group_rows_pays(int M, int K, const int* cols, int count, int num_cus) {
+    return group_rows_pays(M, K, cols, count, num_cus) ? 1 : 0;
+}
+
 int tcsc_gpu_plan_has_i8(const tcsc_gpu_plan* p) {
     if (!p) {
         set_error("tcsc_gpu_plan_has_i8: NULL plan");
@@ -2453,8 +2529,9 @@ int tcsc_gpu_sgemm_q8_res(const tcsc_gpu_plan* p, const void* dX, int xtype, con
 
 // ---- the gated FFN call -----------------------------------------
 // Y = act(X Wg) (X Wu) on two plans with the 2-bit image and the same K and H.  The route is fixed by
-// M alone, whatever the cost models, $TCSC_PATH or $TCSC_DECODE say: up to 16 rows the one gated decode
-// launch, above k_pack8 once and k_gemm8w2 twice on the gate plan's workspace -- the gate half into the
+// M and, from 17 to 64 rows, the two plans' decode_rows_multi setting (glu_decodes, §28), whatever the cost
+// models, $TCSC_PATH or $TCSC_DECODE say: up to 16 rows, and up to 64 where the setting admits M, the one gated
+// decode launch, otherwise k_pack8 once and k_gemm8w2 twice on the gate plan's workspace -- the gate half into the
 // caller's G through the plain epilogue, the up half with the gated one.
 static_assert(TCSC_GLU_RELU2 == tcsc::kGluRelu2 && TCSC_GLU_SILU == tcsc::kGluSilu, "the public gate activations are i8_glu's");
 
@@ -2535,13 +2612,13 @@ static int sgemm_glu_i8(const tcsc_gpu_plan* gate, const Call& c) {
     eu.y = YOut{c.y.Y, c.y.ytype, c.glu.cscale};
     eu.ldy = c.ldy;
     eu.act = c.glu.act;
-    if (M <= tcsc::kDecodeMaxM) {  // TCSC_PATH_DECODE: one launch, G untouched
+    if (glu_decodes(gate, up, M)) {  // TCSC_PATH_DECODE: one launch, G untouched
         HIP_TRY(tcsc::decode_glu(tcsc::DecodeX{c.X, kI8, nullptr, nullptr}, gate->w2, up->w2, K, M, H, eg, eu, gate->num_cus,
                                  st));
         return TCSC_OK;
     }
     if (!c.glu.G) {
-        set_error("%s: NULL dG on the MFMA route (M=%d > %d)", who, M, tcsc::kDecodeMaxM);
+        set_error("%s: NULL dG on the MFMA route (M=%d)", who, M);
         return TCSC_E_ARG;
     }
     if (gate->ws_bytes < glu_ws_bytes(gate, M)) {  // grown on first use, as every tcsc_gpu_sgemm* does
@@ -2646,8 +2723,8 @@ int tcsc_gpu_sgemm_q8_glu(const tcsc_gpu_plan* gate, const tcsc_gpu_plan* up, co
         set_error("%s: NULL dXq on a route that is not fused (M=%d)", who, M);
         return TCSC_E_ARG;
     }
-    if (M > tcsc::kDecodeMaxM && !dG) {  // ahead of the quantizer's launch
-        set_error("%s: NULL dG on the MFMA route (M=%d > %d)", who, M, tcsc::kDecodeMaxM);
+    if (!glu_decodes(gate, up, M) && !dG) {  // ahead of the quantizer's launch
+        set_error("%s: NULL dG on the MFMA route (M=%d)", who, M);
         return TCSC_E_ARG;
     }
     rc = has_norm ? tcsc_gpu_quantize_rows_i8_norm(dX, xtype, dGamma, eps, M, K, dXq, dScale, stream)
@@ -2668,7 +2745,7 @@ int tcsc_gpu_launch_info_glu(const tcsc_gpu_plan* gate, const tcsc_gpu_plan* up,
     }
     const int rc = glu_plans(who, gate, up);
     if (rc != TCSC_OK) return rc;
-    const bool decode = M <= tcsc::kDecodeMaxM;
+    const bool decode = glu_decodes(gate, up, M);
     *path = decode ? TCSC_PATH_DECODE : TCSC_PATH_MFMA;
     *slices = decode ? 1 : tcsc::mfma8_slices(std::min(M, kMaxLaunchRows), gate->cols, gate->rows);
     *fused = glu_fused(M, gate->rows, gate->cols, xtype, false) ? 1 : 0;
@@ -2677,8 +2754,9 @@ int tcsc_gpu_launch_info_glu(const tcsc_gpu_plan* gate, const tcsc_gpu_plan* up,
 
 // ---- the grouped call -------------------------------------------
 // Up to TCSC_GROUP_MAX plans with the 2-bit image and one K on one X: member i gets the bits of
-// tcsc_gpu_sgemm_i8_out on its own plan.  The route is fixed by M alone, as the gated call's: up to 16
-// rows one grouped decode launch, above k_pack8 once (into the first member's workspace) and k_gemm8w2
+// tcsc_gpu_sgemm_i8_out on its own plan.  The route is fixed as the gated call's (group_plans_decode, §28):
+// up to 16 rows, and up to 64 where every member's decode_rows_multi setting admits M, one grouped decode launch,
+// otherwise k_pack8 once (into the first member's workspace) and k_gemm8w2
 // once per member, each GEMM's slabs in its own plan's workspace.
 static_assert(TCSC_GROUP_MAX == tcsc::kGroupMax, "the public group size is the launch table's");
 
@@ -2774,6 +2852,32 @@ static GroupView group_view(const tcsc_gpu_plan* first, const Call& c) {
     return v;
 }
 
+// a grouped call of M rows takes TCSC_PATH_DECODE: up to 16 rows always, above where every member's plan admits M
+// (decode_rows_multi, §28; AUTO asks group_rows_pays on the members that have columns)
+static bool group_plans_decode(const tcsc_gpu_plan* const* plan, int count, int M) {
+    if (M <= tcsc::kDecodeMaxM) return true;
+    if (M > tcsc::kDecodeRowsMax) return false;
+    int cols[TCSC_GROUP_MAX], n = 0;
+    for (int i = 0; i < count; ++i)
+        if (plan[i]->cols > 0) cols[n++] = plan[i]->cols;
+    const bool pays = n > 0 && group_rows_pays(M, plan[0]->rows, cols, n, plan[0]->num_cus);
+    for (int i = 0; i < count; ++i)
+        if (!multi_rows_admits(plan[i], M, pays)) return false;
+    return true;
+}
+static bool group_decodes(const tcsc_gpu_group_member* m, int count, int M) {
+    const tcsc_gpu_plan* plan[TCSC_GROUP_MAX];
+    for (int i = 0; i < count; ++i) plan[i] = m[i].plan;
+    return group_plans_decode(plan, count, M);
+}
+// the same of a call: member 0 is the call's own plan, the rest c.group's
+static bool group_call_decodes(const tcsc_gpu_plan* first, const Call& c) {
+    const tcsc_gpu_plan* plan[TCSC_GROUP_MAX];
+    plan[0] = first;
+    for (int i = 0; i < c.group.count; ++i) plan[i + 1] = c.group.m[i].plan;
+    return group_plans_decode(plan, c.group.count + 1, c.M);
+}
+
 // A grouped call on an int8 X (c.xtype == kI8; the members checked by group_plans).
 static int sgemm_group_i8(const tcsc_gpu_plan* first, const Call& c) {
     const char* who = c.who;
@@ -2788,8 +2892,8 @@ static int sgemm_group_i8(const tcsc_gpu_plan* first, const Call& c) {
         return TCSC_E_ARG;
     }
     hipStream_t st = static_cast<hipStream_t>(c.stream);
-    if (M <= tcsc::kDecodeMaxM) {  // TCSC_PATH_DECODE: one launch
-        const GroupView v = group_view(first, c);
+    if (group_call_decodes(first, c)) {
+        const GroupView v = group_view(first, c);  // TCSC_PATH_DECODE: one launch
         if (!v.count) return TCSC_OK;
         HIP_TRY(tcsc::decode_group(tcsc::DecodeX{c.X, kI8, nullptr, nullptr}, v.m, v.count, K, M, first->num_cus, st));
         return TCSC_OK;
@@ -2920,13 +3024,62 @@ int tcsc_gpu_launch_info_group(const tcsc_gpu_group_member* members, int count, 
     }
     rc = group_plans(who, members, count, false);
     if (rc != TCSC_OK) return rc;
-    const bool decode = M <= tcsc::kDecodeMaxM;
+    const bool decode = group_decodes(members, count, M);
     *path = decode ? TCSC_PATH_DECODE : TCSC_PATH_MFMA;
     for (int i = 0; i < count; ++i)
         slices[i] = decode || members[i].plan->cols == 0
                         ? 1
                         : tcsc::mfma8_slices(std::min(M, kMaxLaunchRows), members[i].plan->cols, members[i].plan->rows);
     *fused = group_fused(members, count, M, xtype) ? 1 : 0;
+    return TCSC_OK;
+}
+
+int tcsc_gpu_launch_info_glu_decode(const tcsc_gpu_plan* gate, const tcsc_gpu_plan* up, int M, int* row_tiles,
+                                    int* col_tiles, long long* workgroups) {
+    const char* who = "tcsc_gpu_launch_info_glu_decode";
+    if (!row_tiles || !col_tiles || !workgroups) {
+        set_error("%s: bad arguments", who);
+        return TCSC_E_ARG;
+    }
+    const int rc = glu_plans(who, gate, up);
+    if (rc != TCSC_OK) return rc;
+    if (M < 1 || M > tcsc::kDecodeRowsMax) {
+        set_error("%s: no decode launch of M=%d rows (1 .. %d)", who, M, tcsc::kDecodeRowsMax);
+        return TCSC_E_ARG;
+    }
+    const int rt = tcsc::decode_row_tiles(M);
+    const int t = rt > 1 ? tcsc::decode_glu_rows_tiles_per_wg(M, gate->cols, gate->num_cus)
+                         : tcsc::decode_glu_tiles_per_wg(M, gate->cols, gate->num_cus);
+    *row_tiles = rt;
+    *col_tiles = t;
+    *workgroups = (tcsc::w2_col_tiles(gate->cols) + t - 1) / t;
+    return TCSC_OK;
+}
+
+int tcsc_gpu_launch_info_group_decode(const tcsc_gpu_group_member* members, int count, int M, int* row_tiles,
+                                      int* col_tiles, long long* workgroups) {
+    const char* who = "tcsc_gpu_launch_info_group_decode";
+    int rc = group_members(who, members, count);
+    if (rc != TCSC_OK) return rc;
+    if (!row_tiles || !col_tiles || !workgroups) {
+        set_error("%s: bad arguments", who);
+        return TCSC_E_ARG;
+    }
+    rc = group_plans(who, members, count, false);
+    if (rc != TCSC_OK) return rc;
+    if (M < 1 || M > tcsc::kDecodeRowsMax) {
+        set_error("%s: no decode launch of M=%d rows (1 .. %d)", who, M, tcsc::kDecodeRowsMax);
+        return TCSC_E_ARG;
+    }
+    int cols[TCSC_GROUP_MAX], n = 0;  // the launch's members: those with columns (group_view)
+    for (int i = 0; i < count; ++i)
+        if (members[i].plan->cols > 0) cols[n++] = members[i].plan->cols;
+    const int rt = tcsc::decode_row_tiles(M), cus = members[0].plan->num_cus;
+    const int t = rt > 1 ? tcsc::decode_group_rows_tiles_per_wg(M, cols, n, cus)
+                         : tcsc::decode_group_tiles_per_wg(M, cols, n, cus);
+    *row_tiles = rt;
+    *col_tiles = t;
+    *workgroups = tcsc::decode_group_wgs(cols, n, t);
     return TCSC_OK;
 }
 

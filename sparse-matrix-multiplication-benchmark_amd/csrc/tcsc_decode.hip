@@ -1340,6 +1340,176 @@ __global__ void __launch_bounds__(kDecWaves * 64) k_decode8r(const int8_t* __res
                                                                ldy, a, R, ldr);
 }
 
+// ---- the gated and grouped row-tiled forms -------------------------
+// k_decode8gr and k_decode8mr are k_decode8g and k_decode8m with RT 16-row tiles
+// per workgroup, on an int8 X alone: the images, the grids, the member table and
+// the epilogues are theirs, the K loop and its prefetch are k_decode8r's.
+// k_decode8r above is left as it is, text and code (§24's finding: the same text
+// behind a function boundary moves the register allocation of the existing
+// instantiations), so its body up to the tail is repeated here once, over an
+// image type, for both new kernels: decode8r_body is decode8g_sums over xf[RT].
+//
+// This wave's share of sum q c of the workgroup's RT x IMG::T accumulator tiles
+// and of the row sums, handed to tail(acc, rs) -- as decode8qg_body hands its
+// sums on.  The accumulators are the function's own: as arrays of the kernel
+// filled through references, the RT T = 8 forms kept them in memory (up to
+// 372 B of scratch a lane and 285 spilled VGPRs in the first version).
+template <int RT, bool ALIGNED, typename IMG, typename Tail>
+__device__ __forceinline__ void decode8r_body(const int8_t* __restrict__ X, const IMG& img, int K, int M, int nkb,
+                                             int ntiles, int t0, int wave, int lane, Tail tail) {
+    constexpr int T = IMG::T;
+    i32x4 acc[RT][T], rs[RT];
+    static_assert(RT >= 2 && RT * T <= kDecRowsAcc, "all row tiles' sums at once in 64 KiB");
+    const int xr = lane & 15, kq = lane >> 4;
+    bool row_ok[RT];
+    const int8_t* xrow[RT];
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt) {
+        row_ok[rt] = 16 * rt + xr < M;
+        xrow[rt] = X + (size_t)(row_ok[rt] ? 16 * rt + xr : 0) * K;
+    }
+
+    const u32x4* wp[T];
+    img.ptrs(t0, ntiles, nkb, lane, wp);
+
+    constexpr int H = RT > 2 ? 2 : 4;  // steps of an X batch
+    auto load_x = [&](int kb, int batch, i32x4 (&xf)[RT][H]) {
+#pragma unroll
+        for (int rt = 0; rt < RT; ++rt) {
+#pragma unroll
+            for (int ii = 0; ii < H; ++ii) {
+                const int k = kW2Blk * kb + 64 * (H * batch + ii) + 16 * kq;
+                xf[rt][ii] = i32x4{0, 0, 0, 0};
+                if constexpr (ALIGNED) {
+                    if (row_ok[rt] && k < K) xf[rt][ii] = *reinterpret_cast<const i32x4*>(xrow[rt] + k);
+                } else {
+                    if (row_ok[rt] && k < K) {
+#pragma unroll
+                        for (int j = 0; j < 16; ++j) {
+                            const uint32_t b = k + j < K ? (uint32_t)(uint8_t)xrow[rt][k + j] : 0u;
+                            xf[rt][ii][j >> 2] |= (int)(b << (8 * (j & 3)));
+                        }
+                    }
+                }
+            }
+        }
+    };
+
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt) {
+        rs[rt] = i32x4{0, 0, 0, 0};
+#pragma unroll
+        for (int t = 0; t < T; ++t) acc[rt][t] = i32x4{0, 0, 0, 0};
+    }
+
+    i32x4 xa[RT][H], xb[RT][H];
+    u32x4 pa[T], pb[T];
+    int kb = wave;
+    if (kb < nkb) {
+        decode_load_w<T>(wp, kb, pa);
+        load_x(kb, 0, xa);
+    }
+    while (kb < nkb) {  // uniform
+        int nx = kb + kDecWaves;
+        if constexpr (H == 4) {  // two blocks a round: a's, then b's
+            if (nx < nkb) {
+                decode_load_w<T>(wp, nx, pb);
+                load_x(nx, 0, xb);
+            }
+            decode_steps_rows<RT, T, 4, 0>(xa, pa, M, acc, rs);
+            kb = nx;
+            if (kb >= nkb) break;
+            nx = kb + kDecWaves;
+            if (nx < nkb) {
+                decode_load_w<T>(wp, nx, pa);
+                load_x(nx, 0, xa);
+            }
+            decode_steps_rows<RT, T, 4, 0>(xb, pb, M, acc, rs);
+        } else {  // one block a round: its first half in a, its second in b
+            load_x(kb, 1, xb);
+            if (nx < nkb) decode_load_w<T>(wp, nx, pb);
+            decode_steps_rows<RT, T, 2, 0>(xa, pa, M, acc, rs);
+            if (nx < nkb) load_x(nx, 0, xa);
+            decode_steps_rows<RT, T, 2, 1>(xb, pa, M, acc, rs);
+#pragma unroll
+            for (int t = 0; t < T; ++t) pa[t] = pb[t];
+        }
+        kb = nx;
+    }
+    tail(acc, rs);
+}
+
+// decode_reduce_store_glu over RT row tiles: `red` holds WAVES x RT x 2 TG
+// accumulator tiles, of each row tile the TG gate tiles and then the TG up
+// tiles; row r of tile rt is row 16 rt + r of Y.  One thread per output adds the
+// WAVES shares of Sg and of Su, applies i8_out to each and i8_glu to the pair,
+// and does the one store.  Every thread of the workgroup calls this.
+template <int WAVES, int RT, int TG, typename TY>
+__device__ __forceinline__ void decode_reduce_store_glu_rows(int* red, const i32x4 (&acc)[RT][2 * TG],
+                                                             const i32x4 (&rs)[RT], int wave, int lane, int t0, int M,
+                                                             int N, const float* __restrict__ scale, const GluEpi& e,
+                                                             TY* __restrict__ Y, int ldy) {
+    constexpr int T = 2 * TG;
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+        for (int t = 0; t < T; ++t)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) red[((wave * RT + rt) * T + t) * 256 + r * 64 + lane] = acc[rt][t][r] - rs[rt][r];
+    __syncthreads();
+    for (int o = threadIdx.x; o < RT * TG * 256; o += WAVES * 64) {
+        const int row = o / (16 * TG), cg = o % (16 * TG), t = cg >> 4, c = cg & 15;
+        const int col = (t0 + t) * kW2Cols + c;
+        if (row >= M || col >= N) continue;
+        const int rt = row >> 4, r = row & 15;
+        int Sg = 0, Su = 0;
+#pragma unroll
+        for (int w = 0; w < WAVES; ++w) {
+            Sg += red[((w * RT + rt) * T + t) * 256 + (r & 3) * 64 + (r >> 2) * 16 + c];
+            Su += red[((w * RT + rt) * T + TG + t) * 256 + (r & 3) * 64 + (r >> 2) * 16 + c];
+        }
+        const float s = scale ? scale[row] : 1.0f;
+        const float g = i8_out<false>(Sg, s, i8_cscale(e.cg, col), e.bg[col], 0.0f);
+        const float u = i8_out<false>(Su, s, i8_cscale(e.cu, col), e.bu[col], 0.0f);
+        I8Y<TY>::put(Y + (size_t)row * ldy + col, i8_glu(g, u, e.act));
+    }
+}
+
+// The gated k_decode8r; act is a uniform branch in the tail.
+template <int RT, int TG, bool ALIGNED, typename TY>
+__global__ void __launch_bounds__(kDecWaves * 64) k_decode8gr(const int8_t* __restrict__ X,
+                                                               const uint32_t* __restrict__ Wg,
+                                                               const uint32_t* __restrict__ Wu, int K, int M, int N,
+                                                               int nkb, int ntiles, const float* __restrict__ scale,
+                                                               GluEpi e, TY* __restrict__ Y, int ldy) {
+    __shared__ int red[kDecWaves * RT * 2 * TG * 256];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int t0 = blockIdx.x * TG;
+    decode8r_body<RT, ALIGNED>(X, DecodeImg2<TG>{Wg, Wu}, K, M, nkb, ntiles, t0, wave, lane,
+                               [&](const i32x4(&acc)[RT][2 * TG], const i32x4(&rs)[RT]) {
+                                   decode_reduce_store_glu_rows<kDecWaves, RT, TG>(red, acc, rs, wave, lane, t0, M, N, scale,
+                                                                                   e, Y, ldy);
+                               });
+}
+
+// The grouped k_decode8r: k_decode8m's grid and member table.
+template <int RT, int T, bool ALIGNED, typename TY>
+__global__ void __launch_bounds__(kDecWaves * 64) k_decode8mr(const int8_t* __restrict__ X, GroupTable g, int K, int M,
+                                                               int nkb, const float* __restrict__ scale) {
+    __shared__ int red[kDecWaves * RT * T * 256];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const GroupSlot s = decode_group_slot(g, blockIdx.x);
+    const int t0 = (blockIdx.x - s.first) * T;  // in the member's own tiles
+    decode8r_body<RT, ALIGNED>(X, DecodeImg1<T>{s.W2, 0}, K, M, nkb, s.ntiles, t0, wave, lane,
+                               [&](const i32x4(&acc)[RT][T], const i32x4(&rs)[RT]) {
+                                   decode_reduce_store_rows<kDecWaves, RT, T, false, false, TY>(
+                                       red, acc, rs, wave, lane, t0, M, s.N, scale, s.cscale, s.bias, static_cast<TY*>(s.Y),
+                                       s.ldy, 0.0f, nullptr, 0);
+                               });
+}
+
 }  // namespace
 
 hipError_t decode_build_w2(const int8_t* w8, int ncols, int K, int ld8, uint32_t* w2, int* bad, hipStream_t st) {
@@ -1531,20 +1701,56 @@ int decode_glu_tiles_per_wg(int M, int N, int num_cus) {
     return T / 2;
 }
 
+// Column tiles per workgroup of a gated launch of 17 .. 64 rows (k_decode8gr,
+// DESIGN.md §28): decode_rows_tiles_per_wg's rule on the 2 TG image tiles the
+// workgroup streams -- from the most the accumulators allow, RT 2 TG = 8
+// (kDecRowsAcc), halved while the grid of ceil(tiles / TG) workgroups is below
+// the CU count, down to TG = 1.
+int decode_glu_rows_tiles_per_wg(int M, int N, int num_cus) {
+    const int ntiles = w2_col_tiles(N), cus = num_cus > 0 ? num_cus : 256;
+    int TG = kDecRowsAcc / (2 * decode_row_tiles(M));
+    if (kDecRowsTiles) return kDecRowsTiles >= 2 * TG ? TG : kDecRowsTiles > 1 ? kDecRowsTiles / 2 : 1;
+    while (TG > 1 && (ntiles + TG - 1) / TG < cus) TG >>= 1;
+    return TG;
+}
+
 // The gated decode launch (tcsc_internal.h): decode_gemm's dispatch without the
-// PReLU axis and over TG in {1, 2}; the activation is a kernel argument.
+// PReLU axis and over TG in {1, 2}; the activation is a kernel argument.  Above
+// 16 rows (§28) the kernel is k_decode8gr over (RT, TG) in {(2, 2), (2, 1), (4, 1)},
+// on an int8 X alone.
 hipError_t decode_glu(const DecodeX& x, const uint32_t* wg, const uint32_t* wu, int K, int M, int N, const I8Epi& gate,
                       const I8Epi& up, int num_cus, hipStream_t st) {
     const bool quant = x.xtype != kI8;
-    if (M < 1 || M > kDecodeMaxM || K < 1 || K >= kDecodeMaxK || N < 1 || !x.X || !wg || !wu || (quant && !x.scale_out) ||
+    if (M < 1 || M > kDecodeRowsMax || (quant && M > kDecodeMaxM) || K < 1 || K >= kDecodeMaxK || N < 1 || !x.X || !wg || !wu || (quant && !x.scale_out) ||
         !gate.B || !up.B || !up.y.Y || up.ldy < N || (up.act != kGluRelu2 && up.act != kGluSilu))
         return hipErrorInvalidValue;
-    const int ntiles = w2_col_tiles(N), nkb = w2_kblocks(K), tiles = decode_glu_tiles_per_wg(M, N, num_cus);
+    const int rtiles = decode_row_tiles(M);
+    const int ntiles = w2_col_tiles(N), nkb = w2_kblocks(K);
+    const int tiles = rtiles > 1 ? decode_glu_rows_tiles_per_wg(M, N, num_cus) : decode_glu_tiles_per_wg(M, N, num_cus);
     const dim3 grid((ntiles + tiles - 1) / tiles);
     const bool aligned = x.xtype == kI8    ? XSrc<int8_t>::vec_ok(static_cast<const int8_t*>(x.X), K)
                          : x.xtype == kBf16 ? XSrc<uint16_t>::vec_ok(static_cast<const uint16_t*>(x.X), K)
                                             : XSrc<float>::vec_ok(static_cast<const float*>(x.X), K);
     const GluEpi e{gate.y.cscale, gate.B, up.y.cscale, up.B, up.act};
+    if (rtiles > 1) {
+        with_elem(up.y.ytype == kYBf16, [&](auto ty) {
+            using TY = typename decltype(ty)::type;
+            TY* Y = static_cast<TY*>(up.y.Y);
+            with_bool(tiles == 2, [&](auto t2) {
+                with_bool(aligned, [&](auto al) {
+                    with_bool(rtiles == 4, [&](auto r4) {
+                        constexpr int TG = decltype(t2)::value ? 2 : 1, RT = decltype(r4)::value ? 4 : 2;
+                        constexpr bool AL = decltype(al)::value;
+                        if constexpr (RT * 2 * TG <= kDecRowsAcc)  // the rule never asks for more
+                            hipLaunchKernelGGL((k_decode8gr<RT, TG, AL, TY>), grid, dim3(kDecWaves * 64), 0, st,
+                                               static_cast<const int8_t*>(x.X), wg, wu, K, M, N, nkb, ntiles, up.rscale, e,
+                                               Y, up.ldy);
+                    });
+                });
+            });
+        });
+        return hipGetLastError();
+    }
     with_elem(up.y.ytype == kYBf16, [&](auto ty) {
         using TY = typename decltype(ty)::type;
         TY* Y = static_cast<TY*>(up.y.Y);
@@ -1588,11 +1794,24 @@ int decode_group_tiles_per_wg(int M, const int* cols, int count, int num_cus) {
     return T;
 }
 
+// The one T of a grouped launch of 17 .. 64 rows (k_decode8mr):
+// decode_rows_tiles_per_wg's rule -- from RT T = 8 (kDecRowsAcc) down to T = 1
+// -- tested against the whole concatenated grid.
+int decode_group_rows_tiles_per_wg(int M, const int* cols, int count, int num_cus) {
+    const int cus = num_cus > 0 ? num_cus : 256;
+    int T = kDecRowsAcc / decode_row_tiles(M);
+    if (kDecRowsTiles) return kDecRowsTiles < T ? kDecRowsTiles : T;
+    while (T > 1 && decode_group_wgs(cols, count, T) < cus) T >>= 1;
+    return T;
+}
+
 // The grouped decode launch (tcsc_internal.h): decode_gemm's dispatch without
-// the PReLU and norm axes; the members travel as one table by value.
+// the PReLU and norm axes; the members travel as one table by value.  Above 16
+// rows (§28) the kernel is k_decode8mr over (RT, T) in {(2, 4), (2, 2), (2, 1),
+// (4, 2), (4, 1)}, on an int8 X alone.
 hipError_t decode_group(const DecodeX& x, const DecodeMember* m, int count, int K, int M, int num_cus, hipStream_t st) {
     const bool quant = x.xtype != kI8;
-    if (M < 1 || M > kDecodeMaxM || K < 1 || K >= kDecodeMaxK || count < 1 || count > kGroupMax || !m || !x.X ||
+    if (M < 1 || M > kDecodeRowsMax || (quant && M > kDecodeMaxM) || K < 1 || K >= kDecodeMaxK || count < 1 || count > kGroupMax || !m || !x.X ||
         (quant && !x.scale_out) || x.norm)
         return hipErrorInvalidValue;
     int cols[kGroupMax];
@@ -1602,7 +1821,9 @@ hipError_t decode_group(const DecodeX& x, const DecodeMember* m, int count, int 
             return hipErrorInvalidValue;
         cols[i] = m[i].N;
     }
-    const int nkb = w2_kblocks(K), tiles = decode_group_tiles_per_wg(M, cols, count, num_cus);
+    const int rtiles = decode_row_tiles(M);
+    const int nkb = w2_kblocks(K), tiles = rtiles > 1 ? decode_group_rows_tiles_per_wg(M, cols, count, num_cus)
+                                                      : decode_group_tiles_per_wg(M, cols, count, num_cus);
     const long long wgs = decode_group_wgs(cols, count, tiles);
     if (wgs > 0x7fffffffLL) return hipErrorInvalidValue;
     GroupTable g{};
@@ -1623,6 +1844,23 @@ hipError_t decode_group(const DecodeX& x, const DecodeMember* m, int count, int 
         if (tiles == 2) return f(std::integral_constant<int, 2>{});
         return f(std::integral_constant<int, 1>{});
     };
+    if (rtiles > 1) {
+        with_elem(m[0].e.y.ytype == kYBf16, [&](auto ty) {
+            using TY = typename decltype(ty)::type;
+            with_tiles([&](auto t) {
+                with_bool(aligned, [&](auto al) {
+                    with_bool(rtiles == 4, [&](auto r4) {
+                        constexpr int T = decltype(t)::value, RT = decltype(r4)::value ? 4 : 2;
+                        constexpr bool AL = decltype(al)::value;
+                        if constexpr (RT * T <= kDecRowsAcc)  // the rule never asks for more
+                            hipLaunchKernelGGL((k_decode8mr<RT, T, AL, TY>), grid, dim3(kDecWaves * 64), 0, st,
+                                               static_cast<const int8_t*>(x.X), g, K, M, nkb, m[0].e.rscale);
+                    });
+                });
+            });
+        });
+        return hipGetLastError();
+    }
     with_elem(m[0].e.y.ytype == kYBf16, [&](auto ty) {
         using TY = typename decltype(ty)::type;
         with_tiles([&](auto t) {

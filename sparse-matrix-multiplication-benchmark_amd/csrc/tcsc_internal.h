@@ -590,7 +590,10 @@ hipError_t decode_gemm(const DecodeX& x, const uint32_t* w2, int K, int M, int N
 // `up`'s column scales and biases (neither's PReLU is read).  Y, its type and
 // pitch are up's; x as in decode_gemm.  decode_glu_tiles_per_wg: the column
 // tiles TG of a workgroup (1 or 2; it streams 2 TG image tiles).
+// Above 16 rows, on a kI8 x alone: k_decode8gr with decode_row_tiles(M) row tiles and
+// decode_glu_rows_tiles_per_wg's TG (2 or 1 at two row tiles, 1 at four: RT 2 TG <= 8); the same Y.
 int decode_glu_tiles_per_wg(int M, int N, int num_cus);
+int decode_glu_rows_tiles_per_wg(int M, int N, int num_cus);
 hipError_t decode_glu(const DecodeX& x, const uint32_t* wg, const uint32_t* wu, int K, int M, int N, const I8Epi& gate,
                       const I8Epi& up, int num_cus, hipStream_t st);
 // The grouped decode launch, k_decode8m / k_decode8qm: `count`
@@ -608,7 +611,10 @@ struct DecodeMember {
     I8Epi e;
 };
 long long decode_group_wgs(const int* cols, int count, int T);
+// Above 16 rows, on a kI8 x alone: k_decode8mr with decode_row_tiles(M) row tiles and
+// decode_group_rows_tiles_per_wg's T (RT T <= 8, halved while the whole grid is below the CU count).
 int decode_group_tiles_per_wg(int M, const int* cols, int count, int num_cus);
+int decode_group_rows_tiles_per_wg(int M, const int* cols, int count, int num_cus);
 hipError_t decode_group(const DecodeX& x, const DecodeMember* m, int count, int K, int M, int num_cus, hipStream_t st);
 
 // Rewrites the flagged rows in k_stream's fast order (no-op when none is).

@@ -65,6 +65,8 @@ EXPORTED_SYMBOLS = (
     "tcsc_gpu_sgemm_i8_res", "tcsc_gpu_sgemm_q8_res",
     "tcsc_gpu_plan_set_decode_rows", "tcsc_gpu_plan_decode_rows", "tcsc_gpu_decode_rows_pays",
     "tcsc_gpu_launch_info_decode",
+    "tcsc_gpu_plan_set_decode_rows_multi", "tcsc_gpu_plan_decode_rows_multi", "tcsc_gpu_glu_rows_pays",
+    "tcsc_gpu_group_rows_pays", "tcsc_gpu_launch_info_glu_decode", "tcsc_gpu_launch_info_group_decode",
     # include/sparse/bcsr.h
     "bcsr_from_dense", "bcsr_sgemm_basic", "bcsr_sgemm_prelu_basic", "bcsr_sgemm_avx", "bcsr_sgemm_prelu_avx",
     "bcsr_sgemm_avx2", "bcsr_free",
@@ -225,6 +227,12 @@ def lib():
     L.tcsc_gpu_plan_decode_rows.argtypes = [vp]
     L.tcsc_gpu_decode_rows_pays.argtypes = [i, i, i, i]
     L.tcsc_gpu_launch_info_decode.argtypes = [vp, i, C.POINTER(i), C.POINTER(i), C.POINTER(C.c_longlong)]
+    L.tcsc_gpu_plan_set_decode_rows_multi.argtypes = [vp, i]
+    L.tcsc_gpu_plan_decode_rows_multi.argtypes = [vp]
+    L.tcsc_gpu_glu_rows_pays.argtypes = [i, i, i, i]
+    L.tcsc_gpu_group_rows_pays.argtypes = [i, i, C.POINTER(i), i, i]
+    L.tcsc_gpu_launch_info_glu_decode.argtypes = [vp, vp, i, C.POINTER(i), C.POINTER(i), C.POINTER(C.c_longlong)]
+    L.tcsc_gpu_launch_info_group_decode.argtypes = [gm, i, i, C.POINTER(i), C.POINTER(i), C.POINTER(C.c_longlong)]
     L.tcsc_gpu_prepare_x.argtypes = [vp, vp, i, vp]
     L.tcsc_gpu_sgemm_prepared.argtypes = [vp, vp, vp, i, i, i, f, vp]
     L.tcsc_gpu_from_dense.argtypes = [vp, i, i, vp, vp, vp, vp, C.POINTER(i), C.POINTER(i), vp]
@@ -775,6 +783,18 @@ class Plan:
         """The setting of :meth:`set_decode_rows` (tcsc_gpu_plan_decode_rows)."""
         return int(lib().tcsc_gpu_plan_decode_rows(self.handle))
 
+    def set_decode_rows_multi(self, rows: int) -> None:
+        """The most rows a gated or grouped int8 call takes to the decode path where every plan of the call says
+        so (tcsc_gpu_plan_set_decode_rows_multi): 16 .. 64, or :data:`DECODE_ROWS_AUTO` for wherever
+        :func:`glu_rows_pays` / :func:`group_rows_pays` say so.  The default, 16, routes every call as before;
+        :meth:`set_decode_rows` is not read by those calls.  Needs the 2-bit image; allocates nothing."""
+        _check(lib().tcsc_gpu_plan_set_decode_rows_multi(self.handle, int(rows)), "tcsc_gpu_plan_set_decode_rows_multi")
+
+    @property
+    def decode_rows_multi(self) -> int:
+        """The setting of :meth:`set_decode_rows_multi` (tcsc_gpu_plan_decode_rows_multi)."""
+        return int(lib().tcsc_gpu_plan_decode_rows_multi(self.handle))
+
     def launch_info_decode(self, M: int) -> tuple[int, int, int]:
         """(row tiles, column tiles per workgroup, workgroups) of a decode launch of M rows on this plan
         (tcsc_gpu_launch_info_decode), whether or not M routes there: 1 <= M <= 64 on a plan with the image."""
@@ -1055,8 +1075,8 @@ def _glu_act(act) -> int:
 
 
 def launch_info_glu(gate_plan, up_plan, M: int, dtype="f32") -> tuple[str, int, bool]:
-    """(path, K slices, fused) of a gated call of M rows (tcsc_gpu_launch_info_glu): 'decode' up to 16 rows and
-    'mfma' above; fused: whether :func:`sgemm_q8_glu` of that dtype, without a norm, quantizes inside the launch."""
+    """(path, K slices, fused) of a gated call of M rows (tcsc_gpu_launch_info_glu): 'decode' up to 16 rows -- up
+    to 64 where both plans' :meth:`Plan.set_decode_rows_multi` setting admits M -- and 'mfma' above; fused: whether :func:`sgemm_q8_glu` of that dtype, without a norm, quantizes inside the launch."""
     path, slices, fused = C.c_int(), C.c_int(), C.c_int()
     _check(lib().tcsc_gpu_launch_info_glu(gate_plan.handle, up_plan.handle, int(M), _xtype(dtype), C.byref(path),
                                           C.byref(slices), C.byref(fused)), "tcsc_gpu_launch_info_glu")
@@ -1106,6 +1126,21 @@ def sgemm_q8_glu(gate_plan, up_plan, X, Xq, scale, bias_gate, bias_up, Y, M: int
                                        int(ldy), _glu_act(act), C.c_void_p(stream)), "tcsc_gpu_sgemm_q8_glu")
 
 
+def launch_info_glu_decode(gate_plan, up_plan, M: int) -> tuple[int, int, int]:
+    """(row tiles, column tiles per workgroup, workgroups) of a gated decode launch of M rows
+    (tcsc_gpu_launch_info_glu_decode), whether or not M routes there: 1 <= M <= 64."""
+    rt, ct, wg = C.c_int(), C.c_int(), C.c_longlong()
+    _check(lib().tcsc_gpu_launch_info_glu_decode(gate_plan.handle, up_plan.handle, int(M), C.byref(rt), C.byref(ct),
+                                                 C.byref(wg)), "tcsc_gpu_launch_info_glu_decode")
+    return rt.value, ct.value, wg.value
+
+
+def glu_rows_pays(M: int, K: int, H: int, num_cus: int = 0) -> bool:
+    """Where the gated row-tiled decode launch of 16 < M <= 64 rows beats the MFMA route (tcsc_gpu_glu_rows_pays;
+    host arithmetic): what plans set to :data:`DECODE_ROWS_AUTO` ask per gated call."""
+    return bool(lib().tcsc_gpu_glu_rows_pays(int(M), int(K), int(H), int(num_cus)))
+
+
 def glu_fuse_pays(M: int, K: int, N: int, dtype="f32", norm: bool = False) -> bool:
     """The default rule for fusing the quantizer (norm: and the norm) into the gated decode launch
     (tcsc_gpu_glu_fuse_pays; host arithmetic)."""
@@ -1136,7 +1171,8 @@ def _group_members(plans, biases=None, Ys=None, ldys=None, col_scales=None):
 
 def launch_info_group(plans, M: int, dtype="f32") -> tuple[str, list[int], bool]:
     """(path, [K slices of each member], fused) of a grouped call of M rows (tcsc_gpu_launch_info_group): 'decode'
-    up to 16 rows and 'mfma' above; fused: whether :func:`sgemm_q8_group` of that dtype, without a norm,
+    up to 16 rows -- up to 64 where every plan's :meth:`Plan.set_decode_rows_multi` setting admits M -- and 'mfma'
+    above; fused: whether :func:`sgemm_q8_group` of that dtype, without a norm,
     quantizes inside the launch (with a norm it never does)."""
     arr, n = _group_members(plans)
     path, fused = C.c_int(), C.c_int()
@@ -1181,6 +1217,25 @@ def sgemm_q8_group(plans, X, Xq, scale, biases, Ys, M: int, ldys=None, col_scale
                                          0.0 if norm_eps is None else float(norm_eps), C.c_void_p(_ptr(Xq)),
                                          C.c_void_p(_ptr(scale)), _group_ytype(Ys, ytype), int(M), C.c_void_p(stream)),
            "tcsc_gpu_sgemm_q8_group")
+
+
+def launch_info_group_decode(plans, M: int) -> tuple[int, int, int]:
+    """(row tiles, column tiles per workgroup, workgroups) of a grouped decode launch of M rows
+    (tcsc_gpu_launch_info_group_decode), whether or not M routes there: 1 <= M <= 64."""
+    arr, n = _group_members(plans)
+    rt, ct, wg = C.c_int(), C.c_int(), C.c_longlong()
+    _check(lib().tcsc_gpu_launch_info_group_decode(arr, n, int(M), C.byref(rt), C.byref(ct), C.byref(wg)),
+           "tcsc_gpu_launch_info_group_decode")
+    return rt.value, ct.value, wg.value
+
+
+def group_rows_pays(M: int, K: int, cols, num_cus: int = 0) -> bool:
+    """Where the grouped row-tiled decode launch of 16 < M <= 64 rows over members with these column counts beats
+    the MFMA route (tcsc_gpu_group_rows_pays; host arithmetic): what plans set to :data:`DECODE_ROWS_AUTO` ask
+    per grouped call."""
+    cols = [int(c) for c in cols]
+    arr = (C.c_int * max(len(cols), 1))(*cols)
+    return bool(lib().tcsc_gpu_group_rows_pays(int(M), int(K), arr, len(cols), int(num_cus)))
 
 
 def group_fuse_pays(M: int, K: int, cols, dtype="f32", norm: bool = False) -> bool:

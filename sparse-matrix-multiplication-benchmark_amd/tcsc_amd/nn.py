@@ -471,7 +471,7 @@ def _define():
         """Inference-only gated pair ``y = act(g) * u`` on two packed plans, with
         ``g = scale * weight_scale_gate * (q . Wg) + bias_gate`` and u the same on Wu: one
         ``tcsc_amd.sgemm_q8_glu`` call -- up to 16 rows a single decode launch that streams both 2-bit images,
-        k_gemm8w2 twice on one packed X above.
+        k_gemm8w2 twice on one packed X above, unless ``set_decode_rows`` admits those rows to the decode launch.
 
         Wg, Wu: K x H each, as :class:`PackedTernaryLinear` takes W.  bias_*, weight_scale_*: as its bias and
         weight_scale, one per half.  act: 'relu2' (``relu(g)**2``) or 'silu'.  norm_weight, norm_eps, out_dtype,
@@ -510,6 +510,16 @@ def _define():
             _, self.norm_eps = _norm_args(None, norm_eps, self.in_features, torch.device("cuda", self.device_index))
             self.plans = None
             self._rows, self._xq, self._scale, self._g = 0, None, None, None
+            self.decode_rows = None
+
+        def set_decode_rows(self, rows) -> None:
+            """Sets ``Plan.set_decode_rows_multi(rows)`` (16 .. 64 or ``tcsc_amd.DECODE_ROWS_AUTO``; None keeps the
+            plans as they are) on both plans, and on those a later ``load_state_dict`` builds: a forward of 17 ..
+            rows rows is then the one gated decode launch, the same bits."""
+            self.decode_rows = None if rows is None else int(rows)
+            if self.plans is not None and self.decode_rows is not None:
+                for plan in self.plans:
+                    plan.set_decode_rows_multi(self.decode_rows)
 
         @classmethod
         def from_float(cls, Wg, Wu, bias_gate=None, bias_up=None, act: str = "relu2", norm_weight=None,
@@ -580,6 +590,9 @@ def _define():
             for h in self._HALVES:
                 if prefix + "w2_" + h in unexpected_keys:
                     unexpected_keys.remove(prefix + "w2_" + h)
+            if getattr(self, "decode_rows", None) is not None:
+                for p in plans:
+                    p.set_decode_rows_multi(self.decode_rows)
             old, self.plans = self.plans, plans
             for p in old or ():
                 p.destroy()
@@ -632,7 +645,7 @@ def _define():
         state dict are the two layers'.  ``forward(x, residual=r, inplace=...)`` passes the residual to ``down``
         (:class:`PackedTernaryLinear`): the FFN with its skip connection in two library calls.
         decode_rows, if given, is set on ``down`` alone (``PackedTernaryLinear.set_decode_rows``): the gated call
-        reads no such setting."""
+        has a setting of its own, ``glu.set_decode_rows``."""
 
         def __init__(self, glu: PackedTernaryGLU, down: PackedTernaryLinear, decode_rows=None):
             super().__init__()
@@ -654,7 +667,8 @@ def _define():
         """Inference-only group of 1 to 4 ternary matrices on one input, the Q, K and V
         projections of an attention block for instance: ``y_i = scale * weight_scale_i * (q . W_i) + bias_i`` for
         every member in one ``tcsc_amd.sgemm_q8_group`` call -- up to 16 rows a single decode launch over all
-        the 2-bit images, one packed X and one k_gemm8w2 per member above.  Each y_i has the bits of a
+        the 2-bit images, one packed X and one k_gemm8w2 per member above (unless ``set_decode_rows`` admits those rows
+        to the decode launch).  Each y_i has the bits of a
         :class:`PackedTernaryLinear` (a None) built from the same inputs.
 
         Ws: the matrices, K x N_i each, as :class:`PackedTernaryLinear` takes W; the N_i are free.  biases,
@@ -702,6 +716,16 @@ def _define():
             _, self.norm_eps = _norm_args(None, norm_eps, self.in_features, torch.device("cuda", self.device_index))
             self.plans = None
             self._rows, self._xq, self._scale = 0, None, None
+            self.decode_rows = None
+
+        def set_decode_rows(self, rows) -> None:
+            """Sets ``Plan.set_decode_rows_multi(rows)`` (16 .. 64 or ``tcsc_amd.DECODE_ROWS_AUTO``; None keeps the
+            plans as they are) on every member's plan, and on those a later ``load_state_dict`` builds: a forward of 17 ..
+            rows rows is then the one grouped decode launch, the same bits."""
+            self.decode_rows = None if rows is None else int(rows)
+            if self.plans is not None and self.decode_rows is not None:
+                for plan in self.plans:
+                    plan.set_decode_rows_multi(self.decode_rows)
 
         @classmethod
         def from_float(cls, Wfs, biases=None, norm_weight=None, norm_eps: float | None = None,
@@ -772,6 +796,9 @@ def _define():
             for k in range(len(self.out_features_list)):
                 if f"{prefix}w2_{k}" in unexpected_keys:
                     unexpected_keys.remove(f"{prefix}w2_{k}")
+            if getattr(self, "decode_rows", None) is not None:
+                for p in plans:
+                    p.set_decode_rows_multi(self.decode_rows)
             old, self.plans = self.plans, plans
             for p in old or ():
                 p.destroy()
